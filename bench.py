@@ -14,7 +14,13 @@ A rank process imports NO torch: it maps one HIP runtime and one RCCL, the ones 
 max-over-ranks clock and the counters run through the library's own collectives (shm_dist_barrier / _allreduce_f64 / _allgather_f64).
 Scene arrays are resident in HBM before the timed region. --width/--height/--spp override either default.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--spp S] [--res R] [--no-cpu-baseline] [--no-side] [--no-live-pmc]
+A plain run sets up, warms up, times K steps and prints the line: `value`, `ms_per_step`, the per-kernel breakdown and the algorithmic
+roofline all come from the timed steps themselves. --full adds what takes work of its own: the dominant kernel's hardware counters
+(rocprofv3 passes in child processes, else the committed profile of the configuration), the side configurations, the CPU oracle
+baseline and the film self-checks; --no-live-pmc / --no-side / --no-cpu-baseline leave one of them out of a --full run.
+--dump-outputs DIR writes the film of the last timed step (rank 0's, gathered at N > 1) as DIR/rgb_sum.npy and DIR/weight_sum.npy.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--spp S] [--res R] [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-side] [--no-live-pmc]]
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -300,6 +306,30 @@ def side_results(lib, args, render, scenes, headline_scene, log):
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(film, out_dir):
+    """The film the last timed step left on the device, as a caller reads it back (shm_film_read): DIR/rgb_sum.npy (H, W, 3) and
+    DIR/weight_sum.npy (H, W), float64. A film larger than DUMP_MAX_BYTES (the C5 frame: 265 MB) is written as a fixed sample of
+    pixels drawn with seed 0, their flat indices in DIR/pixel_index.npy, so that two builds compare the same pixels."""
+    import numpy as np
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    rgb, w = film["rgb_sum"], film["weight_sum"]
+    index = out / "pixel_index.npy"
+    if film.nbytes > DUMP_MAX_BYTES:
+        k = (DUMP_MAX_BYTES - 4096) // (film.itemsize + 8)  # (room for the three .npy headers)
+        idx = np.sort(np.random.default_rng(0).choice(film.size, size=k, replace=False))
+        rgb, w = rgb.reshape(-1, 3)[idx], w.reshape(-1)[idx]
+        np.save(index, idx.astype(np.float64))
+    else:
+        index.unlink(missing_ok=True)
+    np.save(out / "rgb_sum.npy", np.ascontiguousarray(rgb, dtype=np.float64))
+    np.save(out / "weight_sum.npy", np.ascontiguousarray(w, dtype=np.float64))
+    log(f"[bench] outputs of the last timed step -> {out}/ (rgb_sum {rgb.shape}, weight_sum {w.shape})")
+
+
 _STORE = None  # this rank's control-channel store (so that main() can publish a failure)
 
 
@@ -315,9 +345,12 @@ def parse_args(argv=None):
     ap.add_argument("--n", type=int, default=599, help="cube-sphere subdivision (599 -> 4 305 612 triangles)")
     ap.add_argument("--max-depth", type=int, default=5)
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-side", action="store_true", help="skip the side configurations (coated S3, C4, C2, textured Cornell)")
-    ap.add_argument("--no-live-pmc", action="store_true", help="do not collect the dominant kernel's counters in this run (falls back to the committed profile)")
+    ap.add_argument("--full", action="store_true", help="also the hardware counters, the side configurations, the CPU baseline and the film "
+                    "self-checks (a plain run times the headline frame only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the film of the last timed step as DIR/<field>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
+    ap.add_argument("--no-side", action="store_true", help="with --full: skip the side configurations (coated S3, C4, C2, textured Cornell)")
+    ap.add_argument("--no-live-pmc", action="store_true", help="with --full: do not collect the dominant kernel's counters in this run (falls back to the committed profile)")
     ap.add_argument("--pmc-timeout", type=float, default=240.0, help="seconds per live counter pass")
     ap.add_argument("--pmc-child", action="store_true", help="internal: the frame a live counter pass profiles (no baseline, no side runs, prints nothing)")
     ap.add_argument("--coated", action="store_true", help="S3 with a CoatedDiffuse object (LayeredBxDF, SURVEY 8f-1) instead of the "
@@ -334,7 +367,10 @@ def parse_args(argv=None):
     ap.add_argument("--dry-run", action="store_true", help="control plane only (no GPU, no library render call): launcher, environment, id exchange, "
                     "barrier and max-reduce through the store; used by the CPU tests")
     ap.add_argument("--dry-run-fail-rank", type=int, default=-1, help="with --dry-run: this rank exits 7 after the id exchange")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def main():
@@ -378,11 +414,11 @@ def rank_main(args):
 
     headline = world == 1 and not (args.coated or args.variant or args.shard_of or args.force_dist or args.width or args.height or args.pmc_child)
     counters, counters_src = None, "none"
-    if headline and not args.no_live_pmc:
+    if args.full and headline and not args.no_live_pmc:
         # BEFORE this process touches the GPU: the counter passes are child processes under rocprofv3
         counters, counters_src = live_pmc(args)
         log(f"[bench] live counters: {counters_src}" + (f" ({counters['collect_s']:.0f} s)" if counters else ""))
-    if counters is None and world == 1:
+    if args.full and counters is None and world == 1:
         c = committed_pmc(args)
         if c:
             counters, counters_src = c, f"committed profile profiles/traffic_res{args.res}_spp{args.spp}_n{args.n}_depth{args.max_depth}.json" + \
@@ -517,8 +553,8 @@ def rank_main(args):
                                        "instruction (the measured best issue rate; frac_at_guide_peak_2_clocks prices the same numerator against the guide's 2-cycle v_fma_f32: "
                                        "MI355X_MICROARCH.md, per-instruction cycle constants); the gathers are L2 / MALL-served (roofline_hbm_counter), so HBM is not "
                                        "the ceiling; see roofline_valu for every term" if valu else
-                                       "no hardware counters available in this run (rocprofv3 missing and no committed profile of this configuration): "
-                                       "see roofline_hbm_algorithmic"},
+                                       "no hardware counters in this run (they are collected with --full; there, rocprofv3 missing and no committed profile "
+                                       "of this configuration also leave them out): see roofline_hbm_algorithmic"},
             "roofline_hbm_algorithmic": {"bound": "hbm (SURVEY 8d ALGORITHMIC bytes; cache-served, saturated: may exceed 1)",
                                          "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                                          "frac_of_achievable": achieved / HBM_ACHIEVABLE_GBS, "bytes_per_launch": bytes_alg / launches,
@@ -566,7 +602,9 @@ def rank_main(args):
                 out["roofline"]["frac"] = None
         if per_rank is not None:
             out["per_rank"] = per_rank
-    if use_dist and rank == 0:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(r.read_film(), args.dump_outputs)
+    if args.full and use_dist and rank == 0:
         # the gathered film: every pixel of the frame received all its samples, from some rank
         host = r.read_film()
         if not (host["weight_sum"] == float(args.spp)).all():
@@ -576,7 +614,7 @@ def rank_main(args):
             raise SystemExit("gathered film is not finite")
         if world == 1:
             r.dist_selftest()  # film rows through the RCCL send / recv group, looped back to this rank
-    if rank == 0 and world == 1 and not use_dist and not args.shard_of:
+    if args.full and rank == 0 and world == 1 and not use_dist and not args.shard_of:
         # self-check outside the timed region: every pixel received all its samples, all sums finite
         t0 = time.perf_counter()
         host = r.read_film()
@@ -596,7 +634,7 @@ def rank_main(args):
     if use_dist:
         r.dist_barrier()   # nobody tears its communicator down while a peer still checks the film
     r.close()
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         # the side results BEFORE the CPU baseline (round 6): after the oracle's run on every host thread the box's host side stays unsettled for a minute or more and
         # launch-bound frames pay for it — C4's second timed frame 373-381 ms instead of 347, every other side result 0.5-1.5 % slower (profiles/r06_bench_order.txt)
         if not args.no_side and not args.coated and not args.variant and not args.shard_of and (width, height) == (1024, 1024):

@@ -104,9 +104,9 @@ def test_dist_small_collectives_world1(gpu_lib, small_s3):
 
 
 def test_bench_self_launcher_world1_one_runtime_stack(gpu_lib):
-    """`python bench.py --gpus 1 --launch --force-dist`: the parent starts ONE fresh rank process (no torch.distributed.run), which runs the
+    """`python bench.py --gpus 1 --launch --force-dist --full`: the parent starts ONE fresh rank process (no torch.distributed.run), which runs the
     whole N > 1 code path — id through the file store, shm_dist_init, barrier / max clock / counters through the library's RCCL
-    collectives, shm_render_sharded, loop-back self test — on the HIP runtime and the RCCL the library is linked against, without torch."""
+    collectives, shm_render_sharded, the gathered film's checks and the loop-back self test (--full) — on the HIP runtime and the RCCL the library is linked against, without torch."""
     import json
     import subprocess
     import sys
@@ -114,7 +114,7 @@ def test_bench_self_launcher_world1_one_runtime_stack(gpu_lib):
     root = Path(__file__).resolve().parents[1]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "SHM_STORE_DIR")}
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--launch", "--force-dist", "--res", "128", "--spp", "8", "--n", "24", "--steps", "2",
-                        "--warmup", "1", "--no-cpu-baseline", "--no-side"], cwd=root, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+                        "--warmup", "1", "--full", "--no-cpu-baseline", "--no-side"], cwd=root, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     out = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1])
     rt = out["runtime"]
