@@ -412,8 +412,22 @@ typedef struct ShmRenderParams {
      * Transform::operator() (transform.rs:573-608 uses the inverse for everything but the point): instances render as their baked copies. Reference-exact,
      * BASELINE's C1 scene is 19 % darker than an estimator that samples no lights; with 1 it agrees with it (tests/test_quirks_switch.py). */
     uint8_t disable_reference_quirks;
-    uint8_t pad[7];
+    /* The sampler (DESIGN.md "Sampler"). SHM_SAMPLER_INDEPENDENT (0, the default and the reference's only sampler): one PCG32 stream per pixel.
+     * SHM_SAMPLER_ZSOBOL (1): PBRT-v4's ZSobolSampler — a Morton-ordered, per-digit shuffled Sobol' (0, 2)-sequence with log2spp = ceil(log2(spp))
+     * (PBRT-v4 takes the floor); sample indices must stay below 2^log2spp. sampler_randomization applies to ZSobol only: SHM_SAMPLER_FASTOWEN (0,
+     * the default) or SHM_SAMPLER_RANDOMIZE_NONE (1, the bare sequence). Callers that zero `pad` keep the independent sampler. */
+    uint8_t sampler;
+    uint8_t sampler_randomization;
+    uint8_t pad[5];
 } ShmRenderParams;
+enum {
+    SHM_SAMPLER_INDEPENDENT = 0,
+    SHM_SAMPLER_ZSOBOL = 1
+};
+enum {
+    SHM_SAMPLER_FASTOWEN = 0,
+    SHM_SAMPLER_RANDOMIZE_NONE = 1
+};
 enum {
     SHM_INTEGRATOR_PATH = 0,        /* PathIntegrator,       integrator.rs:748-963 */
     SHM_INTEGRATOR_SIMPLE_PATH = 1, /* SimplePathIntegrator, integrator.rs:573-733 */

@@ -30,6 +30,8 @@ SHM_FLOATTEX_CONSTANT, SHM_FLOATTEX_SCALED, SHM_FLOATTEX_MIX, SHM_FLOATTEX_DIREC
  SHM_FLOATSLOT_V2_ROUGHNESS, SHM_FLOATSLOT_THICKNESS, SHM_FLOATSLOT_G, SHM_FLOATSLOT_MIX_AMOUNT) = range(8)
 SHM_CAMERA_PERSPECTIVE, SHM_CAMERA_ORTHOGRAPHIC = 0, 1
 SHM_INTEGRATOR_PATH, SHM_INTEGRATOR_SIMPLE_PATH, SHM_INTEGRATOR_RANDOM_WALK = 0, 1, 2
+SHM_SAMPLER_INDEPENDENT, SHM_SAMPLER_ZSOBOL = 0, 1
+SHM_SAMPLER_FASTOWEN, SHM_SAMPLER_RANDOMIZE_NONE = 0, 1
 
 c_float_p = C.POINTER(C.c_float)
 c_u32_p = C.POINTER(C.c_uint32)
@@ -160,7 +162,7 @@ class ShmRenderParams(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("samples_per_pixel", C.c_int32), ("max_depth", C.c_int32), ("regularize", C.c_uint8),
                 ("disable_pixel_jitter", C.c_uint8), ("disable_wavelength_jitter", C.c_uint8), ("force_diffuse", C.c_uint8),
                 ("integrator", C.c_uint8), ("sample_lights", C.c_uint8), ("sample_bsdf", C.c_uint8), ("disable_texture_filtering", C.c_uint8),
-                ("disable_reference_quirks", C.c_uint8), ("pad", C.c_uint8 * 7)]
+                ("disable_reference_quirks", C.c_uint8), ("sampler", C.c_uint8), ("sampler_randomization", C.c_uint8), ("pad", C.c_uint8 * 5)]
 
 
 class ShmTile(C.Structure):

@@ -70,6 +70,7 @@ struct FlatScene {
     shm::SceneView view() const {
         shm::SceneView v;
         v.quirks_off = 0;
+        v.zsobol = 0;
         v.call_copy = nullptr;  // (device only: set per workgroup by the kernels that evaluate textures)
         v.inst_roots = nullptr;  // (device only)
         v.nodes = nodes.data();

@@ -31,6 +31,8 @@ struct Options {
     bool force_diffuse = false;
     bool disable_texture_filtering = false;
     bool wavefront = true;  // main.rs:152-155: the flag that selects this backend
+    uint8_t sampler = SHM_SAMPLER_INDEPENDENT;                // ShmRenderParams::sampler
+    uint8_t sampler_randomization = SHM_SAMPLER_FASTOWEN;     // ShmRenderParams::sampler_randomization (ZSobol only)
 };
 
 // what create_path_integrator reads from its ParameterDictionary (integrator.rs:188-192) and from the sampler prototype
@@ -99,6 +101,8 @@ public:
         rp.sample_bsdf = params_.sample_bsdf ? 1 : 0;
         rp.disable_pixel_jitter = options.disable_pixel_jitter ? 1 : 0;
         rp.disable_wavelength_jitter = options.disable_wavelength_jitter ? 1 : 0;
+        rp.sampler = options.sampler;
+        rp.sampler_randomization = options.sampler_randomization;
         stats_ = ShmStats{};
         check(shm_film_clear(scene_.get()), "shm_film_clear");
         const int32_t spp = params_.samples_per_pixel;

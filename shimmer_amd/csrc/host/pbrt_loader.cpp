@@ -217,7 +217,7 @@ public:
     struct Settings {
         int spp, max_depth;
         bool regularize = false, sample_lights = true, sample_bsdf = true;
-        std::string integrator = "path", filename = "shimmer.pfm", sampler = "independent";
+        std::string integrator = "path", filename = "shimmer.pfm", sampler = "independent", randomization = "fastowen";
         int seed = 0;
         float white_balance = 0.0f;
         uint32_t render_space = SHM_RENDER_SPACE_CAMERA_WORLD;
@@ -1010,8 +1010,14 @@ private:
             need_world(t, tk, false);
             settings_.sampler = read_string(tk, t);
             const Params ps = read_params(tk);
-            if (settings_.sampler != "independent") fail(tk.where(t.line) + ": sampler \"" + settings_.sampler + "\" is not supported (independent)", SHM_ERR_UNSUPPORTED);
-            settings_.spp = ps.one_int("pixelsamples", 4);
+            if (settings_.sampler != "independent" && settings_.sampler != "zsobol")
+                fail(tk.where(t.line) + ": sampler \"" + settings_.sampler + "\" is not supported (independent, zsobol)", SHM_ERR_UNSUPPORTED);
+            if (settings_.sampler == "zsobol") {  // PBRT-v4's ZSobolSampler::Create: "randomization" defaults to "fastowen"
+                settings_.randomization = ps.one_string("randomization", "fastowen");
+                if (settings_.randomization != "fastowen" && settings_.randomization != "none")
+                    fail(tk.where(t.line) + ": zsobol randomization \"" + settings_.randomization + "\" is not supported (fastowen, none)", SHM_ERR_UNSUPPORTED);
+            }
+            settings_.spp = ps.one_int("pixelsamples", settings_.sampler == "zsobol" ? 16 : 4);  // (PBRT-v4's defaults of the two samplers)
             settings_.seed = ps.one_int("seed", settings_.seed);
         } else if (d == "Integrator") {
             need_world(t, tk, false);
@@ -1149,6 +1155,8 @@ static int load_text(const std::string& text, const std::string& name, const std
         p.disable_texture_filtering = st.disable_texture_filtering;
         p.sample_lights = st.sample_lights;
         p.sample_bsdf = st.sample_bsdf;
+        p.sampler = st.sampler == "zsobol" ? SHM_SAMPLER_ZSOBOL : SHM_SAMPLER_INDEPENDENT;
+        p.sampler_randomization = st.randomization == "none" ? SHM_SAMPLER_RANDOMIZE_NONE : SHM_SAMPLER_FASTOWEN;
         // SHM_REFERENCE_QUIRKS (include/shimmer_hip.h ShmRenderParams::disable_reference_quirks): ON unless the host's environment says 0 / off
         if (const char* q = getenv("SHM_REFERENCE_QUIRKS")) p.disable_reference_quirks = (!strcmp(q, "0") || !strcmp(q, "off") || !strcmp(q, "OFF")) ? 1 : 0;
         p.integrator = st.integrator == "path" ? SHM_INTEGRATOR_PATH : (st.integrator == "simplepath" ? SHM_INTEGRATOR_SIMPLE_PATH : SHM_INTEGRATOR_RANDOM_WALK);

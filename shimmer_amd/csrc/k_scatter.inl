@@ -12,9 +12,19 @@
 #define K_ENV_LIGHT false
 #endif
 #if K_ENV_LIGHT  // (the *_env.hip units' kernels carry their own names: a kernel trace tells them from the units without the light — tools/kernel_coverage.py)
+#if K_ZSOBOL
+#define k_scatter k_scatter_env_zs
+#define k_scatter_specular k_scatter_specular_env_zs
+#define k_scatter_nonspecular k_scatter_nonspecular_env_zs
+#else
 #define k_scatter k_scatter_env
 #define k_scatter_specular k_scatter_specular_env
 #define k_scatter_nonspecular k_scatter_nonspecular_env
+#endif
+#elif K_ZSOBOL  // (the *_zs objects' kernels, wavefront.h)
+#define k_scatter k_scatter_zs
+#define k_scatter_specular k_scatter_specular_zs
+#define k_scatter_nonspecular k_scatter_nonspecular_zs
 #endif
 namespace {
 
@@ -188,12 +198,7 @@ __device__ __forceinline__ void scatter_body(const SceneView& sv, const PathArra
             Rng rng;
             {
                 const uint32_t pix = pa.rec[path].pixel;
-                const uint2 rs = pa.rec[path].rng;
-                rng.state = (uint64_t)rs.x | ((uint64_t)rs.y << 32);
-                // inc is a pure function of (pixel, seed): re-derived instead of stored
-                uint64_t h = mix_bits(((uint64_t)(pix & 0xffffu) << 32) | (uint64_t)(pix >> 16));
-                h = mix_bits(h ^ (params.seed + 0x9e3779b97f4a7c15ULL));
-                rng.inc = (h << 1u) | 1u;
+                rng = sampler_load(pa.rec[path].rng, pix, sv, params);
             }
             // options.force_diffuse (interaction.rs:256-275) draws inside get_bsdf, i.e. before anything else of this half
             if (SUB == 0 && params.force_diffuse) {  // (the SUB kernels are only launched without it, and without regularize)
@@ -312,7 +317,7 @@ __device__ __forceinline__ void scatter_body(const SceneView& sv, const PathArra
                     pa.rec[path].beta = st_spec(beta);
                     pa.rec[path].pb_eta = make_float2(p_b, eta_scale);
                     // (the CtxRec already holds this vertex's context: the next vertex's prev_intr_ctx)
-                    pa.rec[path].rng = make_uint2((uint32_t)rng.state, (uint32_t)(rng.state >> 32));
+                    pa.rec[path].rng = sampler_store(rng);
                     uint32_t aux_bit = 0u;
                     if (HAS_TEX && CLASS != CLASS_DIFFUSE && (fl & (1u << 10)) &&
                         (bs.flags == BXDF_SPECULAR_REFLECTION || bs.flags == BXDF_SPECULAR_TRANSMISSION)) {

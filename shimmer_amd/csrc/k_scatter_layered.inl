@@ -22,7 +22,13 @@
 #define K_ENV_LIGHT false
 #endif
 #if K_ENV_LIGHT  // (the *_env.hip units' kernels carry their own names: a kernel trace tells them from the units without the light — tools/kernel_coverage.py)
+#if K_ZSOBOL
+#define k_scatter_layered k_scatter_layered_env_zs
+#else
 #define k_scatter_layered k_scatter_layered_env
+#endif
+#elif K_ZSOBOL  // (the *_zs objects' kernels, wavefront.h)
+#define k_scatter_layered k_scatter_layered_zs
 #endif
 namespace {
 
@@ -106,16 +112,8 @@ __device__ __forceinline__ void layered_bsdf_of(const SceneView& sv, const PathA
     bsdf.shading_frame.z = ns;
     bsdf.shading_frame.y = cross(ns, bsdf.shading_frame.x);
 }
-__device__ __forceinline__ Rng path_sampler(const PathArrays& pa, uint32_t path, const ShmRenderParams& params) {
-    Rng rng;
-    const uint32_t pix = pa.rec[path].pixel;
-    const uint2 rs = pa.rec[path].rng;
-    rng.state = (uint64_t)rs.x | ((uint64_t)rs.y << 32);
-    // inc is a pure function of (pixel, seed): re-derived instead of stored
-    uint64_t h = mix_bits(((uint64_t)(pix & 0xffffu) << 32) | (uint64_t)(pix >> 16));
-    h = mix_bits(h ^ (params.seed + 0x9e3779b97f4a7c15ULL));
-    rng.inc = (h << 1u) | 1u;
-    return rng;
+__device__ __forceinline__ Rng path_sampler(const SceneView& sv, const PathArrays& pa, uint32_t path, const ShmRenderParams& params) {
+    return sampler_load(pa.rec[path].rng, pa.rec[path].pixel, sv, params);
 }
 
 template <bool TRI_ONLY, bool HAS_TEX>
@@ -201,7 +199,7 @@ __device__ __forceinline__ void scatter_layered_staged(const SceneView& sv, cons
                 bool any_non_specular_bounces = (fl >> 9) & 1u;
                 if (params.regularize && any_non_specular_bounces) bxdf_regularize(bsdf.bxdf);
                 Float eta_scale = pa.rec[path].pb_eta.y;
-                Rng rng = path_sampler(pa, path, params);  // (stage A left the state behind this vertex's seven dimensions)
+                Rng rng = path_sampler(sv, pa, path, params);  // (stage A left the state behind this vertex's seven dimensions)
                 bs.wi = bsdf.shading_frame.from_local(bs.wi);  // bsdf.rs:80
                 // integrator.rs:859-872
                 beta = beta * (bs.f * abs_dot(bs.wi, ns) / bs.pdf);
@@ -240,7 +238,7 @@ __device__ __forceinline__ void scatter_layered_staged(const SceneView& sv, cons
                     pa.rec[path].beta = st_spec(beta);
                     pa.rec[path].pb_eta = make_float2(p_b, eta_scale);
                     // (the CtxRec already holds this vertex's context: the next vertex's prev_intr_ctx)
-                    pa.rec[path].rng = make_uint2((uint32_t)rng.state, (uint32_t)(rng.state >> 32));
+                    pa.rec[path].rng = sampler_store(rng);
                     pa.rec[path].flags = (uint32_t)depth | ((uint32_t)specular_bounce << 8) | ((uint32_t)any_non_specular_bounces << 9) | aux_bit;
                 }
             }
@@ -362,7 +360,7 @@ __device__ __forceinline__ void scatter_layered_staged(const SceneView& sv, cons
                 si_wo = wo;
                 if (!TRI_ONLY) { const float4 w4 = pa.bx[path].siwo; si_wo = v3(w4.x, w4.y, w4.z); }
                 regularized = params.regularize && ((pa.rec[path].flags >> 9) & 1u);
-                Rng rng = path_sampler(pa, path, params);
+                Rng rng = path_sampler(sv, pa, path, params);
                 if (regularized) bxdf_regularize(bsdf.bxdf);
                 bf = bsdf_flags(bsdf);
                 kind = bsdf.bxdf.kind;
@@ -374,7 +372,7 @@ __device__ __forceinline__ void scatter_layered_staged(const SceneView& sv, cons
                 // integrator.rs:843-857: sample the BSDF — here BSDF::sample_f's entry (bsdf.rs:60-74) and the top interface's sample
                 const Float u = sampler_get_1d(rng);
                 const V2 u2 = sampler_get_2d(rng);
-                pa.rec[path].rng = make_uint2((uint32_t)rng.state, (uint32_t)(rng.state >> 32));  // stage C draws Russian roulette from here
+                pa.rec[path].rng = sampler_store(rng);  // stage C draws Russian roulette from here
                 const V3 wo_l = bsdf.shading_frame.to_local(wo);
                 if (!(wo_l.z == 0.0f || !((bf & REFLTRANS_ALL) != 0u))) status = layered_sample_begin(bsdf.bxdf, wo_l, u, u2, MODE_RADIANCE, bs, k);
             }

@@ -8,6 +8,7 @@ int wf_launch_scatter_layered_staged_tri(ShmScene* s, const ShadeArgs& a) {
     return SHM_OK;
 }
 
+#if !K_ZSOBOL  // (once in the library)
 // development build (-DLJ_CENSUS=1): what the four stages did, printed at scene destruction
 void wf_layered_census() {
 #ifdef LJ_CENSUS
@@ -24,3 +25,4 @@ void wf_layered_census() {
     fprintf(stderr, "[layered census] A rounds without a single NEE job %.3e, with at most 8: %.3e (of %.3e)\n", (double)c[18], (double)c[19], (double)c[0]);
 #endif
 }
+#endif

@@ -2,6 +2,9 @@
 // k_shade_lean.hip for the all-diffuse triangle scene class (every other class runs the staged k_vertex -> k_scatter<class>).
 #pragma once
 #include "wavefront.h"
+#if K_ZSOBOL  // (the *_zs objects' kernels, wavefront.h)
+#define k_shade k_shade_zs
+#endif
 
 namespace {
 
@@ -211,11 +214,7 @@ __global__ void __launch_bounds__(SHADE2_BLOCK) K_SHADE_LEAN_ATTR k_shade(SceneV
                     uint32_t pix = first_bounce ? pa.pixel0[path] : pa.rec[path].pixel;
                     uint2 rs = first_bounce ? pa.rng0[path] : pa.rec[path].rng;
                     pix_in = pix;
-                    rng.state = (uint64_t)rs.x | ((uint64_t)rs.y << 32);
-                    // inc is a pure function of (pixel, seed): re-derive instead of storing 8 more bytes per path
-                    uint64_t h = mix_bits(((uint64_t)(pix & 0xffffu) << 32) | (uint64_t)(pix >> 16));
-                    h = mix_bits(h ^ (params.seed + 0x9e3779b97f4a7c15ULL));
-                    rng.inc = (h << 1u) | 1u;
+                    rng = sampler_load(rs, pix, sv, params);
                 };
                 // options.force_diffuse (interaction.rs:256-275) draws inside get_bsdf, before the depth test; only the general
                 // instantiation carries it (the host launches that one when the flag is set)
@@ -324,7 +323,7 @@ __global__ void __launch_bounds__(SHADE2_BLOCK) K_SHADE_LEAN_ATTR k_shade(SceneV
                                 pa.ctx[path].c1 = make_float4(nctx.pi.y.high, nctx.pi.z.high, nctx.n.x, nctx.n.y);
                                 pa.ctx[path].c2 = make_float4(nctx.n.z, nctx.ns.x, nctx.ns.y, nctx.ns.z);
                             }
-                            pa.rec[path].rng = make_uint2((uint32_t)rng.state, (uint32_t)(rng.state >> 32));
+                            pa.rec[path].rng = sampler_store(rng);
                             if (first_bounce) { pa.rec[path].lambda = lambda4_in; pa.rec[path].pixel = pix_in; }  // the record's first sector, complete
                             uint32_t aux_bit = 0u;
                             if (HAS_TEX) {  // spawn_ray_with_differentials, interaction.rs:430-514

@@ -1,6 +1,10 @@
 // k_shade_other.hip — the reference's two debugging integrators on the same queues and path state: SimplePathIntegrator::li
 // (integrator.rs:586-733) and RandomWalkIntegrator (integrator.rs:445-563).
 #include "wavefront.h"
+#if K_ZSOBOL  // (the *_zs objects' kernels, wavefront.h)
+#define k_shade_simple k_shade_simple_zs
+#define k_shade_randomwalk k_shade_randomwalk_zs
+#endif
 
 namespace {
 
@@ -76,15 +80,7 @@ __global__ void __launch_bounds__(SHADE2_BLOCK) K_SHADE_ATTR k_shade_simple(Scen
                     depth += 1;
                     BSDF bsdf = get_bsdf_general(sv, pa, path, fl, si, sv.materials[prim.material], lambda, params);
                     V3 wo = -ray_d;
-                    uint32_t pix = pa.rec[path].pixel;
-                    uint2 rs = pa.rec[path].rng;
-                    Rng rng;
-                    rng.state = (uint64_t)rs.x | ((uint64_t)rs.y << 32);
-                    {
-                        uint64_t h = mix_bits(((uint64_t)(pix & 0xffffu) << 32) | (uint64_t)(pix >> 16));
-                        h = mix_bits(h ^ (params.seed + 0x9e3779b97f4a7c15ULL));
-                        rng.inc = (h << 1u) | 1u;
-                    }
+                    Rng rng = sampler_load(pa.rec[path].rng, pa.rec[path].pixel, sv, params);
                     if (params.force_diffuse) {  // interaction.rs:256-275: rho_hd(wo, [get_1d()], [get_2d()]) inside get_bsdf
                         Float uc = sampler_get_1d(rng);
                         V2 u2f = sampler_get_2d(rng);
@@ -153,7 +149,7 @@ __global__ void __launch_bounds__(SHADE2_BLOCK) K_SHADE_ATTR k_shade_simple(Scen
                         nr.pad = 0.0f;
                         pa.ray[path] = nr;
                         pa.rec[path].beta = st_spec(beta);
-                        pa.rec[path].rng = make_uint2((uint32_t)rng.state, (uint32_t)(rng.state >> 32));
+                        pa.rec[path].rng = sampler_store(rng);
                         pa.rec[path].flags = (uint32_t)depth | ((specular_bounce ? 0u : 1u) << 8);
                         push_next = true;
                     }
@@ -235,15 +231,7 @@ __global__ void __launch_bounds__(SHADE2_BLOCK) K_SHADE_ATTR k_shade_randomwalk(
                 rec[0] = st_spec(le);
                 if (depth != params.max_depth) {
                     BSDF bsdf = get_bsdf_general(sv, pa, path, fl, si, sv.materials[prim.material], lambda, params);
-                    uint32_t pix = pa.rec[path].pixel;
-                    uint2 rs = pa.rec[path].rng;
-                    Rng rng;
-                    rng.state = (uint64_t)rs.x | ((uint64_t)rs.y << 32);
-                    {
-                        uint64_t h = mix_bits(((uint64_t)(pix & 0xffffu) << 32) | (uint64_t)(pix >> 16));
-                        h = mix_bits(h ^ (params.seed + 0x9e3779b97f4a7c15ULL));
-                        rng.inc = (h << 1u) | 1u;
-                    }
+                    Rng rng = sampler_load(pa.rec[path].rng, pa.rec[path].pixel, sv, params);
                     if (params.force_diffuse) {
                         Float uc = sampler_get_1d(rng);
                         V2 u2f = sampler_get_2d(rng);
@@ -260,7 +248,7 @@ __global__ void __launch_bounds__(SHADE2_BLOCK) K_SHADE_ATTR k_shade_randomwalk(
                         nr.t_max = infinity();
                         nr.pad = 0.0f;
                         pa.ray[path] = nr;
-                        pa.rec[path].rng = make_uint2((uint32_t)rng.state, (uint32_t)(rng.state >> 32));
+                        pa.rec[path].rng = sampler_store(rng);
                         pa.rec[path].flags = (uint32_t)(depth + 1);
                         push_next = true;
                     }
@@ -279,6 +267,7 @@ __global__ void __launch_bounds__(SHADE2_BLOCK) K_SHADE_ATTR k_shade_randomwalk(
       __syncthreads();
     }
 }
+#if !K_ZSOBOL  // (draws nothing: only the units without the switch have it)
 // L = le_T; L = le_k + f_k cos_k * L / (1 / (4 pi)) for k = T-1 .. 0 (integrator.rs:549-562)
 __global__ void __launch_bounds__(SHADE_BLOCK) k_fold_randomwalk(PathArrays pa, const float4* __restrict__ rw, uint32_t capacity, uint32_t total) {
     uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
@@ -293,6 +282,7 @@ __global__ void __launch_bounds__(SHADE_BLOCK) k_fold_randomwalk(PathArrays pa, 
     pa.L[slot] = st_spec(l);
 }
 
+#endif
 }  // namespace
 
 int wf_launch_shade_simple(ShmScene* s, const ShadeArgs& a) {
@@ -307,8 +297,10 @@ int wf_launch_shade_randomwalk(ShmScene* s, const ShadeArgs& a, uint32_t cap_eff
     LAUNCH_TRY("k_shade_randomwalk");
     return SHM_OK;
 }
+#if !K_ZSOBOL
 int wf_launch_fold_randomwalk(ShmScene* s, hipStream_t stream, uint32_t cap_eff, uint32_t total) {
     hipLaunchKernelGGL(k_fold_randomwalk, dim3((total + SHADE_BLOCK - 1) / SHADE_BLOCK), dim3(SHADE_BLOCK), 0, stream, s->pa, s->d_rw, cap_eff, total);
     LAUNCH_TRY("k_fold_randomwalk");
     return SHM_OK;
 }
+#endif

@@ -34,6 +34,10 @@ extern "C" __attribute__((visibility("default"))) int shm_debug_eval_leaf(int de
     if (!in_words || !out_words || n_in == 0 || n_out == 0 || op <= 0 || op >= shm::PROBE_N_OPS || n_in > (1u << 20) || n_out > (1u << 20)) { g_probe_err = "shm_debug_eval_leaf: invalid arguments"; return SHM_ERR_INVALID_ARGUMENT; }
     // the one op whose output length is an ARGUMENT (the sampler stream: in[5] draws): it must fit what the caller provided
     if (op == shm::PROBE_SAMPLER_STREAM && (n_in < 6 || in_words[5] > n_out)) { g_probe_err = "shm_debug_eval_leaf: the sampler stream's length exceeds n_out"; return SHM_ERR_INVALID_ARGUMENT; }
+    if (op == shm::PROBE_ZSOBOL_STREAM && (n_in < 10 || in_words[9] > (1u << 16) || n_in < 10 + in_words[9] || 4 * in_words[9] > n_out)) {
+        g_probe_err = "shm_debug_eval_leaf: the zsobol stream needs 10 + n argument words and 4 n output words";
+        return SHM_ERR_INVALID_ARGUMENT;
+    }
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) { g_probe_err = "no HIP device visible (the probe has no CPU fallback)"; return SHM_ERR_NO_DEVICE; }
     if (hipSetDevice(device) != hipSuccess) { g_probe_err = "hipSetDevice"; return SHM_ERR_DEVICE; }

@@ -53,7 +53,7 @@ __device__ __forceinline__ uint32_t slot_of(uint32_t p_local, uint32_t s_local, 
 
 // HAS_TEX: scenes that bind image textures carry the camera ray's auxiliary rays (a compile-time switch: with a run-time pointer the
 // auxiliary-ray record lived in scratch memory, 52 B of stores per path, in every scene)
-template <bool HAS_TEX, bool LEAN = false>
+template <bool HAS_TEX, bool LEAN = false, bool ZS = false>  // ZS: the ZSobol sampler (wavefront.h, K_ZSOBOL)
 __global__ void __launch_bounds__(SHADE_BLOCK) k_generate(SceneView sv, PathArrays pa, const uint32_t* pixels, uint32_t n_pix,
                                                         int sample_begin, int n_samples, ShmRenderParams params,
                                                         uint32_t* q_active, QueueState* qs, uint32_t pix_group) {
@@ -68,7 +68,7 @@ __global__ void __launch_bounds__(SHADE_BLOCK) k_generate(SceneView sv, PathArra
     uint32_t p_local = g0 + (rem - s_local * pg);
     uint32_t pix = pixels[p_local];
     int px = (int)(pix & 0xffffu), py = (int)(pix >> 16);
-    Rng rng = sampler_start_pixel_sample(px, py, sample_begin + (int)s_local, params.seed);
+    Rng rng = sampler_start_pixel_sample(px, py, sample_begin + (int)s_local, params.seed, sampler_word<ZS>(sv));
     Wavelengths lambda;
     Float weight;
     constexpr bool has_tex = HAS_TEX;
@@ -92,12 +92,12 @@ __global__ void __launch_bounds__(SHADE_BLOCK) k_generate(SceneView sv, PathArra
     if (LEAN) {
         // no record: the fused kernel's bounce 0 reads these three arrays and writes the path's first record whole (one full 64-byte store instead of this kernel's
         // partial sectors: k_generate 10.5 -> 6 ms per headline frame)
-        pa.rng0[slot] = make_uint2((uint32_t)rng.state, (uint32_t)(rng.state >> 32));
+        pa.rng0[slot] = sampler_store(rng);
         pa.pixel0[slot] = pix;
     } else {
         PathRec r;
         r.lambda = lambda4;
-        r.rng = make_uint2((uint32_t)rng.state, (uint32_t)(rng.state >> 32));
+        r.rng = sampler_store(rng);
         r.pixel = pix;
         r.flags = has_tex ? (1u << 10) : 0u;  // camera rays always carry auxiliary rays (camera.rs:1070-1078)
         r.beta = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
@@ -640,6 +640,14 @@ int shm_render_wave(ShmScene* s, const ShmRenderParams* params, const ShmTile* t
     if (!s || !params || !tiles || n_tiles == 0 || sample_end <= sample_begin) { g_err = "invalid render arguments"; return SHM_ERR_INVALID_ARGUMENT; }
     if (params->max_depth < 0 || params->max_depth > 254) { g_err = "max_depth out of range"; return SHM_ERR_INVALID_ARGUMENT; }
     if (params->integrator > SHM_INTEGRATOR_RANDOM_WALK) { g_err = "unknown integrator"; return SHM_ERR_UNSUPPORTED; }
+    if (params->sampler > SHM_SAMPLER_ZSOBOL || params->sampler_randomization > SHM_SAMPLER_RANDOMIZE_NONE) { g_err = "unknown sampler or sampler randomization"; return SHM_ERR_INVALID_ARGUMENT; }
+    // ZSobol: the per-render constants of the stream (shm/sampling.h); its sample indices are the low log2spp bits of the Morton index
+    const uint32_t zsobol = zsobol_config(params->samples_per_pixel, s->flat.film.full_resolution[0], s->flat.film.full_resolution[1],
+                                          params->sampler_randomization == SHM_SAMPLER_RANDOMIZE_NONE);
+    if (params->sampler == SHM_SAMPLER_ZSOBOL && (sample_begin < 0 || (int64_t)sample_end > (int64_t)1 << zsobol_log2spp(zsobol))) {
+        g_err = "zsobol: sample index outside [0, 2^ceil(log2(samples_per_pixel)))";
+        return SHM_ERR_INVALID_ARGUMENT;
+    }
     HIP_TRY(hipSetDevice(s->device));
     int rc;
     const int32_t* pb = s->flat.film.pixel_bounds;
@@ -699,6 +707,10 @@ int shm_render_wave(ShmScene* s, const ShmRenderParams* params, const ShmTile* t
 
     const int n_samples = sample_end - sample_begin;
     s->dsv.quirks_off = params->disable_reference_quirks ? 1u : 0u;  // SHM_REFERENCE_QUIRKS: every kernel of this render takes s->dsv by value
+    s->dsv.zsobol = zsobol;  // (read only by the ZSobol kernels: sampler_word)
+    // the sampler is a compile-time constant of the kernels: ZSobol renders launch the *_zs objects' twins (wavefront.h, K_ZSOBOL)
+    const bool zs = params->sampler == SHM_SAMPLER_ZSOBOL;
+#define WF_ZS(launcher) (zs ? launcher##_zs : launcher)
     const bool random_walk = params->integrator == SHM_INTEGRATOR_RANDOM_WALK;
     // (the random walk keeps 32 B per depth per path beside the path state: its batches are capped at 16 Mi paths)
     const bool staged = use_staged(s, params);
@@ -743,15 +755,12 @@ int shm_render_wave(ShmScene* s, const ShmRenderParams* params, const ShmTile* t
         //  (HIT_HAS_SECOND, wavefront.h). Not with instances: a hit inside one names it in the 32-byte record, patched when the instance's marker is popped)
         s->pa.hit16 = ((!s->flat.has_spheres || !s->flat.has_instances) && params->integrator == SHM_INTEGRATOR_PATH && !random_walk) ? 1u : 0u;
         s->pa.hit2 = (s->pa.hit16 && s->flat.has_spheres) ? reinterpret_cast<const float4*>(s->pa.hit) + s->capacity : nullptr;
-        if (s->pa.aux0)
-            hipLaunchKernelGGL(k_generate<true>, dim3((total + SHADE_BLOCK - 1) / SHADE_BLOCK), dim3(SHADE_BLOCK), 0, s->stream, s->dsv, s->pa, pixels, n_pix,
+        {
+            auto* gen = s->pa.aux0 ? (zs ? k_generate<true, false, true> : k_generate<true>)
+                                   : (lean_first ? (zs ? k_generate<false, true, true> : k_generate<false, true>) : (zs ? k_generate<false, false, true> : k_generate<false>));
+            hipLaunchKernelGGL(gen, dim3((total + SHADE_BLOCK - 1) / SHADE_BLOCK), dim3(SHADE_BLOCK), 0, s->stream, s->dsv, s->pa, pixels, n_pix,
                                sample_begin, n_samples, *params, s->d_q_active[0], s->d_qs, s->pix_group);
-        else if (lean_first)
-            hipLaunchKernelGGL((k_generate<false, true>), dim3((total + SHADE_BLOCK - 1) / SHADE_BLOCK), dim3(SHADE_BLOCK), 0, s->stream, s->dsv, s->pa, pixels, n_pix,
-                               sample_begin, n_samples, *params, s->d_q_active[0], s->d_qs, s->pix_group);
-        else
-            hipLaunchKernelGGL(k_generate<false>, dim3((total + SHADE_BLOCK - 1) / SHADE_BLOCK), dim3(SHADE_BLOCK), 0, s->stream, s->dsv, s->pa, pixels, n_pix,
-                               sample_begin, n_samples, *params, s->d_q_active[0], s->d_qs, s->pix_group);
+        }
         LAUNCH_TRY("k_generate");
         int cur = 0;
         // Small batches are tail-dominated (the last rays of a persistent traversal launch take ~0.5 ms whatever its size): there
@@ -815,9 +824,9 @@ int shm_render_wave(ShmScene* s, const ShmRenderParams* params, const ShmTile* t
                 const bool fused_all = staged && bounce >= s->tail_fused_bounce && !s->flat.has_class[CLASS_LAYERED] && params->force_diffuse == 0 &&
                                        (!s->flat.has_textures || env_plain_scene(s) || fused_tex_ok);
                 if (fused_all) {
-                    if (env_plain_scene(s)) rc = tri_only ? wf_launch_shade_tail_sorted_env(s, sa) : wf_launch_shade_fused_gen_env(s, sa);
-                    else rc = tri_only ? (s->flat.has_textures ? wf_launch_shade_fused_tex(s, sa) : wf_launch_shade_tail_sorted(s, sa))
-                                       : (s->flat.has_textures ? wf_launch_shade_fused_gen_tex(s, sa) : wf_launch_shade_fused_gen(s, sa));
+                    if (env_plain_scene(s)) rc = tri_only ? WF_ZS(wf_launch_shade_tail_sorted_env)(s, sa) : WF_ZS(wf_launch_shade_fused_gen_env)(s, sa);
+                    else rc = tri_only ? (s->flat.has_textures ? WF_ZS(wf_launch_shade_fused_tex)(s, sa) : WF_ZS(wf_launch_shade_tail_sorted)(s, sa))
+                                       : (s->flat.has_textures ? WF_ZS(wf_launch_shade_fused_gen_tex)(s, sa) : WF_ZS(wf_launch_shade_fused_gen)(s, sa));
                 } else if (staged) {
                     // hit half (interaction, emission, get_bsdf -> parameter block, class queues), then one scattering kernel per BxDF
                     // class the scene holds, each over its own material-sorted queue
@@ -865,26 +874,26 @@ int shm_render_wave(ShmScene* s, const ShmRenderParams* params, const ShmTile* t
                         }
                         ++k_cls;
                     };
-                    scatter_on(-1, [&](const ShadeArgs& x) { return s->flat.has_image_light ? (tri_only ? wf_launch_shade_lean_env_diverted(s, x) : wf_launch_shade_lean_gen_env_diverted(s, x))
-                                                                                              : (tri_only ? wf_launch_shade_lean_diverted(s, x) : wf_launch_shade_lean_gen_diverted(s, x)); });
-                    scatter_on(CLASS_DIFFUSE, [&](const ShadeArgs& x) { return env ? wf_launch_scatter_diffuse_env(s, x, tri_only) : wf_launch_scatter_diffuse(s, x, tri_only, has_tex); });
-                    scatter_on(CLASS_CONDUCTOR, [&](const ShadeArgs& x) { return env ? wf_launch_scatter_conductor_env(s, x, tri_only) : wf_launch_scatter_conductor(s, x, tri_only, has_tex); });
-                    scatter_on(CLASS_DIELECTRIC, [&](const ShadeArgs& x) { return env ? wf_launch_scatter_dielectric_env(s, x, tri_only) : wf_launch_scatter_dielectric(s, x, tri_only, has_tex); });
+                    scatter_on(-1, [&](const ShadeArgs& x) { return s->flat.has_image_light ? (tri_only ? WF_ZS(wf_launch_shade_lean_env_diverted)(s, x) : WF_ZS(wf_launch_shade_lean_gen_env_diverted)(s, x))
+                                                                                              : (tri_only ? WF_ZS(wf_launch_shade_lean_diverted)(s, x) : WF_ZS(wf_launch_shade_lean_gen_diverted)(s, x)); });
+                    scatter_on(CLASS_DIFFUSE, [&](const ShadeArgs& x) { return env ? WF_ZS(wf_launch_scatter_diffuse_env)(s, x, tri_only) : WF_ZS(wf_launch_scatter_diffuse)(s, x, tri_only, has_tex); });
+                    scatter_on(CLASS_CONDUCTOR, [&](const ShadeArgs& x) { return env ? WF_ZS(wf_launch_scatter_conductor_env)(s, x, tri_only) : WF_ZS(wf_launch_scatter_conductor)(s, x, tri_only, has_tex); });
+                    scatter_on(CLASS_DIELECTRIC, [&](const ShadeArgs& x) { return env ? WF_ZS(wf_launch_scatter_dielectric_env)(s, x, tri_only) : WF_ZS(wf_launch_scatter_dielectric)(s, x, tri_only, has_tex); });
                     scatter_on(CLASS_LAYERED, [&](const ShadeArgs& x) {
                         // (options.force_diffuse replaces the BxDF inside this half: the one-pass kernel has that code)
                         if (params->force_diffuse == 0 && s->capacity < (1u << 30)) {  // (its jobs carry two flag bits above the path index)
-                            if (env) return tri_only ? wf_launch_scatter_layered_staged_tri_env(s, x) : wf_launch_scatter_layered_staged_gen_env(s, x);
-                            return has_tex ? wf_launch_scatter_layered_staged_tex(s, x) : (tri_only ? wf_launch_scatter_layered_staged_tri(s, x) : wf_launch_scatter_layered_staged_gen(s, x));
+                            if (env) return tri_only ? WF_ZS(wf_launch_scatter_layered_staged_tri_env)(s, x) : WF_ZS(wf_launch_scatter_layered_staged_gen_env)(s, x);
+                            return has_tex ? WF_ZS(wf_launch_scatter_layered_staged_tex)(s, x) : (tri_only ? WF_ZS(wf_launch_scatter_layered_staged_tri)(s, x) : WF_ZS(wf_launch_scatter_layered_staged_gen)(s, x));
                         }
                         // (`env` implies params->force_diffuse == 0: the one-pass kernel is reached from here only past 2^30 paths of workspace, which ensure_workspace never grants —
                         //  its K_ENV_LIGHT units left the library in round 6 — and under options.force_diffuse, where the textured class's units run)
-                        return has_tex ? wf_launch_scatter_layered_tex(s, x) : (tri_only ? wf_launch_scatter_layered_tri(s, x) : wf_launch_scatter_layered_gen(s, x)); });
+                        return has_tex ? WF_ZS(wf_launch_scatter_layered_tex)(s, x) : (tri_only ? WF_ZS(wf_launch_scatter_layered_tri)(s, x) : WF_ZS(wf_launch_scatter_layered_gen)(s, x)); });
                     for (hipEvent_t e : side_done) hipStreamWaitEvent(s->stream, e, 0);
                 }
-                else if (random_walk) rc = wf_launch_shade_randomwalk(s, sa, cap_eff);
-                else if (params->integrator == SHM_INTEGRATOR_SIMPLE_PATH) rc = wf_launch_shade_simple(s, sa);
-                else if (env_lean_scene(s)) rc = tri_only ? wf_launch_shade_lean_env(s, sa) : wf_launch_shade_lean_gen_env(s, sa);
-                else rc = tri_only ? wf_launch_shade_lean(s, sa) : wf_launch_shade_lean_gen(s, sa);
+                else if (random_walk) rc = WF_ZS(wf_launch_shade_randomwalk)(s, sa, cap_eff);
+                else if (params->integrator == SHM_INTEGRATOR_SIMPLE_PATH) rc = WF_ZS(wf_launch_shade_simple)(s, sa);
+                else if (env_lean_scene(s)) rc = tri_only ? WF_ZS(wf_launch_shade_lean_env)(s, sa) : WF_ZS(wf_launch_shade_lean_gen_env)(s, sa);
+                else rc = tri_only ? WF_ZS(wf_launch_shade_lean)(s, sa) : WF_ZS(wf_launch_shade_lean_gen)(s, sa);
                 if (rc != SHM_OK) return rc;
                 hipEventRecord(s1, s->stream);
                 ev_shade.push_back({s0, s1});
@@ -953,6 +962,7 @@ int shm_render_wave(ShmScene* s, const ShmRenderParams* params, const ShmTile* t
     }
     return SHM_OK;
 }
+#undef WF_ZS
 
 int shm_render_device(ShmScene* s, const ShmRenderParams* params, const ShmTile* tiles, uint32_t n_tiles, ShmStats* stats) {
     if (!s || !params) { g_err = "invalid render arguments"; return SHM_ERR_INVALID_ARGUMENT; }

@@ -513,7 +513,7 @@ SHM_HD Rng layered_rng(uint64_t sequence, uint64_t seed) {
     rng_set_sequence(r, sequence, seed);
     return r;
 }
-SHM_HD Float layered_r(Rng& rng) { return min(sampler_get_1d(rng), ONE_MINUS_EPSILON); }  // the closure `r` of bxdf.rs:1015-1020
+SHM_HD Float layered_r(Rng& rng) { return min(rng_get_1d(rng), ONE_MINUS_EPSILON); }  // the closure `r` of bxdf.rs:1015-1020 (PCG32 whatever the sampler)
 SHM_HD V2 layered_r2(Rng& rng) { Float a = layered_r(rng); Float b = layered_r(rng); return v2(a, b); }
 
 SHM_HD BaseBxDF layered_top(const BxDF& l) {

@@ -16,7 +16,7 @@ enum : int {
     PROBE_TRIANGLE_PDF_WITH_CONTEXT, PROBE_TRIANGLE_INTERACTION, PROBE_SPHERE_SAMPLE_WITH_CONTEXT, PROBE_SPHERE_PDF_WITH_CONTEXT, PROBE_AREA_LIGHT_L, PROBE_FILM_ADD_SAMPLE,
     PROBE_CAMERA_RAY_DIFFERENTIAL, PROBE_INTERVAL_OP, PROBE_DET3, PROBE_ROTATE_FROM_TO, PROBE_SAMPLE_DISCRETE, PROBE_SAMPLER_STREAM, PROBE_SAMPLE_VISIBLE_WAVELENGTHS,
     PROBE_VISIBLE_WAVELENGTHS_PDF, PROBE_VECMATH, PROBE_TRANSFORM_APPLY, PROBE_BLP_INTERSECT, PROBE_BLP_SAMPLE_WITH_CONTEXT, PROBE_BLP_PDF_WITH_CONTEXT, PROBE_SPHERE_INTERSECT,
-    PROBE_UNARY, PROBE_EQUAL_AREA_SQUARE_TO_SPHERE, PROBE_EQUAL_AREA_SPHERE_TO_SQUARE, PROBE_N_OPS
+    PROBE_UNARY, PROBE_EQUAL_AREA_SQUARE_TO_SPHERE, PROBE_EQUAL_AREA_SPHERE_TO_SQUARE, PROBE_ZSOBOL_STREAM, PROBE_N_OPS
 };
 
 namespace probe_detail {
@@ -248,6 +248,27 @@ SHM_HD int leaf_probe(int op, const uint32_t* in, uint32_t* out) {
             Rng r = sampler_start_pixel_sample((int)in[0], (int)in[1], (int)in[2], (uint64_t)in[3] | ((uint64_t)in[4] << 32));
             for (int i = 0; i < (int)in[5]; ++i) put(out, i, sampler_get_1d(r));
             return 0;
+        }
+        case PROBE_ZSOBOL_STREAM: {  // the ZSobol stream (shm/sampling.h); px, py, sample_index, spp, full_res x, y, seed lo, seed hi, randomization (0 fastowen, 1 none),
+                                     // n, then n draw kinds (1: get_1d, 2: get_2d). Per draw of kind k: k raw u32 values, then their k floats (4 n words at most)
+            Rng r = sampler_start_pixel_sample((int)in[0], (int)in[1], (int)in[2], (uint64_t)in[6] | ((uint64_t)in[7] << 32),
+                                               zsobol_config((int)in[3], (int)in[4], (int)in[5], in[8] != 0u));
+            int o = 0;
+            for (int i = 0; i < (int)in[9]; ++i) {
+                if (in[10 + i] == 2u) {
+                    uint32_t x, y;
+                    zsobol_next_2d_bits(r, x, y);
+                    out[o] = x; out[o + 1] = y;
+                    put(out, o + 2, zsobol_float(x)); put(out, o + 3, zsobol_float(y));
+                    o += 4;
+                } else {
+                    const uint32_t x = zsobol_next_1d_bits(r);
+                    out[o] = x;
+                    put(out, o + 1, zsobol_float(x));
+                    o += 2;
+                }
+            }
+            return o;
         }
         case PROBE_SAMPLE_VISIBLE_WAVELENGTHS: put(out, 0, sample_visible_wavelengths(f(in, 0))); return 0;  // sampling.rs:347-371
         case PROBE_VISIBLE_WAVELENGTHS_PDF: put(out, 0, visible_wavelengths_pdf(f(in, 0))); return 0;

@@ -56,12 +56,17 @@ inline uint64_t ref_stream_next_u64(RefStream& r) {  // xoshiro256++ 1.0 (Blackm
 inline float ref_stream_next_f32(RefStream& r) { return (float)(uint32_t)(ref_stream_next_u64(r) >> 40) * 5.9604644775390625e-8f; }
 #endif
 
+// The sampler state. `zs` selects the stream: 0 is the independent sampler (PCG32: state, inc); otherwise it is the render's
+// zsobol_config() word and the ZSobol stream runs on state = dimension (low 32 bits), inc = pixel x | y << 16 | sample index << 32, with `seed`
+// hashed per dimension.
 struct Rng {
     uint64_t state;
     uint64_t inc;
 #ifdef SHM_ORACLE_REFERENCE_STREAM
     RefStream* ref = nullptr;
 #endif
+    uint32_t zs = 0u;
+    uint64_t seed = 0u;
 };
 constexpr uint64_t PCG32_DEFAULT_STATE = 0x853c49e6748fea9bULL;
 constexpr uint64_t PCG32_MULT = 0x5851f42d4c957f2dULL;
@@ -118,22 +123,193 @@ SHM_HD uint64_t mix_bits(uint64_t v) {
     v ^= (v >> 33);
     return v;
 }
-// start_pixel_sample(p, sample_index, dimension = 0) as the reference's TODO describes it.
-SHM_HD Rng sampler_start_pixel_sample(int px, int py, int sample_index, uint64_t seed) {
+// PCG32's sequence for a pixel: inc = hash(pixel, seed) << 1 | 1 (rng_set_sequence), a pure function of (pixel, seed)
+SHM_HD uint64_t independent_sequence(int px, int py, uint64_t seed) {
     uint64_t h = mix_bits(((uint64_t)(uint32_t)px << 32) | (uint64_t)(uint32_t)py);
-    h = mix_bits(h ^ (seed + 0x9e3779b97f4a7c15ULL));
+    return mix_bits(h ^ (seed + 0x9e3779b97f4a7c15ULL));
+}
+
+// ---- ZSobol (PBR-4e 8.7.4 ZSobolSampler; DESIGN.md "Sampler") ----
+// One word of per-render constants, computed on the host (zsobol_config) and handed to the kernels: 0 = the independent sampler.
+constexpr uint32_t ZS_ON = 1u, ZS_NO_SCRAMBLE = 2u;  // bit 0: ZSobol; bit 1: randomization "none"; bits 8-15 log2spp; bits 16-23 nBase4Digits
+SHM_HD int ceil_log2_u32(uint32_t v) {
+    int l = 0;
+    while (l < 31 && (1u << l) < v) ++l;
+    return l;
+}
+// log2spp = ceil(log2(spp)) (PBRT-v4 takes the floor, which makes neighbouring pixels share sample indices at non-powers of two);
+// nBase4Digits = log2(RoundUpPow2(max(full_res))) + (log2spp + 1) / 2
+SHM_HD uint32_t zsobol_config(int spp, int full_res_x, int full_res_y, bool no_scramble) {
+    const int log2spp = ceil_log2_u32((uint32_t)(spp > 1 ? spp : 1));
+    const int res = full_res_x > full_res_y ? full_res_x : full_res_y;
+    const int n_digits = ceil_log2_u32((uint32_t)(res > 1 ? res : 1)) + (log2spp + 1) / 2;
+    return ZS_ON | (no_scramble ? ZS_NO_SCRAMBLE : 0u) | ((uint32_t)log2spp << 8) | ((uint32_t)n_digits << 16);
+}
+SHM_HD int zsobol_log2spp(uint32_t zs) { return (int)((zs >> 8) & 0xffu); }
+SHM_HD uint32_t reverse_bits32(uint32_t v) {
+#if defined(__clang__)
+    return __builtin_bitreverse32(v);
+#else
+    v = (v << 16) | (v >> 16);
+    v = ((v & 0x00ff00ffu) << 8) | ((v & 0xff00ff00u) >> 8);
+    v = ((v & 0x0f0f0f0fu) << 4) | ((v & 0xf0f0f0f0u) >> 4);
+    v = ((v & 0x33333333u) << 2) | ((v & 0xccccccccu) >> 2);
+    v = ((v & 0x55555555u) << 1) | ((v & 0xaaaaaaaau) >> 1);
+    return v;
+#endif
+}
+SHM_HD uint64_t left_shift2(uint64_t x) {  // spreads the low 32 bits of x to the even bit positions
+    x &= 0xffffffffULL;
+    x = (x ^ (x << 16)) & 0x0000ffff0000ffffULL;
+    x = (x ^ (x << 8)) & 0x00ff00ff00ff00ffULL;
+    x = (x ^ (x << 4)) & 0x0f0f0f0f0f0f0f0fULL;
+    x = (x ^ (x << 2)) & 0x3333333333333333ULL;
+    x = (x ^ (x << 1)) & 0x5555555555555555ULL;
+    return x;
+}
+SHM_HD uint64_t encode_morton2(uint32_t x, uint32_t y) { return (left_shift2(y) << 1) | left_shift2(x); }  // y in the odd bits
+SHM_HD uint64_t shr64(uint64_t v, int s) { return s >= 64 ? 0u : v >> s; }
+// MurmurHash64A (seed 0) of the 12 bytes {int32 dimension, uint64 seed}, little-endian: PBRT-v4's Hash(dimension, seed)
+SHM_HD uint64_t zsobol_hash(uint32_t dimension, uint64_t seed) {
+    const uint64_t m = 0xc6a4a7935bd1e995ULL;
+    uint64_t h = 12ULL * m;
+    uint64_t k = (uint64_t)dimension | (seed << 32);  // bytes 0-7
+    k *= m;
+    k ^= k >> 47;
+    k *= m;
+    h ^= k;
+    h *= m;
+    h ^= seed >> 32;  // the tail, bytes 8-11
+    h *= m;
+    h ^= h >> 47;
+    h *= m;
+    h ^= h >> 47;
+    return h;
+}
+// x % 24 for a 40-bit x in 32-bit arithmetic: 24 = 8 * 3 and 2^32 = 1 (mod 3)
+SHM_HD uint32_t mod24_u64(uint64_t x) {
+    const uint64_t q = x >> 3;
+    const uint32_t m3 = ((uint32_t)q % 3u + (uint32_t)(q >> 32) % 3u) % 3u;
+    return m3 * 8u + (uint32_t)(x & 7u);
+}
+// digit d of the p-th permutation of {0, 1, 2, 3} in lexicographic order: the table packed as 24 bytes of four 2-bit digits
+SHM_HD uint32_t zsobol_perm(uint32_t p, uint32_t d) {
+    const uint32_t bit = p * 8u + d * 2u;
+    const uint64_t w = bit < 64u ? 0xb1e16c9c78d8b4e4ULL : (bit < 128u ? 0x36c672d22d8d39c9ULL : 0x1b4b278763931e4eULL);
+    return (uint32_t)(w >> (bit & 63u)) & 3u;
+}
+// GetSampleIndex: each base-4 digit of the Morton index permuted by a hash of the digits above it and of the dimension
+SHM_HD uint64_t zsobol_sample_index(uint64_t morton, uint32_t dimension, uint32_t zs) {
+    const int log2spp = zsobol_log2spp(zs), n_digits = (int)((zs >> 16) & 0xffu);
+    const int odd = log2spp & 1;
+    const uint32_t dmix = 0x55555555u * dimension;  // (32-bit product, as PBRT-v4's unsigned int arithmetic)
+    uint64_t index = 0u;
+    for (int i = n_digits - 1; i >= odd; --i) {
+        const int shift = 2 * i - odd;
+        const uint32_t digit = (uint32_t)(morton >> shift) & 3u;
+        const uint64_t higher = shr64(morton, shift + 2);
+        const uint32_t p = mod24_u64(mix_bits(higher ^ (uint64_t)dmix) >> 24);
+        index |= (uint64_t)zsobol_perm(p, digit) << shift;
+    }
+    if (odd) index |= (morton & 1u) ^ (mix_bits((morton >> 1) ^ (uint64_t)dmix) & 1u);
+    return index;
+}
+// Sobol dimension 0: generator columns 1 << (31 - k), i.e. the bit reversal of the index's low 32 bits
+SHM_HD uint32_t sobol_dim0(uint64_t a) { return reverse_bits32((uint32_t)a); }
+// Sobol dimension 1: the Pascal matrix mod 2, columns c_0 = 0x80000000, c_k = c_{k-1} ^ (c_{k-1} >> 1): bit 31 - j of c_k is binom(k, j) mod 2, which
+// (Lucas) is 1 iff j & k == j. So bit 31 - j of the sample is the parity of the index bits k that are supersets of j: a superset sum over six bit levels
+SHM_HD uint32_t sobol_dim1(uint64_t a) {
+    a ^= (a >> 1) & 0x5555555555555555ULL;
+    a ^= (a >> 2) & 0x3333333333333333ULL;
+    a ^= (a >> 4) & 0x0f0f0f0f0f0f0f0fULL;
+    a ^= (a >> 8) & 0x00ff00ff00ff00ffULL;
+    a ^= (a >> 16) & 0x0000ffff0000ffffULL;
+    a ^= (a >> 32);
+    return reverse_bits32((uint32_t)a);
+}
+SHM_HD uint32_t fast_owen(uint32_t v, uint32_t s) {
+    v = reverse_bits32(v);
+    v ^= v * 0x3d20adeau;
+    v += s;
+    v *= (s >> 16) | 1u;
+    v ^= v * 0x05526c56u;
+    v ^= v * 0x53a22864u;
+    return reverse_bits32(v);
+}
+SHM_HD Float zsobol_float(uint32_t v) { return min((Float)v * 0x1p-32f, ONE_MINUS_EPSILON); }
+// One ZSobol draw of n = 1 or 2 dimensions at `dimension` of (pixel, sample index) = `ps` (Rng::inc): x | y << 32. A real call on the device
+// (SHM_HD_NOINLINE, arguments by value): inlined at every draw site of a kernel it cost the independent sampler's path registers and spills,
+// although the sampler is a wave-uniform scalar branch.
+SHM_HD_NOINLINE uint64_t zsobol_bits(uint64_t ps, uint32_t dimension, uint32_t zs, uint64_t seed, int n) {
+    const uint64_t morton = (encode_morton2((uint32_t)ps & 0xffffu, ((uint32_t)ps >> 16) & 0xffffu) << zsobol_log2spp(zs)) | (ps >> 32);
+    const uint64_t index = zsobol_sample_index(morton, dimension, zs);
+    uint32_t x = sobol_dim0(index), y = n == 2 ? sobol_dim1(index) : 0u;
+    if (!(zs & ZS_NO_SCRAMBLE)) {
+        const uint64_t h = zsobol_hash(dimension + (uint32_t)n, seed);
+        x = fast_owen(x, (uint32_t)h);
+        if (n == 2) y = fast_owen(y, (uint32_t)(h >> 32));
+    }
+    return (uint64_t)x | ((uint64_t)y << 32);
+}
+SHM_HD uint32_t zsobol_next_1d_bits(Rng& r) {
+    const uint64_t b = zsobol_bits(r.inc, (uint32_t)r.state, r.zs, r.seed, 1);
+    r.state = (uint32_t)r.state + 1u;
+    return (uint32_t)b;
+}
+SHM_HD void zsobol_next_2d_bits(Rng& r, uint32_t& x, uint32_t& y) {
+    const uint64_t b = zsobol_bits(r.inc, (uint32_t)r.state, r.zs, r.seed, 2);
+    r.state = (uint32_t)r.state + 2u;
+    x = (uint32_t)b;
+    y = (uint32_t)(b >> 32);
+}
+
+// start_pixel_sample(p, sample_index, dimension = 0): the independent sampler as the reference's TODO describes it, or (zs != 0) ZSobol
+SHM_HD Rng sampler_start_pixel_sample(int px, int py, int sample_index, uint64_t seed, uint32_t zs = 0u) {
     Rng r;
-    rng_set_sequence(r, h, PCG32_DEFAULT_STATE);
+    if (zs) {
+        r.state = 0u;
+        r.inc = ((uint64_t)(uint32_t)sample_index << 32) | ((uint32_t)py << 16) | ((uint32_t)px & 0xffffu);
+        r.zs = zs;
+        r.seed = seed;
+        return r;
+    }
+    rng_set_sequence(r, independent_sequence(px, py, seed), PCG32_DEFAULT_STATE);
     rng_advance_65536(r, (uint64_t)(uint32_t)sample_index);
     return r;
 }
+// What a path keeps of its sampler between kernels, 8 bytes: the PCG32 state (inc is re-derived from the pixel), or for ZSobol
+// sample index | dimension << 32 (the pixel is the path's own)
+SHM_HD uint64_t sampler_save(const Rng& r) {
+    if (r.zs) return (r.inc >> 32) | ((uint64_t)(uint32_t)r.state << 32);
+    return r.state;
+}
+SHM_HD Rng sampler_resume(uint64_t saved, uint32_t px, uint32_t py, uint64_t seed, uint32_t zs) {
+    Rng r;
+    if (zs) {
+        r.state = saved >> 32;
+        r.inc = (saved << 32) | (py << 16) | (px & 0xffffu);
+        r.zs = zs;
+        r.seed = seed;
+        return r;
+    }
+    r.state = saved;
+    r.inc = (independent_sequence((int)px, (int)py, seed) << 1u) | 1u;
+    return r;
+}
+SHM_HD Float rng_get_1d(Rng& r) { return (Float)(rng_next_u32(r) >> 8) * 5.9604644775390625e-8f; }  // the independent sampler's float
 SHM_HD Float sampler_get_1d(Rng& r) {
 #ifdef SHM_ORACLE_REFERENCE_STREAM
     if (r.ref) return ref_stream_next_f32(*r.ref);
 #endif
-    return (Float)(rng_next_u32(r) >> 8) * 5.9604644775390625e-8f;
+    if (r.zs) return zsobol_float(zsobol_next_1d_bits(r));
+    return rng_get_1d(r);
 }
 SHM_HD V2 sampler_get_2d(Rng& r) {  // sampler.rs:127-131: x drawn first
+    if (r.zs) {
+        uint32_t x, y;
+        zsobol_next_2d_bits(r, x, y);
+        return v2(zsobol_float(x), zsobol_float(y));
+    }
     Float x = sampler_get_1d(r);
     Float y = sampler_get_1d(r);
     return v2(x, y);

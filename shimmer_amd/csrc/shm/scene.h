@@ -104,6 +104,7 @@ struct SceneView {
     const struct ImageLightRec* image_lights;
     const Float* dist_data;
     uint32_t quirks_off;  // ShmRenderParams::disable_reference_quirks of the render in flight (0 = reference-exact; set per render call)
+    uint32_t zsobol;      // zsobol_config() of the render in flight when ShmRenderParams::sampler is SHM_SAMPLER_ZSOBOL (set per render call; shm/sampling.h)
     // device only: the workgroup's copy of this object in LDS, which the texture evaluators that are real calls read the scene through (shm/texture.h,
     // SHM_SV_FOR_CALL; set by stage_scene_tables_tex in the kernels that evaluate textures, never read on the host)
     const SceneView* call_copy;

@@ -80,7 +80,7 @@ struct QueueState {
 struct alignas(64) PathRec {
     // first 32-byte sector: what k_generate writes (all of it, so that a new path costs one full sector, not two partial ones) and bounce 0 reads
     float4 lambda;     // (the film reads its own copy, PathArrays::lambda)
-    uint2 rng;         // PCG32 state (inc is re-derived from pixel + seed)
+    uint2 rng;         // sampler state (sampler_load / sampler_store below: the rest is re-derived from pixel + seed)
     uint32_t pixel;    // x | y << 16 (absolute pixel coordinates, < 65536)
     uint32_t flags;    // depth | specular_bounce << 8 | any_non_specular << 9 | ray has auxiliary rays << 10
     // second sector: written by the first vertex (a new path's constants — beta = 1, p_b = eta_scale = 1 — are not stored where the consumer knows them: k_generate<LEAN>)
@@ -89,6 +89,26 @@ struct alignas(64) PathRec {
     uint32_t pad[2];
 };
 static_assert(sizeof(PathRec) == 64, "PathRec is one half cache line");
+// K_ZSOBOL (a translation unit's switch, like K_ENV_LIGHT): the Makefile compiles every unit whose kernels draw twice, the second time with K_ZSOBOL
+// true into *_zs objects whose kernels and launchers carry a _zs suffix (below, k_shade.inl, k_scatter.inl, k_scatter_layered.inl, k_shade_other.hip).
+// The host picks the set from ShmRenderParams::sampler (render.hip), so the sampler is a compile-time constant of every kernel: with the independent
+// sampler the ZSobol code folds away and the kernels are those of a build without it (tools/kernel_resources.py).
+#ifndef K_ZSOBOL
+#define K_ZSOBOL false
+#endif
+// The sampler state a path carries between kernels (PathRec::rng / PathArrays::rng0: the PCG32 state, or ZSobol's sample index and dimension; shm/sampling.h):
+// the one load and the one store of every kernel that draws.
+template <bool ZS = K_ZSOBOL>
+__device__ __forceinline__ uint32_t sampler_word(const SceneView& sv) {
+    return ZS ? sv.zsobol : 0u;
+}
+__device__ __forceinline__ Rng sampler_load(uint2 rs, uint32_t pix, const SceneView& sv, const ShmRenderParams& params) {
+    return sampler_resume((uint64_t)rs.x | ((uint64_t)rs.y << 32), pix & 0xffffu, pix >> 16, params.seed, sampler_word(sv));
+}
+__device__ __forceinline__ uint2 sampler_store(const Rng& r) {
+    const uint64_t w = sampler_save(r);
+    return make_uint2((uint32_t)w, (uint32_t)(w >> 32));
+}
 // Staged shading's parameter block — what get_bsdf left at a vertex, written by k_vertex and read by the scatter kernel of the vertex's BxDF class (the layered one
 // reads it in each of its stages) — as one 128-byte record, ordered so that a class reads whole 32-byte sectors: {bx0, bx2 | fr, bx1} for diffuse / conductor /
 // dielectric, + {bx3, bx4} for the coated ones, + {siwo} in scenes with quadrics, patches or instances. Six separate arrays before (PathRec, above, for the why).
@@ -423,3 +443,66 @@ WF_INTERNAL int wf_launch_scatter_layered_staged_tex(ShmScene* s, const ShadeArg
 WF_INTERNAL int wf_launch_shade_simple(ShmScene* s, const ShadeArgs& a);
 WF_INTERNAL int wf_launch_shade_randomwalk(ShmScene* s, const ShadeArgs& a, uint32_t cap_eff);
 WF_INTERNAL int wf_launch_fold_randomwalk(ShmScene* s, hipStream_t stream, uint32_t cap_eff, uint32_t total);
+// ... and their twins in the *_zs objects (K_ZSOBOL): the same kernels drawing from ZSobol
+WF_INTERNAL int wf_launch_shade_lean_zs(ShmScene* s, const ShadeArgs& a);
+WF_INTERNAL int wf_launch_shade_lean_diverted_zs(ShmScene* s, const ShadeArgs& a);
+WF_INTERNAL int wf_launch_shade_lean_gen_zs(ShmScene* s, const ShadeArgs& a);
+WF_INTERNAL int wf_launch_shade_lean_gen_diverted_zs(ShmScene* s, const ShadeArgs& a);
+WF_INTERNAL int wf_launch_shade_lean_env_zs(ShmScene* s, const ShadeArgs& a);
+WF_INTERNAL int wf_launch_shade_lean_gen_env_zs(ShmScene* s, const ShadeArgs& a);
+WF_INTERNAL int wf_launch_scatter_diffuse_env_zs(ShmScene* s, const ShadeArgs& a, bool tri_only);
+WF_INTERNAL int wf_launch_scatter_conductor_env_zs(ShmScene* s, const ShadeArgs& a, bool tri_only);
+WF_INTERNAL int wf_launch_scatter_dielectric_env_zs(ShmScene* s, const ShadeArgs& a, bool tri_only);
+WF_INTERNAL int wf_launch_scatter_layered_staged_tri_env_zs(ShmScene* s, const ShadeArgs& a);
+WF_INTERNAL int wf_launch_scatter_layered_staged_gen_env_zs(ShmScene* s, const ShadeArgs& a);
+WF_INTERNAL int wf_launch_shade_lean_env_diverted_zs(ShmScene* s, const ShadeArgs& a);
+WF_INTERNAL int wf_launch_shade_lean_gen_env_diverted_zs(ShmScene* s, const ShadeArgs& a);
+WF_INTERNAL int wf_launch_shade_tail_sorted_env_zs(ShmScene* s, const ShadeArgs& a);
+WF_INTERNAL int wf_launch_shade_fused_gen_env_zs(ShmScene* s, const ShadeArgs& a);
+WF_INTERNAL int wf_launch_shade_fused_gen_zs(ShmScene* s, const ShadeArgs& a);
+WF_INTERNAL int wf_launch_shade_fused_gen_tex_zs(ShmScene* s, const ShadeArgs& a);
+WF_INTERNAL int wf_launch_shade_fused_tex_zs(ShmScene* s, const ShadeArgs& a);
+WF_INTERNAL int wf_launch_shade_tail_sorted_zs(ShmScene* s, const ShadeArgs& a);
+WF_INTERNAL int wf_launch_scatter_diffuse_zs(ShmScene* s, const ShadeArgs& a, bool tri_only, bool has_tex);
+WF_INTERNAL int wf_launch_scatter_conductor_zs(ShmScene* s, const ShadeArgs& a, bool tri_only, bool has_tex);
+WF_INTERNAL int wf_launch_scatter_dielectric_zs(ShmScene* s, const ShadeArgs& a, bool tri_only, bool has_tex);
+WF_INTERNAL int wf_launch_scatter_layered_tri_zs(ShmScene* s, const ShadeArgs& a);
+WF_INTERNAL int wf_launch_scatter_layered_gen_zs(ShmScene* s, const ShadeArgs& a);
+WF_INTERNAL int wf_launch_scatter_layered_tex_zs(ShmScene* s, const ShadeArgs& a);
+WF_INTERNAL int wf_launch_scatter_layered_staged_tri_zs(ShmScene* s, const ShadeArgs& a);
+WF_INTERNAL int wf_launch_scatter_layered_staged_gen_zs(ShmScene* s, const ShadeArgs& a);
+WF_INTERNAL int wf_launch_scatter_layered_staged_tex_zs(ShmScene* s, const ShadeArgs& a);
+WF_INTERNAL int wf_launch_shade_simple_zs(ShmScene* s, const ShadeArgs& a);
+WF_INTERNAL int wf_launch_shade_randomwalk_zs(ShmScene* s, const ShadeArgs& a, uint32_t cap_eff);
+#if K_ZSOBOL
+#define wf_launch_shade_lean wf_launch_shade_lean_zs
+#define wf_launch_shade_lean_diverted wf_launch_shade_lean_diverted_zs
+#define wf_launch_shade_lean_gen wf_launch_shade_lean_gen_zs
+#define wf_launch_shade_lean_gen_diverted wf_launch_shade_lean_gen_diverted_zs
+#define wf_launch_shade_lean_env wf_launch_shade_lean_env_zs
+#define wf_launch_shade_lean_gen_env wf_launch_shade_lean_gen_env_zs
+#define wf_launch_scatter_diffuse_env wf_launch_scatter_diffuse_env_zs
+#define wf_launch_scatter_conductor_env wf_launch_scatter_conductor_env_zs
+#define wf_launch_scatter_dielectric_env wf_launch_scatter_dielectric_env_zs
+#define wf_launch_scatter_layered_staged_tri_env wf_launch_scatter_layered_staged_tri_env_zs
+#define wf_launch_scatter_layered_staged_gen_env wf_launch_scatter_layered_staged_gen_env_zs
+#define wf_launch_shade_lean_env_diverted wf_launch_shade_lean_env_diverted_zs
+#define wf_launch_shade_lean_gen_env_diverted wf_launch_shade_lean_gen_env_diverted_zs
+#define wf_launch_shade_tail_sorted_env wf_launch_shade_tail_sorted_env_zs
+#define wf_launch_shade_fused_gen_env wf_launch_shade_fused_gen_env_zs
+#define wf_launch_shade_fused_gen wf_launch_shade_fused_gen_zs
+#define wf_launch_shade_fused_gen_tex wf_launch_shade_fused_gen_tex_zs
+#define wf_launch_shade_fused_tex wf_launch_shade_fused_tex_zs
+#define wf_launch_shade_tail_sorted wf_launch_shade_tail_sorted_zs
+#define wf_launch_scatter_diffuse wf_launch_scatter_diffuse_zs
+#define wf_launch_scatter_conductor wf_launch_scatter_conductor_zs
+#define wf_launch_scatter_dielectric wf_launch_scatter_dielectric_zs
+#define wf_launch_scatter_layered_tri wf_launch_scatter_layered_tri_zs
+#define wf_launch_scatter_layered_gen wf_launch_scatter_layered_gen_zs
+#define wf_launch_scatter_layered_tex wf_launch_scatter_layered_tex_zs
+#define wf_launch_scatter_layered_staged_tri wf_launch_scatter_layered_staged_tri_zs
+#define wf_launch_scatter_layered_staged_gen wf_launch_scatter_layered_staged_gen_zs
+#define wf_launch_scatter_layered_staged_tex wf_launch_scatter_layered_staged_tex_zs
+#define wf_launch_shade_simple wf_launch_shade_simple_zs
+#define wf_launch_shade_randomwalk wf_launch_shade_randomwalk_zs
+#endif

@@ -16,8 +16,12 @@ FILM_DTYPE = np.dtype([("rgb_sum", "<f8", (3,)), ("weight_sum", "<f8")])
 
 
 def make_params(seed=0, spp=4, max_depth=5, regularize=False, disable_pixel_jitter=False, disable_wavelength_jitter=False,
-                integrator="path", sample_lights=True, sample_bsdf=True, force_diffuse=False, disable_texture_filtering=False, reference_quirks=True):
+                integrator="path", sample_lights=True, sample_bsdf=True, force_diffuse=False, disable_texture_filtering=False, reference_quirks=True,
+                sampler="independent", randomization="fastowen"):
+    """sampler: "independent" (the default) or "zsobol"; randomization ("fastowen" or "none") applies to "zsobol" only."""
     p = abi.ShmRenderParams()
+    p.sampler = {"independent": abi.SHM_SAMPLER_INDEPENDENT, "zsobol": abi.SHM_SAMPLER_ZSOBOL}[sampler]
+    p.sampler_randomization = {"fastowen": abi.SHM_SAMPLER_FASTOWEN, "none": abi.SHM_SAMPLER_RANDOMIZE_NONE}[randomization]
     p.integrator = {"path": abi.SHM_INTEGRATOR_PATH, "simplepath": abi.SHM_INTEGRATOR_SIMPLE_PATH,
                     "randomwalk": abi.SHM_INTEGRATOR_RANDOM_WALK}[integrator]
     p.sample_lights, p.sample_bsdf = int(sample_lights), int(sample_bsdf)
