@@ -408,10 +408,3 @@ __global__ void __launch_bounds__(SHADE2_BLOCK) K_SHADE_ATTR k_scatter_nonspecul
                            s->d_q_active[a.cur ^ 1], s->d_q_shadow, s->d_qs, a.cur, a.params, a.shadow_parity, s->lds_tables);                                \
         LAUNCH_TRY(#KERNEL);                                                                                                                    \
     } while (0)
-// the three scene classes every BxDF class is instantiated for
-#define WF_SCATTER_DISPATCH(CLASS)                                                  \
-    do {                                                                            \
-        if (has_tex) WF_SCATTER_LAUNCH(CLASS, false, true);                         \
-        else if (tri_only) WF_SCATTER_LAUNCH(CLASS, true, false);                   \
-        else WF_SCATTER_LAUNCH(CLASS, false, false);                                \
-    } while (0)

@@ -3,7 +3,8 @@
 #define K_ENV_LIGHT true
 #include "k_scatter.inl"
 
-int wf_launch_scatter_dielectric_env(ShmScene* s, const ShadeArgs& a, bool tri_only) {
+// (one body for both launchers, as in k_scatter_dielectric.hip)
+static int launch_dielectric(ShmScene* s, const ShadeArgs& a, bool tri_only) {
     if (a.params.regularize != 0) {
         if (tri_only) WF_SCATTER_LAUNCH(CLASS_DIELECTRIC, true, false);
         else WF_SCATTER_LAUNCH(CLASS_DIELECTRIC, false, false);
@@ -18,3 +19,5 @@ int wf_launch_scatter_dielectric_env(ShmScene* s, const ShadeArgs& a, bool tri_o
     }
     return SHM_OK;
 }
+template <> int wf_launch_scatter_dielectric_tri_env<K_ZSOBOL>(ShmScene* s, const ShadeArgs& a) { return launch_dielectric(s, a, true); }
+template <> int wf_launch_scatter_dielectric_gen_env<K_ZSOBOL>(ShmScene* s, const ShadeArgs& a) { return launch_dielectric(s, a, false); }

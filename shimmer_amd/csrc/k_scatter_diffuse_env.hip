@@ -2,8 +2,5 @@
 #define K_ENV_LIGHT true
 #include "k_scatter.inl"
 
-int wf_launch_scatter_diffuse_env(ShmScene* s, const ShadeArgs& a, bool tri_only) {
-    if (tri_only) WF_SCATTER_LAUNCH(CLASS_DIFFUSE, true, false);
-    else WF_SCATTER_LAUNCH(CLASS_DIFFUSE, false, false);
-    return SHM_OK;
-}
+template <> int wf_launch_scatter_diffuse_tri_env<K_ZSOBOL>(ShmScene* s, const ShadeArgs& a) { WF_SCATTER_LAUNCH(CLASS_DIFFUSE, true, false); return SHM_OK; }
+template <> int wf_launch_scatter_diffuse_gen_env<K_ZSOBOL>(ShmScene* s, const ShadeArgs& a) { WF_SCATTER_LAUNCH(CLASS_DIFFUSE, false, false); return SHM_OK; }

@@ -285,15 +285,15 @@ __global__ void __launch_bounds__(SHADE_BLOCK) k_fold_randomwalk(PathArrays pa, 
 #endif
 }  // namespace
 
-int wf_launch_shade_simple(ShmScene* s, const ShadeArgs& a) {
+template <> int wf_launch_shade_simple<K_ZSOBOL>(ShmScene* s, const ShadeArgs& a) {
     hipLaunchKernelGGL(k_shade_simple, dim3(a.blocks), dim3(SHADE2_BLOCK), 0, a.stream, s->dsv, s->pa, s->d_q_active[a.cur], s->d_q_active[a.cur ^ 1],
                        s->d_q_shadow, s->d_qs, a.cur, a.params, a.shadow_parity);
     LAUNCH_TRY("k_shade_simple");
     return SHM_OK;
 }
-int wf_launch_shade_randomwalk(ShmScene* s, const ShadeArgs& a, uint32_t cap_eff) {
+template <> int wf_launch_shade_randomwalk<K_ZSOBOL>(ShmScene* s, const ShadeArgs& a) {
     hipLaunchKernelGGL(k_shade_randomwalk, dim3(a.blocks), dim3(SHADE2_BLOCK), 0, a.stream, s->dsv, s->pa, s->d_q_active[a.cur], s->d_q_active[a.cur ^ 1],
-                       s->d_qs, a.cur, a.params, s->d_rw, cap_eff);
+                       s->d_qs, a.cur, a.params, s->d_rw, a.cap_eff);
     LAUNCH_TRY("k_shade_randomwalk");
     return SHM_OK;
 }

@@ -782,28 +782,27 @@ int wf_trace_prepare(ShmScene* s) {
     return SHM_OK;
 }
 
-int wf_launch_trace(ShmScene* s, bool any, hipStream_t stream, const uint32_t* queue, const uint32_t* n_ptr, uint32_t n_direct, const ShmRay* rays,
-                    ShmHit* hits, uint8_t* occluded, float4* L, const float4* contrib, int hit16) {
+int wf_launch_trace(ShmScene* s, bool any, const TraceArgs& t) {
     uint32_t* heads = s->d_heads3 + (any ? 8 * 32 : 0);
     uint32_t* spill = any ? s->d_spill3_any : s->d_spill3;
-    hipLaunchKernelGGL(k_reset_heads3, dim3(1), dim3(64), 0, stream, heads);
+    hipLaunchKernelGGL(k_reset_heads3, dim3(1), dim3(64), 0, t.stream, heads);
     const int leaf_min = any ? s->leaf_min_any : s->leaf_min;
     const bool tri_only = !s->flat.has_spheres;
     // hit16 with the GEN kernels: the split record form (wavefront.h, load_hit_tri) — the second records follow the `capacity` first ones in the hit allocation
-    float4* const hit2 = (hit16 && !tri_only && hits) ? reinterpret_cast<float4*>(hits) + s->capacity : nullptr;
-#define TRACE5_LAUNCH(ANY, ...)                                                                                                               \
-    hipLaunchKernelGGL((k_trace5<ANY, __VA_ARGS__>), dim3(s->trace3_blocks[ANY]), dim3(TRACE_BLOCK), 0, stream, s->dsv, queue, n_ptr, n_direct, heads, rays,  \
-                       hits, occluded, L, contrib, s->d_counters, spill, s->spill3_levels[ANY], (ANY ? s->refill_min_any : s->refill_min), leaf_min, s->queue_parts, s->trace_rays_per_lane, hit16, s->d_big_leaf_n, \
-                       s->d_gen_save[ANY ? 1 : 0], (ANY ? s->other_min_any : s->other_min), hit2)
-    if (any && s->flat.has_instances && s->dsv.quirks_off) {  // (the PBRT-v4 form of the shadow ray's way into an instance: its own instantiations)
-        if (s->gen_heavy) hipLaunchKernelGGL((k_trace5_any_strict<true>), dim3(s->trace3_blocks[1]), dim3(TRACE_BLOCK), 0, stream, s->dsv, queue, n_ptr, n_direct, heads, rays, hits, occluded, L, contrib,
-                                             s->d_counters, spill, s->spill3_levels[1], s->refill_min_any, leaf_min, s->queue_parts, s->trace_rays_per_lane, hit16, s->d_big_leaf_n, s->d_gen_save[1], s->other_min_any, hit2);
-        else hipLaunchKernelGGL((k_trace5_any_strict<false>), dim3(s->trace3_blocks[1]), dim3(TRACE_BLOCK), 0, stream, s->dsv, queue, n_ptr, n_direct, heads, rays, hits, occluded, L, contrib,
-                                s->d_counters, spill, s->spill3_levels[1], s->refill_min_any, leaf_min, s->queue_parts, s->trace_rays_per_lane, hit16, s->d_big_leaf_n, s->d_gen_save[1], s->other_min_any, hit2);
+    float4* const hit2 = (t.hit16 && !tri_only && t.hits) ? reinterpret_cast<float4*>(t.hits) + s->capacity : nullptr;
+#define TRACE5_KERNEL_ARGS(ANY)                                                                                                                          \
+    s->dsv, t.queue, t.n_ptr, t.n_direct, heads, t.rays, t.hits, t.occluded, t.L, t.contrib, s->d_counters, spill, s->spill3_levels[ANY],                 \
+        (ANY ? s->refill_min_any : s->refill_min), leaf_min, s->queue_parts, s->trace_rays_per_lane, t.hit16, s->d_big_leaf_n, s->d_gen_save[ANY ? 1 : 0], \
+        (ANY ? s->other_min_any : s->other_min), hit2
+#define TRACE5_LAUNCH(ANY, ...) hipLaunchKernelGGL((k_trace5<ANY, __VA_ARGS__>), dim3(s->trace3_blocks[ANY]), dim3(TRACE_BLOCK), 0, t.stream, TRACE5_KERNEL_ARGS(ANY))
+    if (any && s->flat.has_instances && t.strict) {  // (the PBRT-v4 form of the shadow ray's way into an instance: its own instantiations)
+        if (s->gen_heavy) hipLaunchKernelGGL((k_trace5_any_strict<true>), dim3(s->trace3_blocks[1]), dim3(TRACE_BLOCK), 0, t.stream, TRACE5_KERNEL_ARGS(1));
+        else hipLaunchKernelGGL((k_trace5_any_strict<false>), dim3(s->trace3_blocks[1]), dim3(TRACE_BLOCK), 0, t.stream, TRACE5_KERNEL_ARGS(1));
     }
     else if (tri_only) { if (any) TRACE5_LAUNCH(true, false); else TRACE5_LAUNCH(false, false); }
     else if (s->gen_heavy) { if (any) TRACE5_LAUNCH(true, true, true); else TRACE5_LAUNCH(false, true, true); }
     else { if (any) TRACE5_LAUNCH(true, true); else TRACE5_LAUNCH(false, true); }
+#undef TRACE5_KERNEL_ARGS
 #undef TRACE5_LAUNCH
     LAUNCH_TRY(any ? "k_trace<any>" : "k_trace<closest>");
     return SHM_OK;

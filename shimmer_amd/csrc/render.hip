@@ -264,6 +264,61 @@ static bool use_staged(const ShmScene* s, const ShmRenderParams* params) {
     // (the lean class through the staged pipeline, measured: shade + generate + film 130 -> 165 ms per headline frame)
     return !scene_is_lean(s) || params->force_diffuse != 0;
 }
+// Which kernels a scene runs: one cell per geometry x image class x sampler
+enum : int { GEO_TRI, GEO_GEN, N_GEO };            // top-level triangles only / spheres, bilinear patches or instances too
+enum : int { IMG_NONE, IMG_TEX, IMG_ENV, N_IMG };  // no image / image textures (ray differentials, MIP filtering) / an ImageInfinitelight alone (the K_ENV_LIGHT units)
+template <bool ZS>
+constexpr ShadeKernels shade_cells[N_GEO][N_IMG] = {
+    {{.generate = {k_generate<false, false, ZS>, k_generate<false, true, ZS>}, .lean = wf_launch_shade_lean<ZS>, .lean_diverted = wf_launch_shade_lean_diverted<ZS>,
+      .fused_all = wf_launch_shade_tail_sorted<ZS>, .vertex = wf_launch_vertex_tri,
+      .scatter = {wf_launch_scatter_diffuse_tri<ZS>, wf_launch_scatter_conductor_tri<ZS>, wf_launch_scatter_dielectric_tri<ZS>, wf_launch_scatter_layered_staged_tri<ZS>},
+      .scatter_layered_onepass = wf_launch_scatter_layered_tri<ZS>, .simple = wf_launch_shade_simple<ZS>, .randomwalk = wf_launch_shade_randomwalk<ZS>},
+     {.generate = {k_generate<true, false, ZS>, nullptr}, .lean = nullptr, .lean_diverted = nullptr,
+      .fused_all = wf_launch_shade_fused_tex<ZS>, .vertex = wf_launch_vertex_tex,
+      .scatter = {wf_launch_scatter_diffuse_tex<ZS>, wf_launch_scatter_conductor_tex<ZS>, wf_launch_scatter_dielectric_tex<ZS>, wf_launch_scatter_layered_staged_tex<ZS>},
+      .scatter_layered_onepass = wf_launch_scatter_layered_tex<ZS>, .simple = wf_launch_shade_simple<ZS>, .randomwalk = wf_launch_shade_randomwalk<ZS>},
+     {.generate = {k_generate<false, false, ZS>, k_generate<false, true, ZS>}, .lean = wf_launch_shade_lean_env<ZS>, .lean_diverted = wf_launch_shade_lean_env_diverted<ZS>,
+      .fused_all = wf_launch_shade_tail_sorted_env<ZS>, .vertex = wf_launch_vertex_tri_env,
+      .scatter = {wf_launch_scatter_diffuse_tri_env<ZS>, wf_launch_scatter_conductor_tri_env<ZS>, wf_launch_scatter_dielectric_tri_env<ZS>, wf_launch_scatter_layered_staged_tri_env<ZS>},
+      .scatter_layered_onepass = wf_launch_scatter_layered_tri<ZS>,  // (no K_ENV_LIGHT build: never reached, select_kernels)
+      .simple = wf_launch_shade_simple<ZS>, .randomwalk = wf_launch_shade_randomwalk<ZS>}},
+    {{.generate = {k_generate<false, false, ZS>, k_generate<false, true, ZS>}, .lean = wf_launch_shade_lean_gen<ZS>, .lean_diverted = wf_launch_shade_lean_gen_diverted<ZS>,
+      .fused_all = wf_launch_shade_fused_gen<ZS>, .vertex = wf_launch_vertex_gen,
+      .scatter = {wf_launch_scatter_diffuse_gen<ZS>, wf_launch_scatter_conductor_gen<ZS>, wf_launch_scatter_dielectric_gen<ZS>, wf_launch_scatter_layered_staged_gen<ZS>},
+      .scatter_layered_onepass = wf_launch_scatter_layered_gen<ZS>, .simple = wf_launch_shade_simple<ZS>, .randomwalk = wf_launch_shade_randomwalk<ZS>},
+     {.generate = {k_generate<true, false, ZS>, nullptr}, .lean = nullptr, .lean_diverted = nullptr,
+      .fused_all = wf_launch_shade_fused_gen_tex<ZS>, .vertex = wf_launch_vertex_tex,
+      .scatter = {wf_launch_scatter_diffuse_tex<ZS>, wf_launch_scatter_conductor_tex<ZS>, wf_launch_scatter_dielectric_tex<ZS>, wf_launch_scatter_layered_staged_tex<ZS>},
+      .scatter_layered_onepass = wf_launch_scatter_layered_tex<ZS>, .simple = wf_launch_shade_simple<ZS>, .randomwalk = wf_launch_shade_randomwalk<ZS>},
+     {.generate = {k_generate<false, false, ZS>, k_generate<false, true, ZS>}, .lean = wf_launch_shade_lean_gen_env<ZS>, .lean_diverted = wf_launch_shade_lean_gen_env_diverted<ZS>,
+      .fused_all = wf_launch_shade_fused_gen_env<ZS>, .vertex = wf_launch_vertex_gen_env,
+      .scatter = {wf_launch_scatter_diffuse_gen_env<ZS>, wf_launch_scatter_conductor_gen_env<ZS>, wf_launch_scatter_dielectric_gen_env<ZS>, wf_launch_scatter_layered_staged_gen_env<ZS>},
+      .scatter_layered_onepass = wf_launch_scatter_layered_gen<ZS>,  // (as above)
+      .simple = wf_launch_shade_simple<ZS>, .randomwalk = wf_launch_shade_randomwalk<ZS>}},
+};
+// A render's kernels, once per call: the only code that reads the scene's classes and the render's options to choose a variant (WHETHER a kernel runs is the bounce loop's)
+static ShadeKernels select_kernels(const ShmScene* s, const ShmRenderParams* params) {
+    const shm_host::FlatScene& f = s->flat;
+    const ShadeKernels(&cells)[N_GEO][N_IMG] = params->sampler == SHM_SAMPLER_ZSOBOL ? shade_cells<true> : shade_cells<false>;
+    const int geo = f.has_spheres ? GEO_GEN : GEO_TRI;
+    // The staged and the all-materials fused kernels: env where the only image is an environment map and options.force_diffuse is off, tex where the scene has
+    // textures, none otherwise — under force_diffuse an env-only scene runs the textured units (the differentials are dead values there: no material binds a texture).
+    const int img = (env_plain_scene(s) && params->force_diffuse == 0) ? IMG_ENV : (f.has_textures ? IMG_TEX : IMG_NONE);
+    ShadeKernels k = cells[geo][img];
+    // The lean kernels, direct or diverted: env exactly where the scene has an image light — also in a textured scene behind the split pass, whose k_vertex runs the
+    // textured class (the lean kernel takes the hits on plain DiffuseMaterials, and nothing filters a texture there).
+    const int img_lean = f.has_image_light ? IMG_ENV : IMG_NONE;
+    k.lean = cells[geo][img_lean].lean;
+    k.lean_diverted = cells[geo][img_lean].lean_diverted;
+    // (k_generate writes the camera rays' auxiliary rays where the workspace holds them: tex_ws — under force_diffuse an env-only scene has none)
+    const int img_generate = tex_ws(s) ? IMG_TEX : IMG_NONE;
+    k.generate[0] = cells[geo][img_generate].generate[0];
+    k.generate[1] = cells[geo][img_generate].generate[1];
+    // the LayeredBxDF class in one pass per vertex under options.force_diffuse, which replaces the BxDF inside this half (the one-pass kernel has that code), and past
+    // 2^30 paths of workspace (the staged kernel's jobs carry two flag bits above the path index), which ensure_workspace never grants: never with env
+    if (params->force_diffuse != 0 || s->capacity >= (1u << 30)) k.scatter[CLASS_LAYERED] = k.scatter_layered_onepass;
+    return k;
+}
 static uint64_t staging_bytes_per_path(const ShmScene* s) {
     const shm_host::FlatScene& f = s->flat;
     uint64_t b = 128;  // the parameter block, one BxRec per path
@@ -708,9 +763,6 @@ int shm_render_wave(ShmScene* s, const ShmRenderParams* params, const ShmTile* t
     const int n_samples = sample_end - sample_begin;
     s->dsv.quirks_off = params->disable_reference_quirks ? 1u : 0u;  // SHM_REFERENCE_QUIRKS: every kernel of this render takes s->dsv by value
     s->dsv.zsobol = zsobol;  // (read only by the ZSobol kernels: sampler_word)
-    // the sampler is a compile-time constant of the kernels: ZSobol renders launch the *_zs objects' twins (wavefront.h, K_ZSOBOL)
-    const bool zs = params->sampler == SHM_SAMPLER_ZSOBOL;
-#define WF_ZS(launcher) (zs ? launcher##_zs : launcher)
     const bool random_walk = params->integrator == SHM_INTEGRATOR_RANDOM_WALK;
     // (the random walk keeps 32 B per depth per path beside the path state: its batches are capped at 16 Mi paths)
     const bool staged = use_staged(s, params);
@@ -733,6 +785,9 @@ int shm_render_wave(ShmScene* s, const ShmRenderParams* params, const ShmTile* t
             s->rw_floats4 = need;
         }
     }
+    const ShadeKernels k = select_kernels(s, params);
+    // the fused kernel's own scene class under the path integrator: bounce 0 runs on known constants (k_generate<., LEAN>, ShadeArgs::first_bounce)
+    const bool lean_first = (!staged || (first_bounce_candidate(s) && params->force_diffuse == 0)) && !random_walk && params->integrator != SHM_INTEGRATOR_SIMPLE_PATH && !s->pa.aux0 && s->pa.rng0;
     uint32_t pix_per_batch = cap_eff / (uint32_t)n_samples;
     if (pix_per_batch == 0) { g_err = "spp-wave larger than the path workspace"; return SHM_ERR_INVALID_ARGUMENT; }
     if (pix_per_batch > 64) pix_per_batch &= ~63u;  // whole 8x8 tiles per wavefront
@@ -746,8 +801,6 @@ int shm_render_wave(ShmScene* s, const ShmRenderParams* params, const ShmTile* t
         uint32_t n_pix = (uint32_t)std::min<uint64_t>(pix_per_batch, n_pixels - p0);
         uint32_t total = n_pix * (uint32_t)n_samples;
         const uint32_t* pixels = s->d_pixels + p0;
-        // the fused kernel's own scene class under the path integrator: bounce 0 runs on known constants (k_generate<., LEAN>, ShadeArgs::first_bounce)
-        const bool lean_first = (!staged || (first_bounce_candidate(s) && params->force_diffuse == 0)) && !random_walk && params->integrator != SHM_INTEGRATOR_SIMPLE_PATH && !s->pa.aux0 && s->pa.rng0;
         // triangle scenes without textures under the path integrator: every kernel that reads the render's hit array is a TRI_ONLY one, and none reads a triangle hit's t —
         // the closest-hit launches write {primitive, b0, b1, b2}, 16 bytes per path instead of the 32-byte ShmHit
         // (round 5: in scenes with textures too — their kernels, compiled for general geometry, read either record form: load_hit_tri)
@@ -755,12 +808,8 @@ int shm_render_wave(ShmScene* s, const ShmRenderParams* params, const ShmTile* t
         //  (HIT_HAS_SECOND, wavefront.h). Not with instances: a hit inside one names it in the 32-byte record, patched when the instance's marker is popped)
         s->pa.hit16 = ((!s->flat.has_spheres || !s->flat.has_instances) && params->integrator == SHM_INTEGRATOR_PATH && !random_walk) ? 1u : 0u;
         s->pa.hit2 = (s->pa.hit16 && s->flat.has_spheres) ? reinterpret_cast<const float4*>(s->pa.hit) + s->capacity : nullptr;
-        {
-            auto* gen = s->pa.aux0 ? (zs ? k_generate<true, false, true> : k_generate<true>)
-                                   : (lean_first ? (zs ? k_generate<false, true, true> : k_generate<false, true>) : (zs ? k_generate<false, false, true> : k_generate<false>));
-            hipLaunchKernelGGL(gen, dim3((total + SHADE_BLOCK - 1) / SHADE_BLOCK), dim3(SHADE_BLOCK), 0, s->stream, s->dsv, s->pa, pixels, n_pix,
-                               sample_begin, n_samples, *params, s->d_q_active[0], s->d_qs, s->pix_group);
-        }
+        hipLaunchKernelGGL(k.generate[lean_first ? 1 : 0], dim3((total + SHADE_BLOCK - 1) / SHADE_BLOCK), dim3(SHADE_BLOCK), 0, s->stream, s->dsv, s->pa, pixels, n_pix,
+                           sample_begin, n_samples, *params, s->d_q_active[0], s->d_qs, s->pix_group);
         LAUNCH_TRY("k_generate");
         int cur = 0;
         // Small batches are tail-dominated (the last rays of a persistent traversal launch take ~0.5 ms whatever its size): there
@@ -802,16 +851,17 @@ int shm_render_wave(ShmScene* s, const ShmRenderParams* params, const ShmTile* t
             hipEvent_t a = ev.get(), b = ev.get();
             hipEventRecord(a, s->stream);
             const bool first_lean = lean_first && bounce == 0;  // (the identity queue was not written: K2 takes slot = queue index, k_shade knows the constants)
-            if ((rc = first_lean ? wf_launch_trace(s, false, s->stream, nullptr, nullptr, total, s->pa.ray, s->pa.hit, nullptr, nullptr, nullptr, (int)s->pa.hit16)
-                                 : wf_launch_trace(s, false, s->stream, s->d_q_active[cur], &s->d_qs->n_active[cur], 0, s->pa.ray, s->pa.hit, nullptr, nullptr, nullptr, (int)s->pa.hit16)) != SHM_OK) return rc;
+            TraceArgs closest{.stream = s->stream, .rays = s->pa.ray, .hits = s->pa.hit, .hit16 = (int)s->pa.hit16};
+            if (first_lean) closest.n_direct = total;
+            else { closest.queue = s->d_q_active[cur]; closest.n_ptr = &s->d_qs->n_active[cur]; }
+            if ((rc = wf_launch_trace(s, false, closest)) != SHM_OK) return rc;
             hipEventRecord(b, s->stream);
             ev_closest.push_back({a, b});
             if (overlap && k3_done) hipStreamWaitEvent(s->stream, k3_done, 0);  // shade(b) touches L and refills the shadow buffers
             {
                 hipEvent_t s0 = ev.get(), s1 = ev.get();
                 hipEventRecord(s0, s->stream);
-                const ShadeArgs sa{s->stream, cur, *params, sh, shade_blocks, first_lean ? 1 : 0, hit_kept ? 1 : 0};
-                const bool tri_only = !s->flat.has_spheres;
+                const ShadeArgs sa{s->stream, cur, *params, sh, shade_blocks, first_lean ? 1 : 0, hit_kept ? 1 : 0, cap_eff};
                 int n_classes_present = 0;
                 for (int c = 0; c < N_BXDF_CLASSES; ++c) n_classes_present += s->flat.has_class[c] ? 1 : 0;
                 // a triangle scene with several BxDF classes but without textures or coated materials: ONE fused all-materials launch per bounce instead of the staged
@@ -823,15 +873,10 @@ int shm_render_wave(ShmScene* s, const ShmRenderParams* params, const ShmTile* t
                 const bool fused_tex_ok = !s->split_pass && n_classes_present > 1;
                 const bool fused_all = staged && bounce >= s->tail_fused_bounce && !s->flat.has_class[CLASS_LAYERED] && params->force_diffuse == 0 &&
                                        (!s->flat.has_textures || env_plain_scene(s) || fused_tex_ok);
-                if (fused_all) {
-                    if (env_plain_scene(s)) rc = tri_only ? WF_ZS(wf_launch_shade_tail_sorted_env)(s, sa) : WF_ZS(wf_launch_shade_fused_gen_env)(s, sa);
-                    else rc = tri_only ? (s->flat.has_textures ? WF_ZS(wf_launch_shade_fused_tex)(s, sa) : WF_ZS(wf_launch_shade_tail_sorted)(s, sa))
-                                       : (s->flat.has_textures ? WF_ZS(wf_launch_shade_fused_gen_tex)(s, sa) : WF_ZS(wf_launch_shade_fused_gen)(s, sa));
-                } else if (staged) {
+                if (fused_all) rc = k.fused_all(s, sa);
+                else if (staged) {
                     // hit half (interaction, emission, get_bsdf -> parameter block, class queues), then one scattering kernel per BxDF
                     // class the scene holds, each over its own material-sorted queue
-                    const bool env = env_plain_scene(s) && params->force_diffuse == 0;  // (the K_ENV_LIGHT units: the class without textures + the image light)
-                    const bool has_tex = s->flat.has_textures && !env;
                     const bool split = s->split_pass && s->d_q_split && s->d_q_lean && params->force_diffuse == 0;
                     ShadeArgs va = sa;  // (k_vertex's arguments: its queue is q_split behind the split pass)
                     if (split) {  // plain-diffuse hits -> q_lean (their whole vertex in the lean fused kernel, below), the rest -> q_split for k_vertex
@@ -840,10 +885,10 @@ int shm_render_wave(ShmScene* s, const ShmRenderParams* params, const ShmTile* t
                         va.q_in = s->d_q_split;
                         va.n_in = &s->d_qs->n_split;
                     }
-                    rc = has_tex ? wf_launch_vertex_tex(s, va) : (env ? (tri_only ? wf_launch_vertex_tri_env(s, va) : wf_launch_vertex_gen_env(s, va))
-                                                                      : (tri_only ? wf_launch_vertex_tri(s, va) : wf_launch_vertex_gen(s, va)));
+                    rc = k.vertex(s, va);
                     // the hits k_vertex diverted (plain diffuse materials): their whole vertex in the fused kernel — the first member of the group below
-                    const bool lean_too = s->lean_divert && s->d_q_lean && params->force_diffuse == 0 && (!has_tex || split);
+                    // (the textured k_vertex diverts nothing: in a textured scene lean_divert is the split pass, which fills q_lean)
+                    const bool lean_too = s->lean_divert && s->d_q_lean && params->force_diffuse == 0;
                     // The classes' scatter kernels are independent of each other (own queue each, disjoint paths, wave-aggregated atomics on the
                     // shared next / shadow queues): the first runs on the render stream, the others beside it on their own streams, and the render
                     // stream waits for them — for small batches only (the same threshold as the K3 / K2 overlap above), where the launches are
@@ -858,15 +903,15 @@ int shm_render_wave(ShmScene* s, const ShmRenderParams* params, const ShmTile* t
                     if ((overlap || group_big) && n_cls > 1) { vertex_done = ev.get(); hipEventRecord(vertex_done, s->stream); }  // (before the first class's launch)
                     std::vector<hipEvent_t> side_done;
                     int k_cls = 0;
-                    auto scatter_on = [&](int cls, auto&& launch) {
-                        if (rc != SHM_OK || !(cls < 0 ? lean_too : s->flat.has_class[cls])) return;
+                    auto scatter_on = [&](bool runs, ShadeFn launch) {
+                        if (rc != SHM_OK || !runs) return;
                         ShadeArgs sc = sa;
                         const bool side = k_cls > 0 && vertex_done != nullptr;
                         if (side) {
                             sc.stream = s->stream_cls[k_cls - 1];
                             hipStreamWaitEvent(sc.stream, vertex_done, 0);
                         }
-                        rc = launch(sc);
+                        rc = launch(s, sc);
                         if (side && rc == SHM_OK) {
                             hipEvent_t done = ev.get();
                             hipEventRecord(done, sc.stream);
@@ -874,26 +919,13 @@ int shm_render_wave(ShmScene* s, const ShmRenderParams* params, const ShmTile* t
                         }
                         ++k_cls;
                     };
-                    scatter_on(-1, [&](const ShadeArgs& x) { return s->flat.has_image_light ? (tri_only ? WF_ZS(wf_launch_shade_lean_env_diverted)(s, x) : WF_ZS(wf_launch_shade_lean_gen_env_diverted)(s, x))
-                                                                                              : (tri_only ? WF_ZS(wf_launch_shade_lean_diverted)(s, x) : WF_ZS(wf_launch_shade_lean_gen_diverted)(s, x)); });
-                    scatter_on(CLASS_DIFFUSE, [&](const ShadeArgs& x) { return env ? WF_ZS(wf_launch_scatter_diffuse_env)(s, x, tri_only) : WF_ZS(wf_launch_scatter_diffuse)(s, x, tri_only, has_tex); });
-                    scatter_on(CLASS_CONDUCTOR, [&](const ShadeArgs& x) { return env ? WF_ZS(wf_launch_scatter_conductor_env)(s, x, tri_only) : WF_ZS(wf_launch_scatter_conductor)(s, x, tri_only, has_tex); });
-                    scatter_on(CLASS_DIELECTRIC, [&](const ShadeArgs& x) { return env ? WF_ZS(wf_launch_scatter_dielectric_env)(s, x, tri_only) : WF_ZS(wf_launch_scatter_dielectric)(s, x, tri_only, has_tex); });
-                    scatter_on(CLASS_LAYERED, [&](const ShadeArgs& x) {
-                        // (options.force_diffuse replaces the BxDF inside this half: the one-pass kernel has that code)
-                        if (params->force_diffuse == 0 && s->capacity < (1u << 30)) {  // (its jobs carry two flag bits above the path index)
-                            if (env) return tri_only ? WF_ZS(wf_launch_scatter_layered_staged_tri_env)(s, x) : WF_ZS(wf_launch_scatter_layered_staged_gen_env)(s, x);
-                            return has_tex ? WF_ZS(wf_launch_scatter_layered_staged_tex)(s, x) : (tri_only ? WF_ZS(wf_launch_scatter_layered_staged_tri)(s, x) : WF_ZS(wf_launch_scatter_layered_staged_gen)(s, x));
-                        }
-                        // (`env` implies params->force_diffuse == 0: the one-pass kernel is reached from here only past 2^30 paths of workspace, which ensure_workspace never grants —
-                        //  its K_ENV_LIGHT units left the library in round 6 — and under options.force_diffuse, where the textured class's units run)
-                        return has_tex ? WF_ZS(wf_launch_scatter_layered_tex)(s, x) : (tri_only ? WF_ZS(wf_launch_scatter_layered_tri)(s, x) : WF_ZS(wf_launch_scatter_layered_gen)(s, x)); });
+                    scatter_on(lean_too, k.lean_diverted);
+                    for (int c = 0; c < N_BXDF_CLASSES; ++c) scatter_on(s->flat.has_class[c], k.scatter[c]);
                     for (hipEvent_t e : side_done) hipStreamWaitEvent(s->stream, e, 0);
                 }
-                else if (random_walk) rc = WF_ZS(wf_launch_shade_randomwalk)(s, sa, cap_eff);
-                else if (params->integrator == SHM_INTEGRATOR_SIMPLE_PATH) rc = WF_ZS(wf_launch_shade_simple)(s, sa);
-                else if (env_lean_scene(s)) rc = tri_only ? WF_ZS(wf_launch_shade_lean_env)(s, sa) : WF_ZS(wf_launch_shade_lean_gen_env)(s, sa);
-                else rc = tri_only ? WF_ZS(wf_launch_shade_lean)(s, sa) : WF_ZS(wf_launch_shade_lean_gen)(s, sa);
+                else if (random_walk) rc = k.randomwalk(s, sa);
+                else if (params->integrator == SHM_INTEGRATOR_SIMPLE_PATH) rc = k.simple(s, sa);
+                else rc = k.lean(s, sa);
                 if (rc != SHM_OK) return rc;
                 hipEventRecord(s1, s->stream);
                 ev_shade.push_back({s0, s1});
@@ -906,7 +938,9 @@ int shm_render_wave(ShmScene* s, const ShmRenderParams* params, const ShmTile* t
                     hipStreamWaitEvent(any_stream, shaded, 0);
                 }
                 hipEventRecord(c, any_stream);
-                if ((rc = wf_launch_trace(s, true, any_stream, s->d_q_shadow, &s->d_qs->n_shadow[sh], 0, s->pa.shadow_ray, nullptr, nullptr, s->pa.L, s->pa.shadow_contrib)) != SHM_OK) return rc;
+                const TraceArgs shadow{.stream = any_stream, .queue = s->d_q_shadow, .n_ptr = &s->d_qs->n_shadow[sh], .rays = s->pa.shadow_ray, .L = s->pa.L,
+                                       .contrib = s->pa.shadow_contrib, .strict = params->disable_reference_quirks != 0};
+                if ((rc = wf_launch_trace(s, true, shadow)) != SHM_OK) return rc;
                 hipEventRecord(d, any_stream);
                 ev_any.push_back({c, d});
                 k3_done = d;
@@ -962,7 +996,6 @@ int shm_render_wave(ShmScene* s, const ShmRenderParams* params, const ShmTile* t
     }
     return SHM_OK;
 }
-#undef WF_ZS
 
 int shm_render_device(ShmScene* s, const ShmRenderParams* params, const ShmTile* tiles, uint32_t n_tiles, ShmStats* stats) {
     if (!s || !params) { g_err = "invalid render arguments"; return SHM_ERR_INVALID_ARGUMENT; }
@@ -1025,8 +1058,11 @@ static int trace_device_impl(ShmScene* s, bool any, const void* rays_dev, uint32
     for (int r = 0; r < repeat; ++r) {
         hipEvent_t a = ev.get(), b = ev.get();
         hipEventRecord(a, s->stream);
-        int rc = any ? wf_launch_trace(s, true, s->stream, nullptr, nullptr, n, (const ShmRay*)rays_dev, nullptr, (uint8_t*)out_dev, nullptr, nullptr)
-                     : wf_launch_trace(s, false, s->stream, nullptr, nullptr, n, (const ShmRay*)rays_dev, (ShmHit*)out_dev, nullptr, nullptr, nullptr);
+        // (strict = false: the reference-exact any-hit kernels, whatever the scene's last render used)
+        TraceArgs t{.stream = s->stream, .n_direct = n, .rays = (const ShmRay*)rays_dev};
+        if (any) t.occluded = (uint8_t*)out_dev;
+        else t.hits = (ShmHit*)out_dev;
+        const int rc = wf_launch_trace(s, any, t);
         if (rc != SHM_OK) return rc;
         hipEventRecord(b, s->stream);
         evs.push_back({a, b});

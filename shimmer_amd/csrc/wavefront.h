@@ -90,8 +90,8 @@ struct alignas(64) PathRec {
 };
 static_assert(sizeof(PathRec) == 64, "PathRec is one half cache line");
 // K_ZSOBOL (a translation unit's switch, like K_ENV_LIGHT): the Makefile compiles every unit whose kernels draw twice, the second time with K_ZSOBOL
-// true into *_zs objects whose kernels and launchers carry a _zs suffix (below, k_shade.inl, k_scatter.inl, k_scatter_layered.inl, k_shade_other.hip).
-// The host picks the set from ShmRenderParams::sampler (render.hip), so the sampler is a compile-time constant of every kernel: with the independent
+// true into *_zs objects whose kernels carry a _zs suffix (k_shade.inl, k_scatter.inl, k_scatter_layered.inl, k_shade_other.hip) and whose launchers are the
+// <true> specializations (WF_SAMPLED_LAUNCHER, below). select_kernels (render.hip) picks the set from ShmRenderParams::sampler, so the sampler is a compile-time constant of every kernel: with the independent
 // sampler the ZSobol code folds away and the kernels are those of a build without it (tools/kernel_resources.py).
 #ifndef K_ZSOBOL
 #define K_ZSOBOL false
@@ -335,7 +335,7 @@ struct ShmScene {
     int leaf_min = 16;             // closest-hit: lanes with a pending leaf before the triangle phase runs (SHM_LEAF_MIN)
     int leaf_min_any = 8;          // any-hit (SHM_LEAF_MIN_ANY)
     uint32_t* d_spill3 = nullptr;
-    LdsTables lds_tables = {};        // the small tables the shading kernels stage in LDS within the full budget (render.hip: wf_lds_tables; SHM_LDS_TABLES=0: nothing)
+    LdsTables lds_tables = {};        // the small tables the shading kernels stage in LDS within the full budget (render.hip: wf_lds_tables)
     LdsTables lds_tables_small = {};  // ... within the 1.5 KB the material-sorted triangle vertex kernel has to spare
     uint32_t* d_q_emit = nullptr;      // paths of the current fused-kernel launch that hit an emitter (k_emit_jobs)
     uint32_t* d_big_leaf_n = nullptr;  // n_prims by first primitive slot, only in scenes with a leaf of >= 7 primitives (LINK_COUNT_MAX: the link word holds smaller counts)
@@ -383,13 +383,25 @@ struct EventPool {
 
 // ---- launchers exported by the kernel translation units (hidden visibility: library-internal) ----
 #define WF_INTERNAL __attribute__((visibility("hidden")))
-// k_trace.hip: BvhAggregate::intersect (any = false) / intersect_predicate (any = true) over a queue of path slots
 WF_INTERNAL LdsTables wf_lds_tables(const ShmScene* s, uint32_t budget);  // render.hip: which small tables fit `budget` bytes of LDS
 WF_INTERNAL void wf_trace_census();  // k_trace.hip: prints the per-phase lane census of a -DK5_CENSUS development build (a no-op otherwise)
 WF_INTERNAL void wf_layered_census();  // k_scatter_layered_staged_tri.hip: the same for a -DLJ_CENSUS build of the staged LayeredBxDF kernel
 WF_INTERNAL int wf_trace_prepare(ShmScene* s);  // grid sizes + stack spill buffers of the two traversal kernels (at scene creation)
-WF_INTERNAL int wf_launch_trace(ShmScene* s, bool any, hipStream_t stream, const uint32_t* queue, const uint32_t* n_ptr, uint32_t n_direct,
-                                const ShmRay* rays, ShmHit* hits, uint8_t* occluded, float4* L, const float4* contrib, int hit16 = 0);
+// k_trace.hip: BvhAggregate::intersect (any = false) / intersect_predicate (any = true) over a queue of path slots, or over slots 0 .. n_direct - 1 without one
+struct TraceArgs {
+    hipStream_t stream;
+    const uint32_t* queue = nullptr;  // the path slots to trace, and their count (on the device)
+    const uint32_t* n_ptr = nullptr;
+    uint32_t n_direct = 0;            // (queue == nullptr: this many rays)
+    const ShmRay* rays = nullptr;
+    ShmHit* hits = nullptr;           // closest hit: the hit records
+    uint8_t* occluded = nullptr;      // any hit: one flag per ray, or
+    float4* L = nullptr;              // ... `contrib` added to L where the ray is unoccluded
+    const float4* contrib = nullptr;
+    int hit16 = 0;                    // the render's compact hit records (PathArrays::hit16)
+    bool strict = false;              // any hit in scenes with instances: PBRT-v4's way into an instance (ShmRenderParams::disable_reference_quirks; k_trace5_any_strict)
+};
+WF_INTERNAL int wf_launch_trace(ShmScene* s, bool any, const TraceArgs& t);
 // shading of one path vertex of PathIntegrator::li for every entry of q_active[cur]
 struct ShadeArgs {
     hipStream_t stream;
@@ -399,110 +411,56 @@ struct ShadeArgs {
     int blocks;
     int first_bounce = 0;  // 1: bounce 0 of a render whose k_generate left the constants out (beta = 1, p_b = eta_scale = 1, flags = 0, the identity queue): the fused kernel knows them
     int hit_kept = 0;      // 1: the hit records are double-buffered by bounce parity (PathArrays::hit_prev is the previous bounce's): the fused kernel leaves nothing for the next vertex
+    uint32_t cap_eff = 0;  // RandomWalk: paths per batch (the stride of ShmScene::d_rw)
     const uint32_t* q_in = nullptr;  // k_vertex: the queue to work through instead of q_active[cur], and its count (the split pass's q_split)
     const uint32_t* n_in = nullptr;
 };
-WF_INTERNAL int wf_launch_shade_lean(ShmScene* s, const ShadeArgs& a);  // the fused kernel: all-diffuse triangle scenes without textures
-WF_INTERNAL int wf_launch_shade_lean_diverted(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_shade_lean_gen(ShmScene* s, const ShadeArgs& a);           // the same kernel with the quadric / patch / instance code: scenes that hold such shapes (k_shade_lean_gen.hip)
-WF_INTERNAL int wf_launch_shade_lean_gen_diverted(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_shade_lean_env(ShmScene* s, const ShadeArgs& a);      // the lean fused kernel with an ImageInfinitelight compiled in (k_shade_lean_env.hip)
-WF_INTERNAL int wf_launch_shade_lean_gen_env(ShmScene* s, const ShadeArgs& a);  // ... for general geometry (k_shade_lean_gen_env.hip)
-// the staged kernels of a scene whose only image is an ImageInfinitelight (K_ENV_LIGHT units: k_vertex_env.hip, k_scatter_*_env.hip, k_scatter_layered*_env.hip)
-WF_INTERNAL int wf_launch_vertex_tri_env(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_vertex_gen_env(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_scatter_diffuse_env(ShmScene* s, const ShadeArgs& a, bool tri_only);
-WF_INTERNAL int wf_launch_scatter_conductor_env(ShmScene* s, const ShadeArgs& a, bool tri_only);
-WF_INTERNAL int wf_launch_scatter_dielectric_env(ShmScene* s, const ShadeArgs& a, bool tri_only);
-WF_INTERNAL int wf_launch_scatter_layered_staged_tri_env(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_scatter_layered_staged_gen_env(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_shade_lean_env_diverted(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_shade_lean_gen_env_diverted(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_shade_tail_sorted_env(ShmScene* s, const ShadeArgs& a);  // the sorted fused all-materials kernel with an ImageInfinitelight compiled in (k_shade_tail_sorted_env.hip)
-WF_INTERNAL int wf_launch_shade_fused_gen_env(ShmScene* s, const ShadeArgs& a);    // ... for general geometry (k_shade_fused_gen_env.hip)
-WF_INTERNAL int wf_launch_shade_fused_gen(ShmScene* s, const ShadeArgs& a);    // ... for scenes with spheres / patches / instances (k_shade_fused_gen.hip)
-WF_INTERNAL int wf_launch_shade_fused_gen_tex(ShmScene* s, const ShadeArgs& a);  // ... and those with textures (k_shade_fused_gen_tex.hip)
-WF_INTERNAL int wf_launch_shade_fused_tex(ShmScene* s, const ShadeArgs& a);    // ... and for triangle scenes with textures, no coated material (k_shade_fused_tex.hip)
-WF_INTERNAL int wf_launch_shade_tail_sorted(ShmScene* s, const ShadeArgs& a);  // ... with material-sorted chunks (k_shade_tail_sorted.hip)
-// (the unsorted tail kernel of rounds 3-4, k_shade_tail.hip, left the library in round 6: k_shade_tail_sorted.hip below takes its scenes)
-// staged shading (k_vertex_*.hip, k_scatter_*.hip): the hit half of a vertex (interaction, emission + MIS, get_bsdf with its texture
-// evaluation -> BxDF parameter block, pushed to the queue of its BxDF class), then per class the scattering half (NEE, sample_f, RR)
-WF_INTERNAL int wf_launch_vertex_tri(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_vertex_gen(ShmScene* s, const ShadeArgs& a);
+// Every shading launcher launches ONE scene-class variant of its kernel: geometry (tri: top-level triangles only, gen: spheres / patches / instances too) x image
+// class (none, tex: image textures — ray differentials, MIP filtering —, env: an ImageInfinitelight alone, the K_ENV_LIGHT units). render.hip puts them in one table,
+// ShadeKernels by (geometry, image class, sampler), and picks a render's cell once (select_kernels).
+using ShadeFn = int (*)(ShmScene*, const ShadeArgs&);
+// The units whose kernels draw are compiled twice (K_ZSOBOL, Makefile): each defines its launchers as the specialization <K_ZSOBOL> of one template, so that the
+// table names both twins and a missing one is a link error (an undefined hidden symbol).
+#define WF_SAMPLED_LAUNCHER(name)                                        \
+    template <bool ZS> int name(ShmScene* s, const ShadeArgs& a);        \
+    template <> WF_INTERNAL int name<false>(ShmScene* s, const ShadeArgs& a); \
+    template <> WF_INTERNAL int name<true>(ShmScene* s, const ShadeArgs& a)
+// the fused kernel k_shade<lean> (k_shade_lean*.hip): all-diffuse scenes without textures — every hit of the queue — and the hits k_vertex or the split pass diverted
+WF_SAMPLED_LAUNCHER(wf_launch_shade_lean); WF_SAMPLED_LAUNCHER(wf_launch_shade_lean_gen); WF_SAMPLED_LAUNCHER(wf_launch_shade_lean_env); WF_SAMPLED_LAUNCHER(wf_launch_shade_lean_gen_env);
+WF_SAMPLED_LAUNCHER(wf_launch_shade_lean_diverted); WF_SAMPLED_LAUNCHER(wf_launch_shade_lean_gen_diverted); WF_SAMPLED_LAUNCHER(wf_launch_shade_lean_env_diverted);
+WF_SAMPLED_LAUNCHER(wf_launch_shade_lean_gen_env_diverted);
+// the material-sorted fused all-materials kernel (k_shade_tail_sorted*.hip, k_shade_fused_*.hip): scenes without coated materials
+WF_SAMPLED_LAUNCHER(wf_launch_shade_tail_sorted); WF_SAMPLED_LAUNCHER(wf_launch_shade_fused_gen); WF_SAMPLED_LAUNCHER(wf_launch_shade_fused_tex);
+WF_SAMPLED_LAUNCHER(wf_launch_shade_fused_gen_tex); WF_SAMPLED_LAUNCHER(wf_launch_shade_tail_sorted_env); WF_SAMPLED_LAUNCHER(wf_launch_shade_fused_gen_env);
+// staged shading (k_vertex_*.hip, k_scatter_*.hip): the hit half of a vertex (interaction, emission + MIS, get_bsdf with its texture evaluation -> BxDF parameter
+// block, pushed to the queue of its BxDF class), then per class the scattering half (NEE, sample_f, RR). k_vertex draws nothing: one build serves both samplers.
+WF_INTERNAL int wf_launch_vertex_tri(ShmScene* s, const ShadeArgs& a); WF_INTERNAL int wf_launch_vertex_gen(ShmScene* s, const ShadeArgs& a);
 WF_INTERNAL int wf_launch_vertex_tex(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_scatter_diffuse(ShmScene* s, const ShadeArgs& a, bool tri_only, bool has_tex);
-WF_INTERNAL int wf_launch_scatter_conductor(ShmScene* s, const ShadeArgs& a, bool tri_only, bool has_tex);
-WF_INTERNAL int wf_launch_scatter_dielectric(ShmScene* s, const ShadeArgs& a, bool tri_only, bool has_tex);
-WF_INTERNAL int wf_launch_scatter_layered_tri(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_scatter_layered_gen(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_scatter_layered_tex(ShmScene* s, const ShadeArgs& a);
-// the same class as dense per-wave stages (k_scatter_layered.inl): every render but options.force_diffuse; SHM_LAYERED_STAGED=0 for A/B
-WF_INTERNAL int wf_launch_scatter_layered_staged_tri(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_scatter_layered_staged_gen(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_scatter_layered_staged_tex(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_shade_simple(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_shade_randomwalk(ShmScene* s, const ShadeArgs& a, uint32_t cap_eff);
+WF_INTERNAL int wf_launch_vertex_tri_env(ShmScene* s, const ShadeArgs& a); WF_INTERNAL int wf_launch_vertex_gen_env(ShmScene* s, const ShadeArgs& a);
+WF_SAMPLED_LAUNCHER(wf_launch_scatter_diffuse_tri); WF_SAMPLED_LAUNCHER(wf_launch_scatter_diffuse_gen); WF_SAMPLED_LAUNCHER(wf_launch_scatter_diffuse_tex);
+WF_SAMPLED_LAUNCHER(wf_launch_scatter_diffuse_tri_env); WF_SAMPLED_LAUNCHER(wf_launch_scatter_diffuse_gen_env);
+WF_SAMPLED_LAUNCHER(wf_launch_scatter_conductor_tri); WF_SAMPLED_LAUNCHER(wf_launch_scatter_conductor_gen); WF_SAMPLED_LAUNCHER(wf_launch_scatter_conductor_tex);
+WF_SAMPLED_LAUNCHER(wf_launch_scatter_conductor_tri_env); WF_SAMPLED_LAUNCHER(wf_launch_scatter_conductor_gen_env);
+WF_SAMPLED_LAUNCHER(wf_launch_scatter_dielectric_tri); WF_SAMPLED_LAUNCHER(wf_launch_scatter_dielectric_gen); WF_SAMPLED_LAUNCHER(wf_launch_scatter_dielectric_tex);
+WF_SAMPLED_LAUNCHER(wf_launch_scatter_dielectric_tri_env); WF_SAMPLED_LAUNCHER(wf_launch_scatter_dielectric_gen_env);
+// the LayeredBxDF class as dense per-wave stages (k_scatter_layered.inl): every render but options.force_diffuse ...
+WF_SAMPLED_LAUNCHER(wf_launch_scatter_layered_staged_tri); WF_SAMPLED_LAUNCHER(wf_launch_scatter_layered_staged_gen); WF_SAMPLED_LAUNCHER(wf_launch_scatter_layered_staged_tex);
+WF_SAMPLED_LAUNCHER(wf_launch_scatter_layered_staged_tri_env); WF_SAMPLED_LAUNCHER(wf_launch_scatter_layered_staged_gen_env);
+// ... and in one pass per vertex (k_scatter.inl), which has force_diffuse's code
+WF_SAMPLED_LAUNCHER(wf_launch_scatter_layered_tri); WF_SAMPLED_LAUNCHER(wf_launch_scatter_layered_gen); WF_SAMPLED_LAUNCHER(wf_launch_scatter_layered_tex);
+// the other integrators (k_shade_other.hip): one kernel each for every scene class
+WF_SAMPLED_LAUNCHER(wf_launch_shade_simple); WF_SAMPLED_LAUNCHER(wf_launch_shade_randomwalk);
 WF_INTERNAL int wf_launch_fold_randomwalk(ShmScene* s, hipStream_t stream, uint32_t cap_eff, uint32_t total);
-// ... and their twins in the *_zs objects (K_ZSOBOL): the same kernels drawing from ZSobol
-WF_INTERNAL int wf_launch_shade_lean_zs(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_shade_lean_diverted_zs(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_shade_lean_gen_zs(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_shade_lean_gen_diverted_zs(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_shade_lean_env_zs(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_shade_lean_gen_env_zs(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_scatter_diffuse_env_zs(ShmScene* s, const ShadeArgs& a, bool tri_only);
-WF_INTERNAL int wf_launch_scatter_conductor_env_zs(ShmScene* s, const ShadeArgs& a, bool tri_only);
-WF_INTERNAL int wf_launch_scatter_dielectric_env_zs(ShmScene* s, const ShadeArgs& a, bool tri_only);
-WF_INTERNAL int wf_launch_scatter_layered_staged_tri_env_zs(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_scatter_layered_staged_gen_env_zs(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_shade_lean_env_diverted_zs(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_shade_lean_gen_env_diverted_zs(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_shade_tail_sorted_env_zs(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_shade_fused_gen_env_zs(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_shade_fused_gen_zs(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_shade_fused_gen_tex_zs(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_shade_fused_tex_zs(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_shade_tail_sorted_zs(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_scatter_diffuse_zs(ShmScene* s, const ShadeArgs& a, bool tri_only, bool has_tex);
-WF_INTERNAL int wf_launch_scatter_conductor_zs(ShmScene* s, const ShadeArgs& a, bool tri_only, bool has_tex);
-WF_INTERNAL int wf_launch_scatter_dielectric_zs(ShmScene* s, const ShadeArgs& a, bool tri_only, bool has_tex);
-WF_INTERNAL int wf_launch_scatter_layered_tri_zs(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_scatter_layered_gen_zs(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_scatter_layered_tex_zs(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_scatter_layered_staged_tri_zs(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_scatter_layered_staged_gen_zs(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_scatter_layered_staged_tex_zs(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_shade_simple_zs(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_shade_randomwalk_zs(ShmScene* s, const ShadeArgs& a, uint32_t cap_eff);
-#if K_ZSOBOL
-#define wf_launch_shade_lean wf_launch_shade_lean_zs
-#define wf_launch_shade_lean_diverted wf_launch_shade_lean_diverted_zs
-#define wf_launch_shade_lean_gen wf_launch_shade_lean_gen_zs
-#define wf_launch_shade_lean_gen_diverted wf_launch_shade_lean_gen_diverted_zs
-#define wf_launch_shade_lean_env wf_launch_shade_lean_env_zs
-#define wf_launch_shade_lean_gen_env wf_launch_shade_lean_gen_env_zs
-#define wf_launch_scatter_diffuse_env wf_launch_scatter_diffuse_env_zs
-#define wf_launch_scatter_conductor_env wf_launch_scatter_conductor_env_zs
-#define wf_launch_scatter_dielectric_env wf_launch_scatter_dielectric_env_zs
-#define wf_launch_scatter_layered_staged_tri_env wf_launch_scatter_layered_staged_tri_env_zs
-#define wf_launch_scatter_layered_staged_gen_env wf_launch_scatter_layered_staged_gen_env_zs
-#define wf_launch_shade_lean_env_diverted wf_launch_shade_lean_env_diverted_zs
-#define wf_launch_shade_lean_gen_env_diverted wf_launch_shade_lean_gen_env_diverted_zs
-#define wf_launch_shade_tail_sorted_env wf_launch_shade_tail_sorted_env_zs
-#define wf_launch_shade_fused_gen_env wf_launch_shade_fused_gen_env_zs
-#define wf_launch_shade_fused_gen wf_launch_shade_fused_gen_zs
-#define wf_launch_shade_fused_gen_tex wf_launch_shade_fused_gen_tex_zs
-#define wf_launch_shade_fused_tex wf_launch_shade_fused_tex_zs
-#define wf_launch_shade_tail_sorted wf_launch_shade_tail_sorted_zs
-#define wf_launch_scatter_diffuse wf_launch_scatter_diffuse_zs
-#define wf_launch_scatter_conductor wf_launch_scatter_conductor_zs
-#define wf_launch_scatter_dielectric wf_launch_scatter_dielectric_zs
-#define wf_launch_scatter_layered_tri wf_launch_scatter_layered_tri_zs
-#define wf_launch_scatter_layered_gen wf_launch_scatter_layered_gen_zs
-#define wf_launch_scatter_layered_tex wf_launch_scatter_layered_tex_zs
-#define wf_launch_scatter_layered_staged_tri wf_launch_scatter_layered_staged_tri_zs
-#define wf_launch_scatter_layered_staged_gen wf_launch_scatter_layered_staged_gen_zs
-#define wf_launch_scatter_layered_staged_tex wf_launch_scatter_layered_staged_tex_zs
-#define wf_launch_shade_simple wf_launch_shade_simple_zs
-#define wf_launch_shade_randomwalk wf_launch_shade_randomwalk_zs
-#endif
+// K1 (render.hip, k_generate<HAS_TEX, LEAN, ZS>)
+using GenerateKernel = void (*)(SceneView, PathArrays, const uint32_t*, uint32_t, int, int, ShmRenderParams, uint32_t*, QueueState*, uint32_t);
+// The kernels of one scene class: a cell of render.hip's table by geometry x image class x sampler (nullptr: no such build), of which
+// select_kernels makes a render's set. The bounce loop decides which of them run and calls them through it.
+struct ShadeKernels {
+    GenerateKernel generate[2];       // [LEAN]: bounce 0 on known constants (ShadeArgs::first_bounce)
+    ShadeFn lean, lean_diverted;      // k_shade<lean>: the whole queue of an all-diffuse scene / the hits k_vertex or the split pass diverted
+    ShadeFn fused_all;                // the material-sorted fused all-materials kernel
+    ShadeFn vertex;                   // staged shading: the hit half ...
+    ShadeFn scatter[N_BXDF_CLASSES];  // ... and the scattering half of each BxDF class
+    ShadeFn scatter_layered_onepass;  // (the LayeredBxDF class in one pass per vertex: select_kernels puts it in scatter[CLASS_LAYERED] where it runs)
+    ShadeFn simple, randomwalk;       // the other integrators
+};

@@ -110,6 +110,24 @@ def test_trace_bitwise_parity(env, name):
     orc.close()
 
 
+def test_trace_any_after_a_quirks_off_render_is_reference_exact(env):
+    """shm_trace_any takes no render parameters: on an instanced scene it runs the reference-exact any-hit kernels whatever the scene's last render
+    used — after a render with disable_reference_quirks too (that render's shadow rays took the STRICT instantiations)."""
+    lib, oracle_py, render, scenes = env
+    sc, spp, depth = SCENES["instanced"](scenes, lib)
+    gpu, orc = render.Renderer(lib, sc.desc, 0), oracle_py.Oracle(sc.desc)
+    gpu.render(render.make_params(seed=3, spp=spp, max_depth=depth, reference_quirks=False))
+    rays = _rays(sc, 30000, 5)
+    ag, sg = gpu.trace(rays, any_hit=True)
+    ao, so = orc.trace(rays, any_hit=True)
+    assert ag.any() and not ag.all()
+    assert np.array_equal(ag, ao)
+    for k in ("rays_any", "nodes_any", "tris_any"):
+        assert sg[k] == so[k], k
+    gpu.close()
+    orc.close()
+
+
 def _stacked_leaf_scene(scenes, lib, copies):
     """The Cornell box plus `copies` coincident triangles (identical centroids: BvhAggregate::new leaves them in ONE leaf, aggregate.rs:345-356) —
     a leaf of more primitives than the device link word's count field holds (15)."""
