@@ -2,6 +2,7 @@
 """Render one of the repository's scenes on the GPU and write a PFM (and a tone-mapped PNG next to it).
 
     python examples/render_scene.py cornell --spp 256 --res 512 -o cornell.pfm
+    python examples/render_scene.py cornell --filter gaussian        (box | gaussian | mitchell | sinc | triangle)
     python examples/render_scene.py textured | coated | patches | instanced | environment | ganesha | crown | fuzz:13
 
 Everything goes through the C ABI of include/shimmer_hip.h (shimmer_amd/abi.py is the ctypes binding): scene description ->
@@ -20,25 +21,25 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from shimmer_amd import abi, render, scenes  # noqa: E402
 
 
-def make_scene(lib, name, w, h):
+def make_scene(lib, name, w, h, film=None):
     if name == "cornell":
-        return scenes.cornell_box(lib, w, h)
+        return scenes.cornell_box(lib, w, h, film=film)
     if name == "textured":
-        return scenes.cornell_box(lib, w, h, textured=True)
+        return scenes.cornell_box(lib, w, h, textured=True, film=film)
     if name == "coated":
-        return scenes.cornell_box(lib, w, h, coated=True)
+        return scenes.cornell_box(lib, w, h, coated=True, film=film)
     if name == "patches":
-        return scenes.cornell_box(lib, w, h, patches=True)
+        return scenes.cornell_box(lib, w, h, patches=True, film=film)
     if name == "instanced":
-        return scenes.instanced_scene(lib, w, h)
+        return scenes.instanced_scene(lib, w, h, film=film)
     if name == "environment":
-        return scenes.three_spheres(lib, w, h, camera=(0.75, 0.5, 9.0), environment=scenes.environment_image(64))
+        return scenes.three_spheres(lib, w, h, camera=(0.75, 0.5, 9.0), environment=scenes.environment_image(64), film=film)
     if name == "ganesha":
-        return scenes.ganesha_proxy(lib, w, h)
+        return scenes.ganesha_proxy(lib, w, h, film=film)
     if name == "crown":
-        return scenes.crown_proxy(lib, w, h)
+        return scenes.crown_proxy(lib, w, h, film=film)
     if name.startswith("fuzz:"):
-        return scenes.random_scene(lib, int(name.split(":")[1]), w, h)
+        return scenes.random_scene(lib, int(name.split(":")[1]), w, h, film=film)
     raise SystemExit(f"unknown scene {name}")
 
 
@@ -65,6 +66,8 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--exposure", type=float, default=1.0)
     ap.add_argument("--sampler", default="independent", choices=["independent", "zsobol"], help="ShmRenderParams::sampler (DESIGN.md \"Sampler\")")
+    ap.add_argument("--filter", default="box", choices=["box", "gaussian", "mitchell", "sinc", "triangle"],
+                    help="the pixel filter, at PBRT-v4's default radius and parameters (DESIGN.md \"Pixel filters\")")
     ap.add_argument("--quirks-off", action="store_true",
                     help="ShmRenderParams::disable_reference_quirks: PBRT-v4's forms of the reference's deviations (emitter sampling, instancing, ...: DESIGN.md section 2) "
                          "instead of the reference-exact default")
@@ -74,7 +77,7 @@ def main():
     if lib.shm_device_count() < 1:
         raise SystemExit("no HIP device visible (there is no CPU fallback)")
     w, h = args.res, args.height or args.res
-    sc = make_scene(lib, args.scene, w, h)
+    sc = make_scene(lib, args.scene, w, h, film=dict(filter=args.filter))
     r = render.Renderer(lib, sc.desc, 0)
     p = render.make_params(seed=args.seed, spp=args.spp, max_depth=args.max_depth, integrator=args.integrator, reference_quirks=not args.quirks_off,
                            sampler=args.sampler)

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SHM_ABI_VERSION 8
+#define SHM_ABI_VERSION 9
 
 /* The library is built with -fvisibility=hidden; only these entry points are exported. */
 #if defined(__GNUC__)
@@ -329,13 +329,20 @@ typedef struct ShmCamera {
     float min_dir_differential_x[3], min_dir_differential_y[3];
 } ShmCamera;
 
-/* RgbFilm + PixelSensor (film.rs:470-574, 754-914) + BoxFilter radius (filter.rs:61-105). */
+/* The pixel reconstruction filter (ABI v9): the reference's BoxFilter (filter.rs:61-105) and PBRT-v4's gaussian, Mitchell, windowed sinc and triangle filters.
+ * A sample is added to its own pixel with the weight of the importance-sampled filter (PBRT-v4's FilterSampler); nothing is splatted. 0 = box. */
+enum { SHM_FILTER_BOX = 0, SHM_FILTER_GAUSSIAN = 1, SHM_FILTER_MITCHELL = 2, SHM_FILTER_SINC = 3, SHM_FILTER_TRIANGLE = 4 };
+
+/* RgbFilm + PixelSensor (film.rs:470-574, 754-914) + the pixel filter. */
 typedef struct ShmFilm {
     int32_t pixel_bounds[4];      /* min.x, min.y, max.x, max.y (max exclusive) */
     int32_t full_resolution[2];
-    float filter_radius[2];
+    float filter_radius[2];       /* "xradius", "yradius" > 0 (PBRT-v4's defaults: box 0.5, gaussian 1.5, mitchell 2, sinc 4, triangle 2); gaussian / mitchell / sinc: 1/32 <= radius <= 8 */
     float imaging_ratio;
     float max_component_value;
+    uint32_t filter;              /* SHM_FILTER_* (ABI v9); zeroed = box */
+    float filter_params[2];       /* gaussian: {sigma > 0 (0.5), -}; mitchell: {B, C} (1/3, 1/3); sinc: {tau > 0 (3), -}; box, triangle: unused */
+    uint32_t pad;
     const float* sensor_r_bar;    /* DenselySampledSpectrum 360..=830, 471 floats */
     const float* sensor_g_bar;
     const float* sensor_b_bar;
@@ -670,7 +677,7 @@ SHM_API void shm_ply_free(ShmPlyMesh* mesh);
  * The reference's loader (loading/tokenizer.rs, parser.rs:216-351, parser_target.rs:50-184, scene.rs:1221-2033) restated in C++ for the
  * directive set the repository's scenes use: transforms (LookAt Translate Scale Rotate Identity Transform ConcatTransform CoordinateSystem
  * CoordSysTransform ReverseOrientation), Camera (perspective / orthographic, incl. frameaspectratio / screenwindow), Film (rgb, whitebalance),
- * Attribute, Option (incl. rendercoordsys), Sampler (independent), PixelFilter (box),
+ * Attribute, Option (incl. rendercoordsys), Sampler (independent / zsobol), PixelFilter (box gaussian mitchell sinc triangle),
  * Integrator (path / simplepath / randomwalk), Option, WorldBegin, AttributeBegin / End, Material / MakeNamedMaterial / NamedMaterial
  * (diffuse conductor dielectric thindielectric coateddiffuse coatedconductor mix, "normalmap"), Texture (float / spectrum: constant scale
  * mix directionmix imagemap — with the uv / spherical / cylindrical / planar mappings), AreaLightSource (diffuse), LightSource (point,

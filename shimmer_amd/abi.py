@@ -10,7 +10,7 @@ from pathlib import Path
 ROOT = Path(__file__).resolve().parent
 LIB_PATH = ROOT / "csrc" / "libshimmer_hip.so"
 
-SHM_ABI_VERSION = 8
+SHM_ABI_VERSION = 9
 SHM_OK = 0
 SHM_DIST_ID_BYTES = 128
 SHM_SHAPE_TRIANGLE, SHM_SHAPE_SPHERE, SHM_SHAPE_BILINEAR_PATCH, SHM_SHAPE_INSTANCE = 0, 1, 2, 3
@@ -23,6 +23,7 @@ SHM_SPECTRUM_IMAGE_TEXTURE, SHM_SPECTRUM_TEXTURE_NODE = 6, 7
 SHM_SPECTEX_LEAF, SHM_SPECTEX_SCALED, SHM_SPECTEX_MIX, SHM_SPECTEX_DIRECTION_MIX = 0, 1, 2, 3
 SHM_TEXMAP_UV, SHM_TEXMAP_SPHERICAL, SHM_TEXMAP_CYLINDRICAL, SHM_TEXMAP_PLANAR = 0, 1, 2, 3
 SHM_TEXFILTER_POINT, SHM_TEXFILTER_BILINEAR, SHM_TEXFILTER_TRILINEAR, SHM_TEXFILTER_EWA = 0, 1, 2, 3
+SHM_FILTER_BOX, SHM_FILTER_GAUSSIAN, SHM_FILTER_MITCHELL, SHM_FILTER_SINC, SHM_FILTER_TRIANGLE = 0, 1, 2, 3, 4
 SHM_WRAP_BLACK, SHM_WRAP_CLAMP, SHM_WRAP_REPEAT, SHM_WRAP_OCTAHEDRAL_SPHERE = 0, 1, 2, 3
 SHM_SPECTRUM_TYPE_ALBEDO, SHM_SPECTRUM_TYPE_UNBOUNDED, SHM_SPECTRUM_TYPE_ILLUMINANT = 0, 1, 2
 SHM_FLOATTEX_CONSTANT, SHM_FLOATTEX_SCALED, SHM_FLOATTEX_MIX, SHM_FLOATTEX_DIRECTION_MIX, SHM_FLOATTEX_IMAGE = 0, 1, 2, 3, 4
@@ -138,7 +139,8 @@ class ShmColorSpace(C.Structure):
 
 class ShmFilm(C.Structure):
     _fields_ = [("pixel_bounds", C.c_int32 * 4), ("full_resolution", C.c_int32 * 2), ("filter_radius", C.c_float * 2),
-                ("imaging_ratio", C.c_float), ("max_component_value", C.c_float), ("sensor_r_bar", c_float_p),
+                ("imaging_ratio", C.c_float), ("max_component_value", C.c_float), ("filter", C.c_uint32), ("filter_params", C.c_float * 2),
+                ("pad", C.c_uint32), ("sensor_r_bar", c_float_p),
                 ("sensor_g_bar", c_float_p), ("sensor_b_bar", c_float_p)]
 
 

@@ -10,6 +10,7 @@
 #include <utility>
 #include <vector>
 
+#include "../shm/filter.h"
 #include "../shm/scene.h"
 
 static_assert(sizeof(ShmMaterial) == 240 && sizeof(ShmFloatTexture) == 48 && sizeof(ShmSpectrumTexture) == 64 && sizeof(ShmSpectrum) == 32 && sizeof(ShmBvhNode) == 32 && sizeof(ShmPrimitive) == 16,
@@ -100,6 +101,7 @@ struct FlatScene {
         for (int i = 0; i < 4; ++i) v.pixel_bounds[i] = film.pixel_bounds[i];
         v.filter_radius[0] = film.filter_radius[0];
         v.filter_radius[1] = film.filter_radius[1];
+        v.filter_kind = film.filter;
         v.imaging_ratio = film.imaging_ratio;
         v.max_component_value = film.max_component_value;
         v.sensor_r_bar = sensor_r.data();
@@ -201,6 +203,23 @@ inline int flatten_scene(const ShmSceneDesc* d, FlatScene& out, std::string& err
     out.camera = d->camera;
     out.film = d->film;
     out.film.sensor_r_bar = out.film.sensor_g_bar = out.film.sensor_b_bar = nullptr;
+    // the pixel filter (shm/filter.h): a tabulated filter's table, built here once, opens the distribution pool
+    {
+        const ShmFilm& fl = d->film;
+        if (fl.filter > SHM_FILTER_TRIANGLE) { err = "unknown pixel filter"; return SHM_ERR_INVALID_ARGUMENT; }
+        if (!(fl.filter_radius[0] > 0.0f) || !(fl.filter_radius[1] > 0.0f)) { err = "pixel filter: the radius must be positive"; return SHM_ERR_INVALID_ARGUMENT; }
+        if (fl.filter == SHM_FILTER_GAUSSIAN && !(fl.filter_params[0] > 0.0f)) { err = "gaussian pixel filter: sigma must be positive"; return SHM_ERR_INVALID_ARGUMENT; }
+        if (fl.filter == SHM_FILTER_SINC && !(fl.filter_params[0] > 0.0f)) { err = "sinc pixel filter: tau must be positive"; return SHM_ERR_INVALID_ARGUMENT; }
+        out.dist_data.clear();
+        if (shm::filter_class_of(fl.filter) == shm::FILTER_CLASS_TABULATED) {
+            out.dist_data.resize(shm::FILTER_TABLE_MAX_FLOATS);
+            const int n = shm::filter_build_table(fl.filter, fl.filter_radius[0], fl.filter_radius[1], fl.filter_params[0], fl.filter_params[1], out.dist_data.data());
+            if (n == 0) { err = "pixel filter: a tabulated filter (gaussian, mitchell, sinc) has int(32 * radius) cells per axis, between 1 and 256"; return SHM_ERR_INVALID_ARGUMENT; }
+            // (a table that is zero everywhere cannot be sampled: a gaussian whose sigma dwarfs its radius rounds to one)
+            if (!(out.dist_data[0] > 0.0f)) { err = "pixel filter: the filter is zero over its whole support"; return SHM_ERR_INVALID_ARGUMENT; }
+            out.dist_data.resize(((size_t)n + 3u) & ~(size_t)3u, 0.0f);  // (whole 16-byte groups: the generate kernels copy uint4s)
+        }
+    }
 
     // meshes -> global arrays
     std::vector<uint32_t> tri_base(d->n_meshes + 1, 0), vert_base(d->n_meshes + 1, 0);

@@ -8,7 +8,7 @@
 //   material.rs:56-110, 259-285, 353-420, 539-575, 688-720, 820-900, 1055-1170, 1297-1310      Material::create and the per-material defaults
 //   camera.rs:676-705, 850-890, film.rs:225-330, 482-495, 767-800, sampler.rs:95-99, integrator.rs:16-75
 // Scope: the directives the repository's scenes need — LookAt Translate Scale Rotate Identity Transform ConcatTransform CoordinateSystem
-// CoordSysTransform ReverseOrientation Camera (perspective / orthographic) Film (rgb) Sampler PixelFilter (box) Integrator Option
+// CoordSysTransform ReverseOrientation Camera (perspective / orthographic) Film (rgb) Sampler PixelFilter (box gaussian mitchell sinc triangle) Integrator Option
 // WorldBegin AttributeBegin/End Attribute (per-target default parameters) Material MakeNamedMaterial NamedMaterial Texture (float / spectrum: constant scale mix
 // directionmix imagemap) AreaLightSource (diffuse) LightSource (point, infinite: uniform or an environment image) Shape (trianglemesh
 // bilinearmesh sphere plymesh) ObjectBegin/End ObjectInstance Include; spectra as "spectrum" samples / named tables / files, "blackbody",
@@ -916,9 +916,21 @@ private:
         f.imaging_ratio = (shutter_close - shutter_open) * film_params_.one_float("iso", 100.0f) / 100.0f;  // film.rs:785
         f.max_component_value = film_params_.one_float("maxcomponentvalue", INFINITY);
         settings_.filename = film_params_.one_string("filename", "shimmer.pfm");
-        if (filter_type_ != "box") fail(tk.where(line) + ": pixel filter \"" + filter_type_ + "\" is not supported (box)", SHM_ERR_UNSUPPORTED);
-        f.filter_radius[0] = filter_params_.one_float("xradius", 0.5f);  // filter.rs:70-80
-        f.filter_radius[1] = filter_params_.one_float("yradius", 0.5f);
+        // the pixel filter: the reference's box (filter.rs:70-80) and PBRT-v4's other four, with PBRT-v4's parameters and defaults; without a PixelFilter directive: box
+        // (the reference's default). Values are checked where the scene is created (flatten_scene).
+        float default_radius = 0.5f;
+        f.filter_params[0] = f.filter_params[1] = 0.0f;
+        if (filter_type_ == "box") f.filter = SHM_FILTER_BOX;
+        else if (filter_type_ == "gaussian") { f.filter = SHM_FILTER_GAUSSIAN; default_radius = 1.5f; f.filter_params[0] = filter_params_.one_float("sigma", 0.5f); }
+        else if (filter_type_ == "mitchell") {
+            f.filter = SHM_FILTER_MITCHELL; default_radius = 2.0f;
+            f.filter_params[0] = filter_params_.one_float("B", 1.0f / 3.0f); f.filter_params[1] = filter_params_.one_float("C", 1.0f / 3.0f);
+        }
+        else if (filter_type_ == "sinc") { f.filter = SHM_FILTER_SINC; default_radius = 4.0f; f.filter_params[0] = filter_params_.one_float("tau", 3.0f); }
+        else if (filter_type_ == "triangle") { f.filter = SHM_FILTER_TRIANGLE; default_radius = 2.0f; }
+        else fail(tk.where(line) + ": pixel filter \"" + filter_type_ + "\" is not supported (box, gaussian, mitchell, sinc, triangle)", SHM_ERR_UNSUPPORTED);
+        f.filter_radius[0] = filter_params_.one_float("xradius", default_radius);
+        f.filter_radius[1] = filter_params_.one_float("yradius", default_radius);
         // camera: world_from_camera = inverse(CTM at the Camera directive); render space = CameraWorld (camera.rs:507-523)
         const Xf world_from_camera = xf_inverse(camera_from_world_);
         float wfc[16], rfw[16];

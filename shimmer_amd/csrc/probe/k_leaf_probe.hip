@@ -38,6 +38,23 @@ extern "C" __attribute__((visibility("default"))) int shm_debug_eval_leaf(int de
         g_probe_err = "shm_debug_eval_leaf: the zsobol stream needs 10 + n argument words and 4 n output words";
         return SHM_ERR_INVALID_ARGUMENT;
     }
+    // the pixel filters: the table of a tabulated kind is built here, on the host, as flatten_scene builds a scene's (no exp or sin of a filter runs on the device), and appended
+    std::vector<uint32_t> with_table;
+    if (op == shm::PROBE_FILTER_SAMPLE) {
+        if (n_in < 6 || in_words[0] > SHM_FILTER_TRIANGLE || in_words[5] > (1u << 16) || n_in != 6 + 2 * in_words[5] || 3 * in_words[5] > n_out) {
+            g_probe_err = "shm_debug_eval_leaf: the filter sampler needs 6 + 2 n argument words and 3 n output words";
+            return SHM_ERR_INVALID_ARGUMENT;
+        }
+        with_table.assign(in_words, in_words + n_in);
+        if (shm::filter_class_of(in_words[0]) == shm::FILTER_CLASS_TABULATED) {
+            std::vector<float> table(shm::FILTER_TABLE_MAX_FLOATS);
+            const int n = shm::filter_build_table(in_words[0], shm::bits_to_float(in_words[1]), shm::bits_to_float(in_words[2]), shm::bits_to_float(in_words[3]), shm::bits_to_float(in_words[4]), table.data());
+            if (n == 0 || !(table[0] > 0.0f)) { g_probe_err = "shm_debug_eval_leaf: the filter has no table (radius, parameters)"; return SHM_ERR_INVALID_ARGUMENT; }
+            for (int i = 0; i < n; ++i) with_table.push_back(shm::float_to_bits(table[i]));
+        }
+        in_words = with_table.data();
+        n_in = (uint32_t)with_table.size();
+    }
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) { g_probe_err = "no HIP device visible (the probe has no CPU fallback)"; return SHM_ERR_NO_DEVICE; }
     if (hipSetDevice(device) != hipSuccess) { g_probe_err = "hipSetDevice"; return SHM_ERR_DEVICE; }

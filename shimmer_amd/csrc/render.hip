@@ -53,10 +53,12 @@ __device__ __forceinline__ uint32_t slot_of(uint32_t p_local, uint32_t s_local, 
 
 // HAS_TEX: scenes that bind image textures carry the camera ray's auxiliary rays (a compile-time switch: with a run-time pointer the
 // auxiliary-ray record lived in scratch memory, 52 B of stores per path, in every scene)
-template <bool HAS_TEX, bool LEAN = false, bool ZS = false>  // ZS: the ZSobol sampler (wavefront.h, K_ZSOBOL)
-__global__ void __launch_bounds__(SHADE_BLOCK) k_generate(SceneView sv, PathArrays pa, const uint32_t* pixels, uint32_t n_pix,
-                                                        int sample_begin, int n_samples, ShmRenderParams params,
-                                                        uint32_t* q_active, QueueState* qs, uint32_t pix_group) {
+// FC: the pixel filter's class (shm/filter.h). filter_table: the tabulated class's table (the block's copy in LDS); filter_weight: where a filter whose weight differs
+// from sample to sample (Mitchell, sinc) leaves it for k_film_weighted, null otherwise.
+template <bool HAS_TEX, bool LEAN, bool ZS, int FC>
+__device__ __forceinline__ void generate_paths(const SceneView& sv, const PathArrays& pa, const uint32_t* pixels, uint32_t n_pix, int sample_begin, int n_samples,
+                                               const ShmRenderParams& params, uint32_t* q_active, QueueState* qs, uint32_t pix_group, const Float* filter_table,
+                                               float* filter_weight) {
     uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t total = n_pix * (uint32_t)n_samples;
     if (slot >= total) return;
@@ -73,9 +75,10 @@ __global__ void __launch_bounds__(SHADE_BLOCK) k_generate(SceneView sv, PathArra
     Float weight;
     constexpr bool has_tex = HAS_TEX;
     AuxRays aux = aux_none();
-    Ray r = generate_camera_ray(sv, px, py, rng, params.disable_wavelength_jitter != 0, params.disable_pixel_jitter != 0,
-                                lambda, weight, HAS_TEX ? &aux : nullptr, params.samples_per_pixel);
+    Ray r = generate_camera_ray<FC>(sv, px, py, rng, params.disable_wavelength_jitter != 0, params.disable_pixel_jitter != 0,
+                                    lambda, weight, HAS_TEX ? &aux : nullptr, params.samples_per_pixel, filter_table);
     if (HAS_TEX) st_aux(pa, slot, aux);
+    if (FC == FILTER_CLASS_TABULATED && filter_weight) filter_weight[slot] = weight;
     ShmRay ray;
     ray.o[0] = r.o.x; ray.o[1] = r.o.y; ray.o[2] = r.o.z;
     ray.d[0] = r.d.x; ray.d[1] = r.d.y; ray.d[2] = r.d.z;
@@ -115,6 +118,35 @@ __global__ void __launch_bounds__(SHADE_BLOCK) k_generate(SceneView sv, PathArra
         qs->n_emit = 0;
         qs->n_lean = 0;
         qs->n_split = 0;
+    }
+}
+// The box filter's kernel (the reference's filter; the headline path)
+template <bool HAS_TEX, bool LEAN = false, bool ZS = false>  // ZS: the ZSobol sampler (wavefront.h, K_ZSOBOL)
+__global__ void __launch_bounds__(SHADE_BLOCK) k_generate(SceneView sv, PathArrays pa, const uint32_t* pixels, uint32_t n_pix,
+                                                        int sample_begin, int n_samples, ShmRenderParams params,
+                                                        uint32_t* q_active, QueueState* qs, uint32_t pix_group) {
+    generate_paths<HAS_TEX, LEAN, ZS, FILTER_CLASS_BOX>(sv, pa, pixels, n_pix, sample_begin, n_samples, params, q_active, qs, pix_group, nullptr, nullptr);
+}
+// The other pixel filters' kernels. The triangle filter is sampled in closed form. The tabulated class (gaussian, Mitchell, sinc) inverts two 1-D CDFs of up to 257 entries
+// per path by binary search, every lane at an index of its own: the block copies the table (at most 6.2 KB, 3.1 KB at PBRT-v4's widest default radius) into LDS once and
+// searches it there.
+template <bool HAS_TEX, bool LEAN, bool ZS, int FC>
+__global__ void __launch_bounds__(SHADE_BLOCK) k_generate_filtered(SceneView sv, PathArrays pa, const uint32_t* pixels, uint32_t n_pix,
+                                                                 int sample_begin, int n_samples, ShmRenderParams params,
+                                                                 uint32_t* q_active, QueueState* qs, uint32_t pix_group, float* filter_weight) {
+    static_assert(FC == FILTER_CLASS_TRIANGLE || FC == FILTER_CLASS_TABULATED, "the box filter runs k_generate");
+    if constexpr (FC == FILTER_CLASS_TABULATED) {
+        __shared__ uint4 s_table[(FILTER_TABLE_MAX_FLOATS + 3) / 4];
+        // (the table's length is in its head: flatten_scene bounds it by FILTER_TABLE_MAX_FLOATS and pads it to whole uint4s)
+        const uint32_t nx = float_to_bits(sv.dist_data[1]), ny = float_to_bits(sv.dist_data[2]);
+        const uint32_t n4 = min(((uint32_t)filter_table_floats((int)nx, (int)ny) + 3u) / 4u, (uint32_t)((FILTER_TABLE_MAX_FLOATS + 3) / 4));
+        const uint4* g = reinterpret_cast<const uint4*>(sv.dist_data);
+        for (uint32_t i = threadIdx.x; i < n4; i += blockDim.x) s_table[i] = g[i];
+        __syncthreads();
+        generate_paths<HAS_TEX, LEAN, ZS, FC>(sv, pa, pixels, n_pix, sample_begin, n_samples, params, q_active, qs, pix_group, reinterpret_cast<const Float*>(s_table),
+                                              filter_weight);
+    } else {
+        generate_paths<HAS_TEX, LEAN, ZS, FC>(sv, pa, pixels, n_pix, sample_begin, n_samples, params, q_active, qs, pix_group, nullptr, nullptr);
     }
 }
 
@@ -172,8 +204,13 @@ __global__ void __launch_bounds__(SHADE2_BLOCK) k_split_plain(SceneView sv, Path
 // K6: RgbFilm::add_sample for every sample of the batch, per pixel in sample order (f64 sums are
 // order dependent; the reference adds samples of a pixel in increasing sample_index).
 // ---------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(SHADE_BLOCK) k_film(SceneView sv, PathArrays pa, const uint32_t* pixels, uint32_t n_pix, int n_samples,
-                                                    ShmFilmPixel* film, DeviceCounters* counters, uint32_t pix_group) {
+// W: where a sample's filter weight comes from. FILM_WEIGHT_ONE: it is 1 (box, triangle; every filter under options.disable_pixel_jitter); FILM_WEIGHT_CONSTANT: the one
+// constant `weight_k` of the scene's table (gaussian: still accumulated as K, so that weight_sum is spp * K as in the oracle); FILM_WEIGHT_PER_SAMPLE: +-K as k_generate_filtered
+// left it per path slot (Mitchell, sinc).
+enum : int { FILM_WEIGHT_ONE, FILM_WEIGHT_CONSTANT, FILM_WEIGHT_PER_SAMPLE };
+template <int W>
+__device__ __forceinline__ void film_add_samples(const SceneView& sv, const PathArrays& pa, const uint32_t* pixels, uint32_t n_pix, int n_samples, ShmFilmPixel* film,
+                                                 DeviceCounters* counters, uint32_t pix_group, const float* filter_weight, float weight_k) {
     uint32_t p_local = blockIdx.x * blockDim.x + threadIdx.x;
     if (p_local >= n_pix) return;
     uint32_t pix = pixels[p_local];
@@ -190,7 +227,7 @@ __global__ void __launch_bounds__(SHADE_BLOCK) k_film(SceneView sv, PathArrays p
         lambda.lambda[0] = a.x; lambda.lambda[1] = a.y; lambda.lambda[2] = a.z; lambda.lambda[3] = a.w;
         lambda.pdf[0] = c.x; lambda.pdf[1] = c.y; lambda.pdf[2] = c.z; lambda.pdf[3] = c.w;
         V3 rgb = film_sample_rgb(sv, L, lambda);
-        const Float weight = 1.0f;  // BoxFilter::sample weight (filter.rs:104)
+        const Float weight = W == FILM_WEIGHT_ONE ? 1.0f : (W == FILM_WEIGHT_CONSTANT ? weight_k : filter_weight[slot]);  // Filter::sample's weight (shm/filter.h)
         r += (double)(weight * rgb.x);
         g += (double)(weight * rgb.y);
         b += (double)(weight * rgb.z);
@@ -198,6 +235,15 @@ __global__ void __launch_bounds__(SHADE_BLOCK) k_film(SceneView sv, PathArrays p
     }
     fp->rgb_sum[0] = r; fp->rgb_sum[1] = g; fp->rgb_sum[2] = b; fp->weight_sum = w;
     if (p_local == 0) atomicAdd(&counters->paths, (unsigned long long)n_pix * (unsigned long long)n_samples);
+}
+__global__ void __launch_bounds__(SHADE_BLOCK) k_film(SceneView sv, PathArrays pa, const uint32_t* pixels, uint32_t n_pix, int n_samples,
+                                                    ShmFilmPixel* film, DeviceCounters* counters, uint32_t pix_group) {
+    film_add_samples<FILM_WEIGHT_ONE>(sv, pa, pixels, n_pix, n_samples, film, counters, pix_group, nullptr, 1.0f);
+}
+template <int W>
+__global__ void __launch_bounds__(SHADE_BLOCK) k_film_weighted(SceneView sv, PathArrays pa, const uint32_t* pixels, uint32_t n_pix, int n_samples,
+                                                             ShmFilmPixel* film, DeviceCounters* counters, uint32_t pix_group, const float* filter_weight, float weight_k) {
+    film_add_samples<W>(sv, pa, pixels, n_pix, n_samples, film, counters, pix_group, filter_weight, weight_k);
 }
 
 }  // namespace
@@ -296,6 +342,21 @@ constexpr ShadeKernels shade_cells[N_GEO][N_IMG] = {
       .scatter_layered_onepass = wf_launch_scatter_layered_gen<ZS>,  // (as above)
       .simple = wf_launch_shade_simple<ZS>, .randomwalk = wf_launch_shade_randomwalk<ZS>}},
 };
+// ... and per pixel-filter class (shm/filter.h) x sampler: K1 and K6 of the filters that are not the box filter — [TRIANGLE | TABULATED with a constant weight (gaussian) |
+// TABULATED with a signed one (Mitchell, sinc)]; the generate kernels as [HAS_TEX][LEAN]
+enum : int { FLT_TRIANGLE, FLT_TABULATED, FLT_TABULATED_SIGNED, N_FLT };
+struct FilterKernels {
+    FilteredGenerateKernel generate[2][2];
+    WeightedFilmKernel film;  // (null: k_film, weight 1)
+};
+template <bool ZS>
+constexpr FilterKernels filter_cells[N_FLT] = {
+    {{{k_generate_filtered<false, false, ZS, FILTER_CLASS_TRIANGLE>, k_generate_filtered<false, true, ZS, FILTER_CLASS_TRIANGLE>}, {k_generate_filtered<true, false, ZS, FILTER_CLASS_TRIANGLE>, nullptr}}, nullptr},
+    {{{k_generate_filtered<false, false, ZS, FILTER_CLASS_TABULATED>, k_generate_filtered<false, true, ZS, FILTER_CLASS_TABULATED>}, {k_generate_filtered<true, false, ZS, FILTER_CLASS_TABULATED>, nullptr}},
+     k_film_weighted<FILM_WEIGHT_CONSTANT>},
+    {{{k_generate_filtered<false, false, ZS, FILTER_CLASS_TABULATED>, k_generate_filtered<false, true, ZS, FILTER_CLASS_TABULATED>}, {k_generate_filtered<true, false, ZS, FILTER_CLASS_TABULATED>, nullptr}},
+     k_film_weighted<FILM_WEIGHT_PER_SAMPLE>},
+};
 // A render's kernels, once per call: the only code that reads the scene's classes and the render's options to choose a variant (WHETHER a kernel runs is the bounce loop's)
 static ShadeKernels select_kernels(const ShmScene* s, const ShmRenderParams* params) {
     const shm_host::FlatScene& f = s->flat;
@@ -314,6 +375,18 @@ static ShadeKernels select_kernels(const ShmScene* s, const ShmRenderParams* par
     const int img_generate = tex_ws(s) ? IMG_TEX : IMG_NONE;
     k.generate[0] = cells[geo][img_generate].generate[0];
     k.generate[1] = cells[geo][img_generate].generate[1];
+    // the pixel filter: box — and every filter under options.disable_pixel_jitter, where the film point is the pixel centre and the weight 1 whatever was drawn — runs the
+    // kernels above and k_film; the others their own K1 / K6 pair
+    k.generate_filtered[0] = k.generate_filtered[1] = nullptr;
+    k.film_weighted = nullptr;
+    const uint32_t filter = f.film.filter;
+    if (filter != SHM_FILTER_BOX && params->disable_pixel_jitter == 0) {
+        const FilterKernels& fk = (params->sampler == SHM_SAMPLER_ZSOBOL ? filter_cells<true> : filter_cells<false>)[
+            filter == SHM_FILTER_TRIANGLE ? FLT_TRIANGLE : (filter_weight_is_signed(filter) ? FLT_TABULATED_SIGNED : FLT_TABULATED)];
+        k.generate_filtered[0] = fk.generate[img_generate == IMG_TEX ? 1 : 0][0];
+        k.generate_filtered[1] = fk.generate[img_generate == IMG_TEX ? 1 : 0][1];
+        k.film_weighted = fk.film;
+    }
     // the LayeredBxDF class in one pass per vertex under options.force_diffuse, which replaces the BxDF inside this half (the one-pass kernel has that code), and past
     // 2^30 paths of workspace (the staged kernel's jobs carry two flag bits above the path index), which ensure_workspace never grants: never with env
     if (params->force_diffuse != 0 || s->capacity >= (1u << 30)) k.scatter[CLASS_LAYERED] = k.scatter_layered_onepass;
@@ -333,7 +406,7 @@ static uint64_t workspace_cap(const ShmScene* s, bool need_staged) {
     // path state + three queues (+ auxiliary rays) (+ the staging arrays whenever the upcoming render is staged: every scene class but the
     // lean one, and the lean one too under options.force_diffuse — the budget must count them BEFORE the first staged allocation)
     // (ray 32, hit 32, shadow_ray 32, shadow_contrib 16, L 16, the PathRec 64, lambda 16, lambda_pdf 16, the CtxRec 64 = 288)
-    const uint64_t BYTES_PER_PATH = 288 + (first_bounce_candidate(s) ? 12 : 0) + 3 * 4 + (tex_ws(s) ? 48 : 0) + (uses_fused_kernel(s) ? 88 : 0) + ((need_staged || s->ws_staged || !scene_is_lean(s)) ? staging_bytes_per_path(s) : 0);
+    const uint64_t BYTES_PER_PATH = 288 + (filter_weight_is_signed(s->flat.film.filter) ? 4 : 0) + (first_bounce_candidate(s) ? 12 : 0) + 3 * 4 + (tex_ws(s) ? 48 : 0) + (uses_fused_kernel(s) ? 88 : 0) + ((need_staged || s->ws_staged || !scene_is_lean(s)) ? staging_bytes_per_path(s) : 0);
     uint64_t cap = max_batch_paths();
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
@@ -403,6 +476,9 @@ int ensure_workspace(ShmScene* s, uint64_t needed_paths, bool need_staged) {
         WS(e_ray, float4); WS(e_beta, float4); WS(e_ctx0, float4); WS(e_ctx1, float4); WS(e_ctx2, float4); WS(e_flags, uint32_t);
         if ((rc = ws_alloc((size_t)cap * 4, (void**)&s->d_q_emit)) != SHM_OK) return rc;
     }
+    // a pixel filter with negative lobes: the sample's weight, from k_generate_filtered to k_film_weighted (outside PathArrays: no other kernel sees it)
+    s->d_filter_weight = nullptr;
+    if (filter_weight_is_signed(s->flat.film.filter) && (rc = ws_alloc((size_t)cap * sizeof(float), (void**)&s->d_filter_weight)) != SHM_OK) return rc;
     s->pa.aux0 = s->pa.aux1 = s->pa.aux2 = nullptr;
     if (tex_ws(s)) { WS(aux0, float4); WS(aux1, float4); WS(aux2, float4); }
     s->pa.bx = nullptr;
@@ -808,8 +884,12 @@ int shm_render_wave(ShmScene* s, const ShmRenderParams* params, const ShmTile* t
         //  (HIT_HAS_SECOND, wavefront.h). Not with instances: a hit inside one names it in the 32-byte record, patched when the instance's marker is popped)
         s->pa.hit16 = ((!s->flat.has_spheres || !s->flat.has_instances) && params->integrator == SHM_INTEGRATOR_PATH && !random_walk) ? 1u : 0u;
         s->pa.hit2 = (s->pa.hit16 && s->flat.has_spheres) ? reinterpret_cast<const float4*>(s->pa.hit) + s->capacity : nullptr;
-        hipLaunchKernelGGL(k.generate[lean_first ? 1 : 0], dim3((total + SHADE_BLOCK - 1) / SHADE_BLOCK), dim3(SHADE_BLOCK), 0, s->stream, s->dsv, s->pa, pixels, n_pix,
-                           sample_begin, n_samples, *params, s->d_q_active[0], s->d_qs, s->pix_group);
+        if (k.generate_filtered[lean_first ? 1 : 0])
+            hipLaunchKernelGGL(k.generate_filtered[lean_first ? 1 : 0], dim3((total + SHADE_BLOCK - 1) / SHADE_BLOCK), dim3(SHADE_BLOCK), 0, s->stream, s->dsv, s->pa, pixels, n_pix,
+                               sample_begin, n_samples, *params, s->d_q_active[0], s->d_qs, s->pix_group, s->d_filter_weight);
+        else
+            hipLaunchKernelGGL(k.generate[lean_first ? 1 : 0], dim3((total + SHADE_BLOCK - 1) / SHADE_BLOCK), dim3(SHADE_BLOCK), 0, s->stream, s->dsv, s->pa, pixels, n_pix,
+                               sample_begin, n_samples, *params, s->d_q_active[0], s->d_qs, s->pix_group);
         LAUNCH_TRY("k_generate");
         int cur = 0;
         // Small batches are tail-dominated (the last rays of a persistent traversal launch take ~0.5 ms whatever its size): there
@@ -958,8 +1038,12 @@ int shm_render_wave(ShmScene* s, const ShmRenderParams* params, const ShmTile* t
         if (overlap && k3_done) hipStreamWaitEvent(s->stream, k3_done, 0);  // the film reads L
         if (random_walk)
             if ((rc = wf_launch_fold_randomwalk(s, s->stream, cap_eff, total)) != SHM_OK) return rc;
-        hipLaunchKernelGGL(k_film, dim3((n_pix + SHADE_BLOCK - 1) / SHADE_BLOCK), dim3(SHADE_BLOCK), 0, s->stream, s->dsv, s->pa, pixels, n_pix, n_samples,
-                           s->d_film, s->d_counters, s->pix_group);
+        if (k.film_weighted)  // (the weight: the constant K that heads the scene's filter table, with its sign per path slot where the filter has negative lobes)
+            hipLaunchKernelGGL(k.film_weighted, dim3((n_pix + SHADE_BLOCK - 1) / SHADE_BLOCK), dim3(SHADE_BLOCK), 0, s->stream, s->dsv, s->pa, pixels, n_pix, n_samples,
+                               s->d_film, s->d_counters, s->pix_group, s->d_filter_weight, s->flat.dist_data[0]);
+        else
+            hipLaunchKernelGGL(k_film, dim3((n_pix + SHADE_BLOCK - 1) / SHADE_BLOCK), dim3(SHADE_BLOCK), 0, s->stream, s->dsv, s->pa, pixels, n_pix, n_samples,
+                               s->d_film, s->d_counters, s->pix_group);
         LAUNCH_TRY("k_film");
         if (ev.failed) { g_err = "hipEventCreate failed"; return SHM_ERR_DEVICE; }
     }

@@ -11,11 +11,12 @@
 //                                 textures, texture.h: elsewhere they are dead values; bump_map with a constant
 //                                 displacement is executed literally so that signed zeros match, material.rs:1477-1508)
 //   material.rs:301-311,456-499,603-635,723-742   get_bxdf for Diffuse/Conductor/Dielectric/ThinDielectric
-//   sampling.rs:347-371, filter.rs:99-105         get_camera_sample, BoxFilter::sample
+//   sampling.rs:347-371, filter.rs:99-105         get_camera_sample, BoxFilter::sample (the other pixel filters: filter.h)
 //   camera.rs:1003-1079, 769-792  {Perspective,Orthographic}Camera::generate_ray_differential
 //   film.rs:548-574, 907-914      RgbFilm::add_sample, PixelSensor::to_sensor_rgb
 #pragma once
 #include "bxdf.h"
+#include "filter.h"
 #include "scene.h"
 #include "texture.h"
 
@@ -339,24 +340,37 @@ SHM_HD Ray camera_generate_ray_differential(const ShmCamera& cam, V2 p_film, V2 
 
 // evaluate_pixel_sample head (integrator.rs:338-362): wavelength sample, camera sample, camera ray (+ its scaled differentials).
 // The sampler dimension order (1d lambda | 2d filter | 2d lens | 1d time) is the reference's.
+// FC: the pixel filter's class where the caller is compiled for one (k_generate), FILTER_CLASS_ANY where the scene decides (the oracle); `filter_table`: with
+// FC = FILTER_CLASS_TABULATED the table to sample, the caller's own copy (LDS); not read otherwise (the scene's table: SceneView::dist_data).
+template <int FC = FILTER_CLASS_ANY>
 SHM_HD Ray generate_camera_ray(const SceneView& sv, int px, int py, Rng& rng, bool disable_wavelength_jitter,
                                bool disable_pixel_jitter, Wavelengths& lambda, Float& filter_weight, AuxRays* aux = nullptr,
-                               int samples_per_pixel = 1) {
+                               int samples_per_pixel = 1, const Float* filter_table = nullptr) {
     Float lu = disable_wavelength_jitter ? 0.5f : sampler_get_1d(rng);
     lambda = sample_visible(lu);
     // get_camera_sample, sampling.rs:347-371 (filter.sample(get_pixel_2d()) is drawn in both branches)
     V2 uf = sampler_get_2d(rng);
-    V2 fp = v2(lerp(uf.x, -sv.filter_radius[0], sv.filter_radius[0]), lerp(uf.y, -sv.filter_radius[1], sv.filter_radius[1]));
+    V2 fp;
+    Float fw;
+    const int fc = FC == FILTER_CLASS_ANY ? filter_class_of(sv.filter_kind) : FC;
+    if (fc == FILTER_CLASS_BOX) {  // BoxFilter::sample (filter.rs:99-105), weight 1
+        fp = v2(lerp(uf.x, -sv.filter_radius[0], sv.filter_radius[0]), lerp(uf.y, -sv.filter_radius[1], sv.filter_radius[1]));
+        fw = 1.0f;
+    } else {
+        // (the table is chosen at compile time: a kernel's LDS copy stays an LDS pointer through the searches, not a generic one)
+        filter_sample<FC>(sv.filter_kind, sv.filter_radius[0], sv.filter_radius[1], FC == FILTER_CLASS_TABULATED ? filter_table : sv.dist_data, uf, fp, fw);
+    }
     V2 p_film, p_lens;
     if (disable_pixel_jitter) {
         p_film = v2((Float)px, (Float)py) + v2(0.5f, 0.5f);
         p_lens = v2(0.5f, 0.5f);
+        fw = 1.0f;  // (PBRT-v4's GetCameraSample: the pixel centre with weight 1)
     } else {
         p_film = v2((Float)px, (Float)py) + fp + v2(0.5f, 0.5f);
         p_lens = sampler_get_2d(rng);
         (void)sampler_get_1d(rng);  // time
     }
-    filter_weight = 1.0f;
+    filter_weight = fw;
     Ray r = camera_generate_ray_differential(sv.camera, p_film, p_lens, aux);
     if (aux) {  // integrator.rs:356-362
         Float ray_diff_scale = max(0.125f, 1.0f / sqrt((Float)samples_per_pixel));

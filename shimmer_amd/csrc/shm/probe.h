@@ -16,7 +16,7 @@ enum : int {
     PROBE_TRIANGLE_PDF_WITH_CONTEXT, PROBE_TRIANGLE_INTERACTION, PROBE_SPHERE_SAMPLE_WITH_CONTEXT, PROBE_SPHERE_PDF_WITH_CONTEXT, PROBE_AREA_LIGHT_L, PROBE_FILM_ADD_SAMPLE,
     PROBE_CAMERA_RAY_DIFFERENTIAL, PROBE_INTERVAL_OP, PROBE_DET3, PROBE_ROTATE_FROM_TO, PROBE_SAMPLE_DISCRETE, PROBE_SAMPLER_STREAM, PROBE_SAMPLE_VISIBLE_WAVELENGTHS,
     PROBE_VISIBLE_WAVELENGTHS_PDF, PROBE_VECMATH, PROBE_TRANSFORM_APPLY, PROBE_BLP_INTERSECT, PROBE_BLP_SAMPLE_WITH_CONTEXT, PROBE_BLP_PDF_WITH_CONTEXT, PROBE_SPHERE_INTERSECT,
-    PROBE_UNARY, PROBE_EQUAL_AREA_SQUARE_TO_SPHERE, PROBE_EQUAL_AREA_SPHERE_TO_SQUARE, PROBE_ZSOBOL_STREAM, PROBE_N_OPS
+    PROBE_UNARY, PROBE_EQUAL_AREA_SQUARE_TO_SPHERE, PROBE_EQUAL_AREA_SPHERE_TO_SQUARE, PROBE_ZSOBOL_STREAM, PROBE_FILTER_SAMPLE, PROBE_N_OPS
 };
 
 namespace probe_detail {
@@ -269,6 +269,18 @@ SHM_HD int leaf_probe(int op, const uint32_t* in, uint32_t* out) {
                 }
             }
             return o;
+        }
+        case PROBE_FILTER_SAMPLE: {  // Filter::Sample of a pixel filter (shm/filter.h); kind, xradius, yradius, two parameters (sigma | B, C | tau), n, then n pairs u; behind them the
+                                     // tabulated kinds' table, which the HOST builds (filter_build_table: shm_debug_eval_leaf appends it, a CPU driver does the same). Per draw: p.x, p.y, weight
+            const int n = (int)in[5];
+            const Float* table = reinterpret_cast<const Float*>(in + 6 + 2 * n);
+            for (int i = 0; i < n; ++i) {
+                V2 p;
+                Float w;
+                filter_sample(in[0], f(in, 1), f(in, 2), table, v2(f(in, 6 + 2 * i), f(in, 7 + 2 * i)), p, w);
+                put(out, 3 * i, p.x); put(out, 3 * i + 1, p.y); put(out, 3 * i + 2, w);
+            }
+            return n;
         }
         case PROBE_SAMPLE_VISIBLE_WAVELENGTHS: put(out, 0, sample_visible_wavelengths(f(in, 0))); return 0;  // sampling.rs:347-371
         case PROBE_VISIBLE_WAVELENGTHS_PDF: put(out, 0, visible_wavelengths_pdf(f(in, 0))); return 0;

@@ -81,6 +81,8 @@ struct SceneView {
     Float filter_radius[2];
     Float imaging_ratio;
     Float max_component_value;
+    uint32_t filter_kind;  // SHM_FILTER_* (shm/filter.h); a tabulated filter's table is the first record of dist_data. (In the padding in front of the pointer: the struct is a kernel argument
+                           // of every kernel, and its size and every other member's offset are those of the library without pixel filters)
     const Float* sensor_r_bar;
     const Float* sensor_g_bar;
     const Float* sensor_b_bar;
@@ -101,6 +103,7 @@ struct SceneView {
     const struct FloatTexRange* stex_ranges;  // the same post-order programs for SpectrumTexture trees
     const struct FloatTexOp* stex_ops;
     // image infinite lights: per light its transform + image + the two PiecewiseConstant2D distributions, flattened into dist_data
+    // (in front of them, in a scene with a tabulated pixel filter: the filter's table, shm/filter.h)
     const struct ImageLightRec* image_lights;
     const Float* dist_data;
     uint32_t quirks_off;  // ShmRenderParams::disable_reference_quirks of the render in flight (0 = reference-exact; set per render call)

@@ -313,6 +313,7 @@ struct ShmScene {
     PathArrays pa;
     uint32_t* d_q_active[2] = {nullptr, nullptr};
     uint32_t* d_q_shadow = nullptr;
+    float* d_filter_weight = nullptr;  // per path slot: the pixel filter's weight (scenes whose filter has negative lobes only; render.hip, ensure_workspace)
     uint32_t* d_q_scatter[4] = {nullptr, nullptr, nullptr, nullptr};  // staged shading: one queue per BxDF class present in the scene
     uint32_t* d_q_split = nullptr; // scenes with textures and plain diffuse materials: what the split pass leaves to the textured kernels
     int split_pass = 0;            // ... that pass is on (SHM_SPLIT_PASS; a quarter of the primitives or more are plain diffuse)
@@ -453,10 +454,15 @@ WF_SAMPLED_LAUNCHER(wf_launch_shade_simple); WF_SAMPLED_LAUNCHER(wf_launch_shade
 WF_INTERNAL int wf_launch_fold_randomwalk(ShmScene* s, hipStream_t stream, uint32_t cap_eff, uint32_t total);
 // K1 (render.hip, k_generate<HAS_TEX, LEAN, ZS>)
 using GenerateKernel = void (*)(SceneView, PathArrays, const uint32_t*, uint32_t, int, int, ShmRenderParams, uint32_t*, QueueState*, uint32_t);
+// K1 / K6 of the pixel filters beside the box filter (render.hip, k_generate_filtered<HAS_TEX, LEAN, ZS, FC>, k_film_weighted<W>): + the per-path filter weights (+ the constant K)
+using FilteredGenerateKernel = void (*)(SceneView, PathArrays, const uint32_t*, uint32_t, int, int, ShmRenderParams, uint32_t*, QueueState*, uint32_t, float*);
+using WeightedFilmKernel = void (*)(SceneView, PathArrays, const uint32_t*, uint32_t, int, ShmFilmPixel*, DeviceCounters*, uint32_t, const float*, float);
 // The kernels of one scene class: a cell of render.hip's table by geometry x image class x sampler (nullptr: no such build), of which
 // select_kernels makes a render's set. The bounce loop decides which of them run and calls them through it.
 struct ShadeKernels {
     GenerateKernel generate[2];       // [LEAN]: bounce 0 on known constants (ShadeArgs::first_bounce)
+    FilteredGenerateKernel generate_filtered[2];  // ... of a scene whose pixel filter is not the box filter (null: `generate`), and the film kernel that applies
+    WeightedFilmKernel film_weighted;             // its weights (null: k_film, weight 1) — select_kernels fills the three from the scene's filter class
     ShadeFn lean, lean_diverted;      // k_shade<lean>: the whole queue of an all-diffuse scene / the hits k_vertex or the split pass diverted
     ShadeFn fused_all;                // the material-sorted fused all-materials kernel
     ShadeFn vertex;                   // staged shading: the hit half ...

@@ -557,14 +557,28 @@ class SceneBuilder:
         return prim_index
 
     # ---- camera / film ----
-    def set_film(self, width, height, pixel_bounds=None, filter_radius=(0.5, 0.5), imaging_ratio=1.0, max_component_value=np.inf):
+    # PixelFilter: name -> (SHM_FILTER_*, PBRT-v4's default radius, its default parameters: sigma | B, C | tau)
+    FILTERS = {"box": (abi.SHM_FILTER_BOX, 0.5, ()), "gaussian": (abi.SHM_FILTER_GAUSSIAN, 1.5, (0.5,)), "mitchell": (abi.SHM_FILTER_MITCHELL, 2.0, (1.0 / 3.0, 1.0 / 3.0)),
+               "sinc": (abi.SHM_FILTER_SINC, 4.0, (3.0,)), "triangle": (abi.SHM_FILTER_TRIANGLE, 2.0, ())}
+
+    def set_film(self, width, height, pixel_bounds=None, filter_radius=None, imaging_ratio=1.0, max_component_value=np.inf, filter="box", filter_params=()):
+        """`filter`: box | gaussian | mitchell | sinc | triangle; `filter_radius`: (x, y), default the filter's own (PBRT-v4's); `filter_params`: (sigma,) | (B, C) | (tau,),
+        default the filter's own."""
         t = tables()
         self._sensor = [_as_f32(t["CIE_X"]), _as_f32(t["CIE_Y"]), _as_f32(t["CIE_Z"])]  # PixelSensor::new cie1931 (film.rs:823-837)
         f = abi.ShmFilm()
         pb = pixel_bounds if pixel_bounds is not None else (0, 0, width, height)
         f.pixel_bounds[:] = pb
         f.full_resolution[:] = (width, height)
-        f.filter_radius[:] = filter_radius
+        if filter not in self.FILTERS:
+            raise ValueError(f"unknown pixel filter {filter!r} ({', '.join(self.FILTERS)})")
+        kind, default_radius, default_params = self.FILTERS[filter]
+        params = tuple(filter_params) if len(filter_params) else default_params
+        if len(params) != len(default_params):
+            raise ValueError(f"pixel filter {filter!r} takes {len(default_params)} parameter(s)")
+        f.filter = kind
+        f.filter_radius[:] = filter_radius if filter_radius is not None else (default_radius, default_radius)
+        f.filter_params[:] = (tuple(params) + (0.0, 0.0))[:2]
         f.imaging_ratio = imaging_ratio
         f.max_component_value = max_component_value
         f.sensor_r_bar, f.sensor_g_bar, f.sensor_b_bar = (_fptr(a) for a in self._sensor)

@@ -9,6 +9,9 @@ and are not available offline; SURVEY §8d defines these stand-ins).
 
 All geometry is generated in world space and moved to render space with the camera-world translation
 (camera.rs:507-523), as TriangleMesh::new does at load time (shape/mesh.rs:43-46).
+
+Every builder takes `film`: keyword arguments for SceneBuilder.set_film, e.g. film=dict(filter="gaussian") or
+film=dict(filter="mitchell", filter_radius=(2.0, 1.5), filter_params=(0.5, 0.25)); the default is the box filter.
 """
 import functools
 from types import SimpleNamespace
@@ -60,10 +63,10 @@ def _finish(b, lib, **extra):
     return SimpleNamespace(desc=desc, builder=b, info=info, **extra)
 
 
-def sphere_light(lib, width=128, height=128):
+def sphere_light(lib, width=128, height=128, film=None):
     """S1 (config C1)."""
     b = SceneBuilder()
-    b.set_film(width, height)
+    b.set_film(width, height, **(film or {}))
     rfw = b.set_camera_look_at(lib, (0, 1, 5), (0, 0, 0), (0, 1, 0), 40.0)
     grey = b.material_diffuse(0.5)
     black = b.material_diffuse(0.0)
@@ -97,12 +100,12 @@ def test_image(size=64, channels=3, seed=7):
 
 
 def cornell_box(lib, width=512, height=512, coated=False, mix=False, patches=False, patch_skew=0.0, textured=False,
-                texture_filter=None, textured_coated_ceiling=True, glass=False, emitter_reflects=False, environment=None, glass_too=False):
+                texture_filter=None, textured_coated_ceiling=True, glass=False, emitter_reflects=False, environment=None, glass_too=False, film=None):
     """S2 (config C2): 5 walls x 2 + 2 boxes x 5 faces x 2 + light 2 = 32 triangles.
     coated=True: the tall box becomes CoatedConductor (rough interface, Cu), the short one CoatedDiffuse with a scattering
     medium between the interfaces, the floor CoatedDiffuse with a smooth interface (SURVEY §8f-1 materials)."""
     b = SceneBuilder()
-    b.set_film(width, height)
+    b.set_film(width, height, **(film or {}))
     rfw = b.set_camera_look_at(lib, (0, 1, 3.4), (0, 1, 0), (0, 1, 0), 39.0)
     white = b.material_diffuse(0.75)
     red = b.material_diffuse(_two_point_spectrum(b, 0.05, 0.75))
@@ -307,7 +310,7 @@ def cube_sphere(n, seed=1234, amplitude=0.15, shuffle_seed=99, as_quads=False, q
     return verts, tris
 
 
-def ganesha_proxy(lib, width=1024, height=1024, n=599, with_room=True, coated=False, variant=None, floor_filter="ewa", quad_fraction=None, object_material=None):
+def ganesha_proxy(lib, width=1024, height=1024, n=599, with_room=True, coated=False, variant=None, floor_filter="ewa", quad_fraction=None, object_material=None, film=None):
     """S3 (configs C3/C5): n=599 gives 6*599^2*2 = 4 305 612 triangles and 2 152 808 vertices.
     coated=True: the object is CoatedDiffuse (the material of the reference's Ganesha render, images/shimmer-ganesha-1.png).
     variant (round 5: the shapes a real PBRT-v4 scene mixes into its triangles; same camera, room and object):
@@ -326,7 +329,7 @@ def ganesha_proxy(lib, width=1024, height=1024, n=599, with_room=True, coated=Fa
                        estimation samples its (compensated) piecewise-constant distribution"""
     assert variant in (None, "patch_emitter", "one_sphere", "instanced", "environment", "textured_floor", "textured_hidden", "quads", "smooth", "mesh_emitter", "textured_object", "instance_grid")
     b = SceneBuilder()
-    b.set_film(width, height)
+    b.set_film(width, height, **(film or {}))
     rfw = b.set_camera_look_at(lib, (0.0, 0.6, 4.2), (0.0, 0.0, 0.0), (0, 1, 0), 38.0)
     obj = b.material_coated_diffuse(reflectance=0.4, roughness=0.05, thickness=0.01) if coated else b.material_diffuse(0.4)
     if object_material == "gold":  # (round 6 class probes) a rough conductor / a dispersive glass / a coated conductor object
@@ -457,11 +460,11 @@ def icosphere(level):
     return v.astype(np.float32), f.astype(np.uint32)
 
 
-def crown_proxy(lib, width=1000, height=1400, level=4, n_glass=64, n_gold=16, seed=4242, environment=None):
+def crown_proxy(lib, width=1000, height=1400, level=4, n_glass=64, n_gold=16, seed=4242, environment=None, film=None):
     """S4 (config C4): dispersive smooth dielectric icospheres (BK7 eta table -> terminate_secondary), rough gold
     conductors, diffuse floor, one quad emitter; render with max_depth=32."""
     b = SceneBuilder()
-    b.set_film(width, height)
+    b.set_film(width, height, **(film or {}))
     rfw = b.set_camera_look_at(lib, (0.0, 2.2, 7.5), (0.0, 1.2, 0.0), (0, 1, 0), 32.0)
     glass = b.material_dielectric(b.spectrum_named("glass-BK7"))
     gold = b.material_conductor(b.spectrum_named("metal-Au-eta"), b.spectrum_named("metal-Au-k"), roughness=0.01)  # alpha = sqrt(0.01) = 0.1
@@ -509,12 +512,12 @@ def environment_image(n=32, sun=(0.3, 0.5, 0.81), sun_radiance=40.0):
     return img.astype(np.float32)
 
 
-def three_spheres(lib, width=32, height=32, offsets=(-3.5, 0.0, 5.0), camera=(0.0, 0.0, 0.0), environment=None):
+def three_spheres(lib, width=32, height=32, offsets=(-3.5, 0.0, 5.0), camera=(0.0, 0.0, 0.0), environment=None, film=None):
     """The reference's set_of_spheres BVH test scene (aggregate.rs:631-702): unit spheres at x = -3.5, 0, 5.
     With the default camera at the origin world == render space, as the reference's unit tests assume (rays are given
     in render space); pass a camera position outside the spheres to render it."""
     b = SceneBuilder()
-    b.set_film(width, height)
+    b.set_film(width, height, **(film or {}))
     cam = np.asarray(camera, np.float64)
     rfw = b.set_camera_look_at(lib, cam, cam + np.array([0.0, 0.0, -1.0]), (0, 1, 0), 60.0)
     m = b.material_diffuse(0.5)
@@ -533,14 +536,14 @@ def three_spheres(lib, width=32, height=32, offsets=(-3.5, 0.0, 5.0), camera=(0.
     return _finish(b, lib, name="three spheres" + ("" if environment is None else " (environment map)"))
 
 
-def instanced_scene(lib, width=64, height=48, n_instances=5, only_object=False, baked=False, environment=None):
+def instanced_scene(lib, width=64, height=48, n_instances=5, only_object=False, baked=False, environment=None, film=None):
     """Object instancing: one object definition (an icosphere with per-vertex normals, a partial sphere and a curved
     bilinear patch, three materials) placed several times with rotated, non-uniformly scaled transforms over a floor lit by a quad
     light and a point light. `only_object`: just the object's shapes at top level, untransformed, no floor. `baked`: the same
     placements as explicitly transformed triangle copies (icosphere only) instead of instances — for cross-checks."""
     rng = np.random.Generator(np.random.PCG64(77))
     b = SceneBuilder()
-    b.set_film(width, height)
+    b.set_film(width, height, **(film or {}))
     rfw = b.set_camera_look_at(lib, (0.0, 2.2, 7.0), (0.0, 0.8, 0.0), (0, 1, 0), 40.0)
     mats = [b.material_diffuse(_two_point_spectrum(b, 0.7, 0.2)), b.material_conductor(b.spectrum_named("metal-Cu-eta"), b.spectrum_named("metal-Cu-k"), roughness=0.2),
             b.material_coated_diffuse(reflectance=0.5, roughness=0.1)]
@@ -598,14 +601,14 @@ def instanced_scene(lib, width=64, height=48, n_instances=5, only_object=False, 
     return sc
 
 
-def random_scene(lib, seed, width=40, height=32):
+def random_scene(lib, seed, width=40, height=32, film=None):
     """A seeded random scene for parity fuzzing: every shape kind (triangle meshes with and without per-vertex N / S / uv,
     full and partial transformed spheres, flat and curved bilinear patches), every material kind (including nested mixes
     and both coated ones), area lights on every shape kind, a point light, optionally a uniform infinite light, and a
     thin-lens camera for odd seeds. Nothing here is tuned to look good; it is tuned to reach code."""
     rng = np.random.Generator(np.random.PCG64(seed))
     b = SceneBuilder()
-    b.set_film(width, height)
+    b.set_film(width, height, **(film or {}))
     lens = 0.05 if seed % 2 else 0.0
     # every fourth seed looks through an OrthographicCamera (camera.rs:658-840; its screen window spans [-aspect, aspect] x [-1, 1]
     # world units, so it sees the middle of the scene)
