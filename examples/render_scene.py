@@ -3,7 +3,7 @@
 
     python examples/render_scene.py cornell --spp 256 --res 512 -o cornell.pfm
     python examples/render_scene.py cornell --filter gaussian        (box | gaussian | mitchell | sinc | triangle)
-    python examples/render_scene.py textured | coated | patches | instanced | environment | ganesha | crown | fuzz:13
+    python examples/render_scene.py textured | coated | patches | instanced | environment | ganesha | crown | spotlit | fuzz:13
 
 Everything goes through the C ABI of include/shimmer_hip.h (shimmer_amd/abi.py is the ctypes binding): scene description ->
 shm_scene_create -> shm_render_device -> shm_film_read -> shm_film_get_image -> shm_write_pfm. Needs an MI355X: there is no CPU path.
@@ -24,6 +24,9 @@ from shimmer_amd import abi, render, scenes  # noqa: E402
 def make_scene(lib, name, w, h, film=None):
     if name == "cornell":
         return scenes.cornell_box(lib, w, h, film=film)
+    if name == "spotlit":  # the Cornell box under PBRT-v4's spot and distant lights as well (the *_dl kernels; examples/scenes/spot_and_sun.pbrt is the file form of such a scene)
+        return scenes.cornell_box(lib, w, h, film=film, extra_lights=scenes.spot_and_distant(spot_from=(0.5, 1.7, 0.8), spot_to=(-0.2, 0.3, -0.2), sun_from=(0.3, 0.4, 3.0),
+                                                                                             sun_to=(0.0, 0.8, 0.0)))
     if name == "textured":
         return scenes.cornell_box(lib, w, h, textured=True, film=film)
     if name == "coated":

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SHM_ABI_VERSION 9
+#define SHM_ABI_VERSION 10
 
 /* The library is built with -fvisibility=hidden; only these entry points are exported. */
 #if defined(__GNUC__)
@@ -235,19 +235,33 @@ enum {
     SHM_LIGHT_POINT = 0,            /* light.rs:392-497 */
     SHM_LIGHT_DIFFUSE_AREA = 1,     /* light.rs:499-690; one per emissive shape (loading/scene.rs:609-624) */
     SHM_LIGHT_UNIFORM_INFINITE = 2, /* light.rs:692-816 */
-    SHM_LIGHT_IMAGE_INFINITE = 3    /* ImageInfinitelight, light.rs:805-981 (ABI v6): `primitive` = index into ShmSceneDesc::image_lights;
+    SHM_LIGHT_IMAGE_INFINITE = 3,   /* ImageInfinitelight, light.rs:805-981 (ABI v6): `primitive` = index into ShmSceneDesc::image_lights;
                                        `scale` as for the others; `spectrum` unused (the radiance is the image's RGB as an
                                        RgbIlluminantSpectrum of ShmSceneDesc::color_space, which must carry table and illuminant) */
+    SHM_LIGHT_DISTANT = 4,          /* PBRT-v4's DistantLight (ABI v10; the reference has none): `position` = the unit vector TOWARDS the light in render space,
+                                       normalize(render_from_light(from - to)); scale * spectrum = the emitted radiance L (numerically the irradiance on a
+                                       surface that faces the light). A delta light; NOT an infinite light for escaped rays */
+    SHM_LIGHT_SPOT = 5              /* PBRT-v4's SpotLight (ABI v10): `position` = the apex render_from_light(0,0,0); `primitive` = index into
+                                       ShmSceneDesc::spot_lights; scale * spectrum = the intensity I on the axis. A delta light */
 };
 typedef struct ShmLight {
     uint32_t kind;
-    uint32_t primitive;    /* DIFFUSE_AREA: index into primitives (leaf order) of its shape */
+    uint32_t primitive;    /* DIFFUSE_AREA: index into primitives (leaf order) of its shape; IMAGE_INFINITE: into image_lights; SPOT: into spot_lights */
     float scale;           /* final scale (after /spectrum_to_photometric, power...) */
     uint32_t two_sided;
-    float position[3];     /* POINT: render_from_light(0,0,0) */
+    float position[3];     /* POINT, SPOT: render_from_light(0,0,0); DISTANT: the unit direction towards the light */
     float area;            /* DIFFUSE_AREA: shape.area() (light.rs:543) */
     ShmSpectrum spectrum;  /* DenselySampledSpectrum of I / Lemit (must be DENSE) */
 } ShmLight;
+
+/* What a SHM_LIGHT_SPOT needs beside its ShmLight (ABI v10; PBRT-v4 SpotLight). Light space: the apex at the origin, the axis along +z. */
+typedef struct ShmSpotLight {
+    float render_from_light[16];  /* SpotLight::renderFromLight, row-major 4x4: render_from_object * translate(from) * inverse(frame with z = normalize(to - from)) */
+    float light_from_render[16];  /* its inverse: a direction w is taken to light space by the 3x3 linear part of THIS matrix (renderFromLight.ApplyInverse) */
+    float cos_falloff_start;      /* SpotLight::cosFalloffStart = cos(radians(coneangle - conedelta)): full intensity inside */
+    float cos_falloff_end;        /* SpotLight::cosFalloffEnd = cos(radians(coneangle)): zero outside; -1 <= cos_falloff_end <= cos_falloff_start <= 1 */
+    uint32_t pad[2];
+} ShmSpotLight;
 
 /* ---- camera, film ---------------------------------------------------------------------------- */
 
@@ -386,6 +400,10 @@ typedef struct ShmSceneDesc {
     uint32_t n_instances;
     const ShmSpectrumTexture* spectrum_textures;
     const ShmInstance* instances;
+    /* ABI v10: the side records of the SHM_LIGHT_SPOT lights (ShmLight::primitive indexes them) */
+    uint32_t n_spot_lights;
+    uint32_t pad2;
+    const ShmSpotLight* spot_lights;
 } ShmSceneDesc;
 
 /* ---- render parameters ----------------------------------------------------------------------- */
@@ -681,7 +699,7 @@ SHM_API void shm_ply_free(ShmPlyMesh* mesh);
  * Integrator (path / simplepath / randomwalk), Option, WorldBegin, AttributeBegin / End, Material / MakeNamedMaterial / NamedMaterial
  * (diffuse conductor dielectric thindielectric coateddiffuse coatedconductor mix, "normalmap"), Texture (float / spectrum: constant scale
  * mix directionmix imagemap — with the uv / spherical / cylindrical / planar mappings), AreaLightSource (diffuse), LightSource (point,
- * infinite: uniform or an environment image), Shape (trianglemesh bilinearmesh sphere plymesh), ObjectBegin / ObjectEnd / ObjectInstance,
+ * spot, distant — the two as PBRT-v4 defines them —, infinite: uniform or an environment image), Shape (trianglemesh bilinearmesh sphere plymesh), ObjectBegin / ObjectEnd / ObjectInstance,
  * Include — with the reference's parameter names and defaults. Spectra: "float", "spectrum" (lambda / value pairs, a named spectrum or a
  * spectrum file), "blackbody", and "rgb" as RgbAlbedo / RgbUnbounded / RgbIlluminantSpectrum by the slot that reads it (paramdict.rs:605-656)
  * through the sRGB rgb2spec coefficient table — the `.spec` file the reference loads from rgbtospec/srgb.spec (rgb_to_spectra.rs:27-31),

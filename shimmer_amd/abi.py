@@ -10,7 +10,7 @@ from pathlib import Path
 ROOT = Path(__file__).resolve().parent
 LIB_PATH = ROOT / "csrc" / "libshimmer_hip.so"
 
-SHM_ABI_VERSION = 9
+SHM_ABI_VERSION = 10
 SHM_OK = 0
 SHM_DIST_ID_BYTES = 128
 SHM_SHAPE_TRIANGLE, SHM_SHAPE_SPHERE, SHM_SHAPE_BILINEAR_PATCH, SHM_SHAPE_INSTANCE = 0, 1, 2, 3
@@ -19,6 +19,7 @@ SHM_SPECTRUM_RGB_ALBEDO, SHM_SPECTRUM_RGB_UNBOUNDED, SHM_SPECTRUM_RGB_ILLUMINANT
 SHM_MATERIAL_DIFFUSE, SHM_MATERIAL_CONDUCTOR, SHM_MATERIAL_DIELECTRIC, SHM_MATERIAL_THIN_DIELECTRIC = 0, 1, 2, 3
 SHM_MATERIAL_COATED_DIFFUSE, SHM_MATERIAL_COATED_CONDUCTOR, SHM_MATERIAL_MIX = 4, 5, 6
 SHM_LIGHT_POINT, SHM_LIGHT_DIFFUSE_AREA, SHM_LIGHT_UNIFORM_INFINITE, SHM_LIGHT_IMAGE_INFINITE = 0, 1, 2, 3
+SHM_LIGHT_DISTANT, SHM_LIGHT_SPOT = 4, 5  # PBRT-v4's DistantLight / SpotLight (ABI v10)
 SHM_SPECTRUM_IMAGE_TEXTURE, SHM_SPECTRUM_TEXTURE_NODE = 6, 7
 SHM_SPECTEX_LEAF, SHM_SPECTEX_SCALED, SHM_SPECTEX_MIX, SHM_SPECTEX_DIRECTION_MIX = 0, 1, 2, 3
 SHM_TEXMAP_UV, SHM_TEXMAP_SPHERICAL, SHM_TEXMAP_CYLINDRICAL, SHM_TEXMAP_PLANAR = 0, 1, 2, 3
@@ -126,6 +127,11 @@ class ShmImageInfiniteLight(C.Structure):
                 ("pad", C.c_uint32)]
 
 
+class ShmSpotLight(C.Structure):
+    _fields_ = [("render_from_light", C.c_float * 16), ("light_from_render", C.c_float * 16), ("cos_falloff_start", C.c_float),
+                ("cos_falloff_end", C.c_float), ("pad", C.c_uint32 * 2)]
+
+
 class ShmPlyMesh(C.Structure):
     _fields_ = [("n_vertices", C.c_uint32), ("n_tri_indices", C.c_uint32), ("n_quad_indices", C.c_uint32), ("n_face_indices", C.c_uint32),
                 ("p", c_float_p), ("n", c_float_p), ("uv", c_float_p), ("tri_indices", C.POINTER(C.c_int32)),
@@ -157,7 +163,8 @@ class ShmSceneDesc(C.Structure):
                 ("color_space", ShmColorSpace), ("ewa_filter_lut", c_float_p), ("n_image_lights", C.c_uint32), ("n_float_textures", C.c_uint32),
                 ("image_lights", C.POINTER(ShmImageInfiniteLight)), ("float_textures", C.POINTER(ShmFloatTexture)),
                 ("n_spectrum_textures", C.c_uint32), ("n_instances", C.c_uint32), ("spectrum_textures", C.POINTER(ShmSpectrumTexture)),
-                ("instances", C.POINTER(ShmInstance))]
+                ("instances", C.POINTER(ShmInstance)),
+                ("n_spot_lights", C.c_uint32), ("pad2", C.c_uint32), ("spot_lights", C.POINTER(ShmSpotLight))]
 
 
 class ShmRenderParams(C.Structure):

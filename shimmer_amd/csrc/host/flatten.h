@@ -6,6 +6,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <cmath>
 #include <string>
 #include <utility>
 #include <vector>
@@ -30,7 +31,9 @@ struct FlatScene {
     std::vector<float> patch_vn, patch_vuv;
     std::vector<ShmMaterial> materials;
     std::vector<ShmLight> lights;
-    std::vector<shm::PrimRec> light_prim_recs;  // per light: the emitter's record (area lights; zeros otherwise): SceneView::light_prim_recs
+    std::vector<shm::PrimRec> light_prim_recs;  // per light: the emitter's record (area lights), the 3x3 of light_from_render + the two cosines (spot lights: shm/path.h,
+                                                // spot_cos_theta), zeros otherwise: SceneView::light_prim_recs
+    bool has_directed_lights = false;  // a SHM_LIGHT_DISTANT or SHM_LIGHT_SPOT: selects the *_dl shading kernels (wavefront.h, K_DELTA_LIGHTS)
     std::vector<uint32_t> infinite_lights;
     std::vector<float> spectrum_data;
     std::vector<float> sensor_r, sensor_g, sensor_b;
@@ -603,7 +606,7 @@ inline int flatten_scene(const ShmSceneDesc* d, FlatScene& out, std::string& err
     }
     for (uint32_t i = 0; i < out.lights.size(); ++i) {
         const ShmLight& l = out.lights[i];
-        if (l.kind > SHM_LIGHT_IMAGE_INFINITE) { err = "unsupported light kind"; return SHM_ERR_UNSUPPORTED; }
+        if (l.kind > SHM_LIGHT_SPOT) { err = "unsupported light kind"; return SHM_ERR_UNSUPPORTED; }
         if (l.kind == SHM_LIGHT_IMAGE_INFINITE) {
             if (l.primitive >= d->n_image_lights) { err = "image infinite light index out of range"; return SHM_ERR_INVALID_ARGUMENT; }
             out.infinite_lights.push_back(i);
@@ -613,11 +616,39 @@ inline int flatten_scene(const ShmSceneDesc* d, FlatScene& out, std::string& err
         if (!check_spectrum(l.spectrum, nsf, err)) return SHM_ERR_INVALID_ARGUMENT;
         if (l.kind == SHM_LIGHT_DIFFUSE_AREA && l.primitive >= d->n_primitives) { err = "area light primitive out of range"; return SHM_ERR_INVALID_ARGUMENT; }
         if (l.kind == SHM_LIGHT_UNIFORM_INFINITE) out.infinite_lights.push_back(i);
+        if (l.kind == SHM_LIGHT_DISTANT || l.kind == SHM_LIGHT_SPOT) {  // (delta lights: never in infinite_lights)
+            if (!std::isfinite(l.scale)) { err = "distant / spot light: scale is not finite"; return SHM_ERR_INVALID_ARGUMENT; }
+            for (int k = 0; k < 3; ++k)
+                if (!std::isfinite(l.position[k])) { err = l.kind == SHM_LIGHT_DISTANT ? "distant light: direction is not finite" : "spot light: position is not finite"; return SHM_ERR_INVALID_ARGUMENT; }
+            out.has_directed_lights = true;
+        }
+        if (l.kind == SHM_LIGHT_DISTANT) {
+            const double len2 = (double)l.position[0] * l.position[0] + (double)l.position[1] * l.position[1] + (double)l.position[2] * l.position[2];
+            if (std::fabs(len2 - 1.0) > 1e-5) { err = "distant light: direction (ShmLight::position) must be a unit vector"; return SHM_ERR_INVALID_ARGUMENT; }
+        }
+        if (l.kind == SHM_LIGHT_SPOT) {
+            if (l.primitive >= d->n_spot_lights || !d->spot_lights) { err = "spot light index out of range"; return SHM_ERR_INVALID_ARGUMENT; }
+            const ShmSpotLight& sp = d->spot_lights[l.primitive];
+            for (int k = 0; k < 16; ++k)
+                if (!std::isfinite(sp.render_from_light[k]) || !std::isfinite(sp.light_from_render[k])) { err = "spot light: transform is not finite"; return SHM_ERR_INVALID_ARGUMENT; }
+            // (negated comparisons: a NaN fails them)
+            if (!(-1.0f <= sp.cos_falloff_end && sp.cos_falloff_end <= sp.cos_falloff_start && sp.cos_falloff_start <= 1.0f)) {
+                err = "spot light: need -1 <= cos_falloff_end <= cos_falloff_start <= 1"; return SHM_ERR_INVALID_ARGUMENT;
+            }
+        }
     }
     // the emitters' records beside the light table (same bytes as prim_recs[light.primitive]: a light sample starts from this small, cacheable / LDS-staged copy)
     out.light_prim_recs.assign(out.lights.size(), shm::PrimRec{});
     for (uint32_t i = 0; i < out.lights.size(); ++i)
         if (out.lights[i].kind == SHM_LIGHT_DIFFUSE_AREA) out.light_prim_recs[i] = out.prim_recs[out.lights[i].primitive];
+    for (uint32_t i = 0; i < out.lights.size(); ++i) {
+        if (out.lights[i].kind != SHM_LIGHT_SPOT) continue;
+        const ShmSpotLight& sp = d->spot_lights[out.lights[i].primitive];
+        shm::PrimRec& r = out.light_prim_recs[i];
+        for (int k = 0; k < 3; ++k) { r.p0[k] = sp.light_from_render[k]; r.p1[k] = sp.light_from_render[4 + k]; r.p2[k] = sp.light_from_render[8 + k]; }
+        r.mesh = shm::float_to_bits(sp.cos_falloff_start);
+        r.tri = shm::float_to_bits(sp.cos_falloff_end);
+    }
 
     // BVH validation + depth (explicit stack; DFS order means child0 = i+1). The top-level tree starts at node 0, the tree of every
     // instanced object at its ShmInstance::root_node; a top-level leaf holding an instance continues into that tree (one more stack

@@ -801,6 +801,10 @@ private:
     std::string resolve(const std::string& f) const { return (f.empty() || f[0] == '/' || base_dir_.empty()) ? f : base_dir_ + "/" + f; }
 
     // ---- lights (light.rs:92-200, 424-452) ----
+    static V3 point_param(const Params& ps, const char* name, V3 dflt) {  // a "point3" parameter, or its default
+        const std::vector<float> v = ps.floats(name);
+        return v.size() == 3 ? shm::v3(v[0], v[1], v[2]) : dflt;
+    }
     void light_source(const std::string& type, const Params& ps, Tokenizer& tk, int line) {
         ShmLight l;
         memset(&l, 0, sizeof(l));
@@ -879,8 +883,68 @@ private:
             if (e_v > 0.0f) scale *= e_v / (4.0f * 3.14159265358979323846f);  // light.rs:128-133 (k_e = 4 pi there)
             l.scale = scale;
             l.spectrum = a_->spec_dense(dense);
+        } else if (type == "distant") {  // PBRT-v4 DistantLight::Create (lights.cpp): the reference has no such light
+            l.kind = SHM_LIGHT_DISTANT;
+            SpectrumValue d65;  // "L" absent: the colour space's illuminant
+            d65.kind = SpectrumValue::DENSE;
+            d65.dense = illuminant_dense(gs_.color_space);
+            const Param* lp = ps.find("L");
+            const std::vector<float> dense = a_->dense_of(lp ? spectrum_of(*lp, tk) : d65);
+            scale /= spectrum_to_photometric(dense);
+            const float e_v = ps.one_float("illuminance", -1.0f);
+            if (e_v > 0.0f) scale *= e_v;  // (the illuminance on a surface that faces the light)
+            const V3 from = point_param(ps, "from", shm::v3(0.0f, 0.0f, 0.0f)), to = point_param(ps, "to", shm::v3(0.0f, 0.0f, 1.0f));
+            if (shm::length_squared(from - to) == 0.0f) fail(tk.where(line) + ": distant light: \"from\" and \"to\" coincide");
+            const V3 w_render = xf_vector(render_from_object().m, shm::normalize(from - to));
+            if (!(shm::length_squared(w_render) > 0.0f)) fail(tk.where(line) + ": distant light: the transform is degenerate");
+            const V3 w = shm::normalize(w_render);  // wi of every sample: towards the light
+            l.position[0] = w.x; l.position[1] = w.y; l.position[2] = w.z;
+            l.scale = scale;
+            l.spectrum = a_->spec_dense(dense);
+        } else if (type == "spot") {  // PBRT-v4 SpotLight::Create
+            l.kind = SHM_LIGHT_SPOT;
+            SpectrumValue d65;
+            d65.kind = SpectrumValue::DENSE;
+            d65.dense = illuminant_dense(gs_.color_space);
+            const Param* ip = ps.find("I");
+            const std::vector<float> dense = a_->dense_of(ip ? spectrum_of(*ip, tk) : d65);
+            scale /= spectrum_to_photometric(dense);
+            const float coneangle = ps.one_float("coneangle", 30.0f), conedelta = ps.one_float("conedelta", 5.0f);
+            const float rad = 3.14159265358979323846f / 180.0f;
+            ShmSpotLight sp;
+            memset(&sp, 0, sizeof(sp));
+            sp.cos_falloff_end = cosf(coneangle * rad);
+            sp.cos_falloff_start = cosf((coneangle - conedelta) * rad);
+            if (!(-1.0f <= sp.cos_falloff_end && sp.cos_falloff_end <= sp.cos_falloff_start && sp.cos_falloff_start <= 1.0f))
+                fail(tk.where(line) + ": spot light: need 0 <= coneangle - conedelta <= coneangle <= 180");
+            const float phi_v = ps.one_float("power", -1.0f);
+            if (phi_v > 0.0f) {  // the integral of the smoothstep ramp over its cosine range is half its width
+                const float k_e = 2.0f * 3.14159265358979323846f * ((1.0f - sp.cos_falloff_start) + (sp.cos_falloff_start - sp.cos_falloff_end) / 2.0f);
+                scale *= phi_v / k_e;
+            }
+            const V3 from = point_param(ps, "from", shm::v3(0.0f, 0.0f, 0.0f)), to = point_param(ps, "to", shm::v3(0.0f, 0.0f, 1.0f));
+            if (shm::length_squared(to - from) == 0.0f) fail(tk.where(line) + ": spot light: \"from\" and \"to\" coincide");
+            // render_from_object * translate(from) * inverse(Frame::FromZ(normalize(to - from))): the frame's inverse has its axes as columns
+            const V3 z = shm::normalize(to - from);
+            V3 x, y;
+            shm::coordinate_system(z, x, y);
+            Xf frame_inv = xf_identity();
+            float(*fm)[4] = frame_inv.m.m;
+            fm[0][0] = x.x; fm[1][0] = x.y; fm[2][0] = x.z;
+            fm[0][1] = y.x; fm[1][1] = y.y; fm[2][1] = y.z;
+            fm[0][2] = z.x; fm[1][2] = z.y; fm[2][2] = z.z;
+            frame_inv.inv = m4_transpose(frame_inv.m);
+            const Xf rfl = xf_mul(render_from_object(), xf_mul(xf_translate(from.x, from.y, from.z), frame_inv));
+            memcpy(sp.render_from_light, rfl.m.m, sizeof(float) * 16);
+            memcpy(sp.light_from_render, rfl.inv.m, sizeof(float) * 16);
+            const V3 pos = xf_point(rfl.m, shm::v3s(0.0f));
+            l.position[0] = pos.x; l.position[1] = pos.y; l.position[2] = pos.z;
+            l.scale = scale;
+            l.spectrum = a_->spec_dense(dense);
+            a_->spot_lights.push_back(sp);
+            l.primitive = (uint32_t)a_->spot_lights.size() - 1;
         } else {
-            fail(tk.where(line) + ": light \"" + type + "\" is not supported by this backend (point, infinite)", SHM_ERR_UNSUPPORTED);
+            fail(tk.where(line) + ": light \"" + type + "\" is not supported by this backend (point, spot, distant, infinite)", SHM_ERR_UNSUPPORTED);
         }
         a_->lights.push_back(l);
     }

@@ -208,6 +208,7 @@ public:
     std::vector<ShmImageLevel> image_levels;
     std::vector<float> texels;
     std::vector<ShmImageInfiniteLight> image_lights;
+    std::vector<ShmSpotLight> spot_lights;  // (ShmLight::primitive of a SHM_LIGHT_SPOT)
     std::vector<float> ewa_lut = PBRT_TABLE(MIP_FILTER_LUT);
     Rgb2SpecTable rgb2spec_tables[N_COLOR_SPACES];    // per named colour space, loaded the first time something needs it
     std::vector<float> cs_illuminants[N_COLOR_SPACES];  // RgbColorSpace::illuminant, densely sampled (colorspace.rs:63-65): StdIllum-D65 / ACES D60
@@ -691,6 +692,7 @@ public:
         d.n_image_levels = (uint32_t)a.image_levels.size(); d.image_levels = a.image_levels.data();
         d.n_texel_floats = a.texels.size(); d.texel_data = a.texels.data();
         d.n_image_lights = (uint32_t)a.image_lights.size(); d.image_lights = a.image_lights.data();
+        d.n_spot_lights = (uint32_t)a.spot_lights.size(); d.spot_lights = a.spot_lights.empty() ? nullptr : a.spot_lights.data();
         if (!a.image_textures.empty() || !a.image_lights.empty()) d.ewa_filter_lut = a.ewa_lut.data();
         if (a.rgb2spec().res) {  // ShmColorSpace (only when something asked for it: RGB images, image lights — the sRGB table, see rgb2spec())
             d.color_space.rgb2spec_res = a.rgb2spec().res;

@@ -13,18 +13,22 @@
 #endif
 #if K_ENV_LIGHT  // (the *_env.hip units' kernels carry their own names: a kernel trace tells them from the units without the light — tools/kernel_coverage.py)
 #if K_ZSOBOL
-#define k_scatter k_scatter_env_zs
-#define k_scatter_specular k_scatter_specular_env_zs
-#define k_scatter_nonspecular k_scatter_nonspecular_env_zs
+#define k_scatter WF_DL_NAME(k_scatter_env_zs)
+#define k_scatter_specular WF_DL_NAME(k_scatter_specular_env_zs)
+#define k_scatter_nonspecular WF_DL_NAME(k_scatter_nonspecular_env_zs)
 #else
-#define k_scatter k_scatter_env
-#define k_scatter_specular k_scatter_specular_env
-#define k_scatter_nonspecular k_scatter_nonspecular_env
+#define k_scatter WF_DL_NAME(k_scatter_env)
+#define k_scatter_specular WF_DL_NAME(k_scatter_specular_env)
+#define k_scatter_nonspecular WF_DL_NAME(k_scatter_nonspecular_env)
 #endif
-#elif K_ZSOBOL  // (the *_zs objects' kernels, wavefront.h)
-#define k_scatter k_scatter_zs
-#define k_scatter_specular k_scatter_specular_zs
-#define k_scatter_nonspecular k_scatter_nonspecular_zs
+#elif K_ZSOBOL  // (the *_zs and *_zs_dl objects' kernels, wavefront.h)
+#define k_scatter WF_DL_NAME(k_scatter_zs)
+#define k_scatter_specular WF_DL_NAME(k_scatter_specular_zs)
+#define k_scatter_nonspecular WF_DL_NAME(k_scatter_nonspecular_zs)
+#elif K_DELTA_LIGHTS  // (the *_dl objects')
+#define k_scatter k_scatter_dl
+#define k_scatter_specular k_scatter_specular_dl
+#define k_scatter_nonspecular k_scatter_nonspecular_dl
 #endif
 namespace {
 

@@ -24,6 +24,6 @@ static int launch_dielectric(ShmScene* s, const ShadeArgs& a, bool tri_only, boo
     }
     return SHM_OK;
 }
-template <> int wf_launch_scatter_dielectric_tex<K_ZSOBOL>(ShmScene* s, const ShadeArgs& a) { return launch_dielectric(s, a, false, true); }
-template <> int wf_launch_scatter_dielectric_tri<K_ZSOBOL>(ShmScene* s, const ShadeArgs& a) { return launch_dielectric(s, a, true, false); }
-template <> int wf_launch_scatter_dielectric_gen<K_ZSOBOL>(ShmScene* s, const ShadeArgs& a) { return launch_dielectric(s, a, false, false); }
+template <> int wf_launch_scatter_dielectric_tex<K_ZSOBOL, K_DELTA_LIGHTS>(ShmScene* s, const ShadeArgs& a) { return launch_dielectric(s, a, false, true); }
+template <> int wf_launch_scatter_dielectric_tri<K_ZSOBOL, K_DELTA_LIGHTS>(ShmScene* s, const ShadeArgs& a) { return launch_dielectric(s, a, true, false); }
+template <> int wf_launch_scatter_dielectric_gen<K_ZSOBOL, K_DELTA_LIGHTS>(ShmScene* s, const ShadeArgs& a) { return launch_dielectric(s, a, false, false); }

@@ -19,5 +19,5 @@ static int launch_dielectric(ShmScene* s, const ShadeArgs& a, bool tri_only) {
     }
     return SHM_OK;
 }
-template <> int wf_launch_scatter_dielectric_tri_env<K_ZSOBOL>(ShmScene* s, const ShadeArgs& a) { return launch_dielectric(s, a, true); }
-template <> int wf_launch_scatter_dielectric_gen_env<K_ZSOBOL>(ShmScene* s, const ShadeArgs& a) { return launch_dielectric(s, a, false); }
+template <> int wf_launch_scatter_dielectric_tri_env<K_ZSOBOL, K_DELTA_LIGHTS>(ShmScene* s, const ShadeArgs& a) { return launch_dielectric(s, a, true); }
+template <> int wf_launch_scatter_dielectric_gen_env<K_ZSOBOL, K_DELTA_LIGHTS>(ShmScene* s, const ShadeArgs& a) { return launch_dielectric(s, a, false); }

@@ -23,12 +23,14 @@
 #endif
 #if K_ENV_LIGHT  // (the *_env.hip units' kernels carry their own names: a kernel trace tells them from the units without the light — tools/kernel_coverage.py)
 #if K_ZSOBOL
-#define k_scatter_layered k_scatter_layered_env_zs
+#define k_scatter_layered WF_DL_NAME(k_scatter_layered_env_zs)
 #else
-#define k_scatter_layered k_scatter_layered_env
+#define k_scatter_layered WF_DL_NAME(k_scatter_layered_env)
 #endif
-#elif K_ZSOBOL  // (the *_zs objects' kernels, wavefront.h)
-#define k_scatter_layered k_scatter_layered_zs
+#elif K_ZSOBOL  // (the *_zs and *_zs_dl objects' kernels, wavefront.h)
+#define k_scatter_layered WF_DL_NAME(k_scatter_layered_zs)
+#elif K_DELTA_LIGHTS  // (the *_dl objects')
+#define k_scatter_layered k_scatter_layered_dl
 #endif
 namespace {
 

@@ -2,8 +2,10 @@
 // k_shade_lean.hip for the all-diffuse triangle scene class (every other class runs the staged k_vertex -> k_scatter<class>).
 #pragma once
 #include "wavefront.h"
-#if K_ZSOBOL  // (the *_zs objects' kernels, wavefront.h)
-#define k_shade k_shade_zs
+#if K_ZSOBOL  // (the *_zs and *_zs_dl objects' kernels, wavefront.h)
+#define k_shade WF_DL_NAME(k_shade_zs)
+#elif K_DELTA_LIGHTS  // (the *_dl objects')
+#define k_shade k_shade_dl
 #endif
 
 namespace {

@@ -38,6 +38,11 @@ extern "C" __attribute__((visibility("default"))) int shm_debug_eval_leaf(int de
         g_probe_err = "shm_debug_eval_leaf: the zsobol stream needs 10 + n argument words and 4 n output words";
         return SHM_ERR_INVALID_ARGUMENT;
     }
+    // the light sample reads a spectrum table of in[16] floats behind its 26 fixed words
+    if (op == shm::PROBE_LIGHT_SAMPLE_LI && (n_in < 26 || in_words[16] > 4096 || n_in < 26 + in_words[16] || n_out < 8)) {
+        g_probe_err = "shm_debug_eval_leaf: the light sample needs 26 + n_table argument words and 8 output words";
+        return SHM_ERR_INVALID_ARGUMENT;
+    }
     // the pixel filters: the table of a tabulated kind is built here, on the host, as flatten_scene builds a scene's (no exp or sin of a filter runs on the device), and appended
     std::vector<uint32_t> with_table;
     if (op == shm::PROBE_FILTER_SAMPLE) {

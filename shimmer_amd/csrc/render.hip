@@ -310,37 +310,37 @@ static bool use_staged(const ShmScene* s, const ShmRenderParams* params) {
     // (the lean class through the staged pipeline, measured: shade + generate + film 130 -> 165 ms per headline frame)
     return !scene_is_lean(s) || params->force_diffuse != 0;
 }
-// Which kernels a scene runs: one cell per geometry x image class x sampler
+// Which kernels a scene runs: one cell per geometry x image class x sampler x delta lights (DL: the *_dl builds, wavefront.h K_DELTA_LIGHTS)
 enum : int { GEO_TRI, GEO_GEN, N_GEO };            // top-level triangles only / spheres, bilinear patches or instances too
 enum : int { IMG_NONE, IMG_TEX, IMG_ENV, N_IMG };  // no image / image textures (ray differentials, MIP filtering) / an ImageInfinitelight alone (the K_ENV_LIGHT units)
-template <bool ZS>
+template <bool ZS, bool DL>
 constexpr ShadeKernels shade_cells[N_GEO][N_IMG] = {
-    {{.generate = {k_generate<false, false, ZS>, k_generate<false, true, ZS>}, .lean = wf_launch_shade_lean<ZS>, .lean_diverted = wf_launch_shade_lean_diverted<ZS>,
-      .fused_all = wf_launch_shade_tail_sorted<ZS>, .vertex = wf_launch_vertex_tri,
-      .scatter = {wf_launch_scatter_diffuse_tri<ZS>, wf_launch_scatter_conductor_tri<ZS>, wf_launch_scatter_dielectric_tri<ZS>, wf_launch_scatter_layered_staged_tri<ZS>},
-      .scatter_layered_onepass = wf_launch_scatter_layered_tri<ZS>, .simple = wf_launch_shade_simple<ZS>, .randomwalk = wf_launch_shade_randomwalk<ZS>},
+    {{.generate = {k_generate<false, false, ZS>, k_generate<false, true, ZS>}, .lean = wf_launch_shade_lean<ZS, DL>, .lean_diverted = wf_launch_shade_lean_diverted<ZS, DL>,
+      .fused_all = wf_launch_shade_tail_sorted<ZS, DL>, .vertex = wf_launch_vertex_tri,
+      .scatter = {wf_launch_scatter_diffuse_tri<ZS, DL>, wf_launch_scatter_conductor_tri<ZS, DL>, wf_launch_scatter_dielectric_tri<ZS, DL>, wf_launch_scatter_layered_staged_tri<ZS, DL>},
+      .scatter_layered_onepass = wf_launch_scatter_layered_tri<ZS, DL>, .simple = wf_launch_shade_simple<ZS, DL>, .randomwalk = wf_launch_shade_randomwalk<ZS, false>},
      {.generate = {k_generate<true, false, ZS>, nullptr}, .lean = nullptr, .lean_diverted = nullptr,
-      .fused_all = wf_launch_shade_fused_tex<ZS>, .vertex = wf_launch_vertex_tex,
-      .scatter = {wf_launch_scatter_diffuse_tex<ZS>, wf_launch_scatter_conductor_tex<ZS>, wf_launch_scatter_dielectric_tex<ZS>, wf_launch_scatter_layered_staged_tex<ZS>},
-      .scatter_layered_onepass = wf_launch_scatter_layered_tex<ZS>, .simple = wf_launch_shade_simple<ZS>, .randomwalk = wf_launch_shade_randomwalk<ZS>},
-     {.generate = {k_generate<false, false, ZS>, k_generate<false, true, ZS>}, .lean = wf_launch_shade_lean_env<ZS>, .lean_diverted = wf_launch_shade_lean_env_diverted<ZS>,
-      .fused_all = wf_launch_shade_tail_sorted_env<ZS>, .vertex = wf_launch_vertex_tri_env,
-      .scatter = {wf_launch_scatter_diffuse_tri_env<ZS>, wf_launch_scatter_conductor_tri_env<ZS>, wf_launch_scatter_dielectric_tri_env<ZS>, wf_launch_scatter_layered_staged_tri_env<ZS>},
-      .scatter_layered_onepass = wf_launch_scatter_layered_tri<ZS>,  // (no K_ENV_LIGHT build: never reached, select_kernels)
-      .simple = wf_launch_shade_simple<ZS>, .randomwalk = wf_launch_shade_randomwalk<ZS>}},
-    {{.generate = {k_generate<false, false, ZS>, k_generate<false, true, ZS>}, .lean = wf_launch_shade_lean_gen<ZS>, .lean_diverted = wf_launch_shade_lean_gen_diverted<ZS>,
-      .fused_all = wf_launch_shade_fused_gen<ZS>, .vertex = wf_launch_vertex_gen,
-      .scatter = {wf_launch_scatter_diffuse_gen<ZS>, wf_launch_scatter_conductor_gen<ZS>, wf_launch_scatter_dielectric_gen<ZS>, wf_launch_scatter_layered_staged_gen<ZS>},
-      .scatter_layered_onepass = wf_launch_scatter_layered_gen<ZS>, .simple = wf_launch_shade_simple<ZS>, .randomwalk = wf_launch_shade_randomwalk<ZS>},
+      .fused_all = wf_launch_shade_fused_tex<ZS, DL>, .vertex = wf_launch_vertex_tex,
+      .scatter = {wf_launch_scatter_diffuse_tex<ZS, DL>, wf_launch_scatter_conductor_tex<ZS, DL>, wf_launch_scatter_dielectric_tex<ZS, DL>, wf_launch_scatter_layered_staged_tex<ZS, DL>},
+      .scatter_layered_onepass = wf_launch_scatter_layered_tex<ZS, DL>, .simple = wf_launch_shade_simple<ZS, DL>, .randomwalk = wf_launch_shade_randomwalk<ZS, false>},
+     {.generate = {k_generate<false, false, ZS>, k_generate<false, true, ZS>}, .lean = wf_launch_shade_lean_env<ZS, DL>, .lean_diverted = wf_launch_shade_lean_env_diverted<ZS, DL>,
+      .fused_all = wf_launch_shade_tail_sorted_env<ZS, DL>, .vertex = wf_launch_vertex_tri_env,
+      .scatter = {wf_launch_scatter_diffuse_tri_env<ZS, DL>, wf_launch_scatter_conductor_tri_env<ZS, DL>, wf_launch_scatter_dielectric_tri_env<ZS, DL>, wf_launch_scatter_layered_staged_tri_env<ZS, DL>},
+      .scatter_layered_onepass = wf_launch_scatter_layered_tri<ZS, DL>,  // (no K_ENV_LIGHT build: never reached, select_kernels)
+      .simple = wf_launch_shade_simple<ZS, DL>, .randomwalk = wf_launch_shade_randomwalk<ZS, false>}},
+    {{.generate = {k_generate<false, false, ZS>, k_generate<false, true, ZS>}, .lean = wf_launch_shade_lean_gen<ZS, DL>, .lean_diverted = wf_launch_shade_lean_gen_diverted<ZS, DL>,
+      .fused_all = wf_launch_shade_fused_gen<ZS, DL>, .vertex = wf_launch_vertex_gen,
+      .scatter = {wf_launch_scatter_diffuse_gen<ZS, DL>, wf_launch_scatter_conductor_gen<ZS, DL>, wf_launch_scatter_dielectric_gen<ZS, DL>, wf_launch_scatter_layered_staged_gen<ZS, DL>},
+      .scatter_layered_onepass = wf_launch_scatter_layered_gen<ZS, DL>, .simple = wf_launch_shade_simple<ZS, DL>, .randomwalk = wf_launch_shade_randomwalk<ZS, false>},
      {.generate = {k_generate<true, false, ZS>, nullptr}, .lean = nullptr, .lean_diverted = nullptr,
-      .fused_all = wf_launch_shade_fused_gen_tex<ZS>, .vertex = wf_launch_vertex_tex,
-      .scatter = {wf_launch_scatter_diffuse_tex<ZS>, wf_launch_scatter_conductor_tex<ZS>, wf_launch_scatter_dielectric_tex<ZS>, wf_launch_scatter_layered_staged_tex<ZS>},
-      .scatter_layered_onepass = wf_launch_scatter_layered_tex<ZS>, .simple = wf_launch_shade_simple<ZS>, .randomwalk = wf_launch_shade_randomwalk<ZS>},
-     {.generate = {k_generate<false, false, ZS>, k_generate<false, true, ZS>}, .lean = wf_launch_shade_lean_gen_env<ZS>, .lean_diverted = wf_launch_shade_lean_gen_env_diverted<ZS>,
-      .fused_all = wf_launch_shade_fused_gen_env<ZS>, .vertex = wf_launch_vertex_gen_env,
-      .scatter = {wf_launch_scatter_diffuse_gen_env<ZS>, wf_launch_scatter_conductor_gen_env<ZS>, wf_launch_scatter_dielectric_gen_env<ZS>, wf_launch_scatter_layered_staged_gen_env<ZS>},
-      .scatter_layered_onepass = wf_launch_scatter_layered_gen<ZS>,  // (as above)
-      .simple = wf_launch_shade_simple<ZS>, .randomwalk = wf_launch_shade_randomwalk<ZS>}},
+      .fused_all = wf_launch_shade_fused_gen_tex<ZS, DL>, .vertex = wf_launch_vertex_tex,
+      .scatter = {wf_launch_scatter_diffuse_tex<ZS, DL>, wf_launch_scatter_conductor_tex<ZS, DL>, wf_launch_scatter_dielectric_tex<ZS, DL>, wf_launch_scatter_layered_staged_tex<ZS, DL>},
+      .scatter_layered_onepass = wf_launch_scatter_layered_tex<ZS, DL>, .simple = wf_launch_shade_simple<ZS, DL>, .randomwalk = wf_launch_shade_randomwalk<ZS, false>},
+     {.generate = {k_generate<false, false, ZS>, k_generate<false, true, ZS>}, .lean = wf_launch_shade_lean_gen_env<ZS, DL>, .lean_diverted = wf_launch_shade_lean_gen_env_diverted<ZS, DL>,
+      .fused_all = wf_launch_shade_fused_gen_env<ZS, DL>, .vertex = wf_launch_vertex_gen_env,
+      .scatter = {wf_launch_scatter_diffuse_gen_env<ZS, DL>, wf_launch_scatter_conductor_gen_env<ZS, DL>, wf_launch_scatter_dielectric_gen_env<ZS, DL>, wf_launch_scatter_layered_staged_gen_env<ZS, DL>},
+      .scatter_layered_onepass = wf_launch_scatter_layered_gen<ZS, DL>,  // (as above)
+      .simple = wf_launch_shade_simple<ZS, DL>, .randomwalk = wf_launch_shade_randomwalk<ZS, false>}},
 };
 // ... and per pixel-filter class (shm/filter.h) x sampler: K1 and K6 of the filters that are not the box filter — [TRIANGLE | TABULATED with a constant weight (gaussian) |
 // TABULATED with a signed one (Mitchell, sinc)]; the generate kernels as [HAS_TEX][LEAN]
@@ -360,7 +360,10 @@ constexpr FilterKernels filter_cells[N_FLT] = {
 // A render's kernels, once per call: the only code that reads the scene's classes and the render's options to choose a variant (WHETHER a kernel runs is the bounce loop's)
 static ShadeKernels select_kernels(const ShmScene* s, const ShmRenderParams* params) {
     const shm_host::FlatScene& f = s->flat;
-    const ShadeKernels(&cells)[N_GEO][N_IMG] = params->sampler == SHM_SAMPLER_ZSOBOL ? shade_cells<true> : shade_cells<false>;
+    // (the *_dl builds for a scene with a distant or spot light, in every class: a kernel built without the two lights would sample them as area lights. This is the
+    // only place a launcher set is chosen, so such a scene cannot reach one.)
+    const bool zs = params->sampler == SHM_SAMPLER_ZSOBOL;
+    const ShadeKernels(&cells)[N_GEO][N_IMG] = f.has_directed_lights ? (zs ? shade_cells<true, true> : shade_cells<false, true>) : (zs ? shade_cells<true, false> : shade_cells<false, false>);
     const int geo = f.has_spheres ? GEO_GEN : GEO_TRI;
     // The staged and the all-materials fused kernels: env where the only image is an environment map and options.force_diffuse is off, tex where the scene has
     // textures, none otherwise — under force_diffuse an env-only scene runs the textured units (the differentials are dead values there: no material binds a texture).
@@ -665,6 +668,7 @@ int shm_scene_create(const ShmSceneDesc* desc, int device, ShmScene** out) {
     if ((rc = dev_upload(s, f.materials, &v.materials)) != SHM_OK) return fail(rc);
     if ((rc = dev_upload(s, f.lights, &v.lights)) != SHM_OK) return fail(rc);
     v.light_prim_recs = nullptr;
+    // (uploaded whenever the scene has a light: a spot light's record lives ONLY here — light_side_rec, shm/scene.h, has no fallback to prim_recs)
     if (!f.light_prim_recs.empty() && (rc = dev_upload(s, f.light_prim_recs, &v.light_prim_recs)) != SHM_OK) return fail(rc);
     if ((rc = dev_upload(s, f.infinite_lights, &v.infinite_lights)) != SHM_OK) return fail(rc);
     if ((rc = dev_upload(s, f.spectrum_data, &v.spectrum_data)) != SHM_OK) return fail(rc);
@@ -862,6 +866,12 @@ int shm_render_wave(ShmScene* s, const ShmRenderParams* params, const ShmTile* t
         }
     }
     const ShadeKernels k = select_kernels(s, params);
+    // a scene with a distant or spot light must run the *_dl set and no other scene does (a kernel built without the two lights would sample them as area lights): checked
+    // on one launcher of the resolved set, which comes from one cell of one table
+    {
+        const ShadeFn dl_simple = params->sampler == SHM_SAMPLER_ZSOBOL ? wf_launch_shade_simple<true, true> : wf_launch_shade_simple<false, true>;
+        if ((k.simple == dl_simple) != s->flat.has_directed_lights) { g_err = "internal: the kernel set does not match the scene's delta lights"; return SHM_ERR_INTERNAL; }
+    }
     // the fused kernel's own scene class under the path integrator: bounce 0 runs on known constants (k_generate<., LEAN>, ShadeArgs::first_bounce)
     const bool lean_first = (!staged || (first_bounce_candidate(s) && params->force_diffuse == 0)) && !random_walk && params->integrator != SHM_INTEGRATOR_SIMPLE_PATH && !s->pa.aux0 && s->pa.rng0;
     uint32_t pix_per_batch = cap_eff / (uint32_t)n_samples;

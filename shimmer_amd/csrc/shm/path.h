@@ -6,6 +6,7 @@
 //   light.rs:632-684              DiffuseAreaLight::{sample_li,pdf_li,l}
 //   light.rs:747-803              UniformInfiniteLight::{sample_li,pdf_li,le}
 //   light.rs:848-904              ImageInfinitelight::{sample_li,pdf_li,le} (arithmetic in texture.h)
+//   (PBRT-v4 lights.h / lights.cpp) DistantLight::SampleLi, SpotLight::{SampleLi,I}: the reference has neither light (SHM_DELTA_LIGHTS, below)
 //   light_sampler.rs:83-111       UniformLightSampler::{sample_light,pmf_light}
 //   interaction.rs:187-278        SurfaceInteraction::get_bsdf (ray differentials are carried only in scenes with image
 //                                 textures, texture.h: elsewhere they are dead values; bump_map with a constant
@@ -40,7 +41,37 @@ struct LightLiSample {  // light.rs:1045-1065
     V3 p_light_n;
 };
 
-SHM_HD bool light_is_delta(const ShmLight& l) { return l.kind == SHM_LIGHT_POINT; }  // light.rs:1098-1102
+// SHM_DELTA_LIGHTS: compile PBRT-v4's distant and spot lights (SHM_LIGHT_DISTANT, SHM_LIGHT_SPOT) into light_is_delta and light_sample_li. ON wherever nobody says
+// otherwise (the oracle, the host mirror, the leaf probe); the kernel units pass their K_DELTA_LIGHTS (wavefront.h), so that the kernels of scenes without such a
+// light are those of a library without them. A scene that holds one never reaches a kernel built with 0 (render.hip, select_kernels).
+#ifndef SHM_DELTA_LIGHTS
+#define SHM_DELTA_LIGHTS 1
+#endif
+
+SHM_HD bool light_is_delta(const ShmLight& l) {  // light.rs:1098-1102; PBRT-v4 LightType::DeltaPosition / DeltaDirection
+    if (SHM_DELTA_LIGHTS && (l.kind == SHM_LIGHT_DISTANT || l.kind == SHM_LIGHT_SPOT)) return true;
+    return l.kind == SHM_LIGHT_POINT;
+}
+
+// PBRT-v4's SmoothStep(x, a, b) (util/math.h)
+SHM_HD Float smoothstep(Float x, Float a, Float b) {
+    if (a == b) return x < a ? 0.0f : 1.0f;
+    Float t = clamp((x - a) / (b - a), 0.0f, 1.0f);
+    return t * t * (3.0f - 2.0f * t);
+}
+// What a spot light keeps in its 64-byte per-light record (SceneView::light_prim_recs, LDS-staged beside the light table; flatten_scene fills it from ShmSpotLight):
+// p0, p1, p2 = the rows of the 3x3 linear part of light_from_render; mesh, tri = cos_falloff_start, cos_falloff_end as bits.
+// cos(theta) of a render-space direction w in the light's space: (M w).z / |M w|, the z of PBRT-v4's Normalize(renderFromLight.ApplyInverse(w)) — the record is read
+// as three running dot products, a row at a time.
+SHM_HD Float spot_cos_theta(const PrimRec& r, V3 w) {
+    Float x = dot(ld3(r.p0), w);
+    Float len2 = x * x;
+    Float y = dot(ld3(r.p1), w);
+    len2 = len2 + y * y;
+    Float z = dot(ld3(r.p2), w);
+    len2 = len2 + z * z;
+    return z / sqrt(len2);
+}
 
 // DiffuseAreaLight::l, light.rs:668-684
 SHM_HD Spec area_light_l(const SceneView& sv, const ShmLight& light, V3 n, V3 w, const Wavelengths& lambda) {
@@ -75,6 +106,28 @@ SHM_HD bool light_sample_li(const SceneView& sv, const ShmLight& light, const Li
         Spec li = light.scale * spectrum_sample(light.spectrum, sv.spectrum_data, lambda) / distance_squared(p, ctx.p());
         out.l = li; out.wi = wi; out.pdf = 1.0f;
         out.p_light_pi = p3i_exact(p);
+        out.p_light_n = v3s(0.0f);
+        return true;
+    }
+    if (SHM_DELTA_LIGHTS && light.kind == SHM_LIGHT_SPOT) {  // PBRT-v4 SpotLight::SampleLi
+        V3 p = ld3(light.position);
+        V3 wi = normalize(p - ctx.p());
+        Float d2 = distance_squared(p, ctx.p());
+        Spec i = spectrum_sample(light.spectrum, sv.spectrum_data, lambda);
+        const PrimRec& r = light_side_rec(sv, light);
+        Float falloff = smoothstep(spot_cos_theta(r, -wi), bits_to_float(r.tri), bits_to_float(r.mesh));
+        Spec li = falloff * light.scale * i / d2;
+        if (is_zero(li)) return false;  // (outside the cone: no sample, no shadow ray)
+        out.l = li; out.wi = wi; out.pdf = 1.0f;
+        out.p_light_pi = p3i_exact(p);
+        out.p_light_n = v3s(0.0f);
+        return true;
+    }
+    if (SHM_DELTA_LIGHTS && light.kind == SHM_LIGHT_DISTANT) {  // PBRT-v4 DistantLight::SampleLi: `position` is the unit vector towards the light
+        V3 wi = ld3(light.position);
+        out.l = light.scale * spectrum_sample(light.spectrum, sv.spectrum_data, lambda);
+        out.wi = wi; out.pdf = 1.0f;
+        out.p_light_pi = p3i_exact(ctx.p() + wi * (2.0f * sv.scene_radius));
         out.p_light_n = v3s(0.0f);
         return true;
     }

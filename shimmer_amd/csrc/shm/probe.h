@@ -16,7 +16,7 @@ enum : int {
     PROBE_TRIANGLE_PDF_WITH_CONTEXT, PROBE_TRIANGLE_INTERACTION, PROBE_SPHERE_SAMPLE_WITH_CONTEXT, PROBE_SPHERE_PDF_WITH_CONTEXT, PROBE_AREA_LIGHT_L, PROBE_FILM_ADD_SAMPLE,
     PROBE_CAMERA_RAY_DIFFERENTIAL, PROBE_INTERVAL_OP, PROBE_DET3, PROBE_ROTATE_FROM_TO, PROBE_SAMPLE_DISCRETE, PROBE_SAMPLER_STREAM, PROBE_SAMPLE_VISIBLE_WAVELENGTHS,
     PROBE_VISIBLE_WAVELENGTHS_PDF, PROBE_VECMATH, PROBE_TRANSFORM_APPLY, PROBE_BLP_INTERSECT, PROBE_BLP_SAMPLE_WITH_CONTEXT, PROBE_BLP_PDF_WITH_CONTEXT, PROBE_SPHERE_INTERSECT,
-    PROBE_UNARY, PROBE_EQUAL_AREA_SQUARE_TO_SPHERE, PROBE_EQUAL_AREA_SPHERE_TO_SQUARE, PROBE_ZSOBOL_STREAM, PROBE_FILTER_SAMPLE, PROBE_N_OPS
+    PROBE_UNARY, PROBE_EQUAL_AREA_SQUARE_TO_SPHERE, PROBE_EQUAL_AREA_SPHERE_TO_SQUARE, PROBE_ZSOBOL_STREAM, PROBE_FILTER_SAMPLE, PROBE_LIGHT_SAMPLE_LI, PROBE_N_OPS
 };
 
 namespace probe_detail {
@@ -196,6 +196,36 @@ SHM_HD int leaf_probe(int op, const uint32_t* in, uint32_t* out) {
             const Spec r = area_light_l(sv, light, f3(in, 4), f3(in, 7), wl);
             for (int i = 0; i < 4; ++i) put(out, i, r.v[i]);
             return 0;
+        }
+        case PROBE_LIGHT_SAMPLE_LI: {  // Light::sample_li of a point, distant or spot light (shm/path.h; PBRT-v4 lights.cpp) as oracle.cpp's orc_fn_light_sample_li returns it, at any context
+                                       // point: kind, scale, position[3], the 3x3 of light_from_render by rows [9], cos_falloff_start, cos_falloff_end, n_table, lambda_min,
+                                       // ctx p[3], scene_radius, lambda[4], table[n_table] -> wi[3], pdf, L[4]; returns 0 for "no sample"
+            if (in[0] != SHM_LIGHT_POINT && in[0] != SHM_LIGHT_DISTANT && in[0] != SHM_LIGHT_SPOT) return -1;
+            ShmLight light;
+            memset(&light, 0, sizeof(light));
+            light.kind = in[0];
+            light.scale = f(in, 1);
+            for (int i = 0; i < 3; ++i) light.position[i] = f(in, 2 + i);
+            light.spectrum.kind = SHM_SPECTRUM_DENSE;
+            light.spectrum.offset = 0; light.spectrum.n = in[16]; light.spectrum.lambda_min = (int)in[17];
+            PrimRec rec;
+            memset(&rec, 0, sizeof(rec));
+            for (int i = 0; i < 3; ++i) { rec.p0[i] = f(in, 5 + i); rec.p1[i] = f(in, 8 + i); rec.p2[i] = f(in, 11 + i); }
+            rec.mesh = in[14]; rec.tri = in[15];
+            SceneView sv;
+            memset(&sv, 0, sizeof(sv));
+            sv.spectrum_data = reinterpret_cast<const Float*>(in + 26);
+            sv.lights = &light; sv.n_lights = 1; sv.light_prim_recs = &rec;
+            sv.scene_radius = f(in, 21);
+            LightSampleContext ctx;
+            ctx.pi = p3i_exact(f3(in, 18)); ctx.n = v3s(0.0f); ctx.ns = v3s(0.0f);
+            Wavelengths wl;
+            for (int i = 0; i < 4; ++i) { wl.lambda[i] = f(in, 22 + i); wl.pdf[i] = 1.0f; }
+            LightLiSample ls;
+            if (!light_sample_li<false, false>(sv, light, ctx, v2(0.5f, 0.5f), wl, ls)) return 0;
+            put3(out, 0, ls.wi); put(out, 3, ls.pdf);
+            for (int i = 0; i < 4; ++i) put(out, 4 + i, ls.l.v[i]);
+            return 1;
         }
         case PROBE_FILM_ADD_SAMPLE: {  // film.rs:548-574, 907-914; imaging_ratio, max_component_value, L[4], lambda[4], pdf[4], weight, pixel (4 doubles), r_bar / g_bar / b_bar [471 each]
             SceneView sv;

@@ -183,6 +183,13 @@ SHM_HD const PrimRec& light_prim_rec(const SceneView& sv, const ShmLight& light)
 #endif
     return sv.light_prim_recs ? sv.light_prim_recs[&light - sv.lights] : sv.prim_recs[light.primitive];
 }
+// the same record of a light that is not an area light (a spot light's: shm/path.h, spot_cos_theta): always the per-light copy, which flatten_scene builds for every scene
+SHM_HD const PrimRec& light_side_rec(const SceneView& sv, const ShmLight& light) {
+#if !defined(__HIP_DEVICE_COMPILE__)
+    assert(&light >= sv.lights && &light < sv.lights + sv.n_lights && sv.light_prim_recs);
+#endif
+    return sv.light_prim_recs[&light - sv.lights];
+}
 
 // BilinearPatch::get_points (bilinear_patch.rs:87-98) + the constants fixed at scene creation
 SHM_HD PatchData load_patch_rec(const SceneView& sv, const PrimRec& pr) {

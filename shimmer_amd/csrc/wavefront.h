@@ -12,7 +12,22 @@
 #include <vector>
 
 #include "host/flatten.h"
+// K_DELTA_LIGHTS (a translation unit's switch, like K_ZSOBOL below): PBRT-v4's distant and spot lights are compiled into a unit's light sampling only where it is true
+// (shm/path.h, SHM_DELTA_LIGHTS). The Makefile compiles every unit that samples lights once more with it into *_dl (and *_zs_dl) objects, whose kernels carry a _dl
+// suffix and whose launchers are the <., true> specializations (WF_SAMPLED_LAUNCHER); select_kernels (render.hip) picks that set for a scene that holds such a light
+// (FlatScene::has_directed_lights). Without the switch the two branches fold away: the kernels of every other scene are those of a build without the lights.
+#ifndef K_DELTA_LIGHTS
+#define K_DELTA_LIGHTS false
+#endif
+#define SHM_DELTA_LIGHTS K_DELTA_LIGHTS
 #include "shm/path.h"
+#define WF_CAT_(a, b) a##b
+#define WF_CAT(a, b) WF_CAT_(a, b)
+#if K_DELTA_LIGHTS
+#define WF_DL_NAME(name) WF_CAT(name, _dl)
+#else
+#define WF_DL_NAME(name) name
+#endif
 
 using namespace shm;
 
@@ -420,12 +435,14 @@ struct ShadeArgs {
 // class (none, tex: image textures — ray differentials, MIP filtering —, env: an ImageInfinitelight alone, the K_ENV_LIGHT units). render.hip puts them in one table,
 // ShadeKernels by (geometry, image class, sampler), and picks a render's cell once (select_kernels).
 using ShadeFn = int (*)(ShmScene*, const ShadeArgs&);
-// The units whose kernels draw are compiled twice (K_ZSOBOL, Makefile): each defines its launchers as the specialization <K_ZSOBOL> of one template, so that the
-// table names both twins and a missing one is a link error (an undefined hidden symbol).
-#define WF_SAMPLED_LAUNCHER(name)                                        \
-    template <bool ZS> int name(ShmScene* s, const ShadeArgs& a);        \
-    template <> WF_INTERNAL int name<false>(ShmScene* s, const ShadeArgs& a); \
-    template <> WF_INTERNAL int name<true>(ShmScene* s, const ShadeArgs& a)
+// The units whose kernels draw and sample lights are compiled four times (K_ZSOBOL x K_DELTA_LIGHTS, Makefile): each defines its launchers as the specialization
+// <K_ZSOBOL, K_DELTA_LIGHTS> of one template, so that the table names all four builds and a missing one is a link error (an undefined hidden symbol).
+#define WF_SAMPLED_LAUNCHER(name)                                                    \
+    template <bool ZS, bool DL> int name(ShmScene* s, const ShadeArgs& a);           \
+    template <> WF_INTERNAL int name<false, false>(ShmScene* s, const ShadeArgs& a); \
+    template <> WF_INTERNAL int name<true, false>(ShmScene* s, const ShadeArgs& a);  \
+    template <> WF_INTERNAL int name<false, true>(ShmScene* s, const ShadeArgs& a);  \
+    template <> WF_INTERNAL int name<true, true>(ShmScene* s, const ShadeArgs& a)
 // the fused kernel k_shade<lean> (k_shade_lean*.hip): all-diffuse scenes without textures — every hit of the queue — and the hits k_vertex or the split pass diverted
 WF_SAMPLED_LAUNCHER(wf_launch_shade_lean); WF_SAMPLED_LAUNCHER(wf_launch_shade_lean_gen); WF_SAMPLED_LAUNCHER(wf_launch_shade_lean_env); WF_SAMPLED_LAUNCHER(wf_launch_shade_lean_gen_env);
 WF_SAMPLED_LAUNCHER(wf_launch_shade_lean_diverted); WF_SAMPLED_LAUNCHER(wf_launch_shade_lean_gen_diverted); WF_SAMPLED_LAUNCHER(wf_launch_shade_lean_env_diverted);
@@ -450,6 +467,7 @@ WF_SAMPLED_LAUNCHER(wf_launch_scatter_layered_staged_tri_env); WF_SAMPLED_LAUNCH
 // ... and in one pass per vertex (k_scatter.inl), which has force_diffuse's code
 WF_SAMPLED_LAUNCHER(wf_launch_scatter_layered_tri); WF_SAMPLED_LAUNCHER(wf_launch_scatter_layered_gen); WF_SAMPLED_LAUNCHER(wf_launch_scatter_layered_tex);
 // the other integrators (k_shade_other.hip): one kernel each for every scene class
+// (RandomWalk samples no light: wf_launch_shade_randomwalk<., true> is declared by the macro and never defined or named — the table's cells take <ZS, false>)
 WF_SAMPLED_LAUNCHER(wf_launch_shade_simple); WF_SAMPLED_LAUNCHER(wf_launch_shade_randomwalk);
 WF_INTERNAL int wf_launch_fold_randomwalk(ShmScene* s, hipStream_t stream, uint32_t cap_eff, uint32_t total);
 // K1 (render.hip, k_generate<HAS_TEX, LEAN, ZS>)

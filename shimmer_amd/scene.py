@@ -8,6 +8,7 @@ PiecewiseLinearSpectrum::from_interleaved (:313-352), spectrum_to_photometric (:
 Everything computed here is INPUT data handed identically to the HIP library and to the CPU oracle.
 """
 import ctypes as C
+import math
 from pathlib import Path
 
 import numpy as np
@@ -114,6 +115,32 @@ def _fptr(a):
 IDENTITY = np.eye(4, dtype=np.float32)
 
 
+# float32 vector helpers of the distant / spot lights, operation for operation what the C++ front end does (shm/vec.h, host/pbrt_math.hpp)
+def _normalize_f32(v):
+    v = _as_f32(v)
+    return v / np.sqrt(f32(f32(v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]))
+
+
+def _xf_vector_f32(m, v):
+    return np.array([f32(f32(m[i, 0] * v[0] + m[i, 1] * v[1]) + m[i, 2] * v[2]) for i in range(3)], np.float32)
+
+
+def _coordinate_system_f32(v):
+    """coordinate_system (Duff et al.; shm/vec.h)"""
+    one = f32(1.0)
+    sign = f32(math.copysign(1.0, float(v[2])))
+    a = f32(-one / f32(sign + v[2]))
+    b = f32(f32(v[0] * v[1]) * a)
+    v2 = np.array([f32(one + f32(f32(sign * f32(v[0] * v[0])) * a)), f32(sign * b), f32(-sign * v[0])], np.float32)
+    v3 = np.array([b, f32(sign + f32(f32(v[1] * v[1]) * a)), f32(-v[1])], np.float32)
+    return v2, v3
+
+
+def _m4_mul_f32(a, b):
+    """m4_mul: every element a double-precision inner product, rounded once"""
+    return (a.astype(np.float64) @ b.astype(np.float64)).astype(np.float32)
+
+
 class SceneBuilder:
     """Accumulates shapes/materials/lights in input order, builds the BVH with the host-side mirror of
     BvhAggregate::new and emits a ShmSceneDesc (keeping every backing array alive)."""
@@ -140,6 +167,7 @@ class SceneBuilder:
         self.texel_len = 0
         self.color_space = None  # dict(res, scale, data, illuminant)
         self.image_lights = []  # abi.ShmImageInfiniteLight
+        self.spot_lights = []   # abi.ShmSpotLight
         self.float_textures = []  # abi.ShmFloatTexture
         self.spectrum_textures = []  # abi.ShmSpectrumTexture
         self.owners = []        # per chunk of self.prims: 0 = the scene, k = object definition k (ObjectBegin / ObjectEnd)
@@ -348,6 +376,57 @@ class SceneBuilder:
         l.kind = abi.SHM_LIGHT_UNIFORM_INFINITE
         l.scale = float(f32(scale) / spectrum_to_photometric(dense_emission))
         l.spectrum = self.spectrum_dense(dense_emission)
+        self.lights.append(l)
+        return len(self.lights) - 1
+
+    def light_distant(self, dense_radiance, scale=1.0, frm=(0.0, 0.0, 0.0), to=(0.0, 0.0, 1.0), illuminance=None, render_from_object=None):
+        """PBRT-v4's DistantLight (DistantLight::Create): light arrives FROM the direction `frm - to`; scale * spectrum is the radiance (numerically the
+        irradiance on a surface that faces the light). `illuminance` > 0 makes that irradiance this many lux."""
+        l = abi.ShmLight()
+        l.kind = abi.SHM_LIGHT_DISTANT
+        sc = f32(f32(scale) / spectrum_to_photometric(dense_radiance))
+        if illuminance is not None and illuminance > 0:
+            sc = f32(sc * f32(illuminance))
+        l.scale = float(sc)
+        w = _normalize_f32(_as_f32(frm) - _as_f32(to))
+        m = _as_f32(IDENTITY if render_from_object is None else render_from_object).reshape(4, 4)
+        l.position[:] = [float(x) for x in _normalize_f32(_xf_vector_f32(m, w))]
+        l.spectrum = self.spectrum_dense(dense_radiance)
+        self.lights.append(l)
+        return len(self.lights) - 1
+
+    def light_spot(self, frm, to, dense_intensity, scale=1.0, coneangle=30.0, conedelta=5.0, power=None, render_from_object=None):
+        """PBRT-v4's SpotLight (SpotLight::Create): apex `frm`, axis towards `to`, total width `coneangle` and falloff start `coneangle - conedelta` in
+        degrees; scale * spectrum is the intensity on the axis. `power` > 0 sets the emitted power in lumens instead."""
+        l = abi.ShmLight()
+        l.kind = abi.SHM_LIGHT_SPOT
+        sc = f32(f32(scale) / spectrum_to_photometric(dense_intensity))
+        rad = f32(3.14159265358979323846 / 180.0)
+        sp = abi.ShmSpotLight()
+        cos_end = f32(math.cos(float(f32(coneangle) * rad)))
+        cos_start = f32(math.cos(float(f32(f32(coneangle) - f32(conedelta)) * rad)))
+        sp.cos_falloff_end, sp.cos_falloff_start = float(cos_end), float(cos_start)
+        if power is not None and power > 0:
+            k_e = f32(f32(2.0) * f32(3.14159265358979323846)) * f32(f32(f32(1.0) - cos_start) + f32(cos_start - cos_end) / f32(2.0))
+            sc = f32(sc * f32(f32(power) / k_e))
+        l.scale = float(sc)
+        frm32, to32 = _as_f32(frm), _as_f32(to)
+        z = _normalize_f32(to32 - frm32)
+        x, y = _coordinate_system_f32(z)
+        frame_inv = np.eye(4, dtype=np.float32)  # inverse(Frame::FromZ(z)): the axes as columns
+        frame_inv[:3, 0], frame_inv[:3, 1], frame_inv[:3, 2] = x, y, z
+        tr, tr_inv = np.eye(4, dtype=np.float32), np.eye(4, dtype=np.float32)
+        tr[:3, 3], tr_inv[:3, 3] = frm32, -frm32
+        rfo = _as_f32(IDENTITY if render_from_object is None else render_from_object).reshape(4, 4)
+        rfo_inv = _as_f32(np.linalg.inv(rfo.astype(np.float64)))
+        m = _m4_mul_f32(rfo, _m4_mul_f32(tr, frame_inv))
+        m_inv = _m4_mul_f32(_m4_mul_f32(frame_inv.T.copy(), tr_inv), rfo_inv)
+        sp.render_from_light[:] = [float(v) for v in m.ravel()]
+        sp.light_from_render[:] = [float(v) for v in m_inv.ravel()]
+        l.position[:] = [float(m[0, 3]), float(m[1, 3]), float(m[2, 3])]
+        l.spectrum = self.spectrum_dense(dense_intensity)
+        self.spot_lights.append(sp)
+        l.primitive = len(self.spot_lights) - 1
         self.lights.append(l)
         return len(self.lights) - 1
 
@@ -777,6 +856,10 @@ class SceneBuilder:
                 ils = (abi.ShmImageInfiniteLight * len(self.image_lights))(*self.image_lights)
                 d.n_image_lights, d.image_lights = len(self.image_lights), ils
                 self._keep.append(ils)
+        if self.spot_lights:
+            sps = (abi.ShmSpotLight * len(self.spot_lights))(*self.spot_lights)
+            d.n_spot_lights, d.spot_lights = len(self.spot_lights), sps
+            self._keep.append(sps)
         if self.float_textures:
             fts = (abi.ShmFloatTexture * len(self.float_textures))(*self.float_textures)
             d.n_float_textures, d.float_textures = len(self.float_textures), fts

@@ -58,9 +58,24 @@ def _box(lo, hi, faces="xXyYzZ"):
     return _merge([_quad(*f[c]) for c in faces])
 
 
-def _finish(b, lib, **extra):
+def _finish(b, lib, extra_lights=None, rfw=None, **extra):
+    """`extra_lights(builder, render_from_world)` (the generators' optional argument) appends lights AFTER the scene's own; absent, the description is
+    byte for byte what the generator always produced."""
+    if extra_lights is not None:
+        extra_lights(b, rfw)
     desc, info = b.build(lib)
     return SimpleNamespace(desc=desc, builder=b, info=info, **extra)
+
+
+def spot_and_distant(spot_from=(0.4, 1.6, 0.6), spot_to=(0.0, 0.0, 0.0), coneangle=35.0, conedelta=10.0, spot_scale=8.0, sun_from=(1.0, 2.0, 1.5), sun_to=(0.0, 0.0, 0.0),
+                     sun_scale=1.5, spot=True, distant=True):
+    """An `extra_lights` argument for the generators below: PBRT-v4's spot light and / or distant light, given in WORLD space."""
+    def add(b, rfw):
+        if spot:
+            b.light_spot(spot_from, spot_to, blackbody_dense(3200.0), scale=spot_scale, coneangle=coneangle, conedelta=conedelta, render_from_object=rfw)
+        if distant:
+            b.light_distant(blackbody_dense(5500.0), scale=sun_scale, frm=sun_from, to=sun_to, render_from_object=rfw)
+    return add
 
 
 def sphere_light(lib, width=128, height=128, film=None):
@@ -100,7 +115,7 @@ def test_image(size=64, channels=3, seed=7):
 
 
 def cornell_box(lib, width=512, height=512, coated=False, mix=False, patches=False, patch_skew=0.0, textured=False,
-                texture_filter=None, textured_coated_ceiling=True, glass=False, emitter_reflects=False, environment=None, glass_too=False, film=None):
+                texture_filter=None, textured_coated_ceiling=True, glass=False, emitter_reflects=False, environment=None, glass_too=False, film=None, extra_lights=None):
     """S2 (config C2): 5 walls x 2 + 2 boxes x 5 faces x 2 + light 2 = 32 triangles.
     coated=True: the tall box becomes CoatedConductor (rough interface, Cu), the short one CoatedDiffuse with a scattering
     medium between the interfaces, the floor CoatedDiffuse with a smooth interface (SURVEY §8f-1 materials)."""
@@ -221,7 +236,7 @@ def cornell_box(lib, width=512, height=512, coated=False, mix=False, patches=Fal
     if environment is not None:  # an ImageInfinitelight shines in through the open front (round 5: the K_ENV_LIGHT units of the staged kernels)
         rot = np.array([[1, 0, 0, 0], [0, 0, 1, 0], [0, -1, 0, 0], [0, 0, 0, 1]], np.float32)
         b.light_image_infinite(environment, scale=0.5, render_from_light=rot)
-    return _finish(b, lib, name="S2 cornell box" + (" (environment map)" if environment is not None else "") + (" (coated)" if coated else "") + (" (mix)" if mix else "") + (" (patches)" if patches else "") + (" (textured)" if textured else "") + (" (glass)" if glass else "") + (" (+ glass)" if glass_too else ""))
+    return _finish(b, lib, extra_lights=extra_lights, rfw=rfw, name="S2 cornell box" + (" (environment map)" if environment is not None else "") + (" (coated)" if coated else "") + (" (mix)" if mix else "") + (" (patches)" if patches else "") + (" (textured)" if textured else "") + (" (glass)" if glass else "") + (" (+ glass)" if glass_too else ""))
 
 
 def _hash3(ix, iy, iz, seed):
@@ -310,7 +325,7 @@ def cube_sphere(n, seed=1234, amplitude=0.15, shuffle_seed=99, as_quads=False, q
     return verts, tris
 
 
-def ganesha_proxy(lib, width=1024, height=1024, n=599, with_room=True, coated=False, variant=None, floor_filter="ewa", quad_fraction=None, object_material=None, film=None):
+def ganesha_proxy(lib, width=1024, height=1024, n=599, with_room=True, coated=False, variant=None, floor_filter="ewa", quad_fraction=None, object_material=None, film=None, extra_lights=None):
     """S3 (configs C3/C5): n=599 gives 6*599^2*2 = 4 305 612 triangles and 2 152 808 vertices.
     coated=True: the object is CoatedDiffuse (the material of the reference's Ganesha render, images/shimmer-ganesha-1.png).
     variant (round 5: the shapes a real PBRT-v4 scene mixes into its triangles; same camera, room and object):
@@ -429,7 +444,7 @@ def ganesha_proxy(lib, width=1024, height=1024, n=599, with_room=True, coated=Fa
             b.add_patch_mesh(_to_render(p, rfw), [[0, 1, 3, 2]], black, emission=blackbody_dense(6500.0), emission_scale=40.0)
         else:
             b.add_mesh(_to_render(p, rfw), vi, black, emission=blackbody_dense(6500.0), emission_scale=40.0)
-    return _finish(b, lib, name=f"S3 ganesha-proxy n={n}" + (" (coated)" if coated else "") + (f" [{variant}]" if variant else ""))
+    return _finish(b, lib, extra_lights=extra_lights, rfw=rfw, name=f"S3 ganesha-proxy n={n}" + (" (coated)" if coated else "") + (f" [{variant}]" if variant else ""))
 
 
 def icosphere(level):
@@ -460,7 +475,7 @@ def icosphere(level):
     return v.astype(np.float32), f.astype(np.uint32)
 
 
-def crown_proxy(lib, width=1000, height=1400, level=4, n_glass=64, n_gold=16, seed=4242, environment=None, film=None):
+def crown_proxy(lib, width=1000, height=1400, level=4, n_glass=64, n_gold=16, seed=4242, environment=None, film=None, extra_lights=None):
     """S4 (config C4): dispersive smooth dielectric icospheres (BK7 eta table -> terminate_secondary), rough gold
     conductors, diffuse floor, one quad emitter; render with max_depth=32."""
     b = SceneBuilder()
@@ -489,7 +504,7 @@ def crown_proxy(lib, width=1000, height=1400, level=4, n_glass=64, n_gold=16, se
     if environment is not None:  # glass and metal under an ImageInfinitelight as well (round 5: the sorted fused kernel's ENV_LIGHT instantiation)
         rot = np.array([[1, 0, 0, 0], [0, 0, 1, 0], [0, -1, 0, 0], [0, 0, 0, 1]], np.float32)
         b.light_image_infinite(environment, scale=1.0, render_from_light=rot)
-    return _finish(b, lib, name="S4 crown-proxy" + ("" if environment is None else " (environment map)"))
+    return _finish(b, lib, extra_lights=extra_lights, rfw=rfw, name="S4 crown-proxy" + ("" if environment is None else " (environment map)"))
 
 
 def environment_image(n=32, sun=(0.3, 0.5, 0.81), sun_radiance=40.0):
@@ -512,7 +527,7 @@ def environment_image(n=32, sun=(0.3, 0.5, 0.81), sun_radiance=40.0):
     return img.astype(np.float32)
 
 
-def three_spheres(lib, width=32, height=32, offsets=(-3.5, 0.0, 5.0), camera=(0.0, 0.0, 0.0), environment=None, film=None):
+def three_spheres(lib, width=32, height=32, offsets=(-3.5, 0.0, 5.0), camera=(0.0, 0.0, 0.0), environment=None, film=None, extra_lights=None):
     """The reference's set_of_spheres BVH test scene (aggregate.rs:631-702): unit spheres at x = -3.5, 0, 5.
     With the default camera at the origin world == render space, as the reference's unit tests assume (rays are given
     in render space); pass a camera position outside the spheres to render it."""
@@ -533,10 +548,10 @@ def three_spheres(lib, width=32, height=32, offsets=(-3.5, 0.0, 5.0), camera=(0.
     else:  # ImageInfinitelight (light.rs:805-981), turned so that +z of the map is the world's +y
         rot = np.array([[1, 0, 0, 0], [0, 0, 1, 0], [0, -1, 0, 0], [0, 0, 0, 1]], np.float32)
         b.light_image_infinite(environment, scale=0.01, render_from_light=rot)
-    return _finish(b, lib, name="three spheres" + ("" if environment is None else " (environment map)"))
+    return _finish(b, lib, extra_lights=extra_lights, rfw=rfw, name="three spheres" + ("" if environment is None else " (environment map)"))
 
 
-def instanced_scene(lib, width=64, height=48, n_instances=5, only_object=False, baked=False, environment=None, film=None):
+def instanced_scene(lib, width=64, height=48, n_instances=5, only_object=False, baked=False, environment=None, film=None, extra_lights=None):
     """Object instancing: one object definition (an icosphere with per-vertex normals, a partial sphere and a curved
     bilinear patch, three materials) placed several times with rotated, non-uniformly scaled transforms over a floor lit by a quad
     light and a point light. `only_object`: just the object's shapes at top level, untransformed, no floor. `baked`: the same
@@ -576,7 +591,7 @@ def instanced_scene(lib, width=64, height=48, n_instances=5, only_object=False, 
     if only_object:
         object_shapes()
         b.light_point((0.0, 0.0, 0.0), blackbody_dense(5000.0), scale=1.0)
-        return _finish(b, lib, name="instanced object alone")
+        return _finish(b, lib, extra_lights=extra_lights, rfw=rfw, name="instanced object alone")
     if baked:
         for m in placements:
             object_shapes(to_render=m, ico_only=True)
@@ -596,12 +611,12 @@ def instanced_scene(lib, width=64, height=48, n_instances=5, only_object=False, 
     if environment is not None:
         rot = np.array([[1, 0, 0, 0], [0, 0, 1, 0], [0, -1, 0, 0], [0, 0, 0, 1]], np.float32)
         b.light_image_infinite(environment, scale=0.5, render_from_light=rot)
-    sc = _finish(b, lib, name="instanced objects" + (" (baked)" if baked else "") + ("" if environment is None else " (environment map)"))
+    sc = _finish(b, lib, extra_lights=extra_lights, rfw=rfw, name="instanced objects" + (" (baked)" if baked else "") + ("" if environment is None else " (environment map)"))
     sc.placements = placements
     return sc
 
 
-def random_scene(lib, seed, width=40, height=32, film=None):
+def random_scene(lib, seed, width=40, height=32, film=None, extra_lights=None):
     """A seeded random scene for parity fuzzing: every shape kind (triangle meshes with and without per-vertex N / S / uv,
     full and partial transformed spheres, flat and curved bilinear patches), every material kind (including nested mixes
     and both coated ones), area lights on every shape kind, a point light, optionally a uniform infinite light, and a
@@ -757,4 +772,4 @@ def random_scene(lib, seed, width=40, height=32, film=None):
         rot[:3, :3] = np.eye(3) + np.sin(ang) * k + (1 - np.cos(ang)) * (k @ k)
         b.light_image_infinite(environment_image(int(trng.choice([8, 16])), sun=tuple(trng.normal(size=3)), sun_radiance=float(trng.uniform(5, 60))),
                                scale=float(trng.uniform(0.002, 0.01)), render_from_light=rot)
-    return _finish(b, lib, name=f"random scene {seed}")
+    return _finish(b, lib, extra_lights=extra_lights, rfw=rfw, name=f"random scene {seed}")

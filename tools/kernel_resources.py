@@ -3,6 +3,9 @@
 ELF images embedded in the library) — the numbers occupancy follows from: waves per SIMD = min(8, 512 / VGPRs rounded up to 8, ...). (rocprofv3's
 kernel-trace `vgpr` column is NOT this count: it read 40 for a kernel that holds 76.)   python tools/kernel_resources.py [library]"""
 import re, subprocess, sys, tempfile, os
+WIDE = "--wide" in sys.argv  # full kernel names (the template arguments of k_shade do not fit 44 columns)
+if WIDE:
+    sys.argv.remove("--wide")
 lib = sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "shimmer_amd", "csrc", "libshimmer_hip.so")
 data = open(lib, "rb").read()
 readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
@@ -42,4 +45,4 @@ for r in rows:
     v, lds = int(r["vgpr_count"]), int(r.get("group_segment_fixed_size", 0))
     by_v = min(8, 512 // max(8, (v + 7) // 8 * 8))
     by_l = min(8, 163840 // lds) if lds else 8
-    print(f"{demangle(r['name'])[:44]:44s} {v:5d} {int(r['sgpr_count']):5d} {r.get('vgpr_spill_count', '?'):>5}/{r.get('sgpr_spill_count', '?'):<4} {lds:7d} {int(r.get('private_segment_fixed_size', 0)):9d} {by_v:>14d}, {by_l:d}")
+    print(f"{demangle(r['name'])[:200 if WIDE else 44]:44s} {v:5d} {int(r['sgpr_count']):5d} {r.get('vgpr_spill_count', '?'):>5}/{r.get('sgpr_spill_count', '?'):<4} {lds:7d} {int(r.get('private_segment_fixed_size', 0)):9d} {by_v:>14d}, {by_l:d}")
