@@ -3,7 +3,7 @@
 
     python examples/render_scene.py cornell --spp 256 --res 512 -o cornell.pfm
     python examples/render_scene.py cornell --filter gaussian        (box | gaussian | mitchell | sinc | triangle)
-    python examples/render_scene.py textured | coated | patches | instanced | environment | ganesha | crown | spotlit | fuzz:13
+    python examples/render_scene.py textured | checkerboard | coated | patches | instanced | environment | ganesha | crown | spotlit | fuzz:13
 
 Everything goes through the C ABI of include/shimmer_hip.h (shimmer_amd/abi.py is the ctypes binding): scene description ->
 shm_scene_create -> shm_render_device -> shm_film_read -> shm_film_get_image -> shm_write_pfm. Needs an MI355X: there is no CPU path.
@@ -31,6 +31,16 @@ def make_scene(lib, name, w, h, film=None):
         return scenes.cornell_box(lib, w, h, textured=True, film=film)
     if name == "coated":
         return scenes.cornell_box(lib, w, h, coated=True, film=film)
+    if name == "checkerboard":  # PBRT-v4's procedural textures, from the scene FILE examples/scenes/checkerboard.pbrt through the C++ front end (its own film size; --filter is the file's)
+        import ctypes as C
+        from types import SimpleNamespace
+        out = C.POINTER(abi.ShmPbrtScene)()
+        path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "scenes", "checkerboard.pbrt")
+        abi.check(lib, lib.shm_scene_load_pbrt(path.encode(), C.byref(out)), "shm_scene_load_pbrt")
+        res = out.contents.desc.film.full_resolution
+        return SimpleNamespace(desc=out.contents.desc, name="checkerboard.pbrt", res=(res[0], res[1]), keep=out)
+    if name in ("procedural", "procedural-general", "procedural-coated"):  # the same textures through the Python builder (scenes.procedural_cornell)
+        return scenes.procedural_cornell(lib, w, h, which={"procedural": "checker", "procedural-general": "general", "procedural-coated": "coated"}[name], film=film)
     if name == "patches":
         return scenes.cornell_box(lib, w, h, patches=True, film=film)
     if name == "instanced":
@@ -81,6 +91,7 @@ def main():
         raise SystemExit("no HIP device visible (there is no CPU fallback)")
     w, h = args.res, args.height or args.res
     sc = make_scene(lib, args.scene, w, h, film=dict(filter=args.filter))
+    w, h = getattr(sc, "res", (w, h))
     r = render.Renderer(lib, sc.desc, 0)
     p = render.make_params(seed=args.seed, spp=args.spp, max_depth=args.max_depth, integrator=args.integrator, reference_quirks=not args.quirks_off,
                            sampler=args.sampler)

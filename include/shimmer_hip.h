@@ -25,6 +25,8 @@
 extern "C" {
 #endif
 
+/* Enum values added WITHOUT a version step are additive: no struct changes size or layout and a caller built against the earlier header never passes them.
+ * Under version 10 these are SHM_TEXMAP_POINT3D, SHM_FLOATTEX_CHECKERBOARD .. SHM_FLOATTEX_BILERP and the mapping-only ShmImageTexture record (n_levels == 0). */
 #define SHM_ABI_VERSION 10
 
 /* The library is built with -fvisibility=hidden; only these entry points are exported. */
@@ -173,8 +175,19 @@ enum {
     SHM_FLOATTEX_SCALED = 1,        /* FloatScaledTexture:  tex = a, scale = b */
     SHM_FLOATTEX_MIX = 2,           /* FloatMixTexture:     tex1 = a, tex2 = b, amount = c */
     SHM_FLOATTEX_DIRECTION_MIX = 3, /* FloatDirectionMixTexture: tex1 = a, tex2 = b, dir */
-    SHM_FLOATTEX_IMAGE = 4          /* FloatImageTexture: image = index into ShmSceneDesc::image_textures (its spectrum_type and
+    SHM_FLOATTEX_IMAGE = 4,         /* FloatImageTexture: image = index into ShmSceneDesc::image_textures (its spectrum_type and
                                        has_color_space are ignored) */
+    /* PBRT-v4's procedural float textures (the reference has none). `image` names the texture MAPPING: the index of a mapping-only ShmImageTexture
+     * (n_levels == 0; only mapping, su sv du dv, vs vt and texture_from_render are read). CHECKERBOARD and DOTS compute a weight w and
+     * t1 = (w != 1) ? a : 0, t2 = (w != 0) ? b : 0, value = (1 - w) * t1 + w * t2, with a, b child nodes; a == b == 0xffffffff is the WEIGHT FORM:
+     * the node yields w itself (tex1 = 0, tex2 = 1 folded), a tree of one node. A spectrum checkerboard / dots texture is SHM_SPECTEX_MIX(tex1, tex2,
+     * f = the weight form): the same arithmetic as PBRT-v4's SpectrumCheckerboardTexture / SpectrumDotsTexture. */
+    SHM_FLOATTEX_CHECKERBOARD = 5,  /* tex1 = a, tex2 = b; image: a 2-D mapping (PBRT's dimension 2) or SHM_TEXMAP_POINT3D (dimension 3); w = the box-filtered checkerboard weight */
+    SHM_FLOATTEX_DOTS = 6,          /* inside = a, outside = b; image: a 2-D mapping; w = 0 inside a dot, 1 outside */
+    SHM_FLOATTEX_FBM = 7,           /* value = roughness (omega), pad[0] = octaves (<= 32); image: a SHM_TEXMAP_POINT3D mapping; FBm(p, dpdx, dpdy, omega, octaves) */
+    SHM_FLOATTEX_WRINKLED = 8,      /* as FBM; Turbulence(p, dpdx, dpdy, omega, octaves) */
+    SHM_FLOATTEX_WINDY = 9,         /* image: a SHM_TEXMAP_POINT3D mapping; |FBm(0.1 p, 0.1 dpdx, 0.1 dpdy, 0.5, 3)| * FBm(p, dpdx, dpdy, 0.5, 6) */
+    SHM_FLOATTEX_BILERP = 10        /* value, dir[0], dir[1], dir[2] = v00, v01, v10, v11; image: a 2-D mapping; (1-s)(1-t) v00 + s(1-t) v10 + (1-s) t v01 + s t v11 */
 };
 typedef struct ShmFloatTexture {
     uint32_t kind;
@@ -182,7 +195,7 @@ typedef struct ShmFloatTexture {
     uint32_t a, b, c;
     float dir[3];
     uint32_t image;
-    uint32_t pad[3];
+    uint32_t pad[3];          /* pad[0]: FBM / WRINKLED: octaves */
 } ShmFloatTexture;
 /* SpectrumTexture node table (texture.rs:411-503): a LEAF is a spectrum or an image texture (SpectrumConstantTexture /
  * SpectrumImageTexture); composites name their children by index (children precede parents; a tree holds at most 8 nodes) and
@@ -280,7 +293,9 @@ typedef struct ShmImageLevel {
     uint32_t texel_offset;
     uint32_t pad;
 } ShmImageLevel;
-enum { SHM_TEXMAP_UV = 0, SHM_TEXMAP_SPHERICAL = 1, SHM_TEXMAP_CYLINDRICAL = 2, SHM_TEXMAP_PLANAR = 3 }; /* texture.rs:838-843 */
+enum { SHM_TEXMAP_UV = 0, SHM_TEXMAP_SPHERICAL = 1, SHM_TEXMAP_CYLINDRICAL = 2, SHM_TEXMAP_PLANAR = 3, /* texture.rs:838-843 */
+       SHM_TEXMAP_POINT3D = 4 /* PBRT-v4's PointTransformMapping: p = texture_from_render(ctx.p) as a point, dpdx and dpdy as vectors through the same matrix. Only on a
+                                 mapping-only record (n_levels == 0), for the procedural float textures that take a 3-D point */ };
 enum { SHM_TEXFILTER_POINT = 0, SHM_TEXFILTER_BILINEAR = 1, SHM_TEXFILTER_TRILINEAR = 2, SHM_TEXFILTER_EWA = 3 }; /* mipmap.rs:334-341 */
 enum { SHM_WRAP_BLACK = 0, SHM_WRAP_CLAMP = 1, SHM_WRAP_REPEAT = 2, SHM_WRAP_OCTAHEDRAL_SPHERE = 3 };  /* image.rs:73-78 */
 enum { SHM_SPECTRUM_TYPE_ALBEDO = 0, SHM_SPECTRUM_TYPE_UNBOUNDED = 1, SHM_SPECTRUM_TYPE_ILLUMINANT = 2 };
@@ -300,7 +315,7 @@ typedef struct ShmImageTexture {
     uint8_t n_channels;          /* 1 or 3 (an RGBA image hands over its RGB: texel_rgb / bilerp read channels 0..2, mipmap.rs:204-231) */
     uint8_t has_color_space;     /* MIPMap::get_color_space().is_some(); 0: one-channel texture -> constant spectrum (texture.rs:801-805) */
     uint32_t first_level;        /* index into ShmSceneDesc::image_levels, finest level first */
-    uint32_t n_levels;
+    uint32_t n_levels;           /* 0: a MAPPING-ONLY record, which only the procedural SHM_FLOATTEX_* kinds may name (filter .. first_level are not read) */
 } ShmImageTexture;
 /* What RgbColorSpace::to_rgb_coeffs reads (colorspace.rs:95-98 -> rgb_to_spectra.rs:16-25): the rgb2spec coefficient table of
  * the colour space's gamut (the `.spec` file the reference loads: res, scale[res], data[3][res][res][res][3]) and its
@@ -698,7 +713,8 @@ SHM_API void shm_ply_free(ShmPlyMesh* mesh);
  * Attribute, Option (incl. rendercoordsys), Sampler (independent / zsobol), PixelFilter (box gaussian mitchell sinc triangle),
  * Integrator (path / simplepath / randomwalk), Option, WorldBegin, AttributeBegin / End, Material / MakeNamedMaterial / NamedMaterial
  * (diffuse conductor dielectric thindielectric coateddiffuse coatedconductor mix, "normalmap"), Texture (float / spectrum: constant scale
- * mix directionmix imagemap — with the uv / spherical / cylindrical / planar mappings), AreaLightSource (diffuse), LightSource (point,
+ * mix directionmix imagemap — with the uv / spherical / cylindrical / planar mappings —, PBRT-v4's procedural checkerboard dots (float / spectrum) fbm windy bilerp (float);
+ * marble, ptex, spectrum bilerp: SHM_ERR_UNSUPPORTED), AreaLightSource (diffuse), LightSource (point,
  * spot, distant — the two as PBRT-v4 defines them —, infinite: uniform or an environment image), Shape (trianglemesh bilinearmesh sphere plymesh), ObjectBegin / ObjectEnd / ObjectInstance,
  * Include — with the reference's parameter names and defaults. Spectra: "float", "spectrum" (lambda / value pairs, a named spectrum or a
  * spectrum file), "blackbody", and "rgb" as RgbAlbedo / RgbUnbounded / RgbIlluminantSpectrum by the slot that reads it (paramdict.rs:605-656)

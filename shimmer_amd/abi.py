@@ -23,11 +23,15 @@ SHM_LIGHT_DISTANT, SHM_LIGHT_SPOT = 4, 5  # PBRT-v4's DistantLight / SpotLight (
 SHM_SPECTRUM_IMAGE_TEXTURE, SHM_SPECTRUM_TEXTURE_NODE = 6, 7
 SHM_SPECTEX_LEAF, SHM_SPECTEX_SCALED, SHM_SPECTEX_MIX, SHM_SPECTEX_DIRECTION_MIX = 0, 1, 2, 3
 SHM_TEXMAP_UV, SHM_TEXMAP_SPHERICAL, SHM_TEXMAP_CYLINDRICAL, SHM_TEXMAP_PLANAR = 0, 1, 2, 3
+SHM_TEXMAP_POINT3D = 4  # PBRT-v4's PointTransformMapping: only on a mapping-only ShmImageTexture (n_levels == 0)
 SHM_TEXFILTER_POINT, SHM_TEXFILTER_BILINEAR, SHM_TEXFILTER_TRILINEAR, SHM_TEXFILTER_EWA = 0, 1, 2, 3
 SHM_FILTER_BOX, SHM_FILTER_GAUSSIAN, SHM_FILTER_MITCHELL, SHM_FILTER_SINC, SHM_FILTER_TRIANGLE = 0, 1, 2, 3, 4
 SHM_WRAP_BLACK, SHM_WRAP_CLAMP, SHM_WRAP_REPEAT, SHM_WRAP_OCTAHEDRAL_SPHERE = 0, 1, 2, 3
 SHM_SPECTRUM_TYPE_ALBEDO, SHM_SPECTRUM_TYPE_UNBOUNDED, SHM_SPECTRUM_TYPE_ILLUMINANT = 0, 1, 2
 SHM_FLOATTEX_CONSTANT, SHM_FLOATTEX_SCALED, SHM_FLOATTEX_MIX, SHM_FLOATTEX_DIRECTION_MIX, SHM_FLOATTEX_IMAGE = 0, 1, 2, 3, 4
+# PBRT-v4's procedural float textures (ShmFloatTexture::image = a mapping-only ShmImageTexture)
+SHM_FLOATTEX_CHECKERBOARD, SHM_FLOATTEX_DOTS, SHM_FLOATTEX_FBM, SHM_FLOATTEX_WRINKLED, SHM_FLOATTEX_WINDY, SHM_FLOATTEX_BILERP = 5, 6, 7, 8, 9, 10
+SHM_FLOATTEX_WEIGHT_FORM = 0xffffffff  # a == b == this: a CHECKERBOARD / DOTS node that yields its weight (tex1 = 0, tex2 = 1 folded)
 (SHM_FLOATSLOT_DISPLACEMENT, SHM_FLOATSLOT_U_ROUGHNESS, SHM_FLOATSLOT_V_ROUGHNESS, SHM_FLOATSLOT_U2_ROUGHNESS,
  SHM_FLOATSLOT_V2_ROUGHNESS, SHM_FLOATSLOT_THICKNESS, SHM_FLOATSLOT_G, SHM_FLOATSLOT_MIX_AMOUNT) = range(8)
 SHM_CAMERA_PERSPECTIVE, SHM_CAMERA_ORTHOGRAPHIC = 0, 1

@@ -55,7 +55,8 @@ struct FlatScene {
     std::vector<float> texel_data;
     std::vector<float> rgb2spec_scale, rgb2spec_data, cs_illuminant, ewa_lut;
     uint32_t rgb2spec_res = 0;
-    bool has_textures = false;  // a material slot binds an image texture (the path carries ray differentials) or an image infinite
+    bool has_textures = false;  // a material slot binds a texture, image or PROCEDURAL (any bound float texture node or spectrum texture tree counts: a scene whose only
+                                // textures are checkerboards or noise is a textured scene) (the path carries ray differentials) or an image infinite
                                 // light exists (both read the colour-space tables): selects k_shade<.., HAS_TEX>
     bool has_material_textures = false, has_image_light = false;
     double area_plain_diffuse = 0.0, area_total = 0.0;  // surface area of those primitives / of all (instances' placements not counted): the split pass's second criterion
@@ -181,6 +182,67 @@ inline shm::Dist2DRec build_pc2d(const std::vector<float>& d, size_t n, std::vec
     for (size_t v = 0; v < n; ++v) integrals[v] = build_pc1d(d.data() + v * n, n, pool, r.func + v * n, r.cdf + v * (n + 1));
     r.marginal_int = build_pc1d(integrals.data(), n, pool, r.marginal_func, r.marginal_cdf);
     return r;
+}
+
+// FloatTexture node table (texture.rs:88-305): per node its post-order evaluation program. Children precede parents. Shared by flatten_scene and the device leaf probe
+// (probe/k_leaf_probe.hip), which evaluates a node table without a scene.
+inline int build_float_texture_programs(const ShmFloatTexture* float_textures, uint32_t n_float_textures, const ShmImageTexture* image_textures, uint32_t n_image_textures,
+                                        std::vector<shm::FloatTexRange>& ranges, std::vector<shm::FloatTexOp>& ops, std::string& err) {
+    // per node its post-order evaluation program (children first; a child shared by two parents is evaluated once per use, as
+    // the reference's recursion does)
+    ranges.resize(n_float_textures);
+    for (uint32_t i = 0; i < n_float_textures; ++i) {
+        const ShmFloatTexture& t = float_textures[i];
+        if (t.kind > SHM_FLOATTEX_BILERP) { err = "unknown float texture kind"; return SHM_ERR_INVALID_ARGUMENT; }
+        std::vector<shm::FloatTexOp> prog;
+        auto append_child = [&](uint32_t k) -> int {  // copies the child's program, returns the slot of its root, or -1
+            if (k >= i) return -1;
+            const shm::FloatTexRange cr = ranges[k];
+            const uint32_t base = (uint32_t)prog.size();
+            for (uint32_t q = 0; q < cr.count; ++q) {
+                shm::FloatTexOp op = ops[cr.first + q];
+                op.a = (uint8_t)(op.a + base); op.b = (uint8_t)(op.b + base); op.c = (uint8_t)(op.c + base);
+                prog.push_back(op);
+            }
+            return (int)prog.size() - 1;
+        };
+        shm::FloatTexOp self{};
+        self.node = i;
+        if (t.kind == SHM_FLOATTEX_IMAGE) {
+            if (t.image >= n_image_textures) { err = "float image texture: image index out of range"; return SHM_ERR_INVALID_ARGUMENT; }
+            if (image_textures[t.image].n_levels == 0) { err = "float image texture: its image is a mapping-only record (n_levels == 0)"; return SHM_ERR_INVALID_ARGUMENT; }
+        } else if (t.kind >= SHM_FLOATTEX_CHECKERBOARD) {
+            // PBRT-v4's procedurals: `image` names a mapping-only record
+            if (t.image >= n_image_textures) { err = "procedural float texture: texture mapping index out of range"; return SHM_ERR_INVALID_ARGUMENT; }
+            const ShmImageTexture& map = image_textures[t.image];
+            if (map.n_levels != 0) { err = "procedural float texture: its texture mapping must be a mapping-only record (n_levels == 0)"; return SHM_ERR_INVALID_ARGUMENT; }
+            const bool is_3d = map.mapping == SHM_TEXMAP_POINT3D;
+            const bool noise_kind = t.kind == SHM_FLOATTEX_FBM || t.kind == SHM_FLOATTEX_WRINKLED || t.kind == SHM_FLOATTEX_WINDY;
+            if (noise_kind && !is_3d) { err = "fbm / wrinkled / windy float texture: needs the 3-D point mapping (SHM_TEXMAP_POINT3D), not a 2-D mapping"; return SHM_ERR_INVALID_ARGUMENT; }
+            if ((t.kind == SHM_FLOATTEX_DOTS || t.kind == SHM_FLOATTEX_BILERP) && is_3d) { err = "dots / bilerp float texture: needs (s, t), a 2-D mapping, not the 3-D point mapping"; return SHM_ERR_INVALID_ARGUMENT; }
+            // (the device loop runs `octaves` times: bounded; PBRT-v4's default is 8)
+            if ((t.kind == SHM_FLOATTEX_FBM || t.kind == SHM_FLOATTEX_WRINKLED) && t.pad[0] > 32u) { err = "fbm / wrinkled float texture: more than 32 octaves"; return SHM_ERR_UNSUPPORTED; }
+            if (t.kind == SHM_FLOATTEX_CHECKERBOARD || t.kind == SHM_FLOATTEX_DOTS) {
+                if (t.a == 0xffffffffu && t.b == 0xffffffffu) {
+                    // the weight form: a program of one op (the leaf path of float_texture_evaluate_v)
+                } else {
+                    int a = append_child(t.a), b = append_child(t.b);
+                    if (a < 0 || b < 0) { err = "checkerboard / dots float texture: child index out of range (children must precede their parent; both 0xffffffff = the weight form)"; return SHM_ERR_INVALID_ARGUMENT; }
+                    self.a = (uint8_t)a; self.b = (uint8_t)b;
+                }
+            }
+        } else if (t.kind != SHM_FLOATTEX_CONSTANT) {
+            int a = append_child(t.a), b = append_child(t.b), c = (t.kind == SHM_FLOATTEX_MIX) ? append_child(t.c) : 0;
+            if (a < 0 || b < 0 || c < 0) { err = "float texture children must precede their parent"; return SHM_ERR_INVALID_ARGUMENT; }
+            self.a = (uint8_t)a; self.b = (uint8_t)b; self.c = (uint8_t)c;
+        }
+        prog.push_back(self);
+        if (prog.size() > (size_t)shm::FTEX_MAX_OPS) { err = "float texture tree larger than 32 nodes"; return SHM_ERR_UNSUPPORTED; }
+        ranges[i].first = (uint32_t)ops.size();
+        ranges[i].count = (uint32_t)prog.size();
+        ops.insert(ops.end(), prog.begin(), prog.end());
+    }
+    return SHM_OK;
 }
 
 // Returns 0 or a negative ShmError; err receives a message.
@@ -383,13 +445,25 @@ inline int flatten_scene(const ShmSceneDesc* d, FlatScene& out, std::string& err
 
     // image textures
     if (d->n_image_textures) {
-        if (!d->image_textures || !d->image_levels || !d->texel_data) { err = "image texture arrays missing"; return SHM_ERR_INVALID_ARGUMENT; }
+        if (!d->image_textures) { err = "image texture arrays missing"; return SHM_ERR_INVALID_ARGUMENT; }
+        // (a scene whose records are all mapping-only — n_levels == 0, the texture mappings of procedural float textures — has no levels and no texels)
+        bool any_image = false;
+        for (uint32_t i = 0; i < d->n_image_textures; ++i) any_image = any_image || d->image_textures[i].n_levels != 0;
+        if (any_image && (!d->image_levels || !d->texel_data)) { err = "image texture arrays missing"; return SHM_ERR_INVALID_ARGUMENT; }
         if (d->n_texel_floats >= (1ull << 32)) { err = "more than 2^32 texel floats"; return SHM_ERR_UNSUPPORTED; }
         out.image_textures.assign(d->image_textures, d->image_textures + d->n_image_textures);
-        out.image_levels.assign(d->image_levels, d->image_levels + d->n_image_levels);
-        out.texel_data.assign(d->texel_data, d->texel_data + d->n_texel_floats);
+        if (d->image_levels && d->texel_data) {
+            out.image_levels.assign(d->image_levels, d->image_levels + d->n_image_levels);
+            out.texel_data.assign(d->texel_data, d->texel_data + d->n_texel_floats);
+        }
         bool need_cs = false, need_illum = false, need_lut = false;
         for (const ShmImageTexture& t : out.image_textures) {
+            if (t.n_levels == 0) {
+                // a mapping-only record: only its mapping fields are read, and only by procedural float texture nodes (every image use is refused below)
+                if (t.mapping > SHM_TEXMAP_POINT3D) { err = "texture mapping record: unknown mapping"; return SHM_ERR_INVALID_ARGUMENT; }
+                continue;
+            }
+            if (t.mapping == SHM_TEXMAP_POINT3D) { err = "image texture: the 3-D point mapping has no (s, t): it is valid on a mapping-only record (n_levels == 0) alone"; return SHM_ERR_INVALID_ARGUMENT; }
             if (t.mapping > SHM_TEXMAP_PLANAR || t.filter > SHM_TEXFILTER_EWA || t.wrap > SHM_WRAP_OCTAHEDRAL_SPHERE || t.spectrum_type > SHM_SPECTRUM_TYPE_ILLUMINANT) { err = "image texture: unknown mapping / filter / wrap / spectrum type"; return SHM_ERR_INVALID_ARGUMENT; }
             if (t.n_channels != 1 && t.n_channels != 3) { err = "image texture: n_channels must be 1 or 3"; return SHM_ERR_INVALID_ARGUMENT; }
             // the EWA footprint at its level spans about 2 * max_anisotropy texels per axis: bound the device loop
@@ -474,39 +548,8 @@ inline int flatten_scene(const ShmSceneDesc* d, FlatScene& out, std::string& err
     if (d->n_float_textures) {
         if (!d->float_textures) { err = "float texture array missing"; return SHM_ERR_INVALID_ARGUMENT; }
         out.float_textures.assign(d->float_textures, d->float_textures + d->n_float_textures);
-        // per node its post-order evaluation program (children first; a child shared by two parents is evaluated once per use, as
-        // the reference's recursion does)
-        out.ftex_ranges.resize(d->n_float_textures);
-        for (uint32_t i = 0; i < d->n_float_textures; ++i) {
-            const ShmFloatTexture& t = out.float_textures[i];
-            if (t.kind > SHM_FLOATTEX_IMAGE) { err = "unknown float texture kind"; return SHM_ERR_INVALID_ARGUMENT; }
-            std::vector<shm::FloatTexOp> prog;
-            auto append_child = [&](uint32_t k) -> int {  // copies the child's program, returns the slot of its root, or -1
-                if (k >= i) return -1;
-                const shm::FloatTexRange cr = out.ftex_ranges[k];
-                const uint32_t base = (uint32_t)prog.size();
-                for (uint32_t q = 0; q < cr.count; ++q) {
-                    shm::FloatTexOp op = out.ftex_ops[cr.first + q];
-                    op.a = (uint8_t)(op.a + base); op.b = (uint8_t)(op.b + base); op.c = (uint8_t)(op.c + base);
-                    prog.push_back(op);
-                }
-                return (int)prog.size() - 1;
-            };
-            shm::FloatTexOp self{};
-            self.node = i;
-            if (t.kind == SHM_FLOATTEX_IMAGE) {
-                if (t.image >= d->n_image_textures) { err = "float image texture: image index out of range"; return SHM_ERR_INVALID_ARGUMENT; }
-            } else if (t.kind != SHM_FLOATTEX_CONSTANT) {
-                int a = append_child(t.a), b = append_child(t.b), c = (t.kind == SHM_FLOATTEX_MIX) ? append_child(t.c) : 0;
-                if (a < 0 || b < 0 || c < 0) { err = "float texture children must precede their parent"; return SHM_ERR_INVALID_ARGUMENT; }
-                self.a = (uint8_t)a; self.b = (uint8_t)b; self.c = (uint8_t)c;
-            }
-            prog.push_back(self);
-            if (prog.size() > (size_t)shm::FTEX_MAX_OPS) { err = "float texture tree larger than 32 nodes"; return SHM_ERR_UNSUPPORTED; }
-            out.ftex_ranges[i].first = (uint32_t)out.ftex_ops.size();
-            out.ftex_ranges[i].count = (uint32_t)prog.size();
-            out.ftex_ops.insert(out.ftex_ops.end(), prog.begin(), prog.end());
-        }
+        const int rc = build_float_texture_programs(out.float_textures.data(), d->n_float_textures, out.image_textures.data(), d->n_image_textures, out.ftex_ranges, out.ftex_ops, err);
+        if (rc != SHM_OK) return rc;
     }
 
     // SpectrumTexture node table: the same post-order programs (<= 8 ops)
@@ -536,6 +579,7 @@ inline int flatten_scene(const ShmSceneDesc* d, FlatScene& out, std::string& err
                 if (t.leaf.kind == SHM_SPECTRUM_TEXTURE_NODE) { err = "a spectrum texture leaf cannot be a texture node"; return SHM_ERR_INVALID_ARGUMENT; }
                 bool is_tex = false;
                 if (!check_spectrum(t.leaf, nsf0, err, d->n_image_textures, &is_tex)) return SHM_ERR_INVALID_ARGUMENT;
+                if (t.leaf.kind == SHM_SPECTRUM_IMAGE_TEXTURE && out.image_textures[t.leaf.offset].n_levels == 0) { err = "spectrum texture leaf: its image is a mapping-only record (n_levels == 0)"; return SHM_ERR_INVALID_ARGUMENT; }
             } else {
                 int a = append_child(t.a), b = (t.kind == SHM_SPECTEX_SCALED) ? 0 : append_child(t.b);
                 if (a < 0 || b < 0) { err = "spectrum texture children must precede their parent"; return SHM_ERR_INVALID_ARGUMENT; }
@@ -571,9 +615,11 @@ inline int flatten_scene(const ShmSceneDesc* d, FlatScene& out, std::string& err
         for (const ShmSpectrum* sp : {&m.a, &m.b, &m.c})
             if (sp->kind == SHM_SPECTRUM_TEXTURE_NODE && sp->offset >= d->n_spectrum_textures) { err = "material spectrum texture index out of range"; return SHM_ERR_INVALID_ARGUMENT; }
         if (m.normal_map != 0u) {
-            if (m.normal_map > d->n_image_textures || out.image_textures[m.normal_map - 1].n_channels != 3) { err = "normal map: image texture index out of range or not RGB"; return SHM_ERR_INVALID_ARGUMENT; }
+            if (m.normal_map > d->n_image_textures || out.image_textures[m.normal_map - 1].n_channels != 3 || out.image_textures[m.normal_map - 1].n_levels == 0) { err = "normal map: image texture index out of range or not RGB"; return SHM_ERR_INVALID_ARGUMENT; }
             out.has_textures = true;
         }
+        for (const ShmSpectrum* sp : {&m.a, &m.b, &m.c})
+            if (sp->kind == SHM_SPECTRUM_IMAGE_TEXTURE && sp->offset < d->n_image_textures && out.image_textures[sp->offset].n_levels == 0) { err = "material image texture: a mapping-only record (n_levels == 0) is not an image"; return SHM_ERR_INVALID_ARGUMENT; }
         if (m.kind == SHM_MATERIAL_MIX) {
             // both branches must reach a single material: follow every path with a step bound (a cycle never terminates)
             if (m.mix_material[0] >= d->n_materials || m.mix_material[1] >= d->n_materials) { err = "mix material index out of range"; return SHM_ERR_INVALID_ARGUMENT; }

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../../include/shimmer_hip_probe.h"
+#include "../host/flatten.h"
 #include "../shm/probe.h"
 
 namespace {
@@ -57,6 +58,35 @@ extern "C" __attribute__((visibility("default"))) int shm_debug_eval_leaf(int de
             if (n == 0 || !(table[0] > 0.0f)) { g_probe_err = "shm_debug_eval_leaf: the filter has no table (radius, parameters)"; return SHM_ERR_INVALID_ARGUMENT; }
             for (int i = 0; i < n; ++i) with_table.push_back(shm::float_to_bits(table[i]));
         }
+        in_words = with_table.data();
+        n_in = (uint32_t)with_table.size();
+    }
+    // a float texture node table: the nodes' post-order programs are built here, on the host, with flatten_scene's own routine (which validates every index the device follows), and appended
+    if (op == shm::PROBE_FLOAT_TEXTURE) {
+        const uint32_t wf = sizeof(ShmFloatTexture) / 4, wi = sizeof(ShmImageTexture) / 4;
+        if (n_in < 5 || in_words[1] == 0 || in_words[1] > 1024 || in_words[2] > 1024 || in_words[0] >= in_words[1] || in_words[4] == 0 || in_words[4] > (1u << 14) ||
+            n_in != 5 + 18 * in_words[4] + wf * in_words[1] + wi * in_words[2] || in_words[4] > n_out) {
+            g_probe_err = "shm_debug_eval_leaf: the float texture probe needs 5 + 18 n + 12 n_float_textures + 34 n_image_textures argument words and n output words";
+            return SHM_ERR_INVALID_ARGUMENT;
+        }
+        const uint32_t* rec = in_words + 5 + 18 * in_words[4];
+        std::vector<ShmFloatTexture> ft(in_words[1]);
+        std::vector<ShmImageTexture> it(in_words[2]);
+        memcpy(ft.data(), rec, ft.size() * sizeof(ShmFloatTexture));
+        if (!it.empty()) memcpy(it.data(), rec + wf * in_words[1], it.size() * sizeof(ShmImageTexture));
+        for (const ShmFloatTexture& t : ft)
+            if (t.kind == SHM_FLOATTEX_IMAGE) { g_probe_err = "shm_debug_eval_leaf: the float texture probe carries no image levels or texels (no imagemap node)"; return SHM_ERR_INVALID_ARGUMENT; }
+        for (const ShmImageTexture& t : it)
+            if (t.n_levels != 0 || t.mapping > SHM_TEXMAP_POINT3D) { g_probe_err = "shm_debug_eval_leaf: the float texture probe takes mapping-only records (n_levels == 0)"; return SHM_ERR_INVALID_ARGUMENT; }
+        std::vector<shm::FloatTexRange> ranges;
+        std::vector<shm::FloatTexOp> ops;
+        const int rc = shm_host::build_float_texture_programs(ft.data(), (uint32_t)ft.size(), it.data(), (uint32_t)it.size(), ranges, ops, g_probe_err);
+        if (rc != SHM_OK) return rc;
+        static_assert(sizeof(shm::FloatTexRange) == 8 && sizeof(shm::FloatTexOp) == 8, "two words each");
+        with_table.assign(in_words, in_words + n_in);
+        with_table.resize(n_in + 2 * ranges.size() + 2 * ops.size());
+        memcpy(with_table.data() + n_in, ranges.data(), ranges.size() * 8);
+        memcpy(with_table.data() + n_in + 2 * ranges.size(), ops.data(), ops.size() * 8);
         in_words = with_table.data();
         n_in = (uint32_t)with_table.size();
     }

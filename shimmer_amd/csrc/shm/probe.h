@@ -16,7 +16,7 @@ enum : int {
     PROBE_TRIANGLE_PDF_WITH_CONTEXT, PROBE_TRIANGLE_INTERACTION, PROBE_SPHERE_SAMPLE_WITH_CONTEXT, PROBE_SPHERE_PDF_WITH_CONTEXT, PROBE_AREA_LIGHT_L, PROBE_FILM_ADD_SAMPLE,
     PROBE_CAMERA_RAY_DIFFERENTIAL, PROBE_INTERVAL_OP, PROBE_DET3, PROBE_ROTATE_FROM_TO, PROBE_SAMPLE_DISCRETE, PROBE_SAMPLER_STREAM, PROBE_SAMPLE_VISIBLE_WAVELENGTHS,
     PROBE_VISIBLE_WAVELENGTHS_PDF, PROBE_VECMATH, PROBE_TRANSFORM_APPLY, PROBE_BLP_INTERSECT, PROBE_BLP_SAMPLE_WITH_CONTEXT, PROBE_BLP_PDF_WITH_CONTEXT, PROBE_SPHERE_INTERSECT,
-    PROBE_UNARY, PROBE_EQUAL_AREA_SQUARE_TO_SPHERE, PROBE_EQUAL_AREA_SPHERE_TO_SQUARE, PROBE_ZSOBOL_STREAM, PROBE_FILTER_SAMPLE, PROBE_LIGHT_SAMPLE_LI, PROBE_N_OPS
+    PROBE_UNARY, PROBE_EQUAL_AREA_SQUARE_TO_SPHERE, PROBE_EQUAL_AREA_SPHERE_TO_SQUARE, PROBE_ZSOBOL_STREAM, PROBE_FILTER_SAMPLE, PROBE_LIGHT_SAMPLE_LI, PROBE_FLOAT_TEXTURE, PROBE_N_OPS
 };
 
 namespace probe_detail {
@@ -309,6 +309,31 @@ SHM_HD int leaf_probe(int op, const uint32_t* in, uint32_t* out) {
                 Float w;
                 filter_sample(in[0], f(in, 1), f(in, 2), table, v2(f(in, 6 + 2 * i), f(in, 7 + 2 * i)), p, w);
                 put(out, 3 * i, p.x); put(out, 3 * i + 1, p.y); put(out, 3 * i + 2, w);
+            }
+            return n;
+        }
+        case PROBE_FLOAT_TEXTURE: {  // FloatTexture::evaluate of node `node` of a node table (shm/texture.h: float_texture_evaluate_v) at n explicit contexts; node, n_float_textures,
+                                     // n_image_textures, disable_reference_quirks, n, then n contexts of 18 floats (p, dpdx, dpdy, n, uv, dudx, dudy, dvdx, dvdy), the ShmFloatTexture
+                                     // records' bytes, the ShmImageTexture records' bytes (mapping-only ones: no level or texel is read); behind them the nodes' post-order programs —
+                                     // ranges, then ops —, which the HOST builds (build_float_texture_programs: shm_debug_eval_leaf appends them, as flatten_scene does for a scene).
+                                     // Per context: the value
+            const uint32_t nf = in[1], ni = in[2];
+            const int n = (int)in[4];
+            const uint32_t* rec = in + 5 + 18 * n;
+            SceneView sv;
+            memset(&sv, 0, sizeof(sv));
+            sv.float_textures = reinterpret_cast<const ShmFloatTexture*>(rec);
+            sv.image_textures = reinterpret_cast<const ShmImageTexture*>(rec + nf * (sizeof(ShmFloatTexture) / 4));
+            sv.ftex_ranges = reinterpret_cast<const FloatTexRange*>(rec + nf * (sizeof(ShmFloatTexture) / 4) + ni * (sizeof(ShmImageTexture) / 4));
+            sv.ftex_ops = reinterpret_cast<const FloatTexOp*>(reinterpret_cast<const uint32_t*>(sv.ftex_ranges) + 2 * nf);
+            sv.quirks_off = in[3];
+            sv.call_copy = &sv;  // (the evaluators that are real calls read the scene through this pointer on the device)
+            for (int i = 0; i < n; ++i) {
+                const uint32_t* c = in + 5 + 18 * i;
+                TextureEvalContext ctx;
+                ctx.p = f3(c, 0); ctx.dpdx = f3(c, 3); ctx.dpdy = f3(c, 6); ctx.n = f3(c, 9); ctx.uv = v2(f(c, 12), f(c, 13));
+                ctx.dudx = f(c, 14); ctx.dudy = f(c, 15); ctx.dvdx = f(c, 16); ctx.dvdy = f(c, 17);
+                put(out, i, float_texture_evaluate(sv, in[0], ctx));
             }
             return n;
         }

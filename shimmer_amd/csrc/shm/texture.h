@@ -505,6 +505,159 @@ SHM_HD_NOINLINE Float float_image_texture_evaluate_v(const SceneView* svp, uint3
 SHM_HD Float float_image_texture_evaluate(const SceneView& sv, uint32_t texture_index, const TextureEvalContext& ctx) {
     return float_image_texture_evaluate_v(SHM_SV_FOR_CALL(sv), texture_index, SHM_TEXCTX_ARGS(ctx));
 }
+// ---------------------------------------------------------------------------------------------
+// PBRT-v4's procedural float textures (textures.cpp / util/noise.cpp; the reference has none, and no noise function): Perlin noise, FBm and turbulence with
+// the octave clamp from the ray differentials, the box-filtered checkerboard in two and three dimensions, polka dots, bilinear interpolation of four values.
+// All float32, evaluated in the order written (no contraction), so the device and the CPU oracle agree bit for bit.
+// ---------------------------------------------------------------------------------------------
+// Ken Perlin's permutation as PBRT-v4's NoisePerm holds it. PBRT-v4 stores it twice in a row so that perm[perm[x] + y] needs no wrap; 256 entries indexed
+// `& 255` are the same function. On the device: 256 bytes of constant memory, read with per-lane gathers (24 dependent ones per Noise).
+static constexpr uint8_t NOISE_PERM[256] = {
+    151, 160, 137, 91, 90, 15, 131, 13, 201, 95, 96, 53, 194, 233, 7, 225, 140, 36, 103, 30, 69, 142, 8, 99, 37, 240, 21, 10, 23, 190, 6, 148,
+    247, 120, 234, 75, 0, 26, 197, 62, 94, 252, 219, 203, 117, 35, 11, 32, 57, 177, 33, 88, 237, 149, 56, 87, 174, 20, 125, 136, 171, 168, 68, 175,
+    74, 165, 71, 134, 139, 48, 27, 166, 77, 146, 158, 231, 83, 111, 229, 122, 60, 211, 133, 230, 220, 105, 92, 41, 55, 46, 245, 40, 244, 102, 143, 54,
+    65, 25, 63, 161, 1, 216, 80, 73, 209, 76, 132, 187, 208, 89, 18, 169, 200, 196, 135, 130, 116, 188, 159, 86, 164, 100, 109, 198, 173, 186, 3, 64,
+    52, 217, 226, 250, 124, 123, 5, 202, 38, 147, 118, 126, 255, 82, 85, 212, 207, 206, 59, 227, 47, 16, 58, 17, 182, 189, 28, 42, 223, 183, 170, 213,
+    119, 248, 152, 2, 44, 154, 163, 70, 221, 153, 101, 155, 167, 43, 172, 9, 129, 22, 39, 253, 19, 98, 108, 110, 79, 113, 224, 232, 178, 185, 112, 104,
+    218, 246, 97, 228, 251, 34, 242, 193, 238, 210, 144, 12, 191, 179, 162, 241, 81, 51, 145, 235, 249, 14, 239, 107, 49, 192, 214, 31, 181, 199, 106, 157,
+    184, 84, 204, 176, 115, 121, 50, 45, 127, 4, 150, 254, 138, 236, 205, 93, 222, 114, 67, 29, 24, 72, 243, 141, 128, 195, 78, 66, 215, 61, 156, 180};
+SHM_HD int noise_perm(int i) { return (int)NOISE_PERM[i & 255]; }
+// Grad: the corner's gradient (one of Perlin's sixteen) dotted with the offset from the corner
+SHM_HD Float noise_grad(int x, int y, int z, Float dx, Float dy, Float dz) {
+    int h = noise_perm(noise_perm(noise_perm(x) + y) + z) & 15;
+    Float u = (h < 8 || h == 12 || h == 13) ? dx : dy;
+    Float v = (h < 4 || h == 12 || h == 13) ? dy : dz;
+    return ((h & 1) ? -u : u) + ((h & 2) ? -v : v);
+}
+SHM_HD Float noise_weight(Float t) {
+    Float t3 = t * t * t;
+    Float t4 = t3 * t;
+    return 6.0f * t4 * t - 15.0f * t4 + 10.0f * t3;
+}
+// (a real call on the device, below float_procedural_evaluate_v: inlined eight-fold into FBm, Turbulence and dots it cost the textured kernels more scratch — DESIGN §4e)
+SHM_HD_NOINLINE Float noise(Float x, Float y, Float z) {
+    // (a coordinate beyond the int range saturates: its cell is then arbitrary but defined, and the same on both sides)
+    int ix = float_to_i32(floor(x)), iy = float_to_i32(floor(y)), iz = float_to_i32(floor(z));
+    Float dx = x - (Float)ix, dy = y - (Float)iy, dz = z - (Float)iz;
+    ix &= 255; iy &= 255; iz &= 255;
+    Float w000 = noise_grad(ix, iy, iz, dx, dy, dz);
+    Float w100 = noise_grad(ix + 1, iy, iz, dx - 1.0f, dy, dz);
+    Float w010 = noise_grad(ix, iy + 1, iz, dx, dy - 1.0f, dz);
+    Float w110 = noise_grad(ix + 1, iy + 1, iz, dx - 1.0f, dy - 1.0f, dz);
+    Float w001 = noise_grad(ix, iy, iz + 1, dx, dy, dz - 1.0f);
+    Float w101 = noise_grad(ix + 1, iy, iz + 1, dx - 1.0f, dy, dz - 1.0f);
+    Float w011 = noise_grad(ix, iy + 1, iz + 1, dx, dy - 1.0f, dz - 1.0f);
+    Float w111 = noise_grad(ix + 1, iy + 1, iz + 1, dx - 1.0f, dy - 1.0f, dz - 1.0f);
+    Float wx = noise_weight(dx), wy = noise_weight(dy), wz = noise_weight(dz);
+    Float x00 = lerp(wx, w000, w100), x10 = lerp(wx, w010, w110), x01 = lerp(wx, w001, w101), x11 = lerp(wx, w011, w111);
+    Float y0 = lerp(wy, x00, x10), y1 = lerp(wy, x01, x11);
+    return lerp(wz, y0, y1);
+}
+SHM_HD Float noise(V3 p) { return noise(p.x, p.y, p.z); }
+SHM_HD Float noise2(Float x, Float y) { return noise(x, y, 0.5f); }
+SHM_HD Float smooth_step(Float x, Float a, Float b) {
+    Float t = clamp((x - a) / (b - a), 0.0f, 1.0f);
+    return t * t * (3.0f - 2.0f * t);
+}
+// the number of octaves the footprint admits: zero differentials give log2(0) = -inf, n = +inf, clamped to max_octaves
+SHM_HD Float noise_octaves(V3 dpdx, V3 dpdy, int max_octaves) {
+    Float len2 = max(length_squared(dpdx), length_squared(dpdy));
+    return clamp(-1.0f - log2(len2) / 2.0f, 0.0f, (Float)max_octaves);
+}
+SHM_HD Float fbm(V3 p, V3 dpdx, V3 dpdy, Float omega, int max_octaves) {
+    Float n = noise_octaves(dpdx, dpdy, max_octaves);
+    int n_int = float_to_i32(floor(n));
+    Float sum = 0.0f, lambda = 1.0f, o = 1.0f;
+    for (int i = 0; i < n_int; ++i) {
+        sum += o * noise(lambda * p);
+        lambda *= 1.99f;
+        o *= omega;
+    }
+    Float n_partial = n - (Float)n_int;
+    sum += o * smooth_step(n_partial, 0.3f, 0.7f) * noise(lambda * p);
+    return sum;
+}
+SHM_HD Float turbulence(V3 p, V3 dpdx, V3 dpdy, Float omega, int max_octaves) {
+    Float n = noise_octaves(dpdx, dpdy, max_octaves);
+    int n_int = float_to_i32(floor(n));
+    Float sum = 0.0f, lambda = 1.0f, o = 1.0f;
+    for (int i = 0; i < n_int; ++i) {
+        sum += o * abs(noise(lambda * p));
+        lambda *= 1.99f;
+        o *= omega;
+    }
+    Float n_partial = n - (Float)n_int;
+    sum += o * lerp(smooth_step(n_partial, 0.3f, 0.7f), 0.2f, abs(noise(lambda * p)));
+    for (int i = n_int; i < max_octaves; ++i) {
+        sum += o * 0.2f;
+        o *= omega;
+    }
+    return sum;
+}
+// Checkerboard: the integral of the +-1 square wave, and the wave box-filtered over [x - r, x + r] from its second difference
+SHM_HD Float checker_d(Float x) {
+    Float y = x / 2.0f - floor(x / 2.0f) - 0.5f;
+    return x / 2.0f + y * (1.0f - 2.0f * abs(y));
+}
+SHM_HD Float checker_bf(Float x, Float r) {
+    if (floor(x - r) == floor(x + r)) return (Float)(1 - 2 * (float_to_i32(floor(x)) & 1));
+    return (checker_d(x + r) - 2.0f * checker_d(x) + checker_d(x - r)) / (r * r);
+}
+// the point p and its differentials in texture space: PBRT-v4's PointTransformMapping (SHM_TEXMAP_POINT3D)
+SHM_HD void texture_map_3d(const ShmImageTexture& t, const TextureEvalContext& ctx, V3& p, V3& dpdx, V3& dpdy) {
+    p = xf_point(t.texture_from_render, ctx.p);
+    dpdx = xf_vector(t.texture_from_render, ctx.dpdx);
+    dpdy = xf_vector(t.texture_from_render, ctx.dpdy);
+}
+// What a procedural node computes by itself (include/shimmer_hip.h, SHM_FLOATTEX_*): CHECKERBOARD and DOTS the weight w of their second operand, FBM, WRINKLED, WINDY
+// and BILERP their value. `ShmFloatTexture::image` names the mapping-only ShmImageTexture record. A real call in the scalar calling form, like the image evaluators:
+// the noise code stays out of the node loop and of every caller's register budget.
+SHM_HD_NOINLINE Float float_procedural_evaluate_v(const SceneView* svp, uint32_t node, SHM_TEXCTX_PARAMS) {
+    const SceneView& sv = *svp;
+    SHM_TEXCTX_FROM_PARAMS(ctx);
+    const ShmFloatTexture& t = sv.float_textures[node];
+    const ShmImageTexture& map = sv.image_textures[t.image];
+    if (map.mapping == SHM_TEXMAP_POINT3D) {
+        V3 p, dpdx, dpdy;
+        texture_map_3d(map, ctx, p, dpdx, dpdy);
+        if (t.kind == SHM_FLOATTEX_FBM) return fbm(p, dpdx, dpdy, t.value, (int)t.pad[0]);
+        if (t.kind == SHM_FLOATTEX_WRINKLED) return turbulence(p, dpdx, dpdy, t.value, (int)t.pad[0]);
+        if (t.kind == SHM_FLOATTEX_WINDY) {
+            Float wind_strength = fbm(0.1f * p, 0.1f * dpdx, 0.1f * dpdy, 0.5f, 3);
+            Float wave_height = fbm(p, dpdx, dpdy, 0.5f, 6);
+            return abs(wind_strength) * wave_height;
+        }
+        // CHECKERBOARD, dimension 3
+        Float bx = checker_bf(p.x, 1.5f * max(abs(dpdx.x), abs(dpdy.x)));
+        Float by = checker_bf(p.y, 1.5f * max(abs(dpdx.y), abs(dpdy.y)));
+        Float bz = checker_bf(p.z, 1.5f * max(abs(dpdx.z), abs(dpdy.z)));
+        return 0.5f - bx * by * bz / 2.0f;
+    }
+    const TexCoord2D c = texture_map(map, ctx, sv.quirks_off != 0);
+    if (t.kind == SHM_FLOATTEX_CHECKERBOARD) {
+        Float ds = 1.5f * max(abs(c.dsdx), abs(c.dsdy));
+        Float dt = 1.5f * max(abs(c.dtdx), abs(c.dtdy));
+        return 0.5f - checker_bf(c.st.x, ds) * checker_bf(c.st.y, dt) / 2.0f;
+    }
+    if (t.kind == SHM_FLOATTEX_DOTS) {
+        Float s_cell = floor(c.st.x + 0.5f), t_cell = floor(c.st.y + 0.5f);
+        if (noise2(s_cell + 0.5f, t_cell + 0.5f) > 0.0f) {
+            const Float radius = 0.35f;
+            const Float max_shift = 0.5f - radius;
+            Float s_center = s_cell + max_shift * noise2(s_cell + 1.5f, t_cell + 2.8f);
+            Float t_center = t_cell + max_shift * noise2(s_cell + 4.5f, t_cell + 9.8f);
+            Float ds = c.st.x - s_center, dt = c.st.y - t_center;
+            if (ds * ds + dt * dt < radius * radius) return 0.0f;  // inside the dot: the first operand
+        }
+        return 1.0f;
+    }
+    // BILERP: value, dir[0..2] = v00, v01, v10, v11
+    const Float s = c.st.x, tt = c.st.y;
+    return (1.0f - s) * (1.0f - tt) * t.value + s * (1.0f - tt) * t.dir[1] + (1.0f - s) * tt * t.dir[0] + s * tt * t.dir[2];
+}
+SHM_HD Float float_procedural_evaluate(const SceneView& sv, uint32_t node, const TextureEvalContext& ctx) {
+    return float_procedural_evaluate_v(SHM_SV_FOR_CALL(sv), node, SHM_TEXCTX_ARGS(ctx));
+}
 // FloatTexture::evaluate (texture.rs:142-152): the node's post-order program (scene.h FloatTexOp), children before parents
 SHM_HD_NOINLINE Float float_texture_evaluate_v(const SceneView* svp, uint32_t index, SHM_TEXCTX_PARAMS) {
     const SceneView& sv = *svp;
@@ -513,9 +666,12 @@ SHM_HD_NOINLINE Float float_texture_evaluate_v(const SceneView* svp, uint32_t in
     if (r.count == 1u) {
         // a program of one op is a leaf (the combining kinds have children before them): evaluated without the value array, which — indexed at run time —
         // lives in scratch memory on the device (a store and a dependent load around the one value)
-        const ShmFloatTexture& t = sv.float_textures[sv.ftex_ops[r.first].node];
+        const uint32_t node = sv.ftex_ops[r.first].node;
+        const ShmFloatTexture& t = sv.float_textures[node];
         if (t.kind == SHM_FLOATTEX_CONSTANT) return t.value;
         if (t.kind == SHM_FLOATTEX_IMAGE) return float_image_texture_evaluate(sv, t.image, ctx);
+        // a procedural leaf: FBM, WRINKLED, WINDY, BILERP, and the weight form of CHECKERBOARD and DOTS (tex1 = 0, tex2 = 1 folded: flatten_scene gives only that form one op)
+        if (t.kind >= SHM_FLOATTEX_CHECKERBOARD) return float_procedural_evaluate(sv, node, ctx);
     }
     Float vals[FTEX_MAX_OPS];
     for (uint32_t k = 0; k < r.count; ++k) {
@@ -534,6 +690,14 @@ SHM_HD_NOINLINE Float float_texture_evaluate_v(const SceneView* svp, uint32_t in
             Float t1 = (amt != 1.0f) ? vals[op.a] : 0.0f;
             Float t2 = (amt != 0.0f) ? vals[op.b] : 0.0f;
             v = t1 * (1.0f - amt) + t2 * amt;
+        } else if (t.kind >= SHM_FLOATTEX_CHECKERBOARD) { // PBRT-v4's procedurals
+            v = float_procedural_evaluate(sv, op.node, ctx);
+            if ((t.kind == SHM_FLOATTEX_CHECKERBOARD || t.kind == SHM_FLOATTEX_DOTS) && t.a != 0xffffffffu) {
+                // FloatCheckerboardTexture / FloatDotsTexture: v is the weight of the second operand; tex1 (inside) = a, tex2 (outside) = b
+                Float t1 = (v != 1.0f) ? vals[op.a] : 0.0f;
+                Float t2 = (v != 0.0f) ? vals[op.b] : 0.0f;
+                v = (1.0f - v) * t1 + v * t2;
+            }
         } else {                                          // FloatDirectionMixTexture, texture.rs:290-305
             Float amt = dot(ctx.n, ld3(t.dir));
             Float t1 = (amt != 0.0f) ? vals[op.a] : 0.0f;

@@ -431,10 +431,11 @@ class SceneBuilder:
         return len(self.lights) - 1
 
     # ---- float textures (texture.rs:88-305) ----
-    def _ftex(self, kind, value=0.0, a=0, b=0, c=0, dir=(0.0, 1.0, 0.0), image=0):
+    def _ftex(self, kind, value=0.0, a=0, b=0, c=0, dir=(0.0, 1.0, 0.0), image=0, octaves=0):
         t = abi.ShmFloatTexture()
         t.kind, t.value, t.a, t.b, t.c, t.image = kind, float(value), int(a), int(b), int(c), int(image)
         t.dir[:] = [float(x) for x in dir]
+        t.pad[0] = int(octaves)
         self.float_textures.append(t)
         return len(self.float_textures) - 1
 
@@ -463,6 +464,54 @@ class SceneBuilder:
         sp = self.add_image_texture(image, **kw)
         return self._ftex(abi.SHM_FLOATTEX_IMAGE, image=sp.offset)
 
+    # ---- PBRT-v4's procedural float textures (the reference has none) ----
+    def add_texture_mapping(self, mapping="uv", su=1.0, sv=1.0, du=0.0, dv=0.0, texture_from_render=None, vs=(1.0, 0.0, 0.0), vt=(0.0, 1.0, 0.0)):
+        """A mapping-only ShmImageTexture record (n_levels == 0): the texture mapping a procedural float texture names through ShmFloatTexture::image.
+        `mapping`: "uv", "spherical", "cylindrical", "planar" (PBRT-v4's TextureMapping2D) or "point3d" (its PointTransformMapping). Returns the record's index."""
+        t = abi.ShmImageTexture()
+        t.mapping = {"uv": abi.SHM_TEXMAP_UV, "spherical": abi.SHM_TEXMAP_SPHERICAL, "cylindrical": abi.SHM_TEXMAP_CYLINDRICAL,
+                     "planar": abi.SHM_TEXMAP_PLANAR, "point3d": abi.SHM_TEXMAP_POINT3D}[mapping]
+        t.su, t.sv, t.du, t.dv = float(su), float(sv), float(du), float(dv)
+        t.vs[:], t.vt[:] = [float(x) for x in vs], [float(x) for x in vt]
+        t.texture_from_render[:] = [float(x) for x in _as_f32(IDENTITY if texture_from_render is None else texture_from_render).ravel()]
+        # what the front end's default record carries in the fields a mapping-only record does not read
+        t.filter, t.max_anisotropy, t.wrap, t.scale, t.n_channels = abi.SHM_TEXFILTER_BILINEAR, 8.0, abi.SHM_WRAP_REPEAT, 1.0, 3
+        self.textures.append(t)
+        return len(self.textures) - 1
+
+    def _mapping_of(self, mapping, default):
+        return self.add_texture_mapping(default) if mapping is None else int(mapping)
+
+    def _ftex_operand(self, v):
+        """An operand of a procedural node: a handle, or a number as the front end writes it (a constant node with every other field zero)."""
+        return v if isinstance(v, (int, np.integer)) and not isinstance(v, bool) else self._ftex(abi.SHM_FLOATTEX_CONSTANT, value=v, dir=(0.0, 0.0, 0.0))
+
+    def _ftex_weight(self, kind, tex1, tex2, mapping):
+        """CHECKERBOARD / DOTS: the weight form when both operands are None, else the child form."""
+        if tex1 is None and tex2 is None:
+            return self._ftex(kind, a=abi.SHM_FLOATTEX_WEIGHT_FORM, b=abi.SHM_FLOATTEX_WEIGHT_FORM, dir=(0.0, 0.0, 0.0), image=mapping)
+        a, b = self._ftex_operand(tex1), self._ftex_operand(tex2)
+        return self._ftex(kind, a=a, b=b, dir=(0.0, 0.0, 0.0), image=mapping)
+
+    def ftex_checkerboard(self, tex1=1.0, tex2=0.0, mapping=None):
+        """"checkerboard": `mapping` is a handle of add_texture_mapping (a 2-D mapping: dimension 2; "point3d": dimension 3; default: uv). tex1 = tex2 = None: the weight form."""
+        return self._ftex_weight(abi.SHM_FLOATTEX_CHECKERBOARD, tex1, tex2, self._mapping_of(mapping, "uv"))
+
+    def ftex_dots(self, inside=1.0, outside=0.0, mapping=None):
+        return self._ftex_weight(abi.SHM_FLOATTEX_DOTS, inside, outside, self._mapping_of(mapping, "uv"))
+
+    def ftex_fbm(self, octaves=8, roughness=0.5, mapping=None):
+        return self._ftex(abi.SHM_FLOATTEX_FBM, value=roughness, octaves=octaves, dir=(0.0, 0.0, 0.0), image=self._mapping_of(mapping, "point3d"))
+
+    def ftex_wrinkled(self, octaves=8, roughness=0.5, mapping=None):
+        return self._ftex(abi.SHM_FLOATTEX_WRINKLED, value=roughness, octaves=octaves, dir=(0.0, 0.0, 0.0), image=self._mapping_of(mapping, "point3d"))
+
+    def ftex_windy(self, mapping=None):
+        return self._ftex(abi.SHM_FLOATTEX_WINDY, dir=(0.0, 0.0, 0.0), image=self._mapping_of(mapping, "point3d"))
+
+    def ftex_bilerp(self, v00=0.0, v01=1.0, v10=0.0, v11=1.0, mapping=None):
+        return self._ftex(abi.SHM_FLOATTEX_BILERP, value=v00, dir=(v01, v10, v11), image=self._mapping_of(mapping, "uv"))
+
     # ---- composite spectrum textures (texture.rs:536-687) ----
     def _stex_node(self, v):
         """A spectrum-texture operand -> node index: a bound ShmSpectrum of kind TEXTURE_NODE is its node, anything else becomes a leaf."""
@@ -488,6 +537,16 @@ class SceneBuilder:
 
     def stex_mix(self, tex1, tex2, amount=0.5):
         return self._stex(abi.SHM_SPECTEX_MIX, self._stex_node(tex1), self._stex_node(tex2), f=self._ftex_of(amount))
+
+    def _stex_weighted(self, weight, tex1, tex2):
+        return self._stex(abi.SHM_SPECTEX_MIX, self._stex_node(tex1), self._stex_node(tex2), f=weight, dir=(0.0, 0.0, 0.0))
+
+    def stex_checkerboard(self, tex1=1.0, tex2=0.0, mapping=None):
+        """PBRT-v4's SpectrumCheckerboardTexture, lowered to SHM_SPECTEX_MIX(tex1, tex2, amount = the checkerboard's weight form): the same arithmetic."""
+        return self._stex_weighted(self.ftex_checkerboard(None, None, mapping), tex1, tex2)
+
+    def stex_dots(self, inside=1.0, outside=0.0, mapping=None):
+        return self._stex_weighted(self.ftex_dots(None, None, mapping), inside, outside)
 
     def stex_direction_mix(self, tex1, tex2, dir=(0.0, 1.0, 0.0)):
         return self._stex(abi.SHM_SPECTEX_DIRECTION_MIX, self._stex_node(tex1), self._stex_node(tex2), dir=dir)
@@ -837,14 +896,14 @@ class SceneBuilder:
         self._keep = [nodes, prim_arr, lights, meshes, spheres, materials, spec, bounds, order, patch_meshes, instances]
         if self.textures or self.image_lights:
             textures = (abi.ShmImageTexture * max(1, len(self.textures)))(*self.textures)
-            levels = (abi.ShmImageLevel * len(self.tex_levels))()
+            levels = (abi.ShmImageLevel * max(1, len(self.tex_levels)))()  # (mapping-only records alone: no levels, no texels)
             for i, (w, h, off) in enumerate(self.tex_levels):
                 levels[i].width, levels[i].height, levels[i].texel_offset = w, h, off
-            texels = np.concatenate(self.texels).astype(np.float32)
+            texels = np.concatenate(self.texels).astype(np.float32) if self.texels else np.zeros(1, np.float32)
             lut = _as_f32(tables()["MIP_FILTER_LUT"])
             d.n_image_textures, d.image_textures = len(self.textures), textures
             d.n_image_levels, d.image_levels = len(self.tex_levels), levels
-            d.n_texel_floats, d.texel_data = texels.size, _fptr(texels)
+            d.n_texel_floats, d.texel_data = (texels.size if self.texels else 0), _fptr(texels)
             d.ewa_filter_lut = _fptr(lut)
             self._keep += [textures, levels, texels, lut]
             if self.color_space is not None:

@@ -239,6 +239,66 @@ def cornell_box(lib, width=512, height=512, coated=False, mix=False, patches=Fal
     return _finish(b, lib, extra_lights=extra_lights, rfw=rfw, name="S2 cornell box" + (" (environment map)" if environment is not None else "") + (" (coated)" if coated else "") + (" (mix)" if mix else "") + (" (patches)" if patches else "") + (" (textured)" if textured else "") + (" (glass)" if glass else "") + (" (+ glass)" if glass_too else ""))
 
 
+def procedural_cornell(lib, width=33, height=31, which="checker", film=None, extra_lights=None):
+    """The Cornell box with PBRT-v4's procedural textures (no image anywhere: a scene whose only textures are procedural is a textured scene).
+    which = "checker": a spectrum checkerboard on the floor (planar mapping), spectrum dots on the back wall (spherical mapping), a float bilerp (cylindrical mapping) scaling
+                       the right wall, a float checkerboard in its child form (3-D point mapping) on the tall box's conductor roughness; every other surface is plain
+                       diffuse (the split pass of a textured scene);
+            "general": as "checker", plus a sphere with a 3-D spectrum checkerboard, a curved bilinear patch with spectrum dots (uv mapping) and a patch light;
+            "coated":  a coated-diffuse floor whose bump map is `wrinkled`, whose interface roughness is driven by `fbm` and whose thickness by `windy` (the LayeredBxDF stages)."""
+    b = SceneBuilder()
+    b.set_film(width, height, **(film or {}))
+    rfw = b.set_camera_look_at(lib, (0, 1, 3.4), (0, 1, 0), (0, 1, 0), 39.0)
+    world_from_render = np.linalg.inv(np.asarray(rfw, np.float64).reshape(4, 4))
+
+    def mapping(kind, scale=1.0, centre=(0.0, 0.0, 0.0), **kw):  # texture space = scale * (world - centre)
+        m = np.diag([scale, scale, scale, 1.0])
+        m[:3, 3] = [-scale * c for c in centre]
+        return b.add_texture_mapping(kind, texture_from_render=m @ world_from_render, **kw)
+    white, black = b.material_diffuse(0.75), b.material_diffuse(0.0)
+    red, green_spec = b.material_diffuse(_two_point_spectrum(b, 0.05, 0.75)), _two_point_spectrum(b, 0.6, 0.08)
+    floor_m = b.material_diffuse(b.stex_checkerboard(0.7, _two_point_spectrum(b, 0.3, 0.05), mapping("planar", vs=(2.0, 0.0, 0.0), vt=(0.0, 0.0, 2.0), du=0.25, dv=0.25)))
+    back_m = b.material_diffuse(b.stex_dots(_two_point_spectrum(b, 0.1, 0.6), 0.7, mapping("spherical", centre=(0.0, 1.0, 0.5))))
+    right_m = b.material_diffuse(b.stex_scaled(green_spec, b.ftex_bilerp(0.2, 1.0, 0.6, 0.3, mapping("cylindrical", centre=(0.0, 0.0, 0.0)))))
+    tall_m = b.material_conductor(b.spectrum_named("metal-Al-eta"), b.spectrum_named("metal-Al-k"), roughness=0.1)
+    b.set_float_texture(tall_m, abi.SHM_FLOATSLOT_U_ROUGHNESS, b.ftex_checkerboard(0.05, 0.3, mapping("point3d", scale=5.0)))
+    short_m = white
+    if which == "coated":
+        floor_m = b.material_coated_diffuse(reflectance=0.6, roughness=0.1, thickness=0.05, albedo=0.3, g=0.2)
+        noise_space = mapping("point3d", scale=6.0)
+        b.set_float_texture(floor_m, abi.SHM_FLOATSLOT_DISPLACEMENT, b.ftex_scaled(b.ftex_wrinkled(6, 0.6, noise_space), 0.05))
+        rough = b.ftex_mix(0.3, 0.1, b.ftex_scaled(b.ftex_fbm(5, 0.5, noise_space), 0.3))  # 0.3 - 0.2 * (0.3 fbm): stays positive
+        b.set_float_texture(floor_m, abi.SHM_FLOATSLOT_U_ROUGHNESS, rough)
+        b.set_float_texture(floor_m, abi.SHM_FLOATSLOT_V_ROUGHNESS, rough)
+        b.set_float_texture(floor_m, abi.SHM_FLOATSLOT_THICKNESS, b.ftex_mix(0.05, 0.07, b.ftex_windy(mapping("point3d", scale=3.0))))
+
+    def inward(q):
+        p, vi = q
+        return p, vi[:, ::-1].copy()
+    quad_uv = np.array([(0, 0), (1, 0), (1, 1), (0, 1)], np.float32)
+    for quad, m in ((_quad((-1, 2, -1), (1, 2, -1), (1, 2, 1), (-1, 2, 1)), white), (_quad((-1, 0, -1), (-1, 2, -1), (1, 2, -1), (1, 0, -1)), back_m),
+                    (inward(_quad((-1, 0, -1), (1, 0, -1), (1, 0, 1), (-1, 0, 1))), floor_m), (_quad((-1, 0, -1), (-1, 0, 1), (-1, 2, 1), (-1, 2, -1)), red),
+                    (inward(_quad((1, 0, -1), (1, 0, 1), (1, 2, 1), (1, 2, -1))), right_m)):
+        b.add_mesh(_to_render(quad[0], rfw), quad[1], m, uv=quad_uv)
+    p, vi = _box((-0.75, 0.0, -0.65), (-0.15, 1.2, -0.05), faces="xXYzZ")
+    b.add_mesh(_to_render(p, rfw), vi, tall_m)
+    if which == "general":
+        rfo = np.eye(4, dtype=np.float32)
+        rfo[:3, 3] = _to_render([(0.4, 0.35, 0.3)], rfw)[0]
+        b.add_sphere(0.35, b.material_diffuse(b.stex_checkerboard(0.8, 0.1, mapping("point3d", scale=4.0))), render_from_object=rfo)
+        q = np.array([(-0.9, 0.9, -0.95), (-0.2, 1.1, -0.7), (-0.9, 1.7, -0.95), (-0.2, 1.6, -0.95)], np.float32)
+        dots_m = b.material_diffuse(b.stex_dots(0.1, green_spec, b.add_texture_mapping("uv", su=4.0, sv=4.0)))
+        b.add_patch_mesh(_to_render(q, rfw), [[0, 1, 2, 3]], dots_m, reverse_orientation=True)
+        q = np.array([(-0.3, 1.98, -0.3), (0.3, 1.98, -0.3), (-0.3, 1.98, 0.3), (0.3, 1.98, 0.3)], np.float32)
+        b.add_patch_mesh(_to_render(q, rfw), [[0, 1, 2, 3]], black, emission=blackbody_dense(6500.0), emission_scale=20.0)
+    else:
+        p, vi = _box((0.1, 0.0, 0.0), (0.7, 0.6, 0.6), faces="xXYzZ")
+        b.add_mesh(_to_render(p, rfw), vi, short_m)
+        p, vi = _quad((-0.3, 1.98, -0.3), (0.3, 1.98, -0.3), (0.3, 1.98, 0.3), (-0.3, 1.98, 0.3))
+        b.add_mesh(_to_render(p, rfw), vi, black, emission=blackbody_dense(6500.0), emission_scale=20.0)
+    return _finish(b, lib, extra_lights=extra_lights, rfw=rfw, name=f"S2 cornell box (procedural textures: {which})")
+
+
 def _hash3(ix, iy, iz, seed):
     """Integer lattice hash -> [0,1) float64 (vectorised, wraps like uint64)."""
     with np.errstate(over="ignore"):
