@@ -529,6 +529,10 @@ typedef struct ShmScene ShmScene;
 SHM_API int shm_scene_create(const ShmSceneDesc* desc, int device, ShmScene** out);
 SHM_API void shm_scene_destroy(ShmScene* scene);
 
+/* How many primitives got a per-primitive shading record at scene creation (flat triangles of the scene classes whose kernels read one; 0 under SHM_TRI_SHADE=0 and
+ * in every other class), and, where build_ms_out is not NULL, the wall-clock milliseconds scene creation spent building them. */
+SHM_API int shm_scene_shading_records(ShmScene* scene, uint64_t* n_records_out, double* build_ms_out);
+
 /* Film accumulation buffer resident in HBM, pixel_bounds-sized, zero-initialised. */
 SHM_API int shm_film_clear(ShmScene* scene);
 /* Render one spp-wave [sample_begin, sample_end) (integrator.rs:257-260) of the given tiles into the

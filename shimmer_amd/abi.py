@@ -239,6 +239,7 @@ EXPORTS = {
     "shm_scene_create": (C.c_int, [C.POINTER(ShmSceneDesc), C.c_int, C.POINTER(C.c_void_p)]),
     "shm_scene_destroy": (None, [C.c_void_p]),
     "shm_film_clear": (C.c_int, [C.c_void_p]),
+    "shm_scene_shading_records": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     "shm_render_wave": (C.c_int, [C.c_void_p, C.POINTER(ShmRenderParams), C.POINTER(ShmTile), C.c_uint32, C.c_int32, C.c_int32,
                                   C.POINTER(ShmStats)]),
     "shm_film_read": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -78,6 +78,7 @@ struct FlatScene {
         v.zsobol = 0;
         v.call_copy = nullptr;  // (device only: set per workgroup by the kernels that evaluate textures)
         v.inst_roots = nullptr;  // (device only)
+        v.tri_shade = nullptr;   // (device only: shm/tri_shade.h)
         v.nodes = nodes.data();
         v.n_nodes = (uint32_t)nodes.size();
         v.prim_recs = prim_recs.data();

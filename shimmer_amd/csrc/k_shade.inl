@@ -171,8 +171,15 @@ __global__ void __launch_bounds__(SHADE2_BLOCK) K_SHADE_LEAN_ATTR k_shade(SceneV
                     }
                 }
             } else {
-                SurfaceInteraction si = hit_interaction<TRI_ONLY>(sv, hit, -ray_d);
                 const PrimRec& prim = sv.prim_recs[hit.prim];  // (material and emitter ride in the record the interaction fetches anyway)
+                // a flat triangle with a shading record (shm/tri_shade.h): normal and BSDF frame are fetched, not recomputed; every other hit — none in a scene
+                // created under SHM_TRI_SHADE=0 — takes the full interaction in the same kernel. Only the lean instantiation without an environment map: beside the image
+                // light's code the record path made the lean kernel spill at three waves, and the material-sorted all-materials kernel, which spills already, spilled 42 VGPRs more.
+                constexpr bool USE_RECS = TRI_ONLY && !HAS_TEX && !ENV_LIGHT && !SORT_CHUNK;
+                const bool flat = USE_RECS && tri_shade_valid(prim);
+                TriShadeRec tsr;
+                if (flat) tsr = sv.tri_shade[hit.prim];
+                SurfaceInteraction si = flat ? tri_shade_interaction(prim, tsr, hit, -ray_d) : hit_interaction<TRI_ONLY>(sv, hit, -ray_d);
                 // integrator.rs:798-813: emission at the hit
                 if (!EMIT_INLINE && prim.area_light >= 0) {
                     // the hit is on an emitter (rare): its `L += beta * Le` — with the MIS weight's inverted light sampling — is k_emit_jobs's, after this launch; what
@@ -208,7 +215,9 @@ __global__ void __launch_bounds__(SHADE2_BLOCK) K_SHADE_LEAN_ATTR k_shade(SceneV
                 }
                 const ShmMaterial& mat = sv.materials[prim.material];
                 if (DIFFUSE_ONLY) __builtin_assume(mat.kind == SHM_MATERIAL_DIFFUSE);
-                BSDF bsdf = get_bsdf<HAS_TEX>(sv, si, mat, lambda, &df);
+                BSDF bsdf;
+                if (USE_RECS) bsdf = tri_shade_bsdf(sv, si, flat ? tri_shade_frame(tsr) : tri_shade_fallback_frame(sv, si, mat, lambda), mat, lambda);
+                else bsdf = get_bsdf<HAS_TEX>(sv, si, mat, lambda, &df);
                 if (!HAS_LAYERED) __builtin_assume(bsdf.bxdf.kind <= SHM_MATERIAL_THIN_DIELECTRIC);
                 if (DIFFUSE_ONLY) __builtin_assume(bsdf.bxdf.kind == SHM_MATERIAL_DIFFUSE);
                 Rng rng;
@@ -395,8 +404,9 @@ __global__ void __launch_bounds__(SHADE2_BLOCK) k_emit_jobs(SceneView sv, PathAr
         const uint32_t fl = pa.e_flags[path];
         const int depth = (int)(fl & 0xffu);
         const bool specular_bounce = (fl >> 8) & 1u;
-        const SurfaceInteraction si = hit_interaction<TRI_ONLY>(sv, hit, -ray_d);
         const PrimRec& prim = sv.prim_recs[hit.prim];  // (material and emitter ride in the record the interaction fetches anyway)
+        const bool use_recs = TRI_ONLY && !HAS_TEX;  // (shading records, shm/tri_shade.h: as in k_shade)
+        const SurfaceInteraction si = (use_recs && tri_shade_valid(prim)) ? tri_shade_interaction(prim, sv.tri_shade[hit.prim], hit, -ray_d) : hit_interaction<TRI_ONLY>(sv, hit, -ray_d);
         const ShmLight& light = sv.lights[prim.area_light];
         const Spec le = area_light_l(sv, light, si.n, -ray_d, lambda);
         if (!is_zero(le)) {
@@ -412,10 +422,16 @@ __global__ void __launch_bounds__(SHADE2_BLOCK) k_emit_jobs(SceneView sv, PathAr
                     Hit ph;
                     ph.prim = __float_as_int(c0.x); ph.t = 0.0f; ph.b0 = c0.y; ph.b1 = c0.z; ph.b2 = c0.w; ph.phi = 0.0f; ph.inst = -1;
                     // (get_bsdf belongs to it: a material with a displacement — the reference's constant one included — resets the shading geometry, interaction.rs:223-245)
-                    SurfaceInteraction sp = hit_interaction<TRI_ONLY>(sv, ph, v3s(0.0f));
-                    Wavelengths lw = lambda;
-                    (void)get_bsdf<HAS_TEX>(sv, sp, sv.materials[sv.prim_recs[ph.prim].material], lw);
-                    c = light_ctx_from(sp);
+                    const PrimRec& pprim = sv.prim_recs[ph.prim];
+                    if (use_recs && tri_shade_valid(pprim)) {
+                        // (its record holds n and the shading normal get_bsdf left)
+                        c = light_ctx_from(tri_shade_interaction(pprim, sv.tri_shade[ph.prim], ph, v3s(0.0f)));
+                    } else {
+                        SurfaceInteraction sp = hit_interaction<TRI_ONLY>(sv, ph, v3s(0.0f));
+                        Wavelengths lw = lambda;
+                        (void)get_bsdf<HAS_TEX>(sv, sp, sv.materials[pprim.material], lw);
+                        c = light_ctx_from(sp);
+                    }
                 } else {
                     const float4 c1 = pa.e_ctx1[path], c2 = pa.e_ctx2[path];
                     c.pi.x = iv2(c0.x, c0.w);

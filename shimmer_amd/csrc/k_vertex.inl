@@ -148,8 +148,12 @@ __device__ __forceinline__ void vertex_body(const SceneView& sv, const PathArray
             } else if (divert && sv.materials[sv.prim_recs[hit.prim].material].kind == SHM_MATERIAL_DIFFUSE) {
                 push_class = N_BXDF_CLASSES;  // the fused kernel takes this vertex from its start (emission included)
             } else {
-                SurfaceInteraction si = hit_interaction<TRI_ONLY>(sv, hit, -ray_d);
                 const PrimRec& prim = sv.prim_recs[hit.prim];  // (material and emitter ride in the record the interaction fetches anyway)
+                // a flat triangle with a shading record (shm/tri_shade.h): normal and BSDF frame are fetched, not recomputed; every other hit takes the full interaction
+                const bool flat = TRI_ONLY && !HAS_TEX && tri_shade_valid(prim);
+                TriShadeRec tsr;
+                if (flat) tsr = sv.tri_shade[hit.prim];
+                SurfaceInteraction si = flat ? tri_shade_interaction(prim, tsr, hit, -ray_d) : hit_interaction<TRI_ONLY>(sv, hit, -ray_d);
                 // integrator.rs:798-813: emission at the hit
                 if (prim.area_light >= 0) {
                     const ShmLight& light = sv.lights[prim.area_light];
@@ -163,7 +167,10 @@ __device__ __forceinline__ void vertex_body(const SceneView& sv, const PathArray
                     if (fl & (1u << 10)) aux = ld_aux(pa, path);
                     df = compute_differentials(sv, si, aux, params.samples_per_pixel, params.disable_pixel_jitter != 0, params.disable_texture_filtering != 0);
                 }
-                BSDF bsdf = get_bsdf<HAS_TEX>(sv, si, sv.materials[prim.material], lambda, &df);
+                const ShmMaterial& mat = sv.materials[prim.material];
+                BSDF bsdf;
+                if (TRI_ONLY && !HAS_TEX) bsdf = tri_shade_bsdf(sv, si, flat ? tri_shade_frame(tsr) : tri_shade_fallback_frame(sv, si, mat, lambda), mat, lambda);
+                else bsdf = get_bsdf<HAS_TEX>(sv, si, mat, lambda, &df);
                 if (depth != params.max_depth) {  // integrator.rs:830-834
                     const BxDF& b = bsdf.bxdf;
                     pa.bx[path].bx0 = st_spec(b.r);

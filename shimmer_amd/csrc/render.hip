@@ -14,6 +14,7 @@
 // trace_closest -> shade -> trace_any over index queues compacted with wave-aggregated atomics; queue
 // sizes stay on the device (persistent / grid-stride kernels read them), so a whole render (all fused spp-waves)
 // is enqueued on one HIP stream without host round trips. There is no CPU fallback anywhere in this file.
+#include <chrono>
 #include "wavefront.h"
 #include "host/integrator.hpp"
 
@@ -150,6 +151,18 @@ __global__ void __launch_bounds__(SHADE_BLOCK) k_generate_filtered(SceneView sv,
     }
 }
 
+// Scene creation: the shading records of the flat triangles (shm/tri_shade.h), one thread per primitive slot. The record is what triangle_interaction + get_bsdf — the
+// code the shading kernels would run at every hit on the slot — leave behind; the slot's PrimRec::pad[1] says that it is there.
+__global__ void __launch_bounds__(256) k_build_tri_shade(SceneView sv, PrimRec* prim_recs, TriShadeRec* recs, uint32_t n_prims, uint32_t* n_built, uint32_t plain_only) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_prims) return;
+    const PrimRec pr = prim_recs[i];
+    TriShadeRec r;
+    if (!tri_shade_eligible(sv, pr, plain_only != 0u) || !tri_shade_record(sv, pr, r)) return;
+    recs[i] = r;
+    prim_recs[i].pad[1] = 1u;
+    atomicAdd(n_built, 1u);
+}
 // Between bounces: recycle the counters (1 thread).
 __global__ void k_next_bounce(QueueState* qs, int cur, int next_shadow_parity) {
     qs->n_active[cur] = 0;
@@ -692,6 +705,7 @@ int shm_scene_create(const ShmSceneDesc* desc, int device, ShmScene** out) {
     if ((rc = dev_upload(s, f.stex_ops, &v.stex_ops)) != SHM_OK) return fail(rc);
     if ((rc = dev_upload(s, f.image_lights, &v.image_lights)) != SHM_OK) return fail(rc);
     if ((rc = dev_upload(s, f.dist_data, &v.dist_data)) != SHM_OK) return fail(rc);
+    v.tri_shade = nullptr;  // (built below, once the scene's kernels are known)
     s->dsv = v;
 
     size_t w = (size_t)(f.film.pixel_bounds[2] - f.film.pixel_bounds[0]);
@@ -740,10 +754,49 @@ int shm_scene_create(const ShmSceneDesc* desc, int device, ShmScene** out) {
     if (const char* e = getenv("SHM_OTHER_MIN")) { int v2 = atoi(e); if (v2 >= 1 && v2 <= 64) s->other_min = s->other_min_any = v2; }
     if (const char* e = getenv("SHM_TAIL_FUSED_BOUNCE")) { const int v2 = atoi(e); s->tail_fused_bounce = v2 >= 0 ? v2 : 1 << 30; }
     if (const char* e = getenv("SHM_OTHER_MIN_ANY")) { int v2 = atoi(e); if (v2 >= 1 && v2 <= 64) s->other_min_any = v2; }
+    // the flat triangles' shading records (shm/tri_shade.h), 48 bytes per primitive slot, for the triangle scenes in which a kernel that reads them shades vertices:
+    //   k_shade<lean> without an environment map — all-diffuse scenes, the lean diversion of scenes with coated materials (or of any mixed scene whose early bounces are
+    //   staged, SHM_TAIL_FUSED_BOUNCE), and, in scenes with material textures, behind the split pass: there only hits on plain DiffuseMaterials reach the kernel, and only
+    //   those primitives get a record;
+    //   the staged k_vertex of scenes without textures.
+    // SHM_TRI_SHADE=0 builds none: every hit takes the fallback of the same kernels (the A/B instrument of the record path; not the parent's code, which had one get_bsdf)
+    const bool lean_reads = !f.has_image_light && (scene_is_lean(s) || (s->lean_divert && (s->split_pass || !fused_all_from_0(s))));
+    const bool vertex_reads = !f.has_material_textures && !scene_is_lean(s) && !fused_all_from_0(s);
+    bool tri_shade = !f.has_spheres && !f.prim_recs.empty() && (lean_reads || vertex_reads);
+    if (const char* e = getenv("SHM_TRI_SHADE")) tri_shade = tri_shade && atoi(e) != 0;
+    if (tri_shade) {
+        TriShadeRec* recs = nullptr;
+        uint32_t* d_n = nullptr;
+        if ((rc = dev_alloc<TriShadeRec>(s, f.prim_recs.size(), &recs)) != SHM_OK) return fail(rc);
+        if ((rc = dev_alloc<uint32_t>(s, 1, &d_n)) != SHM_OK) return fail(rc);
+        const uint32_t n_prims = (uint32_t)f.prim_recs.size();
+        const auto t0 = std::chrono::steady_clock::now();
+        uint32_t n_built = 0;
+        hipError_t err = hipMemset(d_n, 0, sizeof(uint32_t));
+        if (err == hipSuccess) {
+            hipLaunchKernelGGL(k_build_tri_shade, dim3((n_prims + 255u) / 256u), dim3(256), 0, 0, s->dsv, const_cast<PrimRec*>(s->dsv.prim_recs), recs, n_prims, d_n,
+                               f.has_material_textures ? 1u : 0u);
+            err = hipGetLastError();
+        }
+        if (err == hipSuccess) err = hipDeviceSynchronize();
+        if (err == hipSuccess) err = hipMemcpy(&n_built, d_n, sizeof(uint32_t), hipMemcpyDeviceToHost);
+        if (err != hipSuccess) { g_err = std::string("k_build_tri_shade: ") + hipGetErrorString(err); return fail(SHM_ERR_DEVICE); }
+        s->n_tri_shade_records = n_built;
+        s->tri_shade_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        DBG("scene: %u shading records of %u primitives built in %.3f ms (%.1f MB)", n_built, n_prims, s->tri_shade_build_ms, (double)n_prims * sizeof(TriShadeRec) / 1e6);
+        s->dsv.tri_shade = recs;
+    }
     if ((rc = wf_trace_prepare(s)) != SHM_OK) return fail(rc);
     DBG("scene: %u nodes, depth %u, trace blocks %d / %d, spill levels %d / %d", (unsigned)f.nodes.size(), f.max_leaf_depth, s->trace3_blocks[0], s->trace3_blocks[1],
         s->spill3_levels[0], s->spill3_levels[1]);
     *out = s;
+    return SHM_OK;
+}
+
+int shm_scene_shading_records(ShmScene* s, uint64_t* n_records_out, double* build_ms_out) {
+    if (!s || !n_records_out) return SHM_ERR_INVALID_ARGUMENT;
+    *n_records_out = s->n_tri_shade_records;
+    if (build_ms_out) *build_ms_out = s->tri_shade_build_ms;
     return SHM_OK;
 }
 

@@ -30,6 +30,7 @@ struct PrimRec {
     uint32_t material;
     int32_t area_light;
     uint32_t pad[2];      // bilinear patch: pad[0] = p11.z — the fourth corner travels with the record (PatchExtra keeps its own copy for the shading kernels)
+                          // triangle, device copy only: pad[1] != 0 — SceneView::tri_shade holds this slot's shading record (shm/tri_shade.h)
 };
 static_assert(sizeof(PrimRec) == 64, "PrimRec is one aligned 64-byte record");
 // A bilinear patch keeps p00, p10, p01 in {p0, p1, p2}; its fourth corner and the per-patch constants live here.
@@ -114,6 +115,9 @@ struct SceneView {
     // device only (null on the host): per instance, a copy of the device record of its tree's root node — what the traversal kernel tests where a ray enters the instance,
     // fetched with the instance's matrices instead of behind them (render.hip, upload)
     const ShmBvhNode* inst_roots;
+    // device only (null on the host, and on the device where no record was built): per primitive slot, the shading record of a flat triangle — what triangle_interaction +
+    // get_bsdf leave in n, shading.n and the BSDF's frame, stored once at scene creation; valid where PrimRec::pad[1] of the device copy says so (shm/tri_shade.h)
+    const struct TriShadeRec* tri_shade;
 };
 
 // A FloatTexture tree flattened at scene creation into a post-order program: evaluating the ops in order (each into slot k of a

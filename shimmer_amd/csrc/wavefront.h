@@ -21,6 +21,7 @@
 #endif
 #define SHM_DELTA_LIGHTS K_DELTA_LIGHTS
 #include "shm/path.h"
+#include "shm/tri_shade.h"
 #define WF_CAT_(a, b) a##b
 #define WF_CAT(a, b) WF_CAT_(a, b)
 #if K_DELTA_LIGHTS
@@ -379,6 +380,8 @@ struct ShmScene {
     uint32_t* d_heads3 = nullptr;  // [2 (closest, any)][8 partitions][32 dwords: one 128-B line per head word]
     std::vector<hipEvent_t> events;
     struct DistState* dist = nullptr;  // multi-GPU state (dist.hip): communicator, this rank's tile shard, the gather plan
+    uint32_t n_tri_shade_records = 0;   // the flat triangles' shading records built at scene creation (shm/tri_shade.h; shm_scene_shading_records) ...
+    double tri_shade_build_ms = 0.0;    // ... and the wall-clock time that took
 };
 // dist.hip: releases s->dist (RCCL communicator included); called by shm_scene_destroy
 __attribute__((visibility("hidden"))) void wf_dist_release(ShmScene* s);

@@ -95,6 +95,12 @@ class Renderer:
             sub[k] = self.tiles[int(i)]
         return sub, len(tile_indices)
 
+    def shading_records(self):
+        """(records built at scene creation, milliseconds it took): the per-primitive shading records of flat triangles."""
+        n, ms = C.c_uint64(0), C.c_double(0.0)
+        abi.check(self.lib, self.lib.shm_scene_shading_records(self.handle, C.byref(n), C.byref(ms)), "shm_scene_shading_records")
+        return int(n.value), float(ms.value)
+
     def clear(self):
         abi.check(self.lib, self.lib.shm_film_clear(self.handle), "shm_film_clear")
 
