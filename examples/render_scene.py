@@ -4,6 +4,7 @@
     python examples/render_scene.py cornell --spp 256 --res 512 -o cornell.pfm
     python examples/render_scene.py cornell --filter gaussian        (box | gaussian | mitchell | sinc | triangle)
     python examples/render_scene.py textured | checkerboard | coated | patches | instanced | environment | ganesha | crown | spotlit | fuzz:13
+    python examples/render_scene.py diffuse_transmission | translucent   (PBRT-v4's diffuse transmission material: the scene file / the builder)
 
 Everything goes through the C ABI of include/shimmer_hip.h (shimmer_amd/abi.py is the ctypes binding): scene description ->
 shm_scene_create -> shm_render_device -> shm_film_read -> shm_film_get_image -> shm_write_pfm. Needs an MI355X: there is no CPU path.
@@ -31,14 +32,18 @@ def make_scene(lib, name, w, h, film=None):
         return scenes.cornell_box(lib, w, h, textured=True, film=film)
     if name == "coated":
         return scenes.cornell_box(lib, w, h, coated=True, film=film)
-    if name == "checkerboard":  # PBRT-v4's procedural textures, from the scene FILE examples/scenes/checkerboard.pbrt through the C++ front end (its own film size; --filter is the file's)
+    if name in ("checkerboard", "diffuse_transmission"):
+        # scene FILES through the C++ front end (their own film size; --filter is the file's): PBRT-v4's procedural textures (examples/scenes/checkerboard.pbrt); a back-lit
+        # sheet of PBRT-v4's diffuse transmission material in the Cornell box (examples/scenes/diffuse_transmission.pbrt: the extended *_dl kernels)
         import ctypes as C
         from types import SimpleNamespace
         out = C.POINTER(abi.ShmPbrtScene)()
-        path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "scenes", "checkerboard.pbrt")
+        path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "scenes", name + ".pbrt")
         abi.check(lib, lib.shm_scene_load_pbrt(path.encode(), C.byref(out)), "shm_scene_load_pbrt")
         res = out.contents.desc.film.full_resolution
-        return SimpleNamespace(desc=out.contents.desc, name="checkerboard.pbrt", res=(res[0], res[1]), keep=out)
+        return SimpleNamespace(desc=out.contents.desc, name=name + ".pbrt", res=(res[0], res[1]), keep=out)
+    if name == "translucent":  # the same material through the Python builder: the sheet and the tall box of scenes.cornell_box
+        return scenes.cornell_box(lib, w, h, film=film, diffuse_transmission="sheet tall")
     if name in ("procedural", "procedural-general", "procedural-coated"):  # the same textures through the Python builder (scenes.procedural_cornell)
         return scenes.procedural_cornell(lib, w, h, which={"procedural": "checker", "procedural-general": "general", "procedural-coated": "coated"}[name], film=film)
     if name == "patches":

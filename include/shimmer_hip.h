@@ -26,7 +26,8 @@ extern "C" {
 #endif
 
 /* Enum values added WITHOUT a version step are additive: no struct changes size or layout and a caller built against the earlier header never passes them.
- * Under version 10 these are SHM_TEXMAP_POINT3D, SHM_FLOATTEX_CHECKERBOARD .. SHM_FLOATTEX_BILERP and the mapping-only ShmImageTexture record (n_levels == 0). */
+ * Under version 10 these are SHM_TEXMAP_POINT3D, SHM_FLOATTEX_CHECKERBOARD .. SHM_FLOATTEX_BILERP, the mapping-only ShmImageTexture record (n_levels == 0) and
+ * SHM_MATERIAL_DIFFUSE_TRANSMISSION. */
 #define SHM_ABI_VERSION 10
 
 /* The library is built with -fvisibility=hidden; only these entry points are exported. */
@@ -164,9 +165,14 @@ enum {
     SHM_MATERIAL_THIN_DIELECTRIC = 3, /* material.rs:652-768 */
     SHM_MATERIAL_COATED_DIFFUSE = 4,  /* material.rs:772-1005: LayeredBxDF<Dielectric, Diffuse, two-sided> (bxdf.rs:269-290, 883-1620) */
     SHM_MATERIAL_COATED_CONDUCTOR = 5,/* material.rs:1007-1286: LayeredBxDF<Dielectric, Conductor, two-sided> (bxdf.rs:460-480) */
-    SHM_MATERIAL_MIX = 6              /* material.rs:1288-1330: MixMaterial, resolved per hit in get_bsdf (interaction.rs:205-220).
+    SHM_MATERIAL_MIX = 6,             /* material.rs:1288-1330: MixMaterial, resolved per hit in get_bsdf (interaction.rs:205-220).
                                          The reference draws the choice from the tile's entropy-seeded SmallRng (integrator.rs:255);
                                          here it is a hash of (wo, p), the way PBRT-v4 defines it: reproducible, parity unpinned. */
+    /* 7 is reserved: shm_scene_create answers it with SHM_ERR_UNSUPPORTED, as it answers every kind above 8 */
+    SHM_MATERIAL_DIFFUSE_TRANSMISSION = 8 /* PBRT-v4's DiffuseTransmissionMaterial / DiffuseTransmissionBxDF (the reference has none): `a` = reflectance, `b` = transmittance,
+                                         both SpectrumTexture slots, each clamped to [0, 1]; f = a / pi on wo's side, b / pi on the other. No other field is read but
+                                         has_displacement / displacement / float_tex[SHM_FLOATSLOT_DISPLACEMENT] and normal_map (a displacement applies only when given).
+                                         PBRT-v4's `scale` parameter is no field: a front end wraps both slots in a SHM_SPECTEX_SCALED node. May be a Mix child. */
 };
 /* FloatTexture (texture.rs:88-305, 309-403), ABI v6: a node table; children are indices into ShmSceneDesc::float_textures and must
  * precede their parent (no cycles); a tree (counting a shared child once per use) may hold at most 32 nodes. Materials refer to a node through ShmMaterial::float_tex. */
@@ -233,8 +239,8 @@ typedef struct ShmMaterial {
     uint32_t conductor_from_reflectance; /* CoatedConductor: `a` is a reflectance (material.rs:1224-1231), not eta */
     uint32_t mix_material[2];         /* Mix: indices into the material table (may themselves be Mix; no cycles) */
     float mix_amount;                 /* Mix: constant `amount` texture (default 0.5): <= 0 -> [0], >= 1 -> [1], else [amount < u ? 0 : 1] */
-    ShmSpectrum a;  /* Diffuse / CoatedDiffuse: reflectance; Conductor / CoatedConductor: eta (or reflectance); Dielectric/Thin: eta */
-    ShmSpectrum b;  /* Conductor / CoatedConductor: k */
+    ShmSpectrum a;  /* Diffuse / CoatedDiffuse / DiffuseTransmission: reflectance; Conductor / CoatedConductor: eta (or reflectance); Dielectric/Thin: eta */
+    ShmSpectrum b;  /* Conductor / CoatedConductor: k; DiffuseTransmission: transmittance */
     ShmSpectrum c;  /* Coated*: albedo of the medium */
     ShmSpectrum d;  /* Coated*: eta of the dielectric interface */
     uint32_t float_tex[8];  /* ABI v6: SHM_FLOATSLOT_*: 0 = the constant field above, else 1 + index into ShmSceneDesc::float_textures */

@@ -18,6 +18,7 @@ SHM_SPECTRUM_CONSTANT, SHM_SPECTRUM_DENSE, SHM_SPECTRUM_PIECEWISE_LINEAR = 0, 1,
 SHM_SPECTRUM_RGB_ALBEDO, SHM_SPECTRUM_RGB_UNBOUNDED, SHM_SPECTRUM_RGB_ILLUMINANT = 3, 4, 5
 SHM_MATERIAL_DIFFUSE, SHM_MATERIAL_CONDUCTOR, SHM_MATERIAL_DIELECTRIC, SHM_MATERIAL_THIN_DIELECTRIC = 0, 1, 2, 3
 SHM_MATERIAL_COATED_DIFFUSE, SHM_MATERIAL_COATED_CONDUCTOR, SHM_MATERIAL_MIX = 4, 5, 6
+SHM_MATERIAL_DIFFUSE_TRANSMISSION = 8  # (7 is reserved: rejected with SHM_ERR_UNSUPPORTED)
 SHM_LIGHT_POINT, SHM_LIGHT_DIFFUSE_AREA, SHM_LIGHT_UNIFORM_INFINITE, SHM_LIGHT_IMAGE_INFINITE = 0, 1, 2, 3
 SHM_LIGHT_DISTANT, SHM_LIGHT_SPOT = 4, 5  # PBRT-v4's DistantLight / SpotLight (ABI v10)
 SHM_SPECTRUM_IMAGE_TEXTURE, SHM_SPECTRUM_TEXTURE_NODE = 6, 7

@@ -33,6 +33,7 @@ struct FlatScene {
     std::vector<ShmLight> lights;
     std::vector<shm::PrimRec> light_prim_recs;  // per light: the emitter's record (area lights), the 3x3 of light_from_render + the two cosines (spot lights: shm/path.h,
                                                 // spot_cos_theta), zeros otherwise: SceneView::light_prim_recs
+    bool has_diffuse_transmission = false;  // a SHM_MATERIAL_DIFFUSE_TRANSMISSION: selects the same kernels (shm/bxdf.h, SHM_DIFFUSE_TRANSMISSION)
     bool has_directed_lights = false;  // a SHM_LIGHT_DISTANT or SHM_LIGHT_SPOT: selects the *_dl shading kernels (wavefront.h, K_DELTA_LIGHTS)
     std::vector<uint32_t> infinite_lights;
     std::vector<float> spectrum_data;
@@ -599,9 +600,11 @@ inline int flatten_scene(const ShmSceneDesc* d, FlatScene& out, std::string& err
     const uint32_t ntex = d->n_image_textures;
     uint32_t nsf = (uint32_t)out.spectrum_data.size();
     for (const ShmMaterial& m : out.materials) {
-        if (m.kind > SHM_MATERIAL_MIX) { err = "unsupported material kind"; return SHM_ERR_UNSUPPORTED; }
+        // (7 is reserved: the kinds are 0 .. SHM_MATERIAL_MIX and SHM_MATERIAL_DIFFUSE_TRANSMISSION)
+        if (m.kind > SHM_MATERIAL_MIX && m.kind != SHM_MATERIAL_DIFFUSE_TRANSMISSION) { err = "unsupported material kind"; return SHM_ERR_UNSUPPORTED; }
         if (m.kind != SHM_MATERIAL_DIFFUSE) out.diffuse_only = false;
-        if (m.kind == SHM_MATERIAL_DIFFUSE) out.has_class[0] = true;
+        if (m.kind == SHM_MATERIAL_DIFFUSE_TRANSMISSION) out.has_diffuse_transmission = true;
+        if (m.kind == SHM_MATERIAL_DIFFUSE || m.kind == SHM_MATERIAL_DIFFUSE_TRANSMISSION) out.has_class[0] = true;
         else if (m.kind == SHM_MATERIAL_CONDUCTOR) out.has_class[1] = true;
         else if (m.kind == SHM_MATERIAL_DIELECTRIC || m.kind == SHM_MATERIAL_THIN_DIELECTRIC) out.has_class[2] = true;
         else if (m.kind == SHM_MATERIAL_COATED_DIFFUSE || m.kind == SHM_MATERIAL_COATED_CONDUCTOR) out.has_class[3] = true;
@@ -642,7 +645,7 @@ inline int flatten_scene(const ShmSceneDesc* d, FlatScene& out, std::string& err
         const bool a_is_texture_slot = !(m.kind == SHM_MATERIAL_DIELECTRIC || m.kind == SHM_MATERIAL_THIN_DIELECTRIC);
         if (!check_spectrum(m.a, nsf, err, a_is_texture_slot ? ntex : 0, a_is_texture_slot ? &out.has_textures : nullptr)) return SHM_ERR_INVALID_ARGUMENT;
         const bool coated = m.kind == SHM_MATERIAL_COATED_DIFFUSE || m.kind == SHM_MATERIAL_COATED_CONDUCTOR;
-        if ((m.kind == SHM_MATERIAL_CONDUCTOR || (m.kind == SHM_MATERIAL_COATED_CONDUCTOR && !m.conductor_from_reflectance)) &&
+        if ((m.kind == SHM_MATERIAL_CONDUCTOR || m.kind == SHM_MATERIAL_DIFFUSE_TRANSMISSION || (m.kind == SHM_MATERIAL_COATED_CONDUCTOR && !m.conductor_from_reflectance)) &&
             !check_spectrum(m.b, nsf, err, ntex, &out.has_textures))
             return SHM_ERR_INVALID_ARGUMENT;
         if (coated) {
@@ -743,6 +746,20 @@ inline int flatten_scene(const ShmSceneDesc* d, FlatScene& out, std::string& err
     // the lean fused kernel: a diffuse bounce ends the ray differentials (interaction.rs:430-514: only specular bounces carry them on), so nothing a later texture look-up reads
     // depends on which kernel shaded such a vertex
     for (ShmMaterial& m : out.materials) {
+        // A diffuse transmission material reads a, b, the displacement and the normal map. The one kernel that is not built for it but still walks every material, the
+        // builder of the flat triangles' shading records (it keeps get_bsdf's FRAME, which no material kind enters), evaluates the fields of the last kind get_bsdf
+        // knows there: the unvalidated ones are cleared in the copy the device (and the oracle) gets. That arm (shm/path.h, "CoatedConductor") reads a and b — validated above
+        // as texture slots —, c, d, conductor_from_reflectance, remap_roughness, the constants u/v_roughness, u2/v2_roughness, thickness, g, max_depth, n_samples, and the
+        // float_tex slots U_ROUGHNESS, V_ROUGHNESS, U2_ROUGHNESS, V2_ROUGHNESS, THICKNESS and G. Constants cannot fault; c, d and every float_tex slot but the displacement's
+        // (slot 0, validated) are what is cleared. An arm that comes to read another INDEX (a spectrum, a texture slot) must be added here.
+        if (m.kind == SHM_MATERIAL_DIFFUSE_TRANSMISSION) {
+            ShmSpectrum zero;
+            memset(&zero, 0, sizeof(zero));
+            zero.kind = SHM_SPECTRUM_CONSTANT;
+            m.c = m.d = zero;
+            m.conductor_from_reflectance = 0;
+            for (int k = 1; k < 8; ++k) m.float_tex[k] = 0u;
+        }
         const bool tex_a = m.a.kind == SHM_SPECTRUM_IMAGE_TEXTURE || m.a.kind == SHM_SPECTRUM_TEXTURE_NODE;
         bool any_float_tex = false;
         for (int k = 0; k < 8; ++k) any_float_tex = any_float_tex || m.float_tex[k] != 0u;

@@ -475,6 +475,39 @@ private:
             m.c = slot(ps, "albedo", tk, &c0, SPECTRUM_ALBEDO);
             m.remap_roughness = ps.one_bool("remaproughness", true);
             displacement(false);
+        } else if (type == "diffusetransmission") {  // PBRT-v4 DiffuseTransmissionMaterial::Create (the reference has no such material)
+            m.kind = SHM_MATERIAL_DIFFUSE_TRANSMISSION;
+            SpectrumValue c025;
+            c025.kind = SpectrumValue::CONSTANT;
+            c025.c = 0.25f;
+            m.a = slot(ps, "reflectance", tk, &c025, SPECTRUM_ALBEDO);
+            m.b = slot(ps, "transmittance", tk, &c025, SPECTRUM_ALBEDO);
+            // "scale" (a float or a float texture, default 1) is no field of ShmMaterial: tex * scale is a SHM_SPECTEX_SCALED node around each slot, none for a plain 1
+            const Param* sc = ps.find("scale");
+            if (sc && (sc->type == "texture" || (!sc->f.empty() && sc->f[0] != 1.0f))) {
+                const uint32_t f = float_texture_operand(ps, "scale", 1.0f, *tk);
+                for (ShmSpectrum* sp : {&m.a, &m.b}) {
+                    ShmSpectrumTexture t;
+                    memset(&t, 0, sizeof(t));
+                    if (sp->kind == SHM_SPECTRUM_TEXTURE_NODE) {
+                        t.a = sp->offset;
+                    } else {
+                        ShmSpectrumTexture leaf;
+                        memset(&leaf, 0, sizeof(leaf));
+                        leaf.kind = SHM_SPECTEX_LEAF;
+                        leaf.leaf = *sp;
+                        a_->spectrum_textures.push_back(leaf);
+                        t.a = (uint32_t)a_->spectrum_textures.size() - 1;
+                    }
+                    t.kind = SHM_SPECTEX_SCALED;
+                    t.f = f;
+                    a_->spectrum_textures.push_back(t);
+                    memset(sp, 0, sizeof(*sp));
+                    sp->kind = SHM_SPECTRUM_TEXTURE_NODE;
+                    sp->offset = (uint32_t)a_->spectrum_textures.size() - 1;
+                }
+            }
+            displacement(false);
         } else if (type == "mix") {  // material.rs:56-110: "materials" names two NAMED materials
             m.kind = SHM_MATERIAL_MIX;
             const Param* names = ps.find("materials");

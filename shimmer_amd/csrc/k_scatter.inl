@@ -79,7 +79,8 @@ __device__ __forceinline__ void scatter_body(const SceneView& sv, const PathArra
         b.mf.alpha_x = p2.y;
         b.mf.alpha_y = p2.z;
         b.r = ld_spec(pa.bx[path].bx0);
-        b.k = (CLASS == CLASS_CONDUCTOR || CLASS == CLASS_LAYERED) ? ld_spec(pa.bx[path].bx1) : spec_const(0.0f);
+        // (bx1 is the conductor's k — and, in the extended build's diffuse class, the diffuse transmission material's T)
+        b.k = (CLASS == CLASS_CONDUCTOR || CLASS == CLASS_LAYERED || (SHM_DIFFUSE_TRANSMISSION && CLASS == CLASS_DIFFUSE)) ? ld_spec(pa.bx[path].bx1) : spec_const(0.0f);
         if (CLASS == CLASS_LAYERED) {
             b.albedo = ld_spec(pa.bx[path].bx3);
             const float4 p4 = pa.bx[path].bx4;
@@ -90,7 +91,10 @@ __device__ __forceinline__ void scatter_body(const SceneView& sv, const PathArra
         }
         // the class is a property of the queue: the dispatch inside bxdf_f / bxdf_pdf / bxdf_sample_f folds to this class's code
         // (plus DiffuseBxDF, which options.force_diffuse substitutes below)
-        if (CLASS == CLASS_DIFFUSE) __builtin_assume(bsdf.bxdf.kind == SHM_MATERIAL_DIFFUSE);
+        // (the extended build's diffuse class holds two kinds: said as a choice between two constants, which folds every other kind's code away — an assumption
+        //  with an `or` in it did not: the LayeredBxDF walks stayed in the kernel)
+        if (CLASS == CLASS_DIFFUSE && SHM_DIFFUSE_TRANSMISSION) b.kind = b.kind == SHM_MATERIAL_DIFFUSE ? (uint32_t)SHM_MATERIAL_DIFFUSE : (uint32_t)SHM_MATERIAL_DIFFUSE_TRANSMISSION;
+        else if (CLASS == CLASS_DIFFUSE) __builtin_assume(bsdf.bxdf.kind == SHM_MATERIAL_DIFFUSE);
         if (CLASS == CLASS_CONDUCTOR) __builtin_assume(bsdf.bxdf.kind == SHM_MATERIAL_CONDUCTOR);
         if (CLASS == CLASS_DIELECTRIC) __builtin_assume(bsdf.bxdf.kind == SHM_MATERIAL_DIELECTRIC || bsdf.bxdf.kind == SHM_MATERIAL_THIN_DIELECTRIC);
         if (CLASS == CLASS_LAYERED) __builtin_assume(bsdf.bxdf.kind == SHM_MATERIAL_COATED_DIFFUSE || bsdf.bxdf.kind == SHM_MATERIAL_COATED_CONDUCTOR);
@@ -370,11 +374,13 @@ __device__ __forceinline__ void scatter_body(const SceneView& sv, const PathArra
     }
 }
 
+// (the extended build's diffuse class of triangle scenes asks for the three waves it had by itself — 158 VGPRs — before the second lobe took it to 169 under a budget of 256)
+#define K_SCATTER_WAVES(CLASS, TRI_ONLY, HAS_TEX) ((SHM_DIFFUSE_TRANSMISSION && (CLASS) == CLASS_DIFFUSE && (TRI_ONLY) && !(HAS_TEX)) ? 3 : K_SHADE_WAVES)
 // two waves per SIMD (<= 256 VGPRs): every class fits without spilling except the LayeredBxDF walks (586 spilled VGPRs). Measured on the
 // coated S3 (1024^2 x 64 spp): two waves with the spills 85.6 ms of shading per frame, one wave per SIMD without them (the retired k_scatter_w1)
 // 99.2 ms — latency hiding beats the scratch traffic.
 template <int CLASS, bool TRI_ONLY, bool HAS_TEX>
-__global__ void __launch_bounds__(SHADE2_BLOCK) K_SHADE_ATTR k_scatter(SceneView sv_global, PathArrays pa, const uint32_t* __restrict__ q_cur, uint32_t* __restrict__ q_next,
+__global__ void __launch_bounds__(SHADE2_BLOCK) __attribute__((amdgpu_waves_per_eu(K_SCATTER_WAVES(CLASS, TRI_ONLY, HAS_TEX), K_SCATTER_WAVES(CLASS, TRI_ONLY, HAS_TEX)))) k_scatter(SceneView sv_global, PathArrays pa, const uint32_t* __restrict__ q_cur, uint32_t* __restrict__ q_next,
                                                                       uint32_t* __restrict__ q_shadow, QueueState* qs, int cur, ShmRenderParams params,
                                                                       int shadow_parity, LdsTables lds_tables) {
     __shared__ uint4 s_tables[LDS_TABLE_BUDGET / 16];  // the small scene tables (lights, spectra: next-event estimation), staged once per workgroup

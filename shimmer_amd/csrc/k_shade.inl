@@ -218,7 +218,14 @@ __global__ void __launch_bounds__(SHADE2_BLOCK) K_SHADE_LEAN_ATTR k_shade(SceneV
                 BSDF bsdf;
                 if (USE_RECS) bsdf = tri_shade_bsdf(sv, si, flat ? tri_shade_frame(tsr) : tri_shade_fallback_frame(sv, si, mat, lambda), mat, lambda);
                 else bsdf = get_bsdf<HAS_TEX>(sv, si, mat, lambda, &df);
-                if (!HAS_LAYERED) __builtin_assume(bsdf.bxdf.kind <= SHM_MATERIAL_THIN_DIELECTRIC);
+                // (the extended build: a scene without coated materials holds the four kinds below and the diffuse transmission material, 8, nothing else once get_bsdf has
+                //  resolved a MixMaterial — said as a mask that clears bit 2 and changes none of the five: the compiler then knows that the kind is neither 4 nor 5, and the
+                //  LayeredBxDF code folds away as under the assumption. Assumptions did not do it (`<= 3 || == 8`, `!= 4` and `!= 5`: the walks stayed), and a select
+                //  `kind > 3 ? 8 : kind` did, but the fused textured kernels then spilled 500 more VGPRs: profiles/diffuse_transmission.md)
+                static_assert((SHM_MATERIAL_DIFFUSE_TRANSMISSION & 11u) == SHM_MATERIAL_DIFFUSE_TRANSMISSION && (SHM_MATERIAL_THIN_DIELECTRIC & 11u) == SHM_MATERIAL_THIN_DIELECTRIC &&
+                              (SHM_MATERIAL_COATED_DIFFUSE & 4u) && (SHM_MATERIAL_COATED_CONDUCTOR & 4u), "the mask keeps kinds 0..3 and 8 and excludes the coated ones");
+                if (!HAS_LAYERED && !DIFFUSE_ONLY && SHM_DIFFUSE_TRANSMISSION) bsdf.bxdf.kind &= 11u;
+                else if (!HAS_LAYERED) __builtin_assume(bsdf.bxdf.kind <= SHM_MATERIAL_THIN_DIELECTRIC);
                 if (DIFFUSE_ONLY) __builtin_assume(bsdf.bxdf.kind == SHM_MATERIAL_DIFFUSE);
                 Rng rng;
                 auto load_rng = [&]() {

@@ -3,9 +3,10 @@
 #include "wavefront.h"
 #if K_ZSOBOL  // (the *_zs and *_zs_dl objects' kernels, wavefront.h)
 #define k_shade_simple WF_DL_NAME(k_shade_simple_zs)
-#define k_shade_randomwalk k_shade_randomwalk_zs
+#define k_shade_randomwalk WF_DL_NAME(k_shade_randomwalk_zs)
 #elif K_DELTA_LIGHTS  // (the *_dl objects')
 #define k_shade_simple k_shade_simple_dl
+#define k_shade_randomwalk k_shade_randomwalk_dl
 #endif
 
 namespace {
@@ -177,7 +178,7 @@ __global__ void __launch_bounds__(SHADE2_BLOCK) K_SHADE_ATTR k_shade_simple(Scen
     }
 }
 
-#if !K_DELTA_LIGHTS  // (RandomWalk samples no light: the *_dl objects have no copy of it, and the table names this build for every scene)
+// (RandomWalk samples no light, but it evaluates every material: the *_dl objects' copy is the one that knows the diffuse transmission material)
 // ---------------------------------------------------------------------------------------------
 // RandomWalkIntegrator (integrator.rs:445-563). Its estimator L_k = le_k + f_k cos_k L_{k+1} / (1/4pi) is recursive and
 // evaluated innermost-first there; a wavefront walks the path forwards, so each vertex records (le_k, f_k cos_k) in
@@ -270,7 +271,6 @@ __global__ void __launch_bounds__(SHADE2_BLOCK) K_SHADE_ATTR k_shade_randomwalk(
       __syncthreads();
     }
 }
-#endif
 #if !K_ZSOBOL && !K_DELTA_LIGHTS  // (draws nothing, samples no light: only the units without a switch have it)
 // L = le_T; L = le_k + f_k cos_k * L / (1 / (4 pi)) for k = T-1 .. 0 (integrator.rs:549-562)
 __global__ void __launch_bounds__(SHADE_BLOCK) k_fold_randomwalk(PathArrays pa, const float4* __restrict__ rw, uint32_t capacity, uint32_t total) {
@@ -295,14 +295,12 @@ template <> int wf_launch_shade_simple<K_ZSOBOL, K_DELTA_LIGHTS>(ShmScene* s, co
     LAUNCH_TRY("k_shade_simple");
     return SHM_OK;
 }
-#if !K_DELTA_LIGHTS
 template <> int wf_launch_shade_randomwalk<K_ZSOBOL, K_DELTA_LIGHTS>(ShmScene* s, const ShadeArgs& a) {
     hipLaunchKernelGGL(k_shade_randomwalk, dim3(a.blocks), dim3(SHADE2_BLOCK), 0, a.stream, s->dsv, s->pa, s->d_q_active[a.cur], s->d_q_active[a.cur ^ 1],
                        s->d_qs, a.cur, a.params, s->d_rw, a.cap_eff);
     LAUNCH_TRY("k_shade_randomwalk");
     return SHM_OK;
 }
-#endif
 #if !K_ZSOBOL && !K_DELTA_LIGHTS
 int wf_launch_fold_randomwalk(ShmScene* s, hipStream_t stream, uint32_t cap_eff, uint32_t total) {
     hipLaunchKernelGGL(k_fold_randomwalk, dim3((total + SHADE_BLOCK - 1) / SHADE_BLOCK), dim3(SHADE_BLOCK), 0, stream, s->pa, s->d_rw, cap_eff, total);

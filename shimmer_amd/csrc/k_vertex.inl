@@ -14,8 +14,11 @@
 #define K_ENV_LIGHT false
 #endif
 #if K_ENV_LIGHT  // (the *_env.hip units' kernels carry their own names: a kernel trace tells them from the units without the light — tools/kernel_coverage.py)
-#define k_vertex k_vertex_env
-#define k_vertex_w3 k_vertex_w3_env
+#define k_vertex WF_DL_NAME(k_vertex_env)
+#define k_vertex_w3 WF_DL_NAME(k_vertex_w3_env)
+#elif K_DELTA_LIGHTS  // (the *_dl objects': the build that knows the diffuse transmission material, wavefront.h)
+#define k_vertex k_vertex_dl
+#define k_vertex_w3 k_vertex_w3_dl
 #endif
 namespace {
 

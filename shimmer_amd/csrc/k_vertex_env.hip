@@ -3,11 +3,11 @@
 #define K_ENV_LIGHT true
 #include "k_vertex.inl"
 
-int wf_launch_vertex_tri_env(ShmScene* s, const ShadeArgs& a) {
+int WF_DL_NAME(wf_launch_vertex_tri_env)(ShmScene* s, const ShadeArgs& a) {
     WF_VERTEX_LAUNCH_W3(true, false, true);
     return SHM_OK;
 }
-int wf_launch_vertex_gen_env(ShmScene* s, const ShadeArgs& a) {
+int WF_DL_NAME(wf_launch_vertex_gen_env)(ShmScene* s, const ShadeArgs& a) {
     WF_VERTEX_LAUNCH(false, false, true);
     return SHM_OK;
 }

@@ -39,6 +39,9 @@ extern "C" __attribute__((visibility("default"))) int shm_debug_eval_leaf(int de
         g_probe_err = "shm_debug_eval_leaf: the zsobol stream needs 10 + n argument words and 4 n output words";
         return SHM_ERR_INVALID_ARGUMENT;
     }
+    if ((op == shm::PROBE_DIFFUSE_TRANSMISSION_SAMPLE_F || op == shm::PROBE_DIFFUSE_TRANSMISSION_F_PDF) && (n_in != 15 || n_out < 10)) {
+        g_probe_err = "shm_debug_eval_leaf: a diffuse transmission op takes 15 words and gives up to 10"; return SHM_ERR_INVALID_ARGUMENT;
+    }
     // the light sample reads a spectrum table of in[16] floats behind its 26 fixed words
     if (op == shm::PROBE_LIGHT_SAMPLE_LI && (n_in < 26 || in_words[16] > 4096 || n_in < 26 + in_words[16] || n_out < 8)) {
         g_probe_err = "shm_debug_eval_leaf: the light sample needs 26 + n_table argument words and 8 output words";

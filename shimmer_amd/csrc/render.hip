@@ -153,6 +153,9 @@ __global__ void __launch_bounds__(SHADE_BLOCK) k_generate_filtered(SceneView sv,
 
 // Scene creation: the shading records of the flat triangles (shm/tri_shade.h), one thread per primitive slot. The record is what triangle_interaction + get_bsdf — the
 // code the shading kernels would run at every hit on the slot — leave behind; the slot's PrimRec::pad[1] says that it is there.
+// This unit is built without SHM_DIFFUSE_TRANSMISSION (wavefront.h), so get_bsdf here takes a diffuse transmission material down its last arm, the CoatedConductor's. Only
+// the FRAME is kept, which no material kind enters (the displacement and the normal map are read before the kinds part), and flatten_scene (host/flatten.h, "A diffuse
+// transmission material reads ...") clears every field of such a material that that arm reads and validation did not cover: the arm evaluates constants, and its result is dropped.
 __global__ void __launch_bounds__(256) k_build_tri_shade(SceneView sv, PrimRec* prim_recs, TriShadeRec* recs, uint32_t n_prims, uint32_t* n_built, uint32_t plain_only) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_prims) return;
@@ -329,31 +332,31 @@ enum : int { IMG_NONE, IMG_TEX, IMG_ENV, N_IMG };  // no image / image textures 
 template <bool ZS, bool DL>
 constexpr ShadeKernels shade_cells[N_GEO][N_IMG] = {
     {{.generate = {k_generate<false, false, ZS>, k_generate<false, true, ZS>}, .lean = wf_launch_shade_lean<ZS, DL>, .lean_diverted = wf_launch_shade_lean_diverted<ZS, DL>,
-      .fused_all = wf_launch_shade_tail_sorted<ZS, DL>, .vertex = wf_launch_vertex_tri,
+      .fused_all = wf_launch_shade_tail_sorted<ZS, DL>, .vertex = DL ? wf_launch_vertex_tri_dl : wf_launch_vertex_tri,
       .scatter = {wf_launch_scatter_diffuse_tri<ZS, DL>, wf_launch_scatter_conductor_tri<ZS, DL>, wf_launch_scatter_dielectric_tri<ZS, DL>, wf_launch_scatter_layered_staged_tri<ZS, DL>},
-      .scatter_layered_onepass = wf_launch_scatter_layered_tri<ZS, DL>, .simple = wf_launch_shade_simple<ZS, DL>, .randomwalk = wf_launch_shade_randomwalk<ZS, false>},
+      .scatter_layered_onepass = wf_launch_scatter_layered_tri<ZS, DL>, .simple = wf_launch_shade_simple<ZS, DL>, .randomwalk = wf_launch_shade_randomwalk<ZS, DL>},
      {.generate = {k_generate<true, false, ZS>, nullptr}, .lean = nullptr, .lean_diverted = nullptr,
-      .fused_all = wf_launch_shade_fused_tex<ZS, DL>, .vertex = wf_launch_vertex_tex,
+      .fused_all = wf_launch_shade_fused_tex<ZS, DL>, .vertex = DL ? wf_launch_vertex_tex_dl : wf_launch_vertex_tex,
       .scatter = {wf_launch_scatter_diffuse_tex<ZS, DL>, wf_launch_scatter_conductor_tex<ZS, DL>, wf_launch_scatter_dielectric_tex<ZS, DL>, wf_launch_scatter_layered_staged_tex<ZS, DL>},
-      .scatter_layered_onepass = wf_launch_scatter_layered_tex<ZS, DL>, .simple = wf_launch_shade_simple<ZS, DL>, .randomwalk = wf_launch_shade_randomwalk<ZS, false>},
+      .scatter_layered_onepass = wf_launch_scatter_layered_tex<ZS, DL>, .simple = wf_launch_shade_simple<ZS, DL>, .randomwalk = wf_launch_shade_randomwalk<ZS, DL>},
      {.generate = {k_generate<false, false, ZS>, k_generate<false, true, ZS>}, .lean = wf_launch_shade_lean_env<ZS, DL>, .lean_diverted = wf_launch_shade_lean_env_diverted<ZS, DL>,
-      .fused_all = wf_launch_shade_tail_sorted_env<ZS, DL>, .vertex = wf_launch_vertex_tri_env,
+      .fused_all = wf_launch_shade_tail_sorted_env<ZS, DL>, .vertex = DL ? wf_launch_vertex_tri_env_dl : wf_launch_vertex_tri_env,
       .scatter = {wf_launch_scatter_diffuse_tri_env<ZS, DL>, wf_launch_scatter_conductor_tri_env<ZS, DL>, wf_launch_scatter_dielectric_tri_env<ZS, DL>, wf_launch_scatter_layered_staged_tri_env<ZS, DL>},
       .scatter_layered_onepass = wf_launch_scatter_layered_tri<ZS, DL>,  // (no K_ENV_LIGHT build: never reached, select_kernels)
-      .simple = wf_launch_shade_simple<ZS, DL>, .randomwalk = wf_launch_shade_randomwalk<ZS, false>}},
+      .simple = wf_launch_shade_simple<ZS, DL>, .randomwalk = wf_launch_shade_randomwalk<ZS, DL>}},
     {{.generate = {k_generate<false, false, ZS>, k_generate<false, true, ZS>}, .lean = wf_launch_shade_lean_gen<ZS, DL>, .lean_diverted = wf_launch_shade_lean_gen_diverted<ZS, DL>,
-      .fused_all = wf_launch_shade_fused_gen<ZS, DL>, .vertex = wf_launch_vertex_gen,
+      .fused_all = wf_launch_shade_fused_gen<ZS, DL>, .vertex = DL ? wf_launch_vertex_gen_dl : wf_launch_vertex_gen,
       .scatter = {wf_launch_scatter_diffuse_gen<ZS, DL>, wf_launch_scatter_conductor_gen<ZS, DL>, wf_launch_scatter_dielectric_gen<ZS, DL>, wf_launch_scatter_layered_staged_gen<ZS, DL>},
-      .scatter_layered_onepass = wf_launch_scatter_layered_gen<ZS, DL>, .simple = wf_launch_shade_simple<ZS, DL>, .randomwalk = wf_launch_shade_randomwalk<ZS, false>},
+      .scatter_layered_onepass = wf_launch_scatter_layered_gen<ZS, DL>, .simple = wf_launch_shade_simple<ZS, DL>, .randomwalk = wf_launch_shade_randomwalk<ZS, DL>},
      {.generate = {k_generate<true, false, ZS>, nullptr}, .lean = nullptr, .lean_diverted = nullptr,
-      .fused_all = wf_launch_shade_fused_gen_tex<ZS, DL>, .vertex = wf_launch_vertex_tex,
+      .fused_all = wf_launch_shade_fused_gen_tex<ZS, DL>, .vertex = DL ? wf_launch_vertex_tex_dl : wf_launch_vertex_tex,
       .scatter = {wf_launch_scatter_diffuse_tex<ZS, DL>, wf_launch_scatter_conductor_tex<ZS, DL>, wf_launch_scatter_dielectric_tex<ZS, DL>, wf_launch_scatter_layered_staged_tex<ZS, DL>},
-      .scatter_layered_onepass = wf_launch_scatter_layered_tex<ZS, DL>, .simple = wf_launch_shade_simple<ZS, DL>, .randomwalk = wf_launch_shade_randomwalk<ZS, false>},
+      .scatter_layered_onepass = wf_launch_scatter_layered_tex<ZS, DL>, .simple = wf_launch_shade_simple<ZS, DL>, .randomwalk = wf_launch_shade_randomwalk<ZS, DL>},
      {.generate = {k_generate<false, false, ZS>, k_generate<false, true, ZS>}, .lean = wf_launch_shade_lean_gen_env<ZS, DL>, .lean_diverted = wf_launch_shade_lean_gen_env_diverted<ZS, DL>,
-      .fused_all = wf_launch_shade_fused_gen_env<ZS, DL>, .vertex = wf_launch_vertex_gen_env,
+      .fused_all = wf_launch_shade_fused_gen_env<ZS, DL>, .vertex = DL ? wf_launch_vertex_gen_env_dl : wf_launch_vertex_gen_env,
       .scatter = {wf_launch_scatter_diffuse_gen_env<ZS, DL>, wf_launch_scatter_conductor_gen_env<ZS, DL>, wf_launch_scatter_dielectric_gen_env<ZS, DL>, wf_launch_scatter_layered_staged_gen_env<ZS, DL>},
       .scatter_layered_onepass = wf_launch_scatter_layered_gen<ZS, DL>,  // (as above)
-      .simple = wf_launch_shade_simple<ZS, DL>, .randomwalk = wf_launch_shade_randomwalk<ZS, false>}},
+      .simple = wf_launch_shade_simple<ZS, DL>, .randomwalk = wf_launch_shade_randomwalk<ZS, DL>}},
 };
 // ... and per pixel-filter class (shm/filter.h) x sampler: K1 and K6 of the filters that are not the box filter — [TRIANGLE | TABULATED with a constant weight (gaussian) |
 // TABULATED with a signed one (Mitchell, sinc)]; the generate kernels as [HAS_TEX][LEAN]
@@ -376,7 +379,8 @@ static ShadeKernels select_kernels(const ShmScene* s, const ShmRenderParams* par
     // (the *_dl builds for a scene with a distant or spot light, in every class: a kernel built without the two lights would sample them as area lights. This is the
     // only place a launcher set is chosen, so such a scene cannot reach one.)
     const bool zs = params->sampler == SHM_SAMPLER_ZSOBOL;
-    const ShadeKernels(&cells)[N_GEO][N_IMG] = f.has_directed_lights ? (zs ? shade_cells<true, true> : shade_cells<false, true>) : (zs ? shade_cells<true, false> : shade_cells<false, false>);
+    // (... and for a scene with a diffuse transmission material: the same builds are the only ones that know it, shm/bxdf.h SHM_DIFFUSE_TRANSMISSION)
+    const ShadeKernels(&cells)[N_GEO][N_IMG] = (f.has_directed_lights || f.has_diffuse_transmission) ? (zs ? shade_cells<true, true> : shade_cells<false, true>) : (zs ? shade_cells<true, false> : shade_cells<false, false>);
     const int geo = f.has_spheres ? GEO_GEN : GEO_TRI;
     // The staged and the all-materials fused kernels: env where the only image is an environment map and options.force_diffuse is off, tex where the scene has
     // textures, none otherwise — under force_diffuse an env-only scene runs the textured units (the differentials are dead values there: no material binds a texture).
@@ -919,11 +923,12 @@ int shm_render_wave(ShmScene* s, const ShmRenderParams* params, const ShmTile* t
         }
     }
     const ShadeKernels k = select_kernels(s, params);
-    // a scene with a distant or spot light must run the *_dl set and no other scene does (a kernel built without the two lights would sample them as area lights): checked
+    // a scene with a distant or spot light or a diffuse transmission material must run the *_dl set and no other scene does (a kernel built without them would sample the
+    // lights as area lights and shade the material as a CoatedConductor): checked
     // on one launcher of the resolved set, which comes from one cell of one table
     {
         const ShadeFn dl_simple = params->sampler == SHM_SAMPLER_ZSOBOL ? wf_launch_shade_simple<true, true> : wf_launch_shade_simple<false, true>;
-        if ((k.simple == dl_simple) != s->flat.has_directed_lights) { g_err = "internal: the kernel set does not match the scene's delta lights"; return SHM_ERR_INTERNAL; }
+        if ((k.simple == dl_simple) != (s->flat.has_directed_lights || s->flat.has_diffuse_transmission)) { g_err = "internal: the kernel set does not match the scene's delta lights / materials"; return SHM_ERR_INTERNAL; }
     }
     // the fused kernel's own scene class under the path integrator: bounce 0 runs on known constants (k_generate<., LEAN>, ShadeArgs::first_bounce)
     const bool lean_first = (!staged || (first_bounce_candidate(s) && params->force_diffuse == 0)) && !random_walk && params->integrator != SHM_INTEGRATOR_SIMPLE_PATH && !s->pa.aux0 && s->pa.rng0;

@@ -13,6 +13,7 @@
 //   bxdf.rs:518-795              DielectricBxDF
 //   bxdf.rs:797-881              ThinDielectricBxDF
 //   bxdf.rs:1702-1829            BSDFSample, BxDFReflTransFlags, BxDFFLags
+//   (PBRT-v4 bxdfs.h)            DiffuseTransmissionBxDF: the reference has none (SHM_DIFFUSE_TRANSMISSION, below)
 //   bsdf.rs:22-111               BSDF::{new,f,sample_f,pdf,flags,regularize}
 #pragma once
 #include "sampling.h"
@@ -187,6 +188,7 @@ enum : uint32_t {
     BXDF_GLOSSY = 1 << 3,
     BXDF_SPECULAR = 1 << 4,
     BXDF_DIFFUSE_REFLECTION = BXDF_DIFFUSE | BXDF_REFLECTION,
+    BXDF_DIFFUSE_TRANSMISSION = BXDF_DIFFUSE | BXDF_TRANSMISSION,
     BXDF_GLOSSY_REFLECTION = BXDF_GLOSSY | BXDF_REFLECTION,
     BXDF_GLOSSY_TRANSMISSION = BXDF_GLOSSY | BXDF_TRANSMISSION,
     BXDF_SPECULAR_REFLECTION = BXDF_SPECULAR | BXDF_REFLECTION,
@@ -215,9 +217,9 @@ SHM_HD BSDFSample bsdf_sample(const Spec& f, V3 wi, Float pdf, uint32_t flags, F
 
 // One tagged struct for the four single-layer BxDFs (the reference's `enum BxDF`, bxdf.rs:96-103) ...
 struct BaseBxDF {
-    uint32_t kind;       // SHM_MATERIAL_DIFFUSE / CONDUCTOR / DIELECTRIC / THIN_DIELECTRIC
-    Spec r;              // Diffuse: R ; Conductor: eta
-    Spec k;              // Conductor: k
+    uint32_t kind;       // SHM_MATERIAL_DIFFUSE / CONDUCTOR / DIELECTRIC / THIN_DIELECTRIC / DIFFUSE_TRANSMISSION
+    Spec r;              // Diffuse: R ; Conductor: eta ; DiffuseTransmission: R
+    Spec k;              // Conductor: k ; DiffuseTransmission: T
     Float eta;           // Dielectric / ThinDielectric
     TrowbridgeReitz mf;  // Conductor / Dielectric
 };
@@ -418,12 +420,56 @@ SHM_HD bool thin_dielectric_sample_f(const BaseBxDF& b, V3 wo, Float uc, uint32_
     return true;
 }
 
+// SHM_DIFFUSE_TRANSMISSION: compile PBRT-v4's DiffuseTransmissionBxDF (SHM_MATERIAL_DIFFUSE_TRANSMISSION) into the dispatchers below and into get_bsdf (path.h). ON wherever
+// nobody says otherwise (the oracle, the host mirror, the leaf probe); the kernel units pass their K_DELTA_LIGHTS — "the extended kernels", wavefront.h — so that the kernels
+// of scenes without the material are those of a library without it. A scene that holds one never reaches a kernel built with 0 (render.hip, select_kernels).
+#ifndef SHM_DIFFUSE_TRANSMISSION
+#define SHM_DIFFUSE_TRANSMISSION 1
+#endif
+
+// ---- DiffuseTransmissionBxDF (PBRT-v4 bxdfs.h): r = R, k = T ----
+SHM_HD Spec diffuse_transmission_f(const BaseBxDF& b, V3 wo, V3 wi) {
+    return same_hemisphere(wo, wi) ? (b.r * INV_PI) : (b.k * INV_PI);
+}
+SHM_HD bool diffuse_transmission_sample_f(const BaseBxDF& b, V3 wo, Float uc, V2 u, uint32_t sample_flags, BSDFSample& out) {
+    Float pr = max_component_value(b.r), pt = max_component_value(b.k);
+    if ((sample_flags & REFLTRANS_REFLECTION) == 0) pr = 0.0f;
+    if ((sample_flags & REFLTRANS_TRANSMISSION) == 0) pt = 0.0f;
+    if (pr == 0.0f && pt == 0.0f) return false;
+    V3 wi = sample_cosine_hemisphere(u);
+    if (uc < pr / (pr + pt)) {
+        if (wo.z < 0.0f) wi.z *= -1.0f;
+        Float pdf = cosine_hemisphere_pdf(abs_cos_theta(wi)) * pr / (pr + pt);
+        out = bsdf_sample(b.r * INV_PI, wi, pdf, BXDF_DIFFUSE_REFLECTION);
+    } else {
+        if (wo.z > 0.0f) wi.z *= -1.0f;
+        Float pdf = cosine_hemisphere_pdf(abs_cos_theta(wi)) * pt / (pr + pt);
+        out = bsdf_sample(b.k * INV_PI, wi, pdf, BXDF_DIFFUSE_TRANSMISSION);
+    }
+    return true;
+}
+SHM_HD Float diffuse_transmission_pdf(const BaseBxDF& b, V3 wo, V3 wi, uint32_t sample_flags) {
+    Float pr = max_component_value(b.r), pt = max_component_value(b.k);
+    if ((sample_flags & REFLTRANS_REFLECTION) == 0) pr = 0.0f;
+    if ((sample_flags & REFLTRANS_TRANSMISSION) == 0) pt = 0.0f;
+    if (pr == 0.0f && pt == 0.0f) return 0.0f;
+    // (the products in sample_f's order: its pdf is this function's value at the sampled wi, bit for bit)
+    if (same_hemisphere(wo, wi)) return cosine_hemisphere_pdf(abs_cos_theta(wi)) * pr / (pr + pt);
+    return cosine_hemisphere_pdf(abs_cos_theta(wi)) * pt / (pr + pt);
+}
+SHM_HD uint32_t diffuse_transmission_flags(const BaseBxDF& b) {
+    return (is_zero(b.r) ? (uint32_t)BXDF_UNSET : (uint32_t)BXDF_DIFFUSE_REFLECTION) | (is_zero(b.k) ? (uint32_t)BXDF_UNSET : (uint32_t)BXDF_DIFFUSE_TRANSMISSION);
+}
+
 // ---- enum dispatch over the single-layer BxDFs, bxdf.rs:105-182 ----
 SHM_HD uint32_t base_flags(const BaseBxDF& b) {
     switch (b.kind) {
         case SHM_MATERIAL_DIFFUSE: return is_zero(b.r) ? BXDF_UNSET : BXDF_DIFFUSE_REFLECTION;
         case SHM_MATERIAL_CONDUCTOR: return b.mf.effectively_smooth() ? BXDF_SPECULAR_REFLECTION : BXDF_GLOSSY_REFLECTION;
         case SHM_MATERIAL_DIELECTRIC: return dielectric_flags(b);
+#if SHM_DIFFUSE_TRANSMISSION
+        case SHM_MATERIAL_DIFFUSE_TRANSMISSION: return diffuse_transmission_flags(b);
+#endif
         default: return BXDF_REFLECTION | BXDF_TRANSMISSION | BXDF_SPECULAR;
     }
 }
@@ -446,6 +492,9 @@ SHM_BASE_BXDF_CALL Spec base_f_v(BaseBxDF b, V3 wo, Float wi_x, Float wi_y, Floa
         case SHM_MATERIAL_DIFFUSE: return diffuse_f(b, wo, wi);
         case SHM_MATERIAL_CONDUCTOR: return conductor_f(b, wo, wi);
         case SHM_MATERIAL_DIELECTRIC: return dielectric_f(b, wo, wi, mode);
+#if SHM_DIFFUSE_TRANSMISSION
+        case SHM_MATERIAL_DIFFUSE_TRANSMISSION: return diffuse_transmission_f(b, wo, wi);
+#endif
         default: return spec_const(0.0f);
     }
 }
@@ -458,6 +507,9 @@ SHM_BASE_BXDF_CALL BSDFSampleOpt base_sample_f_v(BaseBxDF b, V3 wo, Float uc, Fl
         case SHM_MATERIAL_DIFFUSE: ok = diffuse_sample_f(b, wo, u, sample_flags, r.s); break;
         case SHM_MATERIAL_CONDUCTOR: ok = conductor_sample_f(b, wo, u, sample_flags, r.s); break;
         case SHM_MATERIAL_DIELECTRIC: ok = dielectric_sample_f(b, wo, uc, u, sample_flags, r.s, mode); break;
+#if SHM_DIFFUSE_TRANSMISSION
+        case SHM_MATERIAL_DIFFUSE_TRANSMISSION: ok = diffuse_transmission_sample_f(b, wo, uc, u, sample_flags, r.s); break;
+#endif
         default: ok = thin_dielectric_sample_f(b, wo, uc, sample_flags, r.s); break;
     }
     r.ok = ok ? 1u : 0u;
@@ -469,6 +521,9 @@ SHM_BASE_BXDF_CALL Float base_pdf_v(BaseBxDF b, V3 wo, Float wi_x, Float wi_y, F
         case SHM_MATERIAL_DIFFUSE: return diffuse_pdf(b, wo, wi, sample_flags);
         case SHM_MATERIAL_CONDUCTOR: return conductor_pdf(b, wo, wi, sample_flags);
         case SHM_MATERIAL_DIELECTRIC: return dielectric_pdf(b, wo, wi, sample_flags);
+#if SHM_DIFFUSE_TRANSMISSION
+        case SHM_MATERIAL_DIFFUSE_TRANSMISSION: return diffuse_transmission_pdf(b, wo, wi, sample_flags);
+#endif
         default: return 0.0f;
     }
 }

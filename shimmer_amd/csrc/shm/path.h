@@ -12,6 +12,7 @@
 //                                 textures, texture.h: elsewhere they are dead values; bump_map with a constant
 //                                 displacement is executed literally so that signed zeros match, material.rs:1477-1508)
 //   material.rs:301-311,456-499,603-635,723-742   get_bxdf for Diffuse/Conductor/Dielectric/ThinDielectric
+//   (PBRT-v4 materials.h)         DiffuseTransmissionMaterial::GetBxDF: the reference has none (SHM_DIFFUSE_TRANSMISSION, bxdf.h)
 //   sampling.rs:347-371, filter.rs:99-105         get_camera_sample, BoxFilter::sample (the other pixel filters: filter.h)
 //   camera.rs:1003-1079, 769-792  {Perspective,Orthographic}Camera::generate_ray_differential
 //   film.rs:548-574, 907-914      RgbFilm::add_sample, PixelSensor::to_sensor_rgb
@@ -296,6 +297,9 @@ SHM_HD BSDF get_bsdf(const SceneView& sv, SurfaceInteraction& si, const ShmMater
         b.g = clamp(fval(m, SHM_FLOATSLOT_G, m.g), -1.0f, 1.0f);
         b.max_depth = m.max_depth;
         b.n_samples = m.n_samples;
+    } else if (SHM_DIFFUSE_TRANSMISSION && m.kind == SHM_MATERIAL_DIFFUSE_TRANSMISSION) {  // PBRT-v4 DiffuseTransmissionMaterial (`scale` is lowered to texture nodes by the front ends)
+        b.r = clamp(tex(m.a), 0.0f, 1.0f);
+        b.k = clamp(tex(m.b), 0.0f, 1.0f);
     } else {  // CoatedConductor, material.rs:1189-1256
         Float iur = fval(m, SHM_FLOATSLOT_U_ROUGHNESS, m.u_roughness), ivr = fval(m, SHM_FLOATSLOT_V_ROUGHNESS, m.v_roughness);
         if (m.remap_roughness) { iur = roughness_to_alpha(iur); ivr = roughness_to_alpha(ivr); }

@@ -16,7 +16,8 @@ enum : int {
     PROBE_TRIANGLE_PDF_WITH_CONTEXT, PROBE_TRIANGLE_INTERACTION, PROBE_SPHERE_SAMPLE_WITH_CONTEXT, PROBE_SPHERE_PDF_WITH_CONTEXT, PROBE_AREA_LIGHT_L, PROBE_FILM_ADD_SAMPLE,
     PROBE_CAMERA_RAY_DIFFERENTIAL, PROBE_INTERVAL_OP, PROBE_DET3, PROBE_ROTATE_FROM_TO, PROBE_SAMPLE_DISCRETE, PROBE_SAMPLER_STREAM, PROBE_SAMPLE_VISIBLE_WAVELENGTHS,
     PROBE_VISIBLE_WAVELENGTHS_PDF, PROBE_VECMATH, PROBE_TRANSFORM_APPLY, PROBE_BLP_INTERSECT, PROBE_BLP_SAMPLE_WITH_CONTEXT, PROBE_BLP_PDF_WITH_CONTEXT, PROBE_SPHERE_INTERSECT,
-    PROBE_UNARY, PROBE_EQUAL_AREA_SQUARE_TO_SPHERE, PROBE_EQUAL_AREA_SPHERE_TO_SQUARE, PROBE_ZSOBOL_STREAM, PROBE_FILTER_SAMPLE, PROBE_LIGHT_SAMPLE_LI, PROBE_FLOAT_TEXTURE, PROBE_N_OPS
+    PROBE_UNARY, PROBE_EQUAL_AREA_SQUARE_TO_SPHERE, PROBE_EQUAL_AREA_SPHERE_TO_SQUARE, PROBE_ZSOBOL_STREAM, PROBE_FILTER_SAMPLE, PROBE_LIGHT_SAMPLE_LI, PROBE_FLOAT_TEXTURE,
+    PROBE_DIFFUSE_TRANSMISSION_SAMPLE_F, PROBE_DIFFUSE_TRANSMISSION_F_PDF, PROBE_N_OPS
 };
 
 namespace probe_detail {
@@ -31,6 +32,15 @@ SHM_HD BxDF plain_bxdf(const uint32_t* in) {  // kind, r[4], k[4], eta, ax, ay: 
     for (int i = 0; i < 4; ++i) { b.r.v[i] = f(in, 1 + i); b.k.v[i] = f(in, 5 + i); }
     b.eta = f(in, 9);
     b.mf = trowbridge_reitz_new(f(in, 10), f(in, 11));
+    return b;
+}
+SHM_HD BxDF diffuse_transmission_bxdf(const uint32_t* in) {  // R[4], T[4]: 8 words
+    BxDF b;
+    b.strict = 0;
+    b.kind = SHM_MATERIAL_DIFFUSE_TRANSMISSION;
+    for (int i = 0; i < 4; ++i) { b.r.v[i] = f(in, i); b.k.v[i] = f(in, 4 + i); }
+    b.eta = 1.0f;
+    b.mf = trowbridge_reitz_new(0.0f, 0.0f);
     return b;
 }
 SHM_HD BxDF layered_bxdf(const uint32_t* in) {  // kind, p[19], max_depth, n_samples: 22 words (oracle.cpp: make_layered)
@@ -115,6 +125,23 @@ SHM_HD int leaf_probe(int op, const uint32_t* in, uint32_t* out) {
             const Spec r = bxdf_f(b, f3(in, 12), f3(in, 15));
             for (int i = 0; i < 4; ++i) put(out, i, r.v[i]);
             put(out, 4, bxdf_pdf(b, f3(in, 12), f3(in, 15), REFLTRANS_ALL));
+            return 0;
+        }
+        // PBRT-v4's DiffuseTransmissionBxDF (shm/bxdf.h) through the BxDF dispatch, with the caller's BxDFReflTransFlags (the two ops above pass ALL)
+        case PROBE_DIFFUSE_TRANSMISSION_SAMPLE_F: {  // R[4], T[4], wo[3], uc, u[2], sample_flags -> f[4], wi[3], pdf, flags, eta
+            const BxDF b = diffuse_transmission_bxdf(in);
+            BSDFSample bs;
+            if (!bxdf_sample_f(b, f3(in, 8), f(in, 11), v2(f(in, 12), f(in, 13)), in[14], bs)) return 0;
+            for (int i = 0; i < 4; ++i) put(out, i, bs.f.v[i]);
+            put3(out, 4, bs.wi); put(out, 7, bs.pdf); put(out, 8, (Float)bs.flags); put(out, 9, bs.eta);
+            return 1;
+        }
+        case PROBE_DIFFUSE_TRANSMISSION_F_PDF: {  // R[4], T[4], wo[3], wi[3], sample_flags -> f[4], pdf, BxDF::flags
+            const BxDF b = diffuse_transmission_bxdf(in);
+            const Spec r = bxdf_f(b, f3(in, 8), f3(in, 11));
+            for (int i = 0; i < 4; ++i) put(out, i, r.v[i]);
+            put(out, 4, bxdf_pdf(b, f3(in, 8), f3(in, 11), in[14]));
+            put(out, 5, (Float)bxdf_flags(b));
             return 0;
         }
         case PROBE_LAYERED_F_PDF: {  // bxdf.rs:883-1620; layered[22], wo[3], wi[3]

@@ -20,6 +20,10 @@
 #define K_DELTA_LIGHTS false
 #endif
 #define SHM_DELTA_LIGHTS K_DELTA_LIGHTS
+// The same switch is "the extended kernels": PBRT-v4's diffuse transmission material (shm/bxdf.h, SHM_DIFFUSE_TRANSMISSION) is compiled only into the *_dl / *_zs_dl builds —
+// which k_vertex_*.hip gets for it too (get_bsdf and the class of kind 8; it draws nothing, so no *_zs_dl) — and select_kernels takes that set for a scene that holds the
+// material (FlatScene::has_diffuse_transmission), as it does for one that holds a distant or spot light.
+#define SHM_DIFFUSE_TRANSMISSION K_DELTA_LIGHTS
 #include "shm/path.h"
 #include "shm/tri_shade.h"
 #define WF_CAT_(a, b) a##b
@@ -180,7 +184,11 @@ struct PathArrays {
     uint32_t* e_flags;      // the path's flags word at the hit (depth, specular_bounce)
 };
 enum : int { CLASS_DIFFUSE = 0, CLASS_CONDUCTOR = 1, CLASS_DIELECTRIC = 2, CLASS_LAYERED = 3, N_BXDF_CLASSES = 4 };
-__host__ __device__ inline int bxdf_class_of(uint32_t kind) {
+// (device only: its body depends on the unit's SHM_DIFFUSE_TRANSMISSION, and host code of a unit built without the switch — render.hip — would file kind 8 under
+//  CLASS_LAYERED. The same holds for every shm:: function that reads SHM_DELTA_LIGHTS or SHM_DIFFUSE_TRANSMISSION (get_bsdf, base_f_v, base_sample_f_v, base_pdf_v,
+//  base_flags, the light sampling): the kernel units differ in them, so no HOST code of a kernel unit may call one: the linker would keep one unit's body for all of them.)
+__device__ inline int bxdf_class_of(uint32_t kind) {
+    if (SHM_DIFFUSE_TRANSMISSION && kind == SHM_MATERIAL_DIFFUSE_TRANSMISSION) return CLASS_DIFFUSE;  // non-specular, takes NEE, no microfacet code
     return kind == SHM_MATERIAL_DIFFUSE ? CLASS_DIFFUSE : (kind == SHM_MATERIAL_CONDUCTOR ? CLASS_CONDUCTOR : (kind <= SHM_MATERIAL_THIN_DIELECTRIC ? CLASS_DIELECTRIC : CLASS_LAYERED));
 }
 
@@ -458,6 +466,10 @@ WF_SAMPLED_LAUNCHER(wf_launch_shade_fused_gen_tex); WF_SAMPLED_LAUNCHER(wf_launc
 WF_INTERNAL int wf_launch_vertex_tri(ShmScene* s, const ShadeArgs& a); WF_INTERNAL int wf_launch_vertex_gen(ShmScene* s, const ShadeArgs& a);
 WF_INTERNAL int wf_launch_vertex_tex(ShmScene* s, const ShadeArgs& a);
 WF_INTERNAL int wf_launch_vertex_tri_env(ShmScene* s, const ShadeArgs& a); WF_INTERNAL int wf_launch_vertex_gen_env(ShmScene* s, const ShadeArgs& a);
+// ... and a second one, K_DELTA_LIGHTS, knows the diffuse transmission material (the *_dl objects of k_vertex_*.hip)
+WF_INTERNAL int wf_launch_vertex_tri_dl(ShmScene* s, const ShadeArgs& a); WF_INTERNAL int wf_launch_vertex_gen_dl(ShmScene* s, const ShadeArgs& a);
+WF_INTERNAL int wf_launch_vertex_tex_dl(ShmScene* s, const ShadeArgs& a);
+WF_INTERNAL int wf_launch_vertex_tri_env_dl(ShmScene* s, const ShadeArgs& a); WF_INTERNAL int wf_launch_vertex_gen_env_dl(ShmScene* s, const ShadeArgs& a);
 WF_SAMPLED_LAUNCHER(wf_launch_scatter_diffuse_tri); WF_SAMPLED_LAUNCHER(wf_launch_scatter_diffuse_gen); WF_SAMPLED_LAUNCHER(wf_launch_scatter_diffuse_tex);
 WF_SAMPLED_LAUNCHER(wf_launch_scatter_diffuse_tri_env); WF_SAMPLED_LAUNCHER(wf_launch_scatter_diffuse_gen_env);
 WF_SAMPLED_LAUNCHER(wf_launch_scatter_conductor_tri); WF_SAMPLED_LAUNCHER(wf_launch_scatter_conductor_gen); WF_SAMPLED_LAUNCHER(wf_launch_scatter_conductor_tex);
@@ -470,7 +482,6 @@ WF_SAMPLED_LAUNCHER(wf_launch_scatter_layered_staged_tri_env); WF_SAMPLED_LAUNCH
 // ... and in one pass per vertex (k_scatter.inl), which has force_diffuse's code
 WF_SAMPLED_LAUNCHER(wf_launch_scatter_layered_tri); WF_SAMPLED_LAUNCHER(wf_launch_scatter_layered_gen); WF_SAMPLED_LAUNCHER(wf_launch_scatter_layered_tex);
 // the other integrators (k_shade_other.hip): one kernel each for every scene class
-// (RandomWalk samples no light: wf_launch_shade_randomwalk<., true> is declared by the macro and never defined or named — the table's cells take <ZS, false>)
 WF_SAMPLED_LAUNCHER(wf_launch_shade_simple); WF_SAMPLED_LAUNCHER(wf_launch_shade_randomwalk);
 WF_INTERNAL int wf_launch_fold_randomwalk(ShmScene* s, hipStream_t stream, uint32_t cap_eff, uint32_t total);
 // K1 (render.hip, k_generate<HAS_TEX, LEAN, ZS>)

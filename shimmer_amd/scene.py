@@ -338,6 +338,30 @@ class SceneBuilder:
         self.materials.append(m)
         return len(self.materials) - 1
 
+    def material_diffuse_transmission(self, reflectance=0.25, transmittance=0.25, scale=1.0, displacement=None):
+        """PBRT-v4's DiffuseTransmissionMaterial (the reference has none): reflectance and transmittance are spectra, bound textures or numbers. `scale` (a number
+        or a float texture handle) is no field of the material: as the loader does, it becomes a SHM_SPECTEX_SCALED node around each of the two slots, none for a
+        plain 1. `displacement`: a number or a float texture handle; none unless given."""
+        m = abi.ShmMaterial()
+        m.kind = abi.SHM_MATERIAL_DIFFUSE_TRANSMISSION
+        a, b = self._spec(reflectance), self._spec(transmittance)
+        is_handle = isinstance(scale, (int, np.integer)) and not isinstance(scale, bool)
+        if is_handle or float(scale) != 1.0:
+            f = self._ftex_operand(scale)
+            a = self._stex(abi.SHM_SPECTEX_SCALED, self._stex_node(a), f=f, dir=(0.0, 0.0, 0.0))
+            b = self._stex(abi.SHM_SPECTEX_SCALED, self._stex_node(b), f=f, dir=(0.0, 0.0, 0.0))
+        m.a, m.b = a, b
+        m.c = m.d = self.spectrum_constant(0.0)
+        self.materials.append(m)
+        index = len(self.materials) - 1
+        if displacement is not None:
+            m.has_displacement = 1
+            if isinstance(displacement, (int, np.integer)) and not isinstance(displacement, bool):
+                self.set_float_texture(index, abi.SHM_FLOATSLOT_DISPLACEMENT, displacement)
+            else:
+                m.displacement = float(displacement)
+        return index
+
     def material_mix(self, m0, m1, amount=0.5):
         """MixMaterial::create (material.rs:1296-1306): two material indices (either may be a mix) and a constant amount."""
         m = abi.ShmMaterial()

@@ -115,17 +115,34 @@ def test_image(size=64, channels=3, seed=7):
 
 
 def cornell_box(lib, width=512, height=512, coated=False, mix=False, patches=False, patch_skew=0.0, textured=False,
-                texture_filter=None, textured_coated_ceiling=True, glass=False, emitter_reflects=False, environment=None, glass_too=False, film=None, extra_lights=None):
+                texture_filter=None, textured_coated_ceiling=True, glass=False, emitter_reflects=False, environment=None, glass_too=False, film=None, extra_lights=None,
+                diffuse_transmission=None):
     """S2 (config C2): 5 walls x 2 + 2 boxes x 5 faces x 2 + light 2 = 32 triangles.
     coated=True: the tall box becomes CoatedConductor (rough interface, Cu), the short one CoatedDiffuse with a scattering
-    medium between the interfaces, the floor CoatedDiffuse with a smooth interface (SURVEY §8f-1 materials)."""
+    medium between the interfaces, the floor CoatedDiffuse with a smooth interface (SURVEY §8f-1 materials).
+    diffuse_transmission: PBRT-v4's diffuse transmission material (absent, the description is byte for byte what the generator always produced) — a string of words:
+      "sheet"     a back-lit sheet hangs between the camera and the boxes (wavelength-dependent R and T)
+      "textured"  ... its transmittance an image texture, its reflectance a checkerboard, both under a `scale` of 0.9
+      "mixed"     ... the sheet is a MixMaterial of two diffuse transmission materials
+      "tall"      the tall box is diffuse transmission
+      "gold"      the short box is a rough gold conductor
+      "sphere"    a diffuse transmission sphere stands on the short box
+      "all"       every DiffuseMaterial of the room — walls, boxes, the emitter's — is diffuse transmission instead: no plain diffuse material is left"""
+    dt = set((diffuse_transmission or "").split())
+    assert dt <= {"sheet", "textured", "mixed", "tall", "gold", "sphere", "all"}
     b = SceneBuilder()
     b.set_film(width, height, **(film or {}))
     rfw = b.set_camera_look_at(lib, (0, 1, 3.4), (0, 1, 0), (0, 1, 0), 39.0)
-    white = b.material_diffuse(0.75)
-    red = b.material_diffuse(_two_point_spectrum(b, 0.05, 0.75))
-    green = b.material_diffuse(_two_point_spectrum(b, 0.6, 0.08))
-    black = b.material_diffuse(0.0)
+    if "all" in dt:
+        white = b.material_diffuse_transmission(0.6, 0.15)
+        red = b.material_diffuse_transmission(_two_point_spectrum(b, 0.05, 0.6), _two_point_spectrum(b, 0.0, 0.15))
+        green = b.material_diffuse_transmission(_two_point_spectrum(b, 0.5, 0.08), 0.1)
+        black = b.material_diffuse_transmission(0.0, 0.0)
+    else:
+        white = b.material_diffuse(0.75)
+        red = b.material_diffuse(_two_point_spectrum(b, 0.05, 0.75))
+        green = b.material_diffuse(_two_point_spectrum(b, 0.6, 0.08))
+        black = b.material_diffuse(0.0)
     tall_m = short_m = floor_m = white
     if coated:
         tall_m = b.material_coated_conductor(interface_roughness=0.05, conductor_roughness=0.2, thickness=0.02)
@@ -141,6 +158,10 @@ def cornell_box(lib, width=512, height=512, coated=False, mix=False, patches=Fal
         tall_m = b.material_mix(b.material_mix(red, green, 0.3), b.material_coated_diffuse(reflectance=0.7, roughness=0.1), 0.6)
         floor_m = b.material_mix(white, black, 0.0)  # amount <= 0: always the first
     ceil_m, back_m, left_m, right_m = white, white, red, green
+    if "tall" in dt:
+        tall_m = b.material_diffuse_transmission(_two_point_spectrum(b, 0.1, 0.5), _two_point_spectrum(b, 0.6, 0.2))
+    if "gold" in dt:
+        short_m = b.material_conductor(b.spectrum_named("metal-Au-eta"), b.spectrum_named("metal-Au-k"), roughness=0.3)
     if glass_too:  # beside whatever else the scene holds (coated boxes, ...): a smooth glass short box and a rough dielectric left wall — the dielectric class's specular AND general kernels
         short_m = b.material_dielectric(1.5)
         left_m = b.material_dielectric(1.5, roughness=0.3)
@@ -233,10 +254,24 @@ def cornell_box(lib, width=512, height=512, coated=False, mix=False, patches=Fal
         # emitter_reflects: the emitter's own material is white instead of black, so a path that hits it goes ON (emission at a vertex whose state the vertex
         # kernel overwrites: the deferred evaluation of k_emit_jobs reads its side copies), and it emits from both sides
         b.add_mesh(_to_render(p, rfw), vi, white if emitter_reflects else black, emission=blackbody_dense(6500.0), emission_scale=20.0, two_sided=bool(emitter_reflects))
+    if "sheet" in dt:
+        # the sheet leans a little, so that no ray meets it edge-on; the ceiling light is behind it as the camera sees it
+        if "textured" in dt:
+            sheet_m = b.material_diffuse_transmission(b.stex_checkerboard(_two_point_spectrum(b, 0.1, 0.4), 0.05, b.add_texture_mapping("uv", su=4.0, sv=4.0)),
+                                                      b.add_image_texture(test_image(32, 3), filter="trilinear"), scale=0.9)
+        elif "mixed" in dt:
+            sheet_m = b.material_mix(b.material_diffuse_transmission(0.1, _two_point_spectrum(b, 0.7, 0.2)), b.material_diffuse_transmission(0.5, 0.0), 0.4)
+        else:
+            sheet_m = b.material_diffuse_transmission(_two_point_spectrum(b, 0.05, 0.3), _two_point_spectrum(b, 0.65, 0.35))
+        p, vi = _quad((-0.7, 0.25, 0.55), (0.7, 0.25, 0.55), (0.7, 1.75, 0.85), (-0.7, 1.75, 0.85))
+        b.add_mesh(_to_render(p, rfw), vi, sheet_m, uv=np.array([(0, 0), (1, 0), (1, 1), (0, 1)], np.float32) if "textured" in dt else None)
+    if "sphere" in dt:
+        rfo = np.asarray(rfw, np.float32).reshape(4, 4) @ np.array([[1, 0, 0, 0.4], [0, 1, 0, 0.85], [0, 0, 1, 0.3], [0, 0, 0, 1]], np.float32)
+        b.add_sphere(0.25, b.material_diffuse_transmission(0.2, _two_point_spectrum(b, 0.3, 0.7)), render_from_object=rfo.astype(np.float32))
     if environment is not None:  # an ImageInfinitelight shines in through the open front (round 5: the K_ENV_LIGHT units of the staged kernels)
         rot = np.array([[1, 0, 0, 0], [0, 0, 1, 0], [0, -1, 0, 0], [0, 0, 0, 1]], np.float32)
         b.light_image_infinite(environment, scale=0.5, render_from_light=rot)
-    return _finish(b, lib, extra_lights=extra_lights, rfw=rfw, name="S2 cornell box" + (" (environment map)" if environment is not None else "") + (" (coated)" if coated else "") + (" (mix)" if mix else "") + (" (patches)" if patches else "") + (" (textured)" if textured else "") + (" (glass)" if glass else "") + (" (+ glass)" if glass_too else ""))
+    return _finish(b, lib, extra_lights=extra_lights, rfw=rfw, name="S2 cornell box" + (" (diffuse transmission: %s)" % diffuse_transmission if dt else "") + (" (environment map)" if environment is not None else "") + (" (coated)" if coated else "") + (" (mix)" if mix else "") + (" (patches)" if patches else "") + (" (textured)" if textured else "") + (" (glass)" if glass else "") + (" (+ glass)" if glass_too else ""))
 
 
 def procedural_cornell(lib, width=33, height=31, which="checker", film=None, extra_lights=None):
@@ -413,6 +448,8 @@ def ganesha_proxy(lib, width=1024, height=1024, n=599, with_room=True, coated=Fa
         obj = b.material_dielectric(b.spectrum_named("glass-BK7"))
     elif object_material == "coated_conductor":
         obj = b.material_coated_conductor(interface_roughness=0.05, conductor_roughness=0.2, thickness=0.02)
+    elif object_material == "diffuse_transmission":  # (reflectance as the plain object's, plus a transmitted lobe)
+        obj = b.material_diffuse_transmission(0.4, 0.4)
     wall = b.material_diffuse(0.6)
     black = b.material_diffuse(0.0)
     if quad_fraction is not None:  # (development: where the five-wave traversal kernels start to pay — a share of the object's cells as patches, the rest as triangles)
@@ -611,7 +648,7 @@ def three_spheres(lib, width=32, height=32, offsets=(-3.5, 0.0, 5.0), camera=(0.
     return _finish(b, lib, extra_lights=extra_lights, rfw=rfw, name="three spheres" + ("" if environment is None else " (environment map)"))
 
 
-def instanced_scene(lib, width=64, height=48, n_instances=5, only_object=False, baked=False, environment=None, film=None, extra_lights=None):
+def instanced_scene(lib, width=64, height=48, n_instances=5, only_object=False, baked=False, environment=None, film=None, extra_lights=None, diffuse_transmission=False):
     """Object instancing: one object definition (an icosphere with per-vertex normals, a partial sphere and a curved
     bilinear patch, three materials) placed several times with rotated, non-uniformly scaled transforms over a floor lit by a quad
     light and a point light. `only_object`: just the object's shapes at top level, untransformed, no floor. `baked`: the same
@@ -620,7 +657,8 @@ def instanced_scene(lib, width=64, height=48, n_instances=5, only_object=False, 
     b = SceneBuilder()
     b.set_film(width, height, **(film or {}))
     rfw = b.set_camera_look_at(lib, (0.0, 2.2, 7.0), (0.0, 0.8, 0.0), (0, 1, 0), 40.0)
-    mats = [b.material_diffuse(_two_point_spectrum(b, 0.7, 0.2)), b.material_conductor(b.spectrum_named("metal-Cu-eta"), b.spectrum_named("metal-Cu-k"), roughness=0.2),
+    # (diffuse_transmission: the object's icosphere is PBRT-v4's diffuse transmission material instead of a DiffuseMaterial)
+    mats = [b.material_diffuse_transmission(_two_point_spectrum(b, 0.3, 0.1), _two_point_spectrum(b, 0.2, 0.6)) if diffuse_transmission else b.material_diffuse(_two_point_spectrum(b, 0.7, 0.2)), b.material_conductor(b.spectrum_named("metal-Cu-eta"), b.spectrum_named("metal-Cu-k"), roughness=0.2),
             b.material_coated_diffuse(reflectance=0.5, roughness=0.1)]
     sv, sf = icosphere(1)
     nrm = (sv / np.linalg.norm(sv, axis=1, keepdims=True)).astype(np.float32)

@@ -4,7 +4,14 @@ symbol, the instruction text with addresses, branch targets and the padding behi
 missing in the second, and the second's new symbols. A symbol that several code objects define (an anonymous-namespace kernel or a noinline device function of a
 unit that is compiled more than once) is compared as the SET of its distinct texts: more copies of the same texts are the same code. With tools/kernel_resources.py (registers, spills, LDS, scratch) this is the check that a change left existing kernels alone.
 
-    python tools/kernel_isa_diff.py parent/libshimmer_hip.so shimmer_amd/csrc/libshimmer_hip.so"""
+With --without SUBSTRING the comparison is per CODE OBJECT instead: every code object of the first library that defines no symbol containing SUBSTRING must have a twin in
+the second — the same symbols with the same instruction texts, one to one — and the second may hold no further such object. This is the form for a change that lives in the
+*_dl builds only (--without _dl): a noinline device function that every unit defines (base_f_v, get_bsdf_general, ...) then counts with the object it is linked into, where
+the comparison by name above can only say that the library as a whole holds more distinct texts of it.
+
+    python tools/kernel_isa_diff.py parent/libshimmer_hip.so shimmer_amd/csrc/libshimmer_hip.so
+    python tools/kernel_isa_diff.py --without _dl parent/libshimmer_hip.so shimmer_amd/csrc/libshimmer_hip.so"""
+import collections
 import hashlib
 import os
 import re
@@ -15,7 +22,7 @@ import tempfile
 OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 
 
-def kernels(lib):
+def kernels(lib, per_object=False):
     data = open(lib, "rb").read()
     out = {}
     with tempfile.TemporaryDirectory() as tmp:
@@ -40,6 +47,11 @@ def kernels(lib):
                     continue
                 ins = re.sub(r"<[^>]*>", "<L>", ins)
                 out[cur].append(re.sub(r"\b(s_c?branch\w*|s_call\w*)\s+\S+", r"\1 T", ins))
+    if per_object:  # one {symbol: text} table per code object
+        objs = collections.defaultdict(dict)
+        for (name, k), v in out.items():
+            objs[k][name] = hashlib.sha1("\n".join(v).encode()).hexdigest()
+        return list(objs.values())
     by_name = {}
     for (name, _), v in out.items():
         texts, n_ins, n_copies = by_name.setdefault(name, (set(), 0, 0))
@@ -48,7 +60,26 @@ def kernels(lib):
     return {name: (frozenset(texts), n_ins, n_copies) for name, (texts, n_ins, n_copies) in by_name.items()}
 
 
+def objects_main(sub, lib_a, lib_b):
+    def untouched(lib):
+        return collections.Counter(tuple(sorted(o.items())) for o in kernels(lib, per_object=True) if not any(sub in n for n in o))
+    a, b = untouched(lib_a), untouched(lib_b)
+    twins, extra = sum((a & b).values()), sum((b - a).values())
+    print(f"code objects without a symbol containing '{sub}': {sum(a.values())} in the first library ({sum(len(k) * c for k, c in a.items())} symbol definitions), "
+          f"{sum(b.values())} in the second — {twins} with an identical twin, {sum((a - b).values())} without one, {extra} only in the second")
+    for k in (a - b):  # name the symbols that keep it from matching the second library's closest object (the one that shares most definitions)
+        best = max(b - a, key=lambda o: len(set(k) & set(o)), default=())
+        theirs = dict(best)
+        changed = [n for n, h in k if n in theirs and theirs[n] != h]
+        absent = [n for n, _ in k if n not in theirs]
+        print(f"NO TWIN: the object of {', '.join(n for n, _ in k[:3])} ... ({len(k)} symbols) — against the closest object of the second library: "
+              f"different text: {', '.join(changed) or 'none'}; not defined there: {', '.join(absent) or 'none'}; only there: {', '.join(n for n in theirs if n not in dict(k)) or 'none'}")
+    return 1 if (a - b) or extra else 0
+
+
 def main():
+    if len(sys.argv) == 5 and sys.argv[1] == "--without":
+        return objects_main(*sys.argv[2:])
     if len(sys.argv) != 3:
         raise SystemExit(__doc__)
     a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
