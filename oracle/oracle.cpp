@@ -45,6 +45,8 @@
 
 #define SHM_ORACLE_REFERENCE_STREAM 1  // shm/sampling.h: a sampler may carry the reference's own SmallRng stream (orc_render_reference_stream, below)
 #include "../shimmer_amd/csrc/host/flatten.h"
+#include "../shimmer_amd/csrc/host/bvh_pairs.hpp"
+#include "../shimmer_amd/csrc/host/render_plan.hpp"
 #include "../shimmer_amd/csrc/shm/path.h"
 
 using namespace shm;
@@ -1289,6 +1291,74 @@ void orc_fn_camera_ray_differential(const ShmCamera* cam, const float* p_film, c
     float* o = out18;
     auto put3 = [&](V3 v) { *o++ = v.x; *o++ = v.y; *o++ = v.z; };
     put3(r.o); put3(r.d); put3(aux.rx_o); put3(aux.rx_d); put3(aux.ry_o); put3(aux.ry_d);
+}
+
+// ---- the product's host-side decisions (pure headers of shimmer_amd/csrc/host): tests/test_render_plan.py, tests/test_bvh_pairs.py ----
+// host/render_plan.hpp over `n` rows of ORC_PLAN_IN int32 (class mask, diffuse_only, has_material_textures, has_image_light, has_spheres, has_instances, extended,
+// has_plain_diffuse, plain_quarter, filter, SHM_SPLIT_PASS (-1: unset), SHM_TAIL_FUSED_BOUNCE (negative: never), integrator, force_diffuse, sampler, disable_pixel_jitter,
+// max_depth) -> rows of ORC_PLAN_OUT int32: the RenderPlan's fields, the ScenePlan's classes, the table's null pattern, the workspace budget of this render on a fresh
+// scene and, from column 32 on, the allocation walk's bytes per path of every array (oracle_py.WS_ARRAYS names them, in order). Returns the number of arrays.
+enum { ORC_PLAN_IN = 17, ORC_PLAN_OUT = 72 };
+int orc_fn_render_plan(const int32_t* in, int n, int32_t* out) {
+    using namespace shm_plan;
+    static_assert(32 + N_WS_ARRAYS <= ORC_PLAN_OUT, "ORC_PLAN_OUT");
+    for (int i = 0; i < n; ++i, in += ORC_PLAN_IN, out += ORC_PLAN_OUT) {
+        SceneFacts f;
+        for (int c = 0; c < N_CLS; ++c) f.has_class[c] = (in[0] >> c) & 1;
+        f.diffuse_only = in[1]; f.has_material_textures = in[2]; f.has_image_light = in[3]; f.has_spheres = in[4]; f.has_instances = in[5]; f.extended = in[6];
+        f.has_plain_diffuse = in[7]; f.plain_quarter = in[8]; f.filter = (uint32_t)in[9]; f.has_prims = true;
+        Knobs k;
+        k.split_pass = in[10];
+        k.tail_fused_bounce = in[11] >= 0 ? in[11] : NEVER;
+        ShmRenderParams o;
+        memset(&o, 0, sizeof(o));
+        o.integrator = (uint32_t)in[12]; o.force_diffuse = in[13]; o.sampler = (uint32_t)in[14]; o.disable_pixel_jitter = in[15]; o.max_depth = in[16];
+        const ScenePlan sp = scene_plan(f, k);
+        const RenderPlan p = render_plan(sp, o);
+        const bool staged = ws_staged_layout(sp, p.route == ROUTE_STAGED, false);
+        const int32_t cols[32] = {p.route, p.lean_first, p.hit16, p.hit_split, p.hit_kept, p.fused_from, p.split, p.divert_vertex, p.drain_lean, p.layered_onepass,
+                                  p.geo, p.img, p.img_lean, p.img_generate, p.flt, p.zs, p.dl, p.film_per_sample, render_plan_error(sp, p) != nullptr,
+                                  sp.split_pass, sp.lean_divert, sp.lean, (int32_t)ws_bytes_per_path(sp, staged), N_WS_ARRAYS,
+                                  HAS_LEAN_KERNELS[IMG_NONE], HAS_LEAN_KERNELS[IMG_TEX], HAS_LEAN_KERNELS[IMG_ENV], p.group_big, p.mixed_lean_layered, p.late_overlap_bounce, 0, 0};
+        memcpy(out, cols, sizeof(cols));
+        uint32_t bytes[N_WS_ARRAYS];
+        ws_layout(sp, staged, bytes, nullptr);
+        for (int a = 0; a < N_WS_ARRAYS; ++a) out[32 + a] = (int32_t)bytes[a];
+    }
+    return shm_plan::N_WS_ARRAYS;
+}
+// the workspace table's identifiers, comma-separated, in order
+const char* orc_fn_ws_array_names() {
+    static std::string names;
+    if (names.empty()) {
+        uint32_t bytes[shm_plan::N_WS_ARRAYS];
+        const char* n[shm_plan::N_WS_ARRAYS];
+        shm_plan::ws_layout(shm_plan::ScenePlan(), false, bytes, n);
+        for (int a = 0; a < shm_plan::N_WS_ARRAYS; ++a) names += std::string(a ? "," : "") + n[a];
+    }
+    return names.c_str();
+}
+// host/bvh_pairs.hpp over a depth-first node array, the primitive records' kind words and the instances' root nodes. Outputs (caller-allocated): pair_nodes[2 * n_nodes],
+// big_leaf_n[n_prims] (*has_big_out: whether the scene has the table), and per instance its root in the pair layout, its leaf slot and its root record. Returns
+// SHM_OK and the pair array's length in *n_pair_out, or the error code (orc_last_error has the message).
+int orc_fn_bvh_pairs(const ShmBvhNode* nodes, uint32_t n_nodes, const uint32_t* kind_index, uint32_t n_prims, const uint32_t* inst_root, uint32_t n_inst,
+                     ShmBvhNode* pair_nodes, uint32_t* n_pair_out, uint32_t* big_leaf_n, int* has_big_out, uint32_t* inst_root_out, uint32_t* inst_slot_out, ShmBvhNode* inst_root_rec) {
+    shm_host::FlatScene f;
+    f.nodes.assign(nodes, nodes + n_nodes);
+    f.prim_recs.resize(n_prims);
+    for (uint32_t i = 0; i < n_prims; ++i) { memset(&f.prim_recs[i], 0, sizeof(f.prim_recs[i])); f.prim_recs[i].kind_index = kind_index[i]; }
+    f.instances.resize(n_inst);
+    for (uint32_t i = 0; i < n_inst; ++i) { memset(&f.instances[i], 0, sizeof(ShmInstance)); f.instances[i].root_node = inst_root[i]; }
+    shm_host::BvhPairs b;
+    const int rc = shm_host::bvh_pairs(f, b, g_err);
+    if (rc != SHM_OK) return rc;
+    if (b.nodes.size() > 2 * (size_t)n_nodes) { g_err = "pair array longer than two slots per node"; return SHM_ERR_INTERNAL; }
+    memcpy(pair_nodes, b.nodes.data(), b.nodes.size() * sizeof(ShmBvhNode));
+    *n_pair_out = (uint32_t)b.nodes.size();
+    *has_big_out = b.big_leaf_n.empty() ? 0 : 1;
+    for (uint32_t i = 0; i < n_prims; ++i) big_leaf_n[i] = b.big_leaf_n.empty() ? 0u : b.big_leaf_n[i];
+    for (uint32_t i = 0; i < n_inst; ++i) { inst_root_out[i] = b.instances[i].root_node; inst_slot_out[i] = b.instances[i].pad[0]; inst_root_rec[i] = b.inst_roots[i]; }
+    return SHM_OK;
 }
 
 }  // extern "C"

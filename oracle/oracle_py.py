@@ -129,6 +129,11 @@ def load():
     lib.orc_fn_xoshiro256pp.restype, lib.orc_fn_xoshiro256pp.argtypes = None, [C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_uint64)]
     lib.orc_fn_splitmix64.restype, lib.orc_fn_splitmix64.argtypes = None, [C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]
     lib.orc_fn_reference_stream_f32.restype, lib.orc_fn_reference_stream_f32.argtypes = None, [C.c_uint64, C.c_int, FP, C.POINTER(C.c_uint64)]
+    IP32, UP32, NP = C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(abi.ShmBvhNode)
+    lib.orc_fn_render_plan.restype, lib.orc_fn_render_plan.argtypes = C.c_int, [IP32, C.c_int, IP32]
+    lib.orc_fn_ws_array_names.restype, lib.orc_fn_ws_array_names.argtypes = C.c_char_p, []
+    lib.orc_fn_bvh_pairs.restype = C.c_int
+    lib.orc_fn_bvh_pairs.argtypes = [NP, C.c_uint32, UP32, C.c_uint32, UP32, C.c_uint32, NP, UP32, UP32, C.POINTER(C.c_int), UP32, UP32, NP]
     _lib = lib
     return lib
 
@@ -136,6 +141,51 @@ def load():
 def fa(*vals):
     """float array helper for the orc_fn_* entry points."""
     return (C.c_float * len(vals))(*[float(v) for v in vals])
+
+
+# orc_fn_render_plan's row layouts (oracle.cpp): the inputs, the fixed output columns, then one column per workspace array
+PLAN_IN = ["classes", "diffuse_only", "has_material_textures", "has_image_light", "has_spheres", "has_instances", "extended", "has_plain_diffuse", "plain_quarter", "filter",
+           "split_knob", "tail_fused_bounce", "integrator", "force_diffuse", "sampler", "disable_pixel_jitter", "max_depth"]
+PLAN_OUT = ["route", "lean_first", "hit16", "hit_split", "hit_kept", "fused_from", "split", "divert_vertex", "drain_lean", "layered_onepass", "geo", "img", "img_lean",
+            "img_generate", "flt", "zs", "dl", "film_per_sample", "error", "split_pass", "lean_divert", "lean", "budget", "n_arrays", "has_lean_none", "has_lean_tex",
+            "has_lean_env", "group_big", "mixed_lean_layered", "late_overlap_bounce"]
+PLAN_OUT_COLS, PLAN_WS_COL0 = 72, 32
+
+
+def render_plans(rows):
+    """host/render_plan.hpp over an (n, len(PLAN_IN)) int32 array: a dict of int32 columns by PLAN_OUT name, plus "ws": (n, arrays) bytes per path of the allocation
+    walk, and "ws_names": the arrays' identifiers."""
+    lib = load()
+    rows = np.ascontiguousarray(rows, dtype=np.int32)
+    assert rows.ndim == 2 and rows.shape[1] == len(PLAN_IN)
+    out = np.zeros((rows.shape[0], PLAN_OUT_COLS), np.int32)
+    IP32 = C.POINTER(C.c_int32)
+    n_arrays = lib.orc_fn_render_plan(rows.ctypes.data_as(IP32), rows.shape[0], out.ctypes.data_as(IP32))
+    names = lib.orc_fn_ws_array_names().decode().split(",")
+    assert len(names) == n_arrays
+    res = {name: out[:, i] for i, name in enumerate(PLAN_OUT)}
+    res["ws"], res["ws_names"] = out[:, PLAN_WS_COL0:PLAN_WS_COL0 + n_arrays], names
+    return res
+
+
+def bvh_pairs(nodes, kind_index, inst_roots=()):
+    """host/bvh_pairs.hpp: nodes as (bmin, bmax, offset, n_prims, axis) tuples in depth-first order, the primitive records' kind words, the instances' root nodes.
+    Returns a dict (pair nodes as the same tuples, big_leaf_n or None, inst_root, inst_slot, inst_root_rec), or raises RuntimeError with the library's message."""
+    lib = load()
+    n, m, k = len(nodes), len(kind_index), len(inst_roots)
+    arr = (abi.ShmBvhNode * max(n, 1))()
+    for i, (bmin, bmax, offset, n_prims, axis) in enumerate(nodes):
+        arr[i].bmin[:], arr[i].bmax[:], arr[i].offset, arr[i].n_prims, arr[i].axis = bmin, bmax, offset, n_prims, axis
+    U = C.c_uint32
+    kinds, roots = (U * max(m, 1))(*kind_index), (U * max(k, 1))(*inst_roots)
+    pair, n_pair, big, has_big = (abi.ShmBvhNode * max(2 * n, 1))(), U(), (U * max(m, 1))(), C.c_int()
+    root_out, slot_out, root_rec = (U * max(k, 1))(), (U * max(k, 1))(), (abi.ShmBvhNode * max(k, 1))()
+    rc = lib.orc_fn_bvh_pairs(arr, n, kinds, m, roots, k, pair, C.byref(n_pair), big, C.byref(has_big), root_out, slot_out, root_rec)
+    if rc != 0:
+        raise RuntimeError(lib.orc_last_error().decode())
+    tup = lambda nd: (tuple(nd.bmin), tuple(nd.bmax), nd.offset, nd.n_prims, nd.axis)
+    return {"nodes": [tup(pair[i]) for i in range(n_pair.value)], "big_leaf_n": list(big[:m]) if has_big.value else None,
+            "inst_root": list(root_out[:k]), "inst_slot": list(slot_out[:k]), "inst_root_rec": [tup(root_rec[i]) for i in range(k)]}
 
 
 class Oracle:

@@ -763,7 +763,7 @@ int wf_trace_prepare(ShmScene* s) {
     for (int any = 0; any < 2; ++any) {
         int lds = any ? K5Shape<K5_ANY_WAVES>::LDS : K5Shape<K5_CLOSEST_WAVES>::LDS, per_cu = any ? K5Shape<K5_ANY_WAVES>::PER_CU : K5Shape<K5_CLOSEST_WAVES>::PER_CU;
         if (!tri_only) { lds = any ? K5Shape<K5_GEN_ANY_WAVES>::LDS : K5Shape<K5_GEN_CLOSEST_WAVES>::LDS; per_cu = any ? K5Shape<K5_GEN_ANY_WAVES>::PER_CU : K5Shape<K5_GEN_CLOSEST_WAVES>::PER_CU; }
-        if (!tri_only && s->gen_heavy) { lds = K5_GEN_HEAVY_LDS; per_cu = K5Shape<K5_GEN_HEAVY_WAVES>::PER_CU; }
+        if (!tri_only && s->plan.gen_heavy) { lds = K5_GEN_HEAVY_LDS; per_cu = K5Shape<K5_GEN_HEAVY_WAVES>::PER_CU; }
         s->trace3_blocks[any] = s->n_cu * per_cu;
         s->spill3_levels[any] = std::max(0, (int)s->flat.max_leaf_depth + 1 - lds) + 1;
         const size_t words = (size_t)s->trace3_blocks[any] * (TRACE_BLOCK / WAVE) * (size_t)s->spill3_levels[any] * WAVE * 2u;  // (8-byte stack entries)
@@ -786,21 +786,21 @@ int wf_launch_trace(ShmScene* s, bool any, const TraceArgs& t) {
     uint32_t* heads = s->d_heads3 + (any ? 8 * 32 : 0);
     uint32_t* spill = any ? s->d_spill3_any : s->d_spill3;
     hipLaunchKernelGGL(k_reset_heads3, dim3(1), dim3(64), 0, t.stream, heads);
-    const int leaf_min = any ? s->leaf_min_any : s->leaf_min;
+    const int leaf_min = any ? s->plan.leaf_min_any : s->plan.leaf_min;
     const bool tri_only = !s->flat.has_spheres;
     // hit16 with the GEN kernels: the split record form (wavefront.h, load_hit_tri) — the second records follow the `capacity` first ones in the hit allocation
     float4* const hit2 = (t.hit16 && !tri_only && t.hits) ? reinterpret_cast<float4*>(t.hits) + s->capacity : nullptr;
 #define TRACE5_KERNEL_ARGS(ANY)                                                                                                                          \
     s->dsv, t.queue, t.n_ptr, t.n_direct, heads, t.rays, t.hits, t.occluded, t.L, t.contrib, s->d_counters, spill, s->spill3_levels[ANY],                 \
-        (ANY ? s->refill_min_any : s->refill_min), leaf_min, s->queue_parts, s->trace_rays_per_lane, t.hit16, s->d_big_leaf_n, s->d_gen_save[ANY ? 1 : 0], \
-        (ANY ? s->other_min_any : s->other_min), hit2
+        (ANY ? s->plan.refill_min_any : s->plan.refill_min), leaf_min, s->queue_parts, s->plan.trace_rays_per_lane, t.hit16, s->d_big_leaf_n, s->d_gen_save[ANY ? 1 : 0], \
+        (ANY ? s->plan.other_min_any : s->plan.other_min), hit2
 #define TRACE5_LAUNCH(ANY, ...) hipLaunchKernelGGL((k_trace5<ANY, __VA_ARGS__>), dim3(s->trace3_blocks[ANY]), dim3(TRACE_BLOCK), 0, t.stream, TRACE5_KERNEL_ARGS(ANY))
     if (any && s->flat.has_instances && t.strict) {  // (the PBRT-v4 form of the shadow ray's way into an instance: its own instantiations)
-        if (s->gen_heavy) hipLaunchKernelGGL((k_trace5_any_strict<true>), dim3(s->trace3_blocks[1]), dim3(TRACE_BLOCK), 0, t.stream, TRACE5_KERNEL_ARGS(1));
+        if (s->plan.gen_heavy) hipLaunchKernelGGL((k_trace5_any_strict<true>), dim3(s->trace3_blocks[1]), dim3(TRACE_BLOCK), 0, t.stream, TRACE5_KERNEL_ARGS(1));
         else hipLaunchKernelGGL((k_trace5_any_strict<false>), dim3(s->trace3_blocks[1]), dim3(TRACE_BLOCK), 0, t.stream, TRACE5_KERNEL_ARGS(1));
     }
     else if (tri_only) { if (any) TRACE5_LAUNCH(true, false); else TRACE5_LAUNCH(false, false); }
-    else if (s->gen_heavy) { if (any) TRACE5_LAUNCH(true, true, true); else TRACE5_LAUNCH(false, true, true); }
+    else if (s->plan.gen_heavy) { if (any) TRACE5_LAUNCH(true, true, true); else TRACE5_LAUNCH(false, true, true); }
     else { if (any) TRACE5_LAUNCH(true, true); else TRACE5_LAUNCH(false, true); }
 #undef TRACE5_KERNEL_ARGS
 #undef TRACE5_LAUNCH

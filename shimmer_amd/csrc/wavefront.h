@@ -1,5 +1,6 @@
 // wavefront.h — shared declarations of the gfx950 wavefront path tracer behind include/shimmer_hip.h: path state (SoA in HBM), queue
-// bookkeeping, the scene object, and the launchers each kernel translation unit exports. The kernels are split over several .hip files
+// bookkeeping, the scene object, and the launchers each kernel translation unit exports. WHICH of them a scene and a render run is decided in
+// host/render_plan.hpp (ScenePlan at scene creation, RenderPlan per render: pure C++, tested on the CPU); render.hip looks the launchers up and calls them. The kernels are split over several .hip files
 // (k_trace.hip, k_shade_*.hip, render.hip) so that they compile in parallel; nothing here is exported from the library.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -12,16 +13,19 @@
 #include <vector>
 
 #include "host/flatten.h"
+#include "shm/bvh_link.h"
+#include "host/bvh_pairs.hpp"
+#include "host/render_plan.hpp"
 // K_DELTA_LIGHTS (a translation unit's switch, like K_ZSOBOL below): PBRT-v4's distant and spot lights are compiled into a unit's light sampling only where it is true
 // (shm/path.h, SHM_DELTA_LIGHTS). The Makefile compiles every unit that samples lights once more with it into *_dl (and *_zs_dl) objects, whose kernels carry a _dl
-// suffix and whose launchers are the <., true> specializations (WF_SAMPLED_LAUNCHER); select_kernels (render.hip) picks that set for a scene that holds such a light
+// suffix and whose launchers are the <., true> specializations (WF_SAMPLED_LAUNCHER); the render's plan (host/render_plan.hpp, RenderPlan::dl) names that set for a scene that holds such a light
 // (FlatScene::has_directed_lights). Without the switch the two branches fold away: the kernels of every other scene are those of a build without the lights.
 #ifndef K_DELTA_LIGHTS
 #define K_DELTA_LIGHTS false
 #endif
 #define SHM_DELTA_LIGHTS K_DELTA_LIGHTS
 // The same switch is "the extended kernels": PBRT-v4's diffuse transmission material (shm/bxdf.h, SHM_DIFFUSE_TRANSMISSION) is compiled only into the *_dl / *_zs_dl builds —
-// which k_vertex_*.hip gets for it too (get_bsdf and the class of kind 8; it draws nothing, so no *_zs_dl) — and select_kernels takes that set for a scene that holds the
+// which k_vertex_*.hip gets for it too (get_bsdf and the class of kind 8; it draws nothing, so no *_zs_dl) — and RenderPlan::dl names that set for a scene that holds the
 // material (FlatScene::has_diffuse_transmission), as it does for one that holds a distant or spot light.
 #define SHM_DIFFUSE_TRANSMISSION K_DELTA_LIGHTS
 #include "shm/path.h"
@@ -69,14 +73,14 @@ constexpr int WAVE = 64;
 constexpr int TRACE_BLOCK = 256;  // 4 waves per workgroup
 constexpr int SHADE_BLOCK = 128;
 
-// The DEVICE copy of a BVH node (render.hip lays the tree out by sibling pairs and rewrites `offset` into a link word; the ABI's array and the
+// The DEVICE copy of a BVH node (host/bvh_pairs.hpp lays the tree out by sibling pairs and rewrites `offset` into a link word; the ABI's array and the
 // oracle's keep the reference's fields): everything a traversal step needs to go on from a node without reading it again —
 //   interior  axis << 29 | index of the first child (the second is + 1; pairs start at even indices, so (index << 5) ^ 32 is the sibling's byte offset)
 //   leaf      1 << 31 | min(n_prims, 7) << 27 | offset of its first primitive record (a count of 7 means: read ShmScene::d_big_leaf_n[offset], the primitives left from that slot on);
 //             bit 30 is 0 in the array and set by a traversing lane (k_trace5<., GEN>): "the record at this slot is no triangle, its test is pending"
 // `n_prims` and `axis` stay where they were (no kernel reads them since the one-node-step kernels were retired: the link word holds everything).
 constexpr uint32_t HIT_HAS_SECOND = 0x40000000u;  // the compact hit records' primitive word, split form (scenes with spheres / patches, no instances): this hit has a second record
-constexpr uint32_t LINK_LEAF = 0x80000000u, LINK_OTHER = 0x40000000u, LINK_INDEX_MASK = 0x07ffffffu, LINK_COUNT_SHIFT = 27u, LINK_COUNT_MAX = 7u, LINK_AXIS_SHIFT = 29u;
+// (LINK_LEAF, LINK_OTHER, LINK_INDEX_MASK, LINK_COUNT_SHIFT, LINK_COUNT_MAX, LINK_AXIS_SHIFT: shm/bvh_link.h)
 
 struct DeviceCounters {
     unsigned long long rays_closest, rays_any, nodes_closest, tris_closest, nodes_any, tris_any, paths;
@@ -328,6 +332,7 @@ struct ShmScene {
     hipStream_t stream = nullptr;
     shm_host::FlatScene flat;
     SceneView dsv;                 // device pointers
+    shm_plan::ScenePlan plan;      // which pipeline the scene runs, its thresholds and knobs: fixed at creation (host/render_plan.hpp)
     std::vector<void*> allocs;
     std::vector<void*> ws_allocs;  // path workspace (regrown on demand)
     ShmFilmPixel* d_film = nullptr;
@@ -340,10 +345,7 @@ struct ShmScene {
     float* d_filter_weight = nullptr;  // per path slot: the pixel filter's weight (scenes whose filter has negative lobes only; render.hip, ensure_workspace)
     uint32_t* d_q_scatter[4] = {nullptr, nullptr, nullptr, nullptr};  // staged shading: one queue per BxDF class present in the scene
     uint32_t* d_q_split = nullptr; // scenes with textures and plain diffuse materials: what the split pass leaves to the textured kernels
-    int split_pass = 0;            // ... that pass is on (SHM_SPLIT_PASS; a quarter of the primitives or more are plain diffuse)
     uint32_t* d_q_lean = nullptr;  // the lean diversion's queue (triangle-only scenes without textures that hold plain diffuse materials beside others)
-    bool lean_divert = false;      // (round 4 A/B: DESIGN.md section 6)
-    bool staged = false;           // the scene class runs k_vertex -> k_scatter<class> (everything but all-diffuse triangle scenes without textures)
     bool ws_staged = false;        // the workspace holds the staging arrays
     QueueState* d_qs = nullptr;
     DeviceCounters* d_counters = nullptr;
@@ -357,8 +359,6 @@ struct ShmScene {
     // tuned traversal (k_trace5; the field names date from the retired one-node-step kernels)
     int trace3_blocks[2] = {0, 0};   // persistent grid of the closest-hit [0] / any-hit [1] entry point this scene uses (k_trace.hip: K5Shape)
     int spill3_levels[2] = {1, 1};   // stack levels beyond the entry point's LDS levels (HBM spill)
-    int leaf_min = 16;             // closest-hit: lanes with a pending leaf before the triangle phase runs (SHM_LEAF_MIN)
-    int leaf_min_any = 8;          // any-hit (SHM_LEAF_MIN_ANY)
     uint32_t* d_spill3 = nullptr;
     LdsTables lds_tables = {};        // the small tables the shading kernels stage in LDS within the full budget (render.hip: wf_lds_tables)
     LdsTables lds_tables_small = {};  // ... within the 1.5 KB the material-sorted triangle vertex kernel has to spare
@@ -368,21 +368,8 @@ struct ShmScene {
     size_t rw_floats4 = 0;
     uint32_t* d_spill3_any = nullptr;  // the any-hit kernel may run concurrently with the closest-hit one (second stream)
     float4* d_gen_save[2] = {nullptr, nullptr};  // k_trace5<., GEN> (scenes with spheres / patches / instances): per resident lane two 48-byte areas for the ray state (closest, any)
-    // scenes without a coated material: ONE fused all-materials launch per bounce from this bounce on (SHM_TAIL_FUSED_BOUNCE, negative = never: the staged kernels before
-    // it — the test instrument that holds the two pipelines against each other), its chunks sorted by material
-    int tail_fused_bounce = 0;
-    bool gen_heavy = false;        // a quarter or more of the primitive records are spheres / bilinear patches (a quad PLY file: every face a patch): the traversal kernels'
-                                   // five-wave instantiations (k_trace.hip, K5_GEN_HEAVY_WAVES; SHM_GEN_HEAVY=0 / 1 overrides: the suite runs both)
-    int other_min = 16, other_min_any = 16;     // ... and the parked non-triangle tests a wave collects before it runs them (SHM_OTHER_MIN, SHM_OTHER_MIN_ANY)
     hipStream_t stream2 = nullptr;
     hipStream_t stream_cls[4] = {nullptr, nullptr, nullptr, nullptr};  // staged shading: the scatter kernels of the 2nd .. 4th BxDF class of a bounce run beside the first one's
-    uint64_t overlap_paths = 96ull << 20;  // batches below this many paths run K3(b) beside K2(b+1) (SHM_OVERLAP_PATHS; 0 = never)
-    // idle lanes before a traversal wave refills: the kernels set a ray up with the root test and six IEEE divisions (200 VALU instructions), so that fewer, fuller refills
-    // win although a quarter of the lanes idle (r04 sweep on the headline frame, closest / any ms: 24: 97.4 / 62.3, 40: 96.5 / 60.9, 48: 102.1 / 63.5, 56: 119.1 / 78.1)
-    int refill_min_any = 40;       // the any-hit kernel's threshold (SHM_REFILL_MIN_ANY)
-    int refill_min = 40;           // (SHM_REFILL_MIN)
-    int trace_rays_per_lane = 4;   // a traversal launch uses as much of its persistent grid as gives each resident lane about this many rays (SHM_TRACE_RAYS_PER_LANE; 0 = always
-                                   // the whole grid). profiles/r03_trace_rays_per_lane_sweep.txt: C2 16.8 / 16.1 / 15.8 / 15.8 / 16.5 ms at 0 / 4 / 8 / 16 / 32, C4's K2 276.7 / 276.8 / 282 / 307 / 362
     uint32_t pix_group = 1024;      // path-slot order [tile][sample][pixel in tile] (>= n_pix would be sample-major; swept in round 1: profiles/r01_*)
     int queue_parts = 8;           // the traversal queue's partitions, one per XCD with stealing
     uint32_t* d_heads3 = nullptr;  // [2 (closest, any)][8 partitions][32 dwords: one 128-B line per head word]
@@ -441,10 +428,11 @@ struct ShadeArgs {
     uint32_t cap_eff = 0;  // RandomWalk: paths per batch (the stride of ShmScene::d_rw)
     const uint32_t* q_in = nullptr;  // k_vertex: the queue to work through instead of q_active[cur], and its count (the split pass's q_split)
     const uint32_t* n_in = nullptr;
+    uint32_t* q_divert = nullptr;    // k_vertex: where it diverts the hits on plain diffuse materials (RenderPlan::divert_vertex: q_lean), null: nowhere
 };
 // Every shading launcher launches ONE scene-class variant of its kernel: geometry (tri: top-level triangles only, gen: spheres / patches / instances too) x image
 // class (none, tex: image textures — ray differentials, MIP filtering —, env: an ImageInfinitelight alone, the K_ENV_LIGHT units). render.hip puts them in one table,
-// ShadeKernels by (geometry, image class, sampler), and picks a render's cell once (select_kernels).
+// ShadeKernels by (geometry, image class, sampler, extended build); a render's RenderPlan (host/render_plan.hpp) holds the coordinates and select_kernels looks them up.
 using ShadeFn = int (*)(ShmScene*, const ShadeArgs&);
 // The units whose kernels draw and sample lights are compiled four times (K_ZSOBOL x K_DELTA_LIGHTS, Makefile): each defines its launchers as the specialization
 // <K_ZSOBOL, K_DELTA_LIGHTS> of one template, so that the table names all four builds and a missing one is a link error (an undefined hidden symbol).
@@ -489,8 +477,8 @@ using GenerateKernel = void (*)(SceneView, PathArrays, const uint32_t*, uint32_t
 // K1 / K6 of the pixel filters beside the box filter (render.hip, k_generate_filtered<HAS_TEX, LEAN, ZS, FC>, k_film_weighted<W>): + the per-path filter weights (+ the constant K)
 using FilteredGenerateKernel = void (*)(SceneView, PathArrays, const uint32_t*, uint32_t, int, int, ShmRenderParams, uint32_t*, QueueState*, uint32_t, float*);
 using WeightedFilmKernel = void (*)(SceneView, PathArrays, const uint32_t*, uint32_t, int, ShmFilmPixel*, DeviceCounters*, uint32_t, const float*, float);
-// The kernels of one scene class: a cell of render.hip's table by geometry x image class x sampler (nullptr: no such build), of which
-// select_kernels makes a render's set. The bounce loop decides which of them run and calls them through it.
+// The kernels of one scene class: a cell of render.hip's table by geometry x image class x sampler (nullptr: no such build,
+// shm_plan::HAS_LEAN_KERNELS), of which select_kernels makes a render's set by the RenderPlan's coordinates. The plan says which of them run; the bounce loop calls them.
 struct ShadeKernels {
     GenerateKernel generate[2];       // [LEAN]: bounce 0 on known constants (ShadeArgs::first_bounce)
     FilteredGenerateKernel generate_filtered[2];  // ... of a scene whose pixel filter is not the box filter (null: `generate`), and the film kernel that applies

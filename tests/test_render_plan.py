@@ -1,0 +1,189 @@
+"""host/render_plan.hpp — WHICH pipeline a scene and a render run, and the path workspace that needs — over the whole domain flatten_scene and ShmRenderParams can
+produce, through the oracle library's orc_fn_render_plan (pure host code: no GPU). 2 654 208 (scene, knobs, render) combinations of integer logic.
+
+What is asserted, per combination:
+  * the workspace budget's bytes per path equal the sum over the allocation walk;
+  * every array a planned stage touches is in the layout, and no array the plan's launchers would index is missing;
+  * q_lean is drained exactly where something fills it, by exactly one filler;
+  * no launcher coordinate names a null cell of the kernel table (the table's null pattern is exported as data), and the plan's own validation agrees;
+  * the extended (*_dl) build runs for exactly the scenes with a distant / spot light or a diffuse transmission material.
+"Present exactly when": the layout is the SCENE's, kept from render to render, so exactness is held over the renders of a scene — an array is present if and only if
+some render of that scene touches it — for the auxiliary rays, rng0 / pixel0 and filter_weight. The staging arrays (bx, the class queues, q_lean, q_split) and the
+lean kernel's e_* / q_emit are allocated by scene CLASS, as before the plan existed: every non-lean scene keeps them, also a scene whose every bounce the fused
+all-materials kernel shades (SHM_TAIL_FUSED_BOUNCE=0 without coated materials). There the assertion is the safety half — touched implies present — and
+test_staging_arrays_follow_the_scene_class pins the rule itself."""
+import itertools
+import sys
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent / "oracle"))
+import oracle_py  # noqa: E402
+
+ROUTE_LEAN, ROUTE_STAGED, ROUTE_SIMPLE, ROUTE_RANDOM_WALK = 0, 1, 2, 3
+IMG_NONE, IMG_TEX, IMG_ENV = 0, 1, 2
+NEVER = 1 << 30
+
+
+def _filter_constants():
+    import re
+    text = (Path(__file__).resolve().parent.parent / "include" / "shimmer_hip.h").read_text()
+    return {m.group(1): int(m.group(2)) for m in re.finditer(r"SHM_FILTER_(\w+)\s*=\s*(\d+)", text)}
+
+
+def scene_rows():
+    """Every class combination flatten_scene can produce x the two knobs: BxDF classes (every non-empty subset; diffuse_only only with the diffuse class alone) x
+    material textures x image light x spheres x instances x extended build x plain-diffuse share (none / below a quarter / a quarter or more) x SHM_SPLIT_PASS
+    (unset / 0 / 1) x SHM_TAIL_FUSED_BOUNCE (0 / 2 / never)."""
+    classes = [(m, d) for m in range(1, 16) for d in (0, 1) if not (d and m != 1)]
+    rows = []
+    for (mask, donly), mt, il, sph, inst, ext, plain, split, tail in itertools.product(classes, (0, 1), (0, 1), (0, 1), (0, 1), (0, 1), (0, 1, 2), (-1, 0, 1), (0, 2, -1)):
+        rows.append((mask, donly, mt, il, sph, inst, ext, 1 if plain else 0, 1 if plain == 2 else 0, split, tail))
+    return np.array(rows, np.int32)
+
+
+def render_rows():
+    """integrator x force_diffuse x sampler x disable_pixel_jitter x max_depth 0 / 5"""
+    return np.array(list(itertools.product((0, 1, 2), (0, 1), (0, 1), (0, 1), (0, 5))), np.int32)
+
+
+@pytest.fixture(scope="module", params=["BOX", "TRIANGLE", "GAUSSIAN", "MITCHELL"])
+def plans(request):
+    """One pixel-filter class at a time (box / triangle / gaussian / Mitchell; a quarter of the domain each, 190 MB of columns): {class: the inputs and
+    orc_fn_render_plan's outputs}, rows ordered scene-major."""
+    fc = _filter_constants()
+    sc, rr = scene_rows(), render_rows()
+    S, R = len(sc), len(rr)
+    out = {}
+    for name in (request.param,):
+        rows = np.empty((S * R, len(oracle_py.PLAN_IN)), np.int32)
+        rows[:, 0:9] = np.repeat(sc[:, 0:9], R, axis=0)
+        rows[:, 9] = fc[name]
+        rows[:, 10:12] = np.repeat(sc[:, 9:11], R, axis=0)
+        rows[:, 12:17] = np.tile(rr, (S, 1))
+        res = oracle_py.render_plans(rows)
+        res["in"] = {n: rows[:, i] for i, n in enumerate(oracle_py.PLAN_IN)}
+        res["S"], res["R"] = S, R
+        out[name] = res
+    return out
+
+
+def _present(p, name):
+    return p["ws"][:, p["ws_names"].index(name)] != 0
+
+
+def test_the_domain_is_whole(plans):
+    (p,) = plans.values()
+    assert p["S"] == 16 * 2 * 2 * 2 * 2 * 2 * 3 * 3 * 3 and p["R"] == 3 * 2 * 2 * 2 * 2
+    assert len(p["route"]) * 4 == 2654208  # (x the four filter classes of the fixture)
+    for q in plans.values():
+        assert set(np.unique(q["route"])) == {ROUTE_LEAN, ROUTE_STAGED, ROUTE_SIMPLE, ROUTE_RANDOM_WALK}
+        assert q["ws"].shape[1] == q["n_arrays"][0] == len(q["ws_names"]) == 35
+
+
+def test_budget_is_the_sum_of_the_allocation_walk(plans):
+    for q in plans.values():
+        assert np.array_equal(q["budget"], q["ws"].sum(axis=1))
+        assert q["budget"].min() >= 288 + 12  # the path state and the three queues every render has
+
+
+def test_every_array_a_planned_stage_touches_is_in_the_layout(plans):
+    for name, q in plans.items():
+        i = q["in"]
+        S, R = q["S"], q["R"]
+        staged_bounce = (q["route"] == ROUTE_STAGED) & (q["fused_from"] > 0)   # bounce 0 exists in every render
+        over_scene = lambda a: a.reshape(S, R)
+        # auxiliary rays: exactly where the generate kernel is a HAS_TEX one
+        for a in ("AUX0", "AUX1", "AUX2"):
+            assert np.array_equal(_present(q, a), q["img_generate"] == IMG_TEX)
+        # rng0 / pixel0: a lean_first render reads them; the scene holds them exactly when some render of it does
+        for a in ("RNG0", "PIXEL0"):
+            pr = _present(q, a)
+            assert not np.any((q["lean_first"] != 0) & ~pr)
+            assert np.array_equal(over_scene(pr).all(axis=1), over_scene(q["lean_first"] != 0).any(axis=1))
+            assert np.array_equal(over_scene(pr).any(axis=1), over_scene(pr).all(axis=1))
+        # q_lean: drained exactly where filled, by one filler; present wherever it is used
+        fills = q["split"] + q["divert_vertex"]
+        assert np.array_equal(fills, q["drain_lean"]) and fills.max() == 1
+        assert not np.any((q["drain_lean"] != 0) & staged_bounce & ~_present(q, "Q_LEAN"))
+        assert not np.any((q["drain_lean"] != 0) & (q["route"] != ROUTE_STAGED))
+        # q_split: the split pass
+        assert not np.any((q["split"] != 0) & ~_present(q, "Q_SPLIT"))
+        assert not np.any((q["split"] != 0) & ~((q["split_pass"] != 0) & (i["force_diffuse"] == 0) & (q["route"] == ROUTE_STAGED)))
+        # e_* and q_emit: a lean kernel, direct or diverted
+        lean_kernel_runs = (q["route"] == ROUTE_LEAN) | ((q["drain_lean"] != 0) & staged_bounce)
+        for a in ("E_RAY", "E_BETA", "E_CTX0", "E_CTX1", "E_CTX2", "E_FLAGS", "Q_EMIT"):
+            assert not np.any(lean_kernel_runs & ~_present(q, a))
+        # bx and the class queues: a staged bounce (the hit half writes the parameter block and pushes to the queue of every class the scene holds)
+        assert not np.any(staged_bounce & ~_present(q, "BX"))
+        for c in range(4):
+            assert not np.any(staged_bounce & ((i["classes"] >> c) & 1 != 0) & ~_present(q, f"Q_SCATTER{c}"))
+        # the staged kernels of a scene with textures carry ray differentials
+        tex = (i["has_material_textures"] != 0) | (i["has_image_light"] != 0)
+        for a in ("DD0", "DD1", "DD2"):
+            assert not np.any((q["route"] == ROUTE_STAGED) & tex & ~_present(q, a))
+        # filter_weight: the film kernel that reads per-sample weights; the scene holds it exactly when some render of it does
+        pr = _present(q, "FILTER_WEIGHT")
+        assert not np.any((q["film_per_sample"] != 0) & ~pr)
+        assert np.array_equal(over_scene(pr).all(axis=1), over_scene(q["film_per_sample"] != 0).any(axis=1))
+        assert pr.any() == (name == "MITCHELL")
+        # what every render has
+        for a in ("RAY", "HIT", "SHADOW_RAY", "SHADOW_CONTRIB", "L", "REC", "LAMBDA", "LAMBDA_PDF", "CTX", "Q_ACTIVE0", "Q_ACTIVE1", "Q_SHADOW"):
+            assert _present(q, a).all()
+
+
+def test_staging_arrays_follow_the_scene_class(plans):
+    """Every non-lean scene keeps the staging arrays whether or not the render uses them; a lean scene has them exactly in a staged render (force_diffuse)."""
+    for q in plans.values():
+        i = q["in"]
+        bx = _present(q, "BX")
+        assert np.array_equal(bx, (q["lean"] == 0) | (q["route"] == ROUTE_STAGED))
+        assert np.array_equal(_present(q, "Q_LEAN"), bx & (q["lean_divert"] != 0))
+        assert np.array_equal(_present(q, "Q_SPLIT"), bx & (q["split_pass"] != 0))
+        for c in range(4):
+            assert np.array_equal(_present(q, f"Q_SCATTER{c}"), bx & ((i["classes"] >> c) & 1 != 0))
+        assert np.array_equal(_present(q, "E_RAY"), (q["lean"] != 0) | (q["lean_divert"] != 0))
+
+
+def test_no_launcher_coordinate_names_a_null_cell(plans):
+    for q in plans.values():
+        # the table's null pattern, as data: the textured image class has no lean kernels and no k_generate<., LEAN>
+        has_lean = np.stack([q["has_lean_none"], q["has_lean_tex"], q["has_lean_env"]], axis=1)
+        assert np.array_equal(has_lean[0], [1, 0, 1]) and (has_lean == has_lean[0]).all()
+        rows = np.arange(len(q["route"]))
+        calls_lean = (q["route"] == ROUTE_LEAN) | (q["drain_lean"] != 0)
+        assert not np.any(calls_lean & (has_lean[rows, q["img_lean"]] == 0))
+        assert not np.any((q["lean_first"] != 0) & (has_lean[rows, q["img_generate"]] == 0))
+        assert not q["error"].any()
+        for col, n in (("geo", 2), ("img", 3), ("img_lean", 3), ("img_generate", 3), ("flt", 4)):
+            assert q[col].min() >= 0 and q[col].max() < n
+        # the one-pass LayeredBxDF launcher has no K_ENV_LIGHT build: it runs under force_diffuse, where the image class is never env
+        assert not np.any((q["layered_onepass"] != 0) & (q["img"] == IMG_ENV))
+
+
+def test_extended_build_and_sampler_coordinates(plans):
+    for name, q in plans.items():
+        i = q["in"]
+        assert np.array_equal(q["dl"], i["extended"])
+        assert np.array_equal(q["zs"], i["sampler"])
+        assert np.array_equal(q["geo"], i["has_spheres"])
+        assert np.array_equal(q["flt"] != 0, (i["disable_pixel_jitter"] == 0) & (name != "BOX"))
+        assert np.array_equal(q["layered_onepass"], i["force_diffuse"])
+
+
+def test_routes_and_hit_record_forms(plans):
+    (q,) = plans.values()
+    i = q["in"]
+    path = i["integrator"] == 0
+    assert np.array_equal(q["route"] == ROUTE_STAGED, path & ((q["lean"] == 0) | (i["force_diffuse"] != 0)))
+    assert np.array_equal(q["route"] == ROUTE_LEAN, path & (q["lean"] != 0) & (i["force_diffuse"] == 0))
+    assert np.array_equal(q["route"] == ROUTE_RANDOM_WALK, i["integrator"] == 2)
+    assert np.array_equal(q["hit16"] != 0, path & ~((i["has_spheres"] != 0) & (i["has_instances"] != 0)))
+    assert np.array_equal(q["hit_split"] != 0, (q["hit16"] != 0) & (i["has_spheres"] != 0))
+    assert np.array_equal(q["hit_kept"] != 0, (q["route"] == ROUTE_LEAN) & (q["hit16"] != 0) & (i["has_spheres"] == 0))
+    # the fused all-materials kernel: never with coated materials, never under force_diffuse, from the knob's bounce on
+    fused = q["fused_from"] != NEVER
+    assert not np.any(fused & (((i["classes"] >> 3) & 1 != 0) | (i["force_diffuse"] != 0) | (q["route"] != ROUTE_STAGED)))
+    assert np.array_equal(q["fused_from"][fused], np.where(i["tail_fused_bounce"][fused] < 0, NEVER, i["tail_fused_bounce"][fused]))
