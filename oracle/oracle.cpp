@@ -456,6 +456,11 @@ struct Oracle {
 
 thread_local std::string g_err;
 
+// zsobol_config() of a render of this scene, as shm_render_wave computes it
+uint32_t zsobol_word(const Oracle* o, int spp, bool no_scramble) {
+    return zsobol_config(spp, o->flat.film.full_resolution[0], o->flat.film.full_resolution[1], no_scramble);
+}
+
 }  // namespace
 
 #pragma GCC visibility push(default)
@@ -504,6 +509,14 @@ int orc_render_wave(OrcScene* s, const ShmRenderParams* params, const ShmTile* t
                     int32_t sample_begin, int32_t sample_end, int n_threads, ShmFilmPixel* film, ShmStats* stats) {
     Oracle* o = reinterpret_cast<Oracle*>(s);
     if (!params || !tiles || !film) { g_err = "invalid render arguments"; return SHM_ERR_INVALID_ARGUMENT; }
+    // the sampler, as shm_render_wave checks and configures it (render.hip): the ZSobol word of this render, 0 for the independent sampler
+    if (params->sampler > SHM_SAMPLER_ZSOBOL || params->sampler_randomization > SHM_SAMPLER_RANDOMIZE_NONE) { g_err = "unknown sampler or sampler randomization"; return SHM_ERR_INVALID_ARGUMENT; }
+    const uint32_t zsobol = zsobol_word(o, params->samples_per_pixel, params->sampler_randomization == SHM_SAMPLER_RANDOMIZE_NONE);
+    if (params->sampler == SHM_SAMPLER_ZSOBOL && (sample_begin < 0 || (int64_t)sample_end > (int64_t)1 << zsobol_log2spp(zsobol))) {
+        g_err = "zsobol: sample index outside [0, 2^ceil(log2(samples_per_pixel)))";
+        return SHM_ERR_INVALID_ARGUMENT;
+    }
+    const uint32_t zs = params->sampler == SHM_SAMPLER_ZSOBOL ? zsobol : 0u;
     SceneView sv = o->sv;
     sv.quirks_off = params->disable_reference_quirks ? 1u : 0u;  // SHM_REFERENCE_QUIRKS: 0 = reference-exact
     const int width = sv.pixel_bounds[2] - sv.pixel_bounds[0];
@@ -522,7 +535,7 @@ int orc_render_wave(OrcScene* s, const ShmRenderParams* params, const ShmTile* t
                 for (int y = tile.y0; y < tile.y1; ++y) {
                     for (int si = sample_begin; si < sample_end; ++si) {
                         // evaluate_pixel_sample, integrator.rs:326-396
-                        Rng rng = sampler_start_pixel_sample(x, y, si, params->seed);
+                        Rng rng = sampler_start_pixel_sample(x, y, si, params->seed, zs);
                         Wavelengths lambda;
                         Float weight;
                         AuxRays aux = aux_none();
@@ -595,6 +608,7 @@ int orc_render_reference_stream(OrcScene* s, const ShmRenderParams* params, cons
     Oracle* o = reinterpret_cast<Oracle*>(s);
     if (!params || !tiles || !film) { g_err = "invalid render arguments"; return SHM_ERR_INVALID_ARGUMENT; }
     if (params->integrator != SHM_INTEGRATOR_PATH && params->integrator != SHM_INTEGRATOR_SIMPLE_PATH && params->integrator != SHM_INTEGRATOR_RANDOM_WALK) return SHM_ERR_INVALID_ARGUMENT;
+    if (params->sampler != SHM_SAMPLER_INDEPENDENT) { g_err = "reference stream: it is the reference's own sampler stream, not ZSobol's"; return SHM_ERR_INVALID_ARGUMENT; }
     bool entropy = o->flat.has_class[3];  // (class 3: the coated materials)
     for (const ShmMaterial& m : o->flat.materials) entropy = entropy || m.kind == SHM_MATERIAL_MIX;
     if (entropy) { g_err = "reference stream: the scene holds a LayeredBxDF or a MixMaterial (the reference seeds those from OS entropy)"; return SHM_ERR_UNSUPPORTED; }
@@ -800,6 +814,24 @@ float orc_fn_sampler_stream(int px, int py, int sample_index, uint64_t seed, int
     for (int i = 0; i < n; ++i) out[i] = sampler_get_1d(r);
     return n > 0 ? out[0] : 0.0f;
 }
+// The ZSobol stream of (pixel, sample index) in a render of `spp` samples per pixel at full resolution (rx, ry): the draws `kinds` (1: get_1d, 2: get_2d) in order,
+// their u32 values and the floats the sampler returns (sum of kinds each). tests/test_zsobol_oracle.py, against tests/test_zsobol_sampler.py's restatement
+void orc_fn_sampler_stream_zs(int px, int py, int sample_index, uint64_t seed, int spp, int rx, int ry, int no_scramble, int n_kinds, const int32_t* kinds,
+                              uint32_t* out_bits, float* out) {
+    Rng r = sampler_start_pixel_sample(px, py, sample_index, seed, zsobol_config(spp, rx, ry, no_scramble != 0));
+    for (int i = 0; i < n_kinds; ++i) {
+        Rng q = r;
+        if (kinds[i] == 2) {
+            zsobol_next_2d_bits(q, out_bits[0], out_bits[1]);
+            V2 f = sampler_get_2d(r);
+            out[0] = f.x; out[1] = f.y;
+            out_bits += 2; out += 2;
+        } else {
+            *out_bits++ = zsobol_next_1d_bits(q);
+            *out++ = sampler_get_1d(r);
+        }
+    }
+}
 void orc_fn_offset_ray_origin(const float* p, const float* err, const float* n, const float* w, float* out3) {
     V3 r = offset_ray_origin(p3i_from_value_and_error(ld3(p), ld3(err)), ld3(n), ld3(w));
     out3[0] = r.x; out3[1] = r.y; out3[2] = r.z;
@@ -970,6 +1002,20 @@ void orc_fn_camera_ray(OrcScene* s, int px, int py, int sample_index, uint64_t s
     out14[0] = r.o.x; out14[1] = r.o.y; out14[2] = r.o.z; out14[3] = r.d.x; out14[4] = r.d.y; out14[5] = r.d.z;
     for (int i = 0; i < 4; ++i) { out14[6 + i] = lambda.lambda[i]; out14[10 + i] = lambda.pdf[i]; }
 }
+// ... under ZSobol at the scene's full resolution, with the render's jitter options. out16 = o[3], d[3], lambda[4], pdf[4], the filter weight, and the dimension the
+// next draw is taken from
+void orc_fn_camera_ray_zs(OrcScene* s, int px, int py, int sample_index, uint64_t seed, int spp, int no_scramble, int disable_wavelength_jitter, int disable_pixel_jitter,
+                          float* out16) {
+    Oracle* o = reinterpret_cast<Oracle*>(s);
+    Rng rng = sampler_start_pixel_sample(px, py, sample_index, seed, zsobol_word(o, spp, no_scramble != 0));
+    Wavelengths lambda;
+    Float w;
+    Ray r = generate_camera_ray(o->sv, px, py, rng, disable_wavelength_jitter != 0, disable_pixel_jitter != 0, lambda, w, nullptr, spp);
+    out16[0] = r.o.x; out16[1] = r.o.y; out16[2] = r.o.z; out16[3] = r.d.x; out16[4] = r.d.y; out16[5] = r.d.z;
+    for (int i = 0; i < 4; ++i) { out16[6 + i] = lambda.lambda[i]; out16[10 + i] = lambda.pdf[i]; }
+    out16[14] = w;
+    out16[15] = (float)(uint32_t)rng.state;
+}
 void orc_fn_film_sample_rgb(OrcScene* s, const float* L4, const float* lambda4, const float* pdf4, float* out3) {
     Oracle* o = reinterpret_cast<Oracle*>(s);
     Spec L;
@@ -1062,10 +1108,19 @@ void orc_fn_approximate_dp_dxy(OrcScene* s, const float* p, const float* n, int 
 // The camera ray of a pixel sample with its (scaled) auxiliary rays, intersected with the scene; at the hit the differentials of
 // compute_differentials, with the ray's auxiliary rays (use_aux) or through approximate_dp_dxy. Returns 0 on a miss.
 // out[0..18): ray o, d, rx_o, rx_d, ry_o, ry_d; out[18..44): p, n, uv, dpdu, dpdv, dpdx, dpdy, dudx, dvdx, dudy, dvdy
+static int camera_hit_differentials(Oracle* o, int px, int py, int sample_index, uint64_t seed, uint32_t zs, int spp, int disable_pixel_jitter, int use_aux, float* out);
 int orc_fn_camera_hit_differentials(OrcScene* s, int px, int py, int sample_index, uint64_t seed, int spp, int disable_pixel_jitter, int use_aux,
                                     float* out) {
+    return camera_hit_differentials(reinterpret_cast<Oracle*>(s), px, py, sample_index, seed, 0u, spp, disable_pixel_jitter, use_aux, out);
+}
+// ... of a ZSobol render's camera ray (the scene's full resolution, `spp` samples per pixel)
+int orc_fn_camera_hit_differentials_zs(OrcScene* s, int px, int py, int sample_index, uint64_t seed, int spp, int no_scramble, int disable_pixel_jitter, int use_aux,
+                                       float* out) {
     Oracle* o = reinterpret_cast<Oracle*>(s);
-    Rng rng = sampler_start_pixel_sample(px, py, sample_index, seed);
+    return camera_hit_differentials(o, px, py, sample_index, seed, zsobol_word(o, spp, no_scramble != 0), spp, disable_pixel_jitter, use_aux, out);
+}
+static int camera_hit_differentials(Oracle* o, int px, int py, int sample_index, uint64_t seed, uint32_t zs, int spp, int disable_pixel_jitter, int use_aux, float* out) {
+    Rng rng = sampler_start_pixel_sample(px, py, sample_index, seed, zs);
     Wavelengths lambda;
     Float w;
     AuxRays aux = aux_none();
@@ -1299,6 +1354,15 @@ void orc_fn_camera_ray_differential(const ShmCamera* cam, const float* p_film, c
 // max_depth) -> rows of ORC_PLAN_OUT int32: the RenderPlan's fields, the ScenePlan's classes, the table's null pattern, the workspace budget of this render on a fresh
 // scene and, from column 32 on, the allocation walk's bytes per path of every array (oracle_py.WS_ARRAYS names them, in order). Returns the number of arrays.
 enum { ORC_PLAN_IN = 17, ORC_PLAN_OUT = 72 };
+// shm_plan::scene_facts of a scene, in the order of the first ten columns of orc_fn_render_plan's input row: which plan a real scene gets (tests/test_zsobol_oracle.py)
+void orc_fn_scene_facts(OrcScene* s, int32_t* out) {
+    const shm_plan::SceneFacts f = shm_plan::scene_facts(reinterpret_cast<Oracle*>(s)->flat);
+    int32_t classes = 0;
+    for (int c = 0; c < shm_plan::N_CLS; ++c) classes |= (f.has_class[c] ? 1 : 0) << c;
+    const int32_t cols[10] = {classes, f.diffuse_only, f.has_material_textures, f.has_image_light, f.has_spheres, f.has_instances, f.extended, f.has_plain_diffuse,
+                              f.plain_quarter, (int32_t)f.filter};
+    memcpy(out, cols, sizeof(cols));
+}
 int orc_fn_render_plan(const int32_t* in, int n, int32_t* out) {
     using namespace shm_plan;
     static_assert(32 + N_WS_ARRAYS <= ORC_PLAN_OUT, "ORC_PLAN_OUT");

@@ -114,6 +114,13 @@ def load():
     lib.orc_fn_sample_discrete.restype, lib.orc_fn_sample_discrete.argtypes = C.c_int, [FP, C.c_int, F, FP, FP]
     lib.orc_fn_sample_cosine_hemisphere.restype, lib.orc_fn_sample_cosine_hemisphere.argtypes = None, [FP, FP]
     lib.orc_fn_sampler_stream.restype, lib.orc_fn_sampler_stream.argtypes = F, [C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, FP]
+    lib.orc_fn_sampler_stream_zs.restype = None
+    lib.orc_fn_sampler_stream_zs.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), FP]
+    lib.orc_fn_camera_ray_zs.restype = None
+    lib.orc_fn_camera_ray_zs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, FP]
+    lib.orc_fn_camera_hit_differentials_zs.restype = C.c_int
+    lib.orc_fn_camera_hit_differentials_zs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, FP]
+    lib.orc_fn_scene_facts.restype, lib.orc_fn_scene_facts.argtypes = None, [C.c_void_p, C.POINTER(C.c_int32)]
     lib.orc_fn_offset_ray_origin.restype, lib.orc_fn_offset_ray_origin.argtypes = None, [FP, FP, FP, FP, FP]
     lib.orc_fn_triangle_sample_with_context.restype = C.c_int
     lib.orc_fn_triangle_sample_with_context.argtypes = [FP] * 8
@@ -166,6 +173,16 @@ def render_plans(rows):
     res = {name: out[:, i] for i, name in enumerate(PLAN_OUT)}
     res["ws"], res["ws_names"] = out[:, PLAN_WS_COL0:PLAN_WS_COL0 + n_arrays], names
     return res
+
+
+def sampler_stream_zs(px, py, index, spp, rx, ry, seed, none, kinds):
+    """The oracle's ZSobol stream, in the argument order of tests/test_zsobol_sampler.py's `stream`: (the draws' u32 values, the bits of the floats the sampler returns)."""
+    lib = load()
+    n = sum(kinds)
+    k = (C.c_int32 * len(kinds))(*kinds)
+    bits, vals = (C.c_uint32 * n)(), (C.c_float * n)()
+    lib.orc_fn_sampler_stream_zs(px, py, index, seed, spp, rx, ry, int(none), len(kinds), k, bits, vals)
+    return list(bits), [int(v) for v in np.frombuffer(bytes(vals), np.uint32)]
 
 
 def bvh_pairs(nodes, kind_index, inst_roots=()):
@@ -223,6 +240,25 @@ class Oracle:
             if rc != 0:
                 raise RuntimeError(f"orc_render_wave failed ({rc}): {self.lib.orc_last_error().decode()}")
         return film, stats.as_dict()
+
+    def scene_facts(self):
+        """shm_plan::scene_facts of this scene as a dict by the first ten names of PLAN_IN."""
+        out = (C.c_int32 * 10)()
+        self.lib.orc_fn_scene_facts(self.handle, out)
+        return dict(zip(PLAN_IN[:10], out))
+
+    def camera_ray_zs(self, px, py, index, seed, spp, none=False, disable_wavelength_jitter=False, disable_pixel_jitter=False):
+        """The camera ray of a ZSobol pixel sample: a dict of o, d, lambda, pdf (float32 arrays), the filter weight and the dimension the next draw is taken from."""
+        out = (C.c_float * 16)()
+        self.lib.orc_fn_camera_ray_zs(self.handle, px, py, index, seed, spp, int(none), int(disable_wavelength_jitter), int(disable_pixel_jitter), out)
+        a = np.array(out[:], np.float32)
+        return {"o": a[0:3], "d": a[3:6], "lambda": a[6:10], "pdf": a[10:14], "weight": float(a[14]), "dimension": int(a[15])}
+
+    def camera_hit_differentials_zs(self, px, py, index, seed, spp, none=False, disable_pixel_jitter=False, use_aux=True):
+        """orc_fn_camera_hit_differentials of a ZSobol pixel sample: (hit, the 44 floats of that entry point)."""
+        out = (C.c_float * 44)()
+        ok = self.lib.orc_fn_camera_hit_differentials_zs(self.handle, px, py, index, seed, spp, int(none), int(disable_pixel_jitter), int(use_aux), out)
+        return bool(ok), np.array(out[:], np.float32)
 
     def render_reference_stream(self, params, tiles=None, n_tiles=None):
         """ImageTileIntegrator::render on the reference's OWN sampler stream, as `RAYON_NUM_THREADS=1 shimmer scene.pbrt --seed S` draws it (oracle.cpp,

@@ -33,6 +33,12 @@ def cases(scenes, lib):
         "random_scene_3": (lambda: scenes.random_scene(lib, 3), dict(spp=2, max_depth=6, seed=11)),
         "random_scene_2_ortho_nojitter": (lambda: scenes.random_scene(lib, 2), dict(spp=2, max_depth=5, seed=12, disable_pixel_jitter=True, disable_wavelength_jitter=True)),
         "random_scene_12_textured": (lambda: scenes.random_scene(lib, 12), dict(spp=2, max_depth=6, seed=13)),
+        # the same under ZSobol (the oracle honours ShmRenderParams::sampler): the fast-Owen stream, the bare sequence, a sample count that is no power of two
+        "cornell_path_zsobol": (lambda: scenes.cornell_box(lib, 32, 32), dict(spp=4, max_depth=5, seed=1, sampler="zsobol")),
+        "crown_proxy_depth16_zsobol": (lambda: scenes.crown_proxy(lib, 20, 28, level=1, n_glass=6, n_gold=2), dict(spp=2, max_depth=16, seed=8, sampler="zsobol")),
+        "cornell_textured_path_zsobol": (lambda: scenes.cornell_box(lib, 32, 32, textured=True), dict(spp=4, max_depth=6, seed=5, sampler="zsobol")),
+        "cornell_coated_path_zsobol_none": (lambda: scenes.cornell_box(lib, 24, 24, coated=True), dict(spp=2, max_depth=5, seed=2, sampler="zsobol", randomization="none")),
+        "cornell_path_zsobol_spp6": (lambda: scenes.cornell_box(lib, 32, 32), dict(spp=6, max_depth=5, seed=1, sampler="zsobol")),
     }
 
 

@@ -1,5 +1,5 @@
 """PBRT-v4's distant and spot lights on the device: the *_dl kernels (wavefront.h, K_DELTA_LIGHTS) of every scene class against the CPU oracle bit for bit — film and
-the seven counters —, the other integrators, ZSobol by decomposition invariance (the oracle has no ZSobol), scenes lit by delta lights alone, the leaf probe on
+the seven counters —, the other integrators, ZSobol against the oracle and by decomposition invariance, scenes lit by delta lights alone, the leaf probe on
 tests/test_delta_lights.py's vectors, and a sweep over the scene classes, options and pipelines that the remaining *_dl kernels serve."""
 import ctypes as C
 import os
@@ -9,6 +9,7 @@ import pytest
 
 import oracle_py
 import test_delta_lights as dl
+import zsobol_cases as zc
 from shimmer_amd import abi, render, scene as scn, scenes
 from shimmer_amd.scenes import _box, _quad, _to_render, blackbody_dense
 from test_gpu_zsobol import probe_op
@@ -101,14 +102,15 @@ def test_the_other_integrators_equal_the_oracle(gpu_lib, integrator, lights, bsd
 
 @pytest.mark.parametrize("which", ["lean", "general"])
 def test_the_other_integrators_under_zsobol(gpu_lib, which):
-    """k_shade_simple_zs_dl (RandomWalk samples no light and has no _dl build: k_shade_randomwalk_zs serves the scene). The oracle has no ZSobol: the renders are
+    """k_shade_simple_zs_dl (RandomWalk samples no light and has no _dl build: k_shade_randomwalk_zs serves the scene). The renders equal the oracle's, are
     repeatable, independent of how the work is cut up, use the lights, and agree with independent sampling in the mean (as tests/test_gpu_zsobol.py has it for the plain kernels)."""
     sc, _, _ = class_scene(gpu_lib, which)
     plain, _, _ = class_scene(gpu_lib, which, lights=False)
     g = render.Renderer(gpu_lib, sc.desc, 0)
     for integ, kw in (("simplepath", dict()), ("simplepath", dict(sample_bsdf=False)), ("randomwalk", dict())):
         pz = render.make_params(seed=3, spp=256, max_depth=4, integrator=integ, sampler="zsobol", **kw)
-        fz, _ = g.render(pz)
+        fz, sz = g.render(pz)
+        zc.assert_equals_oracle(sc.desc, pz, fz, sz, (which, integ, kw))
         fz2, _ = g.render(pz)
         assert np.array_equal(fz, fz2) and np.isfinite(fz["rgb_sum"]).all(), integ
         g.clear()
@@ -158,13 +160,14 @@ def test_a_scene_lit_by_delta_lights_alone(gpu_lib, coated):
 
 @pytest.mark.parametrize("which", ["lean", "staged_coated", "sorted_fused"])
 def test_zsobol_decomposition_invariance(gpu_lib, which):
-    """The oracle has no ZSobol: the *_zs_dl kernels are held to the film not depending on how the work is cut up."""
+    """The *_zs_dl kernels: the oracle's film and counters, and a film that does not depend on how the work is cut up."""
     sc, spp, depth = class_scene(gpu_lib, which)
     p = render.make_params(seed=21, spp=8, max_depth=depth, sampler="zsobol")
     gpu = render.Renderer(gpu_lib, sc.desc, 0)
     f1, s1 = gpu.render(p)
     f2, _ = gpu.render(p)
     assert np.array_equal(f1, f2) and (f1["weight_sum"] == 8.0).all() and np.isfinite(f1["rgb_sum"]).all()
+    zc.assert_equals_oracle(sc.desc, p, f1, s1, which)
     f_ind, _ = gpu.render(render.make_params(seed=21, spp=8, max_depth=depth))
     assert not np.array_equal(f1, f_ind)
     gpu.clear()
@@ -253,7 +256,7 @@ def test_the_probe_replays_the_leaf_vectors(gpu_lib):
 def test_every_delta_light_kernel_runs_and_the_pipelines_agree(gpu_lib, monkeypatch):
     """The remaining *_dl kernels — the general scatter kernels under force_diffuse / regularize, the *_env units, rough dielectrics, the split pass and the lean
     diversion, both samplers: the staged pipeline from the camera ray on (SHM_TAIL_FUSED_BOUNCE=-1) against the default, and the split pass off against on,
-    give the same bits and counters. (Which *_dl kernels a run of this file launches is what tools/kernel_coverage.py shows of a kernel trace: profiles/delta_lights.md.)"""
+    give the same bits and counters; under ZSobol the default's are also the oracle's (under the independent sampler the tests above hold the classes to it). (Which *_dl kernels a run of this file launches is what tools/kernel_coverage.py shows of a kernel trace: profiles/delta_lights.md.)"""
     lib = gpu_lib
     env = scenes.environment_image(32)
     c, cr, sp, ins = scenes.spot_and_distant(**CORNELL), scenes.spot_and_distant(**CROWN), scenes.spot_and_distant(**SPHERES), scenes.spot_and_distant(**INSTANCES)
@@ -282,6 +285,8 @@ def test_every_delta_light_kernel_runs_and_the_pipelines_agree(gpu_lib, monkeypa
                 for v in ("SHM_TAIL_FUSED_BOUNCE", "SHM_SPLIT_PASS"):
                     monkeypatch.delenv(v, raising=False)
                 assert np.isfinite(render.film_to_rgb(out[0][0])).all(), (sc.name, sampler, kw)
+                if sampler == "zsobol":
+                    zc.assert_equals_oracle(sc.desc, p, out[0][0], out[0][1], (sc.name, kw))
                 for f, s in out[1:]:
                     assert np.array_equal(f, out[0][0]), (sc.name, sampler, kw)
                     for k in STATS:

@@ -1,7 +1,7 @@
 """PBRT-v4's diffuse transmission material on the device: every shading pipeline that can meet it — the material-sorted fused kernels, the staged k_vertex ->
 k_scatter_diffuse pair beside a coated material, the lean diversion beside it (and with nothing to divert), the general-geometry, textured and environment builds,
-the other integrators — against the CPU oracle bit for bit (film, weight_sum, the seven counters); ZSobol by decomposition invariance and by the pipelines agreeing
-with each other (the oracle has no ZSobol); the leaf probe on tests/test_diffuse_transmission.py's vectors; and a scene without the material, which renders the film
+the other integrators — against the CPU oracle bit for bit (film, weight_sum, the seven counters); ZSobol against the oracle too, by decomposition invariance and by
+the pipelines agreeing with each other; the leaf probe on tests/test_diffuse_transmission.py's vectors; and a scene without the material, which renders the film
 the parent commit rendered. A scene with the material runs the extended (*_dl) kernel set (wavefront.h)."""
 import ctypes as C
 import hashlib
@@ -13,6 +13,7 @@ import pytest
 
 import oracle_py
 import test_diffuse_transmission as dt
+import zsobol_cases as zc
 from shimmer_amd import abi, render, scene as scn, scenes
 
 pytestmark = pytest.mark.gpu
@@ -112,7 +113,7 @@ def test_a_film_smaller_than_a_tile(gpu_lib):
 
 @pytest.mark.parametrize("which", ["beside_diffuse", "staged_coated"])
 def test_zsobol_decomposition_invariance_and_the_pipelines_agree(gpu_lib, which, monkeypatch):
-    """The oracle has no ZSobol: as tests/test_gpu_zsobol.py does, the *_zs_dl kernels are held to a film that does not depend on how the work is cut up, and the
+    """As tests/test_gpu_zsobol.py does, the *_zs_dl kernels are held to the oracle's film and counters, to a film that does not depend on how the work is cut up, and the
     staged pipeline from the camera ray on (SHM_TAIL_FUSED_BOUNCE=-1) to the same bits and counters as the default."""
     sc = class_scene(gpu_lib, which)
     p = render.make_params(seed=21, spp=8, max_depth=5, sampler="zsobol")
@@ -120,6 +121,7 @@ def test_zsobol_decomposition_invariance_and_the_pipelines_agree(gpu_lib, which,
     f1, s1 = gpu.render(p)
     f2, _ = gpu.render(p)
     assert np.array_equal(f1, f2) and (f1["weight_sum"] == 8.0).all() and np.isfinite(f1["rgb_sum"]).all()
+    zc.assert_equals_oracle(sc.desc, p, f1, s1, which)
     f_ind, _ = gpu.render(render.make_params(seed=21, spp=8, max_depth=5))
     assert not np.array_equal(f1, f_ind)
     gpu.clear()

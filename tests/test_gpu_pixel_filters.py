@@ -1,4 +1,4 @@
-"""The pixel filters on the device: films and counters bit for bit against the oracle in every scene class, ZSobol films invariant under every decomposition of the
+"""The pixel filters on the device: films and counters bit for bit against the oracle in every scene class, ZSobol films equal to the oracle's and invariant under every decomposition of the
 work, the probe's Filter::Sample against the host build of shm/filter.h, and the step-edge scene (signed weights, weight sums of either sign) against the oracle."""
 import ctypes as C
 import os
@@ -8,6 +8,7 @@ import pytest
 
 import oracle_py
 import test_pixel_filters as pf
+import zsobol_cases as zc
 from shimmer_amd import abi, render, scene as scn, scenes
 from test_gpu_zsobol import probe_op
 
@@ -65,13 +66,14 @@ def test_without_pixel_jitter_the_device_film_is_the_box_film(gpu_lib, name):
 
 @pytest.mark.parametrize("name", ["gaussian", "mitchell"])
 def test_zsobol_filtered_film_decomposition_invariance(gpu_lib, monkeypatch, name):
-    """The decomposition set of test_zsobol_film_decomposition_invariance under a pixel filter (the oracle has no ZSobol: invariance is the check)."""
+    """The decomposition set of test_zsobol_film_decomposition_invariance under a pixel filter, and the film and counters of the oracle."""
     sc = scenes.ganesha_proxy(gpu_lib, 160, 120, n=64, film=dict(filter=name))
     p = render.make_params(seed=21, spp=12, max_depth=5, sampler="zsobol")
     gpu = render.Renderer(gpu_lib, sc.desc, 0)
     f1, s1 = gpu.render(p)
     f2, _ = gpu.render(p)
     assert np.array_equal(f1, f2)
+    zc.assert_equals_oracle(sc.desc, p, f1, s1, name)
     f_ind, _ = gpu.render(render.make_params(seed=21, spp=12, max_depth=5))
     assert not np.array_equal(f1, f_ind)  # (the sampler is used ...)
     box = scenes.ganesha_proxy(gpu_lib, 160, 120, n=64)

@@ -1,5 +1,5 @@
 """PBRT-v4's procedural float textures on the device: every kernel class that evaluates textures renders the film, the hit records and the seven counters of the CPU oracle bit
-for bit; ZSobol (which the oracle does not have) by decomposition invariance; the leaf probe (PROBE_FLOAT_TEXTURE) on the CPU test's leaf scene and contexts, bit-equal to the
+for bit; ZSobol against the oracle too and by decomposition invariance; the leaf probe (PROBE_FLOAT_TEXTURE) on the CPU test's leaf scene and contexts, bit-equal to the
 oracle; and the films of two existing textured scenes, which must be what the library before this change rendered (tests/golden/procedural_textures_before.json).
 The film is 33 x 31 at 3 samples: 3069 paths, no multiple of 256 — a partial last wave, and queues that compact."""
 import ctypes as C
@@ -12,6 +12,7 @@ import pytest
 
 import oracle_py
 import test_procedural_textures as pt
+import zsobol_cases as zc
 from oracle_py import fa
 from shimmer_amd import abi, render, scene as scn, scenes
 from test_gpu_zsobol import probe_op
@@ -101,14 +102,15 @@ def test_the_textures_are_used(gpu_lib):
 
 @pytest.mark.parametrize("which", ["checker", "coated"])
 def test_zsobol_decomposition_invariance(gpu_lib, which):
-    """The oracle has no ZSobol: the *_zs textured kernels are held to a film that is repeatable, does not depend on how the work is cut up, and agrees with independent
-    sampling in the mean."""
+    """The *_zs textured kernels are held to the oracle's film and counters, and to a film that is repeatable, does not depend on how the work is cut up, and agrees with
+    independent sampling in the mean."""
     sc = scenes.procedural_cornell(gpu_lib, W, H, which=which)
     p = render.make_params(seed=21, spp=8, max_depth=DEPTH, sampler="zsobol")
     g = render.Renderer(gpu_lib, sc.desc, 0)
-    f1, _ = g.render(p)
+    f1, s1 = g.render(p)
     f2, _ = g.render(p)
     assert np.array_equal(f1, f2) and (f1["weight_sum"] == 8.0).all() and np.isfinite(f1["rgb_sum"]).all()
+    zc.assert_equals_oracle(sc.desc, p, f1, s1, which)
     f_ind, _ = g.render(render.make_params(seed=21, spp=8, max_depth=DEPTH))
     assert not np.array_equal(f1, f_ind)
     g.clear()

@@ -1,6 +1,6 @@
 """The state one ShmScene carries from render to render (run with `pytest -m gpu`): the path workspace — whose staging arrays an all-diffuse scene gains with its first
 staged render and keeps —, the per-batch hit-record form set on the scene's PathArrays and taken back, the random-walk records, the regrown capacity. Seven renders in
-sequence on ONE Renderer, each held bit for bit against a fresh Renderer given the same parameters."""
+sequence on ONE Renderer, each held bit for bit against a fresh Renderer given the same parameters; the ZSobol render also against the CPU oracle."""
 import numpy as np
 import pytest
 
@@ -43,6 +43,9 @@ def test_renders_in_sequence_on_one_scene_equal_fresh_scenes(env, scene):
             for key in ("paths", "rays_closest", "rays_any", "nodes_closest", "tris_closest", "nodes_any", "tris_any"):
                 assert stats[key] == stats_fresh[key], f"step {step} {opts}: {key}"
             assert film["weight_sum"].min() == params.samples_per_pixel
+            if opts.get("sampler") == "zsobol":
+                import zsobol_cases as zc
+                zc.assert_equals_oracle(sc.desc, params, film, stats, (scene, opts))
             films.append(film)
     finally:
         kept.close()

@@ -157,12 +157,15 @@ def test_records_on_equal_records_off(env, monkeypatch):
 
 
 def test_records_under_zsobol(env, monkeypatch):
-    """The *_zs builds of the same kernels (the oracle has no ZSobol: the library without records is the reference)."""
+    """The *_zs builds of the same kernels: with records, the library without them and the oracle agree."""
     monkeypatch.setenv("SHM_TRI_SHADE", "0")
     off = _gpu_render(env, "diffuse", sampler="zsobol")
     monkeypatch.delenv("SHM_TRI_SHADE")
     on = _gpu_render(env, "diffuse", sampler="zsobol")
     _same(on, off)
+    lib, _, render, scenes = env
+    import zsobol_cases as zc
+    zc.assert_equals_oracle(_scene(lib, scenes, "diffuse")[0], render.make_params(seed=SEED, spp=SPP, max_depth=DEPTH, sampler="zsobol"), on[0], on[1], "diffuse")
     assert not np.array_equal(on[0]["rgb_sum"], _gpu_render(env, "diffuse")[0]["rgb_sum"])  # (it was another sampler)
 
 

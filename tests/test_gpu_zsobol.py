@@ -1,5 +1,7 @@
-"""The ZSobol sampler on the device: the probe's stream against the Python restatement (tests/test_zsobol_sampler.py), films invariant under every
-decomposition of the work, every kernel class drawing the same dimensions, unbiased against independent sampling, and a lower error at equal spp."""
+"""The ZSobol sampler on the device: the probe's stream against the Python restatement (tests/test_zsobol_sampler.py), films equal to the CPU oracle's bit for bit
+(the oracle honours ShmRenderParams::sampler; tests/test_zsobol_oracle.py holds it to the restatement) and invariant under every decomposition of the work, every
+kernel class drawing the same dimensions, unbiased against independent sampling, and a lower error at equal spp. tests/test_gpu_zsobol_oracle.py walks the table
+of edge cases."""
 import ctypes as C
 import random
 import re
@@ -8,6 +10,7 @@ import numpy as np
 import pytest
 
 import test_zsobol_sampler as ref
+import zsobol_cases as zc
 from shimmer_amd import abi, render, scene as scn, scenes
 
 pytestmark = pytest.mark.gpu
@@ -50,13 +53,14 @@ def test_device_stream_equals_the_restatement(gpu_lib):
 
 def test_zsobol_film_decomposition_invariance(gpu_lib, monkeypatch):
     """As test_render_decomposition_invariance, with ZSobol: two runs, tile subsets wave by wave, shm_render_device, small batches, no overlap and
-    shm_render_sharded at world 1 all give the same bits."""
+    shm_render_sharded at world 1 all give the same bits, and those are the oracle's."""
     sc = scenes.ganesha_proxy(gpu_lib, 160, 120, n=64)
     p = render.make_params(seed=21, spp=12, max_depth=5, sampler="zsobol")
     gpu = render.Renderer(gpu_lib, sc.desc, 0)
     f1, s1 = gpu.render(p)
     f2, _ = gpu.render(p)
     assert np.array_equal(f1, f2) and (f1["weight_sum"] == 12.0).all()
+    zc.assert_equals_oracle(sc.desc, p, f1, s1, sc.name)
     f_ind, _ = gpu.render(render.make_params(seed=21, spp=12, max_depth=5))
     assert not np.array_equal(f1, f_ind)  # (the sampler is used)
     gpu.clear()
@@ -108,9 +112,9 @@ def class_scenes(lib):
 
 
 def test_zsobol_kernel_classes_agree(gpu_lib, monkeypatch):
-    """The oracle has no ZSobol: what proves that every kernel class of the path integrator draws the same dimensions is that the film and the seven
-    counters stay the same bits whichever kernels run — the fused kernel from bounce -1 / 0 / 3 on, the split pass on and off. SimplePath and
-    RandomWalk have one kernel each: they are only run here (deterministic, finite, image mean within 3 % of independent sampling)."""
+    """Every kernel class of the path integrator draws the same dimensions: the film and the seven counters stay the same bits whichever kernels run — the fused
+    kernel from bounce -1 / 0 / 3 on, the split pass on and off —, and the default pipeline's are the oracle's, whose li draws in the reference's order without a
+    save / resume. SimplePath and RandomWalk have one kernel each: equal to the oracle, deterministic, finite, image mean within 3 % of independent sampling."""
     for sc, spp, depth in class_scenes(gpu_lib):
         p = render.make_params(seed=5, spp=spp, max_depth=depth, sampler="zsobol")
         runs = []
@@ -125,15 +129,17 @@ def test_zsobol_kernel_classes_agree(gpu_lib, monkeypatch):
             g.close()
         monkeypatch.delenv("SHM_TAIL_FUSED_BOUNCE", raising=False)
         monkeypatch.delenv("SHM_SPLIT_PASS", raising=False)
+        zc.assert_equals_oracle(sc.desc, p, runs[0][2], runs[0][3], sc.name)
         for var, val, f, s in runs[1:]:
             assert np.array_equal(f, runs[0][2]), (sc.name, var, val)
             for k in STATS:
                 assert s[k] == runs[0][3][k], (sc.name, var, val, k)
-    # simplepath / randomwalk: run, deterministic, finite, image mean close to independent sampling's
+    # simplepath / randomwalk: the oracle's film, deterministic, finite, image mean close to independent sampling's
     sc = scenes.cornell_box(gpu_lib, 32, 32)
     g = render.Renderer(gpu_lib, sc.desc, 0)
     for integ in ("simplepath", "randomwalk"):
-        fz, _ = g.render(render.make_params(seed=3, spp=256, max_depth=4, integrator=integ, sampler="zsobol"))
+        fz, sz = g.render(render.make_params(seed=3, spp=256, max_depth=4, integrator=integ, sampler="zsobol"))
+        zc.assert_equals_oracle(sc.desc, render.make_params(seed=3, spp=256, max_depth=4, integrator=integ, sampler="zsobol"), fz, sz, integ)
         fz2, _ = g.render(render.make_params(seed=3, spp=256, max_depth=4, integrator=integ, sampler="zsobol"))
         fi, _ = g.render(render.make_params(seed=3, spp=1024, max_depth=4, integrator=integ))
         a, b = render.film_to_rgb(fz), render.film_to_rgb(fi)
@@ -205,7 +211,8 @@ def test_pbrt_zsobol_file_renders_as_make_params(gpu_lib, tmp_path):
 def test_zsobol_kernel_classes_agree_under_every_option(gpu_lib, monkeypatch):
     """The same agreement with force_diffuse and regularize (the general scatter kernels of every class), under environment maps (the *_env kernels)
     and on the random fuzzing scenes (every shape and material kind, rough dielectrics): the staged kernels from the camera ray on
-    (SHM_TAIL_FUSED_BOUNCE=-1) against the default, the same bits and counters. Between them, the ZSobol tests launch every ZSobol kernel."""
+    (SHM_TAIL_FUSED_BOUNCE=-1) against the default, the same bits and counters, and the default's against the oracle. Between them, the ZSobol tests launch every
+    ZSobol kernel."""
     env = scenes.environment_image(32)
     cases = [scenes.crown_proxy(lib := gpu_lib, 30, 42, level=1, n_glass=6, n_gold=2), scenes.crown_proxy(lib, 30, 42, level=1, n_glass=6, n_gold=2, environment=env),
              scenes.cornell_box(lib, 32, 32, textured=True), scenes.cornell_box(lib, 32, 32, glass=True, environment=env),
@@ -227,6 +234,7 @@ def test_zsobol_kernel_classes_agree_under_every_option(gpu_lib, monkeypatch):
                 g.close()
             monkeypatch.delenv("SHM_TAIL_FUSED_BOUNCE", raising=False)
             assert np.array_equal(out[0][0], out[1][0]), (sc.name, kw)
+            zc.assert_equals_oracle(sc.desc, p, out[0][0], out[0][1], (sc.name, kw))
             assert np.isfinite(render.film_to_rgb(out[0][0])).all(), (sc.name, kw)
             for k in STATS:
                 assert out[0][1][k] == out[1][1][k], (sc.name, kw, k)
