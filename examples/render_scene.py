@@ -5,6 +5,8 @@
     python examples/render_scene.py cornell --filter gaussian        (box | gaussian | mitchell | sinc | triangle)
     python examples/render_scene.py textured | checkerboard | coated | patches | instanced | environment | ganesha | crown | spotlit | fuzz:13
     python examples/render_scene.py diffuse_transmission | translucent   (PBRT-v4's diffuse transmission material: the scene file / the builder)
+    python examples/render_scene.py cornell --camera spherical [--mapping equirectangular]   (PBRT-v4's spherical camera in place of the scene's own)
+    python examples/render_scene.py cornell_probe                    (examples/scenes/cornell_probe.pbrt: an equal-area probe in the middle of the Cornell box)
 
 Everything goes through the C ABI of include/shimmer_hip.h (shimmer_amd/abi.py is the ctypes binding): scene description ->
 shm_scene_create -> shm_render_device -> shm_film_read -> shm_film_get_image -> shm_write_pfm. Needs an MI355X: there is no CPU path.
@@ -22,19 +24,22 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from shimmer_amd import abi, render, scenes  # noqa: E402
 
 
-def make_scene(lib, name, w, h, film=None):
+def make_scene(lib, name, w, h, film=None, camera=None):
+    if camera is not None and (name in ("checkerboard", "diffuse_transmission", "cornell_probe") or name.startswith(("procedural", "fuzz:"))):
+        raise SystemExit(f"--camera does not apply to {name}: a scene file has its own camera, and the procedural and fuzz generators take none")
     if name == "cornell":
-        return scenes.cornell_box(lib, w, h, film=film)
+        return scenes.cornell_box(lib, w, h, camera=camera, film=film)
     if name == "spotlit":  # the Cornell box under PBRT-v4's spot and distant lights as well (the *_dl kernels; examples/scenes/spot_and_sun.pbrt is the file form of such a scene)
-        return scenes.cornell_box(lib, w, h, film=film, extra_lights=scenes.spot_and_distant(spot_from=(0.5, 1.7, 0.8), spot_to=(-0.2, 0.3, -0.2), sun_from=(0.3, 0.4, 3.0),
+        return scenes.cornell_box(lib, w, h, camera=camera, film=film, extra_lights=scenes.spot_and_distant(spot_from=(0.5, 1.7, 0.8), spot_to=(-0.2, 0.3, -0.2), sun_from=(0.3, 0.4, 3.0),
                                                                                              sun_to=(0.0, 0.8, 0.0)))
     if name == "textured":
-        return scenes.cornell_box(lib, w, h, textured=True, film=film)
+        return scenes.cornell_box(lib, w, h, camera=camera, textured=True, film=film)
     if name == "coated":
-        return scenes.cornell_box(lib, w, h, coated=True, film=film)
-    if name in ("checkerboard", "diffuse_transmission"):
+        return scenes.cornell_box(lib, w, h, camera=camera, coated=True, film=film)
+    if name in ("checkerboard", "diffuse_transmission", "cornell_probe"):
         # scene FILES through the C++ front end (their own film size; --filter is the file's): PBRT-v4's procedural textures (examples/scenes/checkerboard.pbrt); a back-lit
-        # sheet of PBRT-v4's diffuse transmission material in the Cornell box (examples/scenes/diffuse_transmission.pbrt: the extended *_dl kernels)
+        # sheet of PBRT-v4's diffuse transmission material in the Cornell box (examples/scenes/diffuse_transmission.pbrt: the extended *_dl kernels); PBRT-v4's
+        # spherical camera as an equal-area probe in the middle of the box (examples/scenes/cornell_probe.pbrt; the file's camera: --camera does not apply)
         import ctypes as C
         from types import SimpleNamespace
         out = C.POINTER(abi.ShmPbrtScene)()
@@ -43,19 +48,19 @@ def make_scene(lib, name, w, h, film=None):
         res = out.contents.desc.film.full_resolution
         return SimpleNamespace(desc=out.contents.desc, name=name + ".pbrt", res=(res[0], res[1]), keep=out)
     if name == "translucent":  # the same material through the Python builder: the sheet and the tall box of scenes.cornell_box
-        return scenes.cornell_box(lib, w, h, film=film, diffuse_transmission="sheet tall")
+        return scenes.cornell_box(lib, w, h, camera=camera, film=film, diffuse_transmission="sheet tall")
     if name in ("procedural", "procedural-general", "procedural-coated"):  # the same textures through the Python builder (scenes.procedural_cornell)
         return scenes.procedural_cornell(lib, w, h, which={"procedural": "checker", "procedural-general": "general", "procedural-coated": "coated"}[name], film=film)
     if name == "patches":
-        return scenes.cornell_box(lib, w, h, patches=True, film=film)
+        return scenes.cornell_box(lib, w, h, camera=camera, patches=True, film=film)
     if name == "instanced":
-        return scenes.instanced_scene(lib, w, h, film=film)
+        return scenes.instanced_scene(lib, w, h, camera=camera, film=film)
     if name == "environment":
-        return scenes.three_spheres(lib, w, h, camera=(0.75, 0.5, 9.0), environment=scenes.environment_image(64), film=film)
+        return scenes.three_spheres(lib, w, h, camera=dict(camera, pos=(0.75, 0.5, 9.0), look_at=(0.75, 0.5, 8.0)) if camera else (0.75, 0.5, 9.0), environment=scenes.environment_image(64), film=film)
     if name == "ganesha":
-        return scenes.ganesha_proxy(lib, w, h, film=film)
+        return scenes.ganesha_proxy(lib, w, h, camera=camera, film=film)
     if name == "crown":
-        return scenes.crown_proxy(lib, w, h, film=film)
+        return scenes.crown_proxy(lib, w, h, camera=camera, film=film)
     if name.startswith("fuzz:"):
         return scenes.random_scene(lib, int(name.split(":")[1]), w, h, film=film)
     raise SystemExit(f"unknown scene {name}")
@@ -86,6 +91,9 @@ def main():
     ap.add_argument("--sampler", default="independent", choices=["independent", "zsobol"], help="ShmRenderParams::sampler (DESIGN.md \"Sampler\")")
     ap.add_argument("--filter", default="box", choices=["box", "gaussian", "mitchell", "sinc", "triangle"],
                     help="the pixel filter, at PBRT-v4's default radius and parameters (DESIGN.md \"Pixel filters\")")
+    ap.add_argument("--camera", default="scene", choices=["scene", "spherical"], help="spherical: PBRT-v4's spherical camera where the scene's own camera stands "
+                                                                                    "(the generators' camera= argument; DESIGN.md section 4g)")
+    ap.add_argument("--mapping", default="equalarea", choices=["equalarea", "equirectangular"], help="with --camera spherical")
     ap.add_argument("--quirks-off", action="store_true",
                     help="ShmRenderParams::disable_reference_quirks: PBRT-v4's forms of the reference's deviations (emitter sampling, instancing, ...: DESIGN.md section 2) "
                          "instead of the reference-exact default")
@@ -95,7 +103,7 @@ def main():
     if lib.shm_device_count() < 1:
         raise SystemExit("no HIP device visible (there is no CPU fallback)")
     w, h = args.res, args.height or args.res
-    sc = make_scene(lib, args.scene, w, h, film=dict(filter=args.filter))
+    sc = make_scene(lib, args.scene, w, h, film=dict(filter=args.filter), camera=dict(type="spherical", mapping=args.mapping) if args.camera == "spherical" else None)
     w, h = getattr(sc, "res", (w, h))
     r = render.Renderer(lib, sc.desc, 0)
     p = render.make_params(seed=args.seed, spp=args.spp, max_depth=args.max_depth, integrator=args.integrator, reference_quirks=not args.quirks_off,

@@ -286,8 +286,15 @@ typedef struct ShmSpotLight {
 
 enum {
     SHM_CAMERA_PERSPECTIVE = 0,  /* camera.rs:866-1079 */
-    SHM_CAMERA_ORTHOGRAPHIC = 1  /* camera.rs:658-840: rays start at camera_from_raster(p_film) and run along +z; the reference
+    SHM_CAMERA_ORTHOGRAPHIC = 1, /* camera.rs:658-840: rays start at camera_from_raster(p_film) and run along +z; the reference
                                     has no depth of field for it yet ("TODO Adjust for depth-of-field here", :762) */
+    SHM_CAMERA_SPHERICAL = 2     /* PBRT-v4's SphericalCamera (the reference has none): every direction around the camera's origin, laid out by ShmCamera::mapping.
+                                    No lens. shm_camera_spherical builds it; shm_camera_create / ShmCameraParams know the two projective kinds only */
+};
+/* ShmCamera::mapping of a spherical camera (PBRT-v4's SphericalCamera::Mapping; `"string mapping"` in a scene file) */
+enum {
+    SHM_SPHERICAL_EQUAL_AREA = 0,      /* "equalarea", PBRT-v4's default: the equal-area octahedral square, the layout of an ImageInfinitelight's map */
+    SHM_SPHERICAL_EQUIRECTANGULAR = 1  /* "equirectangular": theta = pi v down the film, phi = 2 pi u across it */
 };
 /* ---- image textures (ABI v6) ------------------------------------------------------------------ */
 
@@ -345,7 +352,10 @@ typedef struct ShmImageInfiniteLight {
     uint32_t pad;
 } ShmImageInfiniteLight;
 
-/* PerspectiveCamera / OrthographicCamera after construction (ProjectiveCameraBase, camera.rs:594-642). Matrices row-major. */
+/* PerspectiveCamera / OrthographicCamera after construction (ProjectiveCameraBase, camera.rs:594-642), or PBRT-v4's SphericalCamera. Matrices row-major.
+ * SHM_CAMERA_SPHERICAL: camera_from_raster is diag(1 / W, 1 / H, 1, 1) of the film's full resolution, so that it takes a film point to (u, v, 0). (PBRT-v4 divides
+ * by the resolution; this multiplies by the rounded reciprocal: the same for power-of-two resolutions, within one ulp of uv otherwise.) dx_camera, dy_camera,
+ * lens_radius and focal_distance are zero and not read. */
 typedef struct ShmCamera {
     float camera_from_raster[16];
     float render_from_camera[16];
@@ -355,10 +365,10 @@ typedef struct ShmCamera {
     float focal_distance;
     float shutter_open, shutter_close;
     uint32_t kind;                /* SHM_CAMERA_* (ABI v4) */
-    uint32_t pad;
+    uint32_t mapping;             /* SHM_SPHERICAL_*: read only for SHM_CAMERA_SPHERICAL (the former pad word: 0 in every projective camera) */
     /* ABI v6, read only by scenes with image textures (the ray-differential fallback Camera::approximate_dp_dxy, camera.rs:307-354):
      * the inverse matrix of render_from_camera and the four vectors CameraBase::find_minimum_differentials leaves (camera.rs:356-440).
-     * shm_camera_perspective / shm_camera_orthographic fill them. */
+     * shm_camera_perspective / shm_camera_orthographic / shm_camera_spherical fill them. */
     float camera_from_render[16];
     float min_pos_differential_x[3], min_pos_differential_y[3];
     float min_dir_differential_x[3], min_dir_differential_y[3];
@@ -680,6 +690,11 @@ typedef struct ShmCameraParams {
     float screen_window[4];       /* "screenwindow" as the file gives it: x0 x1 y0 y1 */
 } ShmCameraParams;
 SHM_API int shm_camera_create(const ShmCameraParams* params, ShmCamera* out, float render_from_world_out[16]);
+/* PBRT-v4's SphericalCamera for a world_from_camera matrix: `mapping` is SHM_SPHERICAL_*, `render_space` SHM_RENDER_SPACE_* (the same CameraTransform as above). Fills
+ * camera_from_raster as described at ShmCamera, camera_from_render and the four minimum differentials (the same 512-sample loop, over this camera's rays).
+ * SHM_ERR_INVALID_ARGUMENT for a mapping above 1, a resolution below 1 or a render space above 2. */
+SHM_API int shm_camera_spherical(const float world_from_camera[16], uint32_t mapping, const int32_t full_resolution[2], uint32_t render_space, ShmCamera* out,
+                                 float render_from_world_out[16]);
 /* C entry to the C++ host mirror of the reference's integrator interface (shimmer_amd/csrc/host/integrator.hpp):
  * create_integrator(name, {maxdepth, regularize, lightsampler "uniform", spp}, scene)->render(options), integrator.rs:16-42,
  * 52-54, 120-210, 226-322. `name`: "path", "simplepath" (sample_lights / sample_bsdf are its "samplelights" / "samplebsdf") or

@@ -35,7 +35,9 @@ SHM_FLOATTEX_CHECKERBOARD, SHM_FLOATTEX_DOTS, SHM_FLOATTEX_FBM, SHM_FLOATTEX_WRI
 SHM_FLOATTEX_WEIGHT_FORM = 0xffffffff  # a == b == this: a CHECKERBOARD / DOTS node that yields its weight (tex1 = 0, tex2 = 1 folded)
 (SHM_FLOATSLOT_DISPLACEMENT, SHM_FLOATSLOT_U_ROUGHNESS, SHM_FLOATSLOT_V_ROUGHNESS, SHM_FLOATSLOT_U2_ROUGHNESS,
  SHM_FLOATSLOT_V2_ROUGHNESS, SHM_FLOATSLOT_THICKNESS, SHM_FLOATSLOT_G, SHM_FLOATSLOT_MIX_AMOUNT) = range(8)
-SHM_CAMERA_PERSPECTIVE, SHM_CAMERA_ORTHOGRAPHIC = 0, 1
+SHM_CAMERA_PERSPECTIVE, SHM_CAMERA_ORTHOGRAPHIC, SHM_CAMERA_SPHERICAL = 0, 1, 2
+SHM_SPHERICAL_EQUAL_AREA, SHM_SPHERICAL_EQUIRECTANGULAR = 0, 1  # ShmCamera.mapping (read only for SHM_CAMERA_SPHERICAL)
+SHM_RENDER_SPACE_CAMERA_WORLD, SHM_RENDER_SPACE_CAMERA, SHM_RENDER_SPACE_WORLD = 0, 1, 2
 SHM_INTEGRATOR_PATH, SHM_INTEGRATOR_SIMPLE_PATH, SHM_INTEGRATOR_RANDOM_WALK = 0, 1, 2
 SHM_SAMPLER_INDEPENDENT, SHM_SAMPLER_ZSOBOL = 0, 1
 SHM_SAMPLER_FASTOWEN, SHM_SAMPLER_RANDOMIZE_NONE = 0, 1
@@ -109,7 +111,7 @@ class ShmLight(C.Structure):
 class ShmCamera(C.Structure):
     _fields_ = [("camera_from_raster", C.c_float * 16), ("render_from_camera", C.c_float * 16), ("dx_camera", C.c_float * 3),
                 ("dy_camera", C.c_float * 3), ("lens_radius", C.c_float), ("focal_distance", C.c_float),
-                ("shutter_open", C.c_float), ("shutter_close", C.c_float), ("kind", C.c_uint32), ("pad", C.c_uint32),
+                ("shutter_open", C.c_float), ("shutter_close", C.c_float), ("kind", C.c_uint32), ("mapping", C.c_uint32),
                 ("camera_from_render", C.c_float * 16), ("min_pos_differential_x", C.c_float * 3),
                 ("min_pos_differential_y", C.c_float * 3), ("min_dir_differential_x", C.c_float * 3),
                 ("min_dir_differential_y", C.c_float * 3)]
@@ -285,6 +287,7 @@ EXPORTS = {
     "shm_image_load_png": (C.c_int, [C.c_char_p, C.c_char_p, C.c_uint32, C.c_int, C.POINTER(ShmLoadedImage)]),
     "shm_image_free": (None, [C.POINTER(ShmLoadedImage)]),
     "shm_camera_create": (C.c_int, [C.POINTER(ShmCameraParams), C.POINTER(ShmCamera), c_float_p]),
+    "shm_camera_spherical": (C.c_int, [c_float_p, C.c_uint32, C.POINTER(C.c_int32), C.c_uint32, C.POINTER(ShmCamera), c_float_p]),
     "shm_render_multi": (C.c_int, [C.POINTER(ShmSceneDesc), C.POINTER(C.c_int32), C.c_int32, C.POINTER(ShmRenderParams), C.c_void_p, C.POINTER(ShmStats)]),
 }
 

@@ -267,6 +267,8 @@ inline int flatten_scene(const ShmSceneDesc* d, FlatScene& out, std::string& err
     out.sensor_r.assign(d->film.sensor_r_bar, d->film.sensor_r_bar + 471);
     out.sensor_g.assign(d->film.sensor_g_bar, d->film.sensor_g_bar + 471);
     out.sensor_b.assign(d->film.sensor_b_bar, d->film.sensor_b_bar + 471);
+    if (d->camera.kind > SHM_CAMERA_SPHERICAL) { err = "unknown camera kind (perspective, orthographic, spherical)"; return SHM_ERR_INVALID_ARGUMENT; }
+    if (d->camera.kind == SHM_CAMERA_SPHERICAL && d->camera.mapping > SHM_SPHERICAL_EQUIRECTANGULAR) { err = "spherical camera: unknown mapping (equal-area, equirectangular)"; return SHM_ERR_INVALID_ARGUMENT; }
     out.camera = d->camera;
     out.film = d->film;
     out.film.sensor_r_bar = out.film.sensor_g_bar = out.film.sensor_b_bar = nullptr;

@@ -422,23 +422,58 @@ int shm_tile_bounds(const int32_t pb[4], int32_t tile_w, int32_t tile_h, ShmTile
     return SHM_OK;
 }
 
+// CameraBase::find_minimum_differentials (camera.rs:356-440; PBRT-v4's is the same loop) over the rays of `out`, whose matrices and kind are set: 512 samples along the
+// film diagonal, p_lens = (0.5, 0.5); fills the four vectors
+static void find_minimum_differentials(ShmCamera* out, const int32_t full_resolution[2]) {
+    using namespace shm;
+    const Float inf = infinity();
+    V3 min_pos_x = v3s(inf), min_pos_y = v3s(inf), min_dir_x = v3s(inf), min_dir_y = v3s(inf);
+    const int n = 512;
+    for (int i = 0; i < n; ++i) {
+        V2 p_film = v2((Float)i / (Float)(n - 1) * (Float)full_resolution[0], (Float)i / (Float)(n - 1) * (Float)full_resolution[1]);
+        AuxRays aux = aux_none();
+        Ray ray = camera_generate_ray_differential(*out, p_film, v2(0.5f, 0.5f), &aux);
+        V3 dox = xf_vector(out->camera_from_render, aux.rx_o - ray.o);
+        if (length(dox) < length(min_pos_x)) min_pos_x = dox;
+        V3 doy = xf_vector(out->camera_from_render, aux.ry_o - ray.o);
+        if (length(doy) < length(min_pos_y)) min_pos_y = doy;
+        ray.d = normalize(ray.d);
+        aux.rx_d = normalize(aux.rx_d);
+        aux.ry_d = normalize(aux.ry_d);
+        Frame f = frame_from_z(ray.d);
+        V3 df = f.to_local(ray.d);
+        V3 dxf = normalize(f.to_local(aux.rx_d));
+        V3 dyf = normalize(f.to_local(aux.ry_d));
+        if (length(dxf - df) < length(min_dir_x)) min_dir_x = dxf - df;
+        if (length(dyf - df) < length(min_dir_y)) min_dir_y = dyf - df;
+    }
+    const V3* src[4] = {&min_pos_x, &min_pos_y, &min_dir_x, &min_dir_y};
+    float* dst[4] = {out->min_pos_differential_x, out->min_pos_differential_y, out->min_dir_differential_x, out->min_dir_differential_y};
+    for (int k = 0; k < 4; ++k) { dst[k][0] = src[k]->x; dst[k][1] = src[k]->y; dst[k][2] = src[k]->z; }
+}
+
+// CameraTransform::new (camera.rs:507-523): CameraWorld (main.rs:66 default) keeps world axes and puts the camera at the origin, Camera renders in camera space,
+// World in world space
+static bool camera_transform(const float world_from_camera[16], uint32_t render_space, M4& render_from_camera, M4& render_from_world) {
+    M4 wfc;
+    for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) wfc.m[i][j] = world_from_camera[i * 4 + j];
+    double origin[3] = {0, 0, 0}, p_camera[3];
+    m4_point(wfc, origin, p_camera);
+    M4 world_from_render = render_space == SHM_RENDER_SPACE_CAMERA ? wfc
+                           : (render_space == SHM_RENDER_SPACE_WORLD ? m4_identity() : m4_translate(p_camera[0], p_camera[1], p_camera[2]));
+    if (!m4_inverse(world_from_render, render_from_world)) return false;
+    render_from_camera = m4_mul(render_from_world, wfc);
+    return true;
+}
+
 // ProjectiveCameraBase::new for either projection (camera.rs:594-642); fov_deg < 0 selects Transform::orthographic(0, 1)
 static int projective_camera(const float world_from_camera[16], float fov_deg, const int32_t full_resolution[2],
                              float lens_radius, float focal_distance, ShmCamera* out, float render_from_world_out[16],
                              uint32_t render_space = SHM_RENDER_SPACE_CAMERA_WORLD, float frame_aspect_ratio = 0.0f, const float* screen_window = nullptr) {
     if (!world_from_camera || !full_resolution || !out || full_resolution[0] <= 0 || full_resolution[1] <= 0 || render_space > SHM_RENDER_SPACE_WORLD)
         return SHM_ERR_INVALID_ARGUMENT;
-    M4 wfc;
-    for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) wfc.m[i][j] = world_from_camera[i * 4 + j];
-    // CameraTransform::new (camera.rs:507-523): CameraWorld (main.rs:66 default) keeps world axes and puts the camera at the origin, Camera
-    // renders in camera space, World in world space
-    double origin[3] = {0, 0, 0}, p_camera[3];
-    m4_point(wfc, origin, p_camera);
-    M4 world_from_render = render_space == SHM_RENDER_SPACE_CAMERA ? wfc
-                           : (render_space == SHM_RENDER_SPACE_WORLD ? m4_identity() : m4_translate(p_camera[0], p_camera[1], p_camera[2]));
-    M4 render_from_world;
-    if (!m4_inverse(world_from_render, render_from_world)) return SHM_ERR_INVALID_ARGUMENT;
-    M4 render_from_camera = m4_mul(render_from_world, wfc);
+    M4 render_from_camera, render_from_world;
+    if (!camera_transform(world_from_camera, render_space, render_from_camera, render_from_world)) return SHM_ERR_INVALID_ARGUMENT;
     // Transform::perspective(fov, 1e-2, 1000) (transform.rs:305-316)
     double n = 1e-2, f = 1000.0;
     M4 persp = m4_identity();
@@ -491,32 +526,7 @@ static int projective_camera(const float world_from_camera[16], float fov_deg, c
             out->min_pos_differential_y[i] = out->dy_camera[i];
         }
     } else {
-        // CameraBase::find_minimum_differentials, camera.rs:356-440: 512 samples along the film diagonal, p_lens = (0.5, 0.5)
-        using namespace shm;
-        const Float inf = infinity();
-        V3 min_pos_x = v3s(inf), min_pos_y = v3s(inf), min_dir_x = v3s(inf), min_dir_y = v3s(inf);
-        const int n = 512;
-        for (int i = 0; i < n; ++i) {
-            V2 p_film = v2((Float)i / (Float)(n - 1) * (Float)full_resolution[0], (Float)i / (Float)(n - 1) * (Float)full_resolution[1]);
-            AuxRays aux = aux_none();
-            Ray ray = camera_generate_ray_differential(*out, p_film, v2(0.5f, 0.5f), &aux);
-            V3 dox = xf_vector(out->camera_from_render, aux.rx_o - ray.o);
-            if (length(dox) < length(min_pos_x)) min_pos_x = dox;
-            V3 doy = xf_vector(out->camera_from_render, aux.ry_o - ray.o);
-            if (length(doy) < length(min_pos_y)) min_pos_y = doy;
-            ray.d = normalize(ray.d);
-            aux.rx_d = normalize(aux.rx_d);
-            aux.ry_d = normalize(aux.ry_d);
-            Frame f = frame_from_z(ray.d);
-            V3 df = f.to_local(ray.d);
-            V3 dxf = normalize(f.to_local(aux.rx_d));
-            V3 dyf = normalize(f.to_local(aux.ry_d));
-            if (length(dxf - df) < length(min_dir_x)) min_dir_x = dxf - df;
-            if (length(dyf - df) < length(min_dir_y)) min_dir_y = dyf - df;
-        }
-        const V3* src[4] = {&min_pos_x, &min_pos_y, &min_dir_x, &min_dir_y};
-        float* dst[4] = {out->min_pos_differential_x, out->min_pos_differential_y, out->min_dir_differential_x, out->min_dir_differential_y};
-        for (int k = 0; k < 4; ++k) { dst[k][0] = src[k]->x; dst[k][1] = src[k]->y; dst[k][2] = src[k]->z; }
+        find_minimum_differentials(out, full_resolution);
     }
     if (render_from_world_out) m4_to_f32(render_from_world, render_from_world_out);
     return SHM_OK;
@@ -530,6 +540,29 @@ int shm_camera_perspective(const float world_from_camera[16], float fov_deg, con
 int shm_camera_orthographic(const float world_from_camera[16], const int32_t full_resolution[2], float lens_radius,
                             float focal_distance, ShmCamera* out, float render_from_world_out[16]) {
     return projective_camera(world_from_camera, -1.0f, full_resolution, lens_radius, focal_distance, out, render_from_world_out);
+}
+
+// PBRT-v4's SphericalCamera: the same CameraTransform; camera_from_raster takes a film point to (u, v, 0) (multiplying by the rounded reciprocal of the resolution where
+// PBRT-v4 divides by it: include/shimmer_hip.h, ShmCamera); no lens, no screen window
+int shm_camera_spherical(const float world_from_camera[16], uint32_t mapping, const int32_t full_resolution[2], uint32_t render_space, ShmCamera* out,
+                         float render_from_world_out[16]) {
+    if (!world_from_camera || !full_resolution || !out || full_resolution[0] < 1 || full_resolution[1] < 1 || mapping > SHM_SPHERICAL_EQUIRECTANGULAR ||
+        render_space > SHM_RENDER_SPACE_WORLD)
+        return SHM_ERR_INVALID_ARGUMENT;
+    M4 render_from_camera, render_from_world, camera_from_render;
+    if (!camera_transform(world_from_camera, render_space, render_from_camera, render_from_world) || !m4_inverse(render_from_camera, camera_from_render))
+        return SHM_ERR_INVALID_ARGUMENT;
+    memset(out, 0, sizeof(*out));  // (dx_camera, dy_camera, lens_radius, focal_distance: zero and not read)
+    m4_to_f32(m4_scale(1.0 / (double)full_resolution[0], 1.0 / (double)full_resolution[1], 1.0), out->camera_from_raster);
+    m4_to_f32(render_from_camera, out->render_from_camera);
+    m4_to_f32(camera_from_render, out->camera_from_render);
+    out->shutter_open = 0.0f;
+    out->shutter_close = 1.0f;
+    out->kind = SHM_CAMERA_SPHERICAL;
+    out->mapping = mapping;
+    find_minimum_differentials(out, full_resolution);
+    if (render_from_world_out) m4_to_f32(render_from_world, render_from_world_out);
+    return SHM_OK;
 }
 
 int shm_camera_create(const ShmCameraParams* p, ShmCamera* out, float render_from_world_out[16]) {

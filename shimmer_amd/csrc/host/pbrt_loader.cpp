@@ -8,7 +8,7 @@
 //   material.rs:56-110, 259-285, 353-420, 539-575, 688-720, 820-900, 1055-1170, 1297-1310      Material::create and the per-material defaults
 //   camera.rs:676-705, 850-890, film.rs:225-330, 482-495, 767-800, sampler.rs:95-99, integrator.rs:16-75
 // Scope: the directives the repository's scenes need — LookAt Translate Scale Rotate Identity Transform ConcatTransform CoordinateSystem
-// CoordSysTransform ReverseOrientation Camera (perspective / orthographic) Film (rgb) Sampler PixelFilter (box gaussian mitchell sinc triangle) Integrator Option
+// CoordSysTransform ReverseOrientation Camera (perspective / orthographic / spherical) Film (rgb) Sampler PixelFilter (box gaussian mitchell sinc triangle) Integrator Option
 // WorldBegin AttributeBegin/End Attribute (per-target default parameters) Material MakeNamedMaterial NamedMaterial Texture (float / spectrum: constant scale mix
 // directionmix imagemap) AreaLightSource (diffuse) LightSource (point, infinite: uniform or an environment image) Shape (trianglemesh
 // bilinearmesh sphere plymesh) ObjectBegin/End ObjectInstance Include; spectra as "spectrum" samples / named tables / files, "blackbody",
@@ -1095,20 +1095,32 @@ private:
         float wfc[16], rfw[16];
         memcpy(wfc, world_from_camera.m.m, sizeof(wfc));
         const float lens = camera_params_.one_float("lensradius", 0.0f), focal = camera_params_.one_float("focaldistance", 1e6f);
-        if (camera_type_ != "perspective" && camera_type_ != "orthographic")
-            fail(tk.where(line) + ": camera \"" + camera_type_ + "\" is not supported (perspective, orthographic)", SHM_ERR_UNSUPPORTED);
-        ShmCameraParams cp;
-        memset(&cp, 0, sizeof(cp));
-        cp.kind = camera_type_ == "perspective" ? SHM_CAMERA_PERSPECTIVE : SHM_CAMERA_ORTHOGRAPHIC;
-        cp.render_space = settings_.render_space;
-        memcpy(cp.world_from_camera, wfc, sizeof(wfc));
-        cp.fov_deg = camera_params_.one_float("fov", 90.0f);
-        cp.full_resolution[0] = xres; cp.full_resolution[1] = yres;
-        cp.lens_radius = lens; cp.focal_distance = focal;
-        cp.frame_aspect_ratio = camera_params_.one_float("frameaspectratio", 0.0f);
-        const std::vector<float> sw = camera_params_.floats("screenwindow");
-        if (sw.size() == 4) { cp.has_screen_window = 1; memcpy(cp.screen_window, sw.data(), 16); }  // (any other count: the reference warns and ignores it)
-        if (shm_camera_create(&cp, &a_->camera, rfw) != SHM_OK) fail(tk.where(line) + ": camera construction failed (fov, screen window or transform)");
+        if (camera_type_ != "perspective" && camera_type_ != "orthographic" && camera_type_ != "spherical")
+            fail(tk.where(line) + ": camera \"" + camera_type_ + "\" is not supported (perspective, orthographic, spherical)", SHM_ERR_UNSUPPORTED);
+        if (camera_type_ == "spherical") {
+            // PBRT-v4's SphericalCamera::Create: "mapping" is all it reads of its own; lensradius, focaldistance, screenwindow, frameaspectratio (CameraBaseParameters)
+            // and fov are accepted and not used
+            const std::string mapping = camera_params_.one_string("mapping", "equalarea");
+            const Param* mp = camera_params_.find("mapping");
+            if (mapping != "equalarea" && mapping != "equirectangular")
+                fail(tk.where(mp ? mp->line : line) + ": " + mapping + ": unknown mapping for spherical camera (equalarea, equirectangular)", SHM_ERR_INVALID_ARGUMENT);
+            const int32_t res[2] = {xres, yres};
+            if (shm_camera_spherical(wfc, mapping == "equalarea" ? SHM_SPHERICAL_EQUAL_AREA : SHM_SPHERICAL_EQUIRECTANGULAR, res, settings_.render_space, &a_->camera, rfw) != SHM_OK)
+                fail(tk.where(line) + ": camera construction failed (transform)");
+        } else {
+            ShmCameraParams cp;
+            memset(&cp, 0, sizeof(cp));
+            cp.kind = camera_type_ == "perspective" ? SHM_CAMERA_PERSPECTIVE : SHM_CAMERA_ORTHOGRAPHIC;
+            cp.render_space = settings_.render_space;
+            memcpy(cp.world_from_camera, wfc, sizeof(wfc));
+            cp.fov_deg = camera_params_.one_float("fov", 90.0f);
+            cp.full_resolution[0] = xres; cp.full_resolution[1] = yres;
+            cp.lens_radius = lens; cp.focal_distance = focal;
+            cp.frame_aspect_ratio = camera_params_.one_float("frameaspectratio", 0.0f);
+            const std::vector<float> sw = camera_params_.floats("screenwindow");
+            if (sw.size() == 4) { cp.has_screen_window = 1; memcpy(cp.screen_window, sw.data(), 16); }  // (any other count: the reference warns and ignores it)
+            if (shm_camera_create(&cp, &a_->camera, rfw) != SHM_OK) fail(tk.where(line) + ": camera construction failed (fov, screen window or transform)");
+        }
         a_->camera.shutter_open = shutter_open;
         a_->camera.shutter_close = shutter_close;
         a_->have_camera = true;

@@ -33,6 +33,7 @@ struct SceneFacts {
     bool patch_heavy = false, has_quadric_patch = false;    // spheres / bilinear patches: a twelfth of the primitive records or more / any
     bool small_tree = false, has_prims = false;             // fewer than 4096 BVH nodes / any primitive record
     uint32_t filter = SHM_FILTER_BOX;
+    bool spherical_camera = false;  // PBRT-v4's spherical camera: K1 is k_generate_spherical.hip's; nothing else depends on it
 };
 inline SceneFacts scene_facts(const shm_host::FlatScene& f) {
     SceneFacts s;
@@ -49,6 +50,7 @@ inline SceneFacts scene_facts(const shm_host::FlatScene& f) {
     s.small_tree = f.nodes.size() < 4096;
     s.has_prims = !f.prim_recs.empty();
     s.filter = f.film.filter;
+    s.spherical_camera = f.camera.kind == SHM_CAMERA_SPHERICAL;
     return s;
 }
 
@@ -160,6 +162,7 @@ struct RenderPlan {
     // table coordinates
     int geo = GEO_TRI, img = IMG_NONE, img_lean = IMG_NONE, img_generate = IMG_NONE, flt = FLT_BOX;
     bool zs = false, dl = false;
+    bool spherical = false;        // the generate kernels of k_generate_spherical.hip, in the same cells (HAS_TEX x LEAN x sampler x filter class)
     bool film_per_sample = false;  // k_film_weighted reads the per-path weights k_generate_filtered left
     // overlap policy
     uint64_t overlap_paths = 0;       // a batch below this many paths runs K3(b) beside K2(b+1) and the class scatter kernels beside each other ...
@@ -206,6 +209,8 @@ inline RenderPlan render_plan(const ScenePlan& s, const ShmRenderParams& o) {
     // (the *_dl builds for a scene with a distant or spot light or a diffuse transmission material, in every class: a kernel built without them would sample the lights as
     //  area lights and shade the material as a CoatedConductor. This is the only place the set is chosen.)
     p.dl = f.extended;
+    // (the generate kernels that know PBRT-v4's spherical camera, for a scene whose camera is one and for no other: every other kernel would read it as a perspective camera)
+    p.spherical = f.spherical_camera;
     // the pixel filter: box — and every filter under options.disable_pixel_jitter, where the film point is the pixel centre and the weight 1 whatever was drawn — runs
     // k_generate and k_film; the others their own K1 / K6 pair
     if (f.filter != SHM_FILTER_BOX && o.disable_pixel_jitter == 0)
@@ -225,6 +230,7 @@ inline RenderPlan render_plan(const ScenePlan& s, const ShmRenderParams& o) {
 // What must hold of a plan before its first launch: the extended set for exactly the scenes that need it, and no coordinate on a null cell of the table.
 inline const char* render_plan_error(const ScenePlan& s, const RenderPlan& p) {
     if (p.dl != s.f.extended) return "internal: the kernel set does not match the scene's delta lights / materials";
+    if (p.spherical != s.f.spherical_camera) return "internal: the generate kernels do not match the scene's camera";
     if ((p.route == ROUTE_LEAN || p.drain_lean) && !HAS_LEAN_KERNELS[p.img_lean]) return "internal: the plan calls a lean kernel of a textured class";
     if (p.lean_first && !HAS_LEAN_KERNELS[p.img_generate]) return "internal: the plan calls k_generate<HAS_TEX, LEAN>";
     return nullptr;

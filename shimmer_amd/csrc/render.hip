@@ -39,117 +39,8 @@ __global__ void k_expand_tiles(const ShmTile* tiles, const uint32_t* tile_offset
         for (int y = tl.y0; y < tl.y1; ++y) pixels[k++] = (uint32_t)x | ((uint32_t)y << 16);
 }
 
-// ---------------------------------------------------------------------------------------------
-// K1: camera rays for one batch. Path slots are ordered [pixel group][sample][pixel in group] with groups of `pix_group`
-// consecutive pixels of the tile-ordered pixel list (pix_group >= n_pix is the plain sample-major order
-// slot = s_local * n_pix + p_local; pix_group = 64 keeps all samples of one 8x8 tile adjacent in the queues, so that a
-// wave's private queue range, and an XCD's queue partition, is a compact image region).
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t slot_of(uint32_t p_local, uint32_t s_local, uint32_t n_pix, uint32_t n_samples, uint32_t pix_group) {
-    uint32_t g = p_local / pix_group;
-    uint32_t g0 = g * pix_group;
-    uint32_t pg = min(pix_group, n_pix - g0);
-    return g0 * n_samples + s_local * pg + (p_local - g0);
-}
-
-// HAS_TEX: scenes that bind image textures carry the camera ray's auxiliary rays (a compile-time switch: with a run-time pointer the
-// auxiliary-ray record lived in scratch memory, 52 B of stores per path, in every scene)
-// FC: the pixel filter's class (shm/filter.h). filter_table: the tabulated class's table (the block's copy in LDS); filter_weight: where a filter whose weight differs
-// from sample to sample (Mitchell, sinc) leaves it for k_film_weighted, null otherwise.
-template <bool HAS_TEX, bool LEAN, bool ZS, int FC>
-__device__ __forceinline__ void generate_paths(const SceneView& sv, const PathArrays& pa, const uint32_t* pixels, uint32_t n_pix, int sample_begin, int n_samples,
-                                               const ShmRenderParams& params, uint32_t* q_active, QueueState* qs, uint32_t pix_group, const Float* filter_table,
-                                               float* filter_weight) {
-    uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
-    uint32_t total = n_pix * (uint32_t)n_samples;
-    if (slot >= total) return;
-    uint32_t g = slot / (pix_group * (uint32_t)n_samples);
-    uint32_t g0 = g * pix_group;
-    uint32_t pg = min(pix_group, n_pix - g0);
-    uint32_t rem = slot - g0 * (uint32_t)n_samples;
-    uint32_t s_local = rem / pg;
-    uint32_t p_local = g0 + (rem - s_local * pg);
-    uint32_t pix = pixels[p_local];
-    int px = (int)(pix & 0xffffu), py = (int)(pix >> 16);
-    Rng rng = sampler_start_pixel_sample(px, py, sample_begin + (int)s_local, params.seed, sampler_word<ZS>(sv));
-    Wavelengths lambda;
-    Float weight;
-    constexpr bool has_tex = HAS_TEX;
-    AuxRays aux = aux_none();
-    Ray r = generate_camera_ray<FC>(sv, px, py, rng, params.disable_wavelength_jitter != 0, params.disable_pixel_jitter != 0,
-                                    lambda, weight, HAS_TEX ? &aux : nullptr, params.samples_per_pixel, filter_table);
-    if (HAS_TEX) st_aux(pa, slot, aux);
-    if (FC == FILTER_CLASS_TABULATED && filter_weight) filter_weight[slot] = weight;
-    ShmRay ray;
-    ray.o[0] = r.o.x; ray.o[1] = r.o.y; ray.o[2] = r.o.z;
-    ray.d[0] = r.d.x; ray.d[1] = r.d.y; ray.d[2] = r.d.z;
-    ray.t_max = infinity();
-    ray.pad = 0.0f;
-    pa.ray[slot] = ray;
-    pa.L[slot] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    // LEAN (the fused kernel shades bounce 0 and knows it is bounce 0): the constants — beta = 1, p_b = eta_scale = 1, flags = 0, the identity queue — are not
-    // written here nor read there (ShadeArgs::first_bounce): 32 of 124 bytes per path
-    const float4 lambda4 = make_float4(lambda.lambda[0], lambda.lambda[1], lambda.lambda[2], lambda.lambda[3]);
-    pa.lambda[slot] = lambda4;  // (the film's copy: k_film reads wavelengths and pdfs of every sample, and a 64-byte record for 16 of its bytes would triple that)
-    pa.lambda_pdf[slot] = make_float4(lambda.pdf[0], lambda.pdf[1], lambda.pdf[2], lambda.pdf[3]);
-    // (the CtxRec, the previous vertex's LightSampleContext, is first read at depth >= 1, after k_shade has written them)
-    if (LEAN) {
-        // no record: the fused kernel's bounce 0 reads these three arrays and writes the path's first record whole (one full 64-byte store instead of this kernel's
-        // partial sectors: k_generate 10.5 -> 6 ms per headline frame)
-        pa.rng0[slot] = sampler_store(rng);
-        pa.pixel0[slot] = pix;
-    } else {
-        PathRec r;
-        r.lambda = lambda4;
-        r.rng = sampler_store(rng);
-        r.pixel = pix;
-        r.flags = has_tex ? (1u << 10) : 0u;  // camera rays always carry auxiliary rays (camera.rs:1070-1078)
-        r.beta = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
-        r.pb_eta = make_float2(1.0f, 1.0f);
-        r.pad[0] = 0u; r.pad[1] = 0u;
-        pa.rec[slot] = r;
-    }
-    if (!LEAN) q_active[slot] = slot;  // first bounce: identity queue
-    if (slot == 0) {
-        qs->n_active[0] = total;
-        qs->n_active[1] = 0;
-        qs->n_shadow[0] = 0;
-        qs->n_shadow[1] = 0;
-        qs->n_scatter[0] = qs->n_scatter[1] = qs->n_scatter[2] = qs->n_scatter[3] = 0;
-        qs->n_emit = 0;
-        qs->n_lean = 0;
-        qs->n_split = 0;
-    }
-}
-// The box filter's kernel (the reference's filter; the headline path)
-template <bool HAS_TEX, bool LEAN = false, bool ZS = false>  // ZS: the ZSobol sampler (wavefront.h, K_ZSOBOL)
-__global__ void __launch_bounds__(SHADE_BLOCK) k_generate(SceneView sv, PathArrays pa, const uint32_t* pixels, uint32_t n_pix,
-                                                        int sample_begin, int n_samples, ShmRenderParams params,
-                                                        uint32_t* q_active, QueueState* qs, uint32_t pix_group) {
-    generate_paths<HAS_TEX, LEAN, ZS, FILTER_CLASS_BOX>(sv, pa, pixels, n_pix, sample_begin, n_samples, params, q_active, qs, pix_group, nullptr, nullptr);
-}
-// The other pixel filters' kernels. The triangle filter is sampled in closed form. The tabulated class (gaussian, Mitchell, sinc) inverts two 1-D CDFs of up to 257 entries
-// per path by binary search, every lane at an index of its own: the block copies the table (at most 6.2 KB, 3.1 KB at PBRT-v4's widest default radius) into LDS once and
-// searches it there.
-template <bool HAS_TEX, bool LEAN, bool ZS, int FC>
-__global__ void __launch_bounds__(SHADE_BLOCK) k_generate_filtered(SceneView sv, PathArrays pa, const uint32_t* pixels, uint32_t n_pix,
-                                                                 int sample_begin, int n_samples, ShmRenderParams params,
-                                                                 uint32_t* q_active, QueueState* qs, uint32_t pix_group, float* filter_weight) {
-    static_assert(FC == FILTER_CLASS_TRIANGLE || FC == FILTER_CLASS_TABULATED, "the box filter runs k_generate");
-    if constexpr (FC == FILTER_CLASS_TABULATED) {
-        __shared__ uint4 s_table[(FILTER_TABLE_MAX_FLOATS + 3) / 4];
-        // (the table's length is in its head: flatten_scene bounds it by FILTER_TABLE_MAX_FLOATS and pads it to whole uint4s)
-        const uint32_t nx = float_to_bits(sv.dist_data[1]), ny = float_to_bits(sv.dist_data[2]);
-        const uint32_t n4 = min(((uint32_t)filter_table_floats((int)nx, (int)ny) + 3u) / 4u, (uint32_t)((FILTER_TABLE_MAX_FLOATS + 3) / 4));
-        const uint4* g = reinterpret_cast<const uint4*>(sv.dist_data);
-        for (uint32_t i = threadIdx.x; i < n4; i += blockDim.x) s_table[i] = g[i];
-        __syncthreads();
-        generate_paths<HAS_TEX, LEAN, ZS, FC>(sv, pa, pixels, n_pix, sample_begin, n_samples, params, q_active, qs, pix_group, reinterpret_cast<const Float*>(s_table),
-                                              filter_weight);
-    } else {
-        generate_paths<HAS_TEX, LEAN, ZS, FC>(sv, pa, pixels, n_pix, sample_begin, n_samples, params, q_active, qs, pix_group, nullptr, nullptr);
-    }
-}
+// K1 (k_generate.inl): generate_paths, k_generate and k_generate_filtered for the reference's two cameras — this unit is built without K_SPHERICAL_CAMERA (wavefront.h)
+#include "k_generate.inl"
 
 // Scene creation: the shading records of the flat triangles (shm/tri_shade.h), one thread per primitive slot. The record is what triangle_interaction + get_bsdf — the
 // code the shading kernels would run at every hit on the slot — leave behind; the slot's PrimRec::pad[1] says that it is there.
@@ -361,6 +252,14 @@ static ShadeKernels select_kernels(const RenderPlan& p) {
         k.film_weighted = fk.film;
     }
     if (p.layered_onepass) k.scatter[CLASS_LAYERED] = k.scatter_layered_onepass;
+    if (p.spherical) {  // PBRT-v4's spherical camera: the same cells of k_generate_spherical.hip; nothing after K1 knows the camera
+        const SphericalGenerateCells& sc = wf_generate_spherical(p.zs);
+        const int tex = p.img_generate == IMG_TEX ? 1 : 0;
+        for (int lean = 0; lean < 2; ++lean) {
+            k.generate[lean] = sc.generate[tex][lean];
+            k.generate_filtered[lean] = p.flt != FLT_BOX ? sc.generate_filtered[p.flt == FLT_TRIANGLE ? 0 : 1][tex][lean] : nullptr;
+        }
+    }
     return k;
 }
 // (the table's null cells are the ones host/render_plan.hpp exports as HAS_LEAN_KERNELS, which its validation and tests/test_render_plan.py go by. Behind select_kernels,

@@ -15,6 +15,7 @@
 //   (PBRT-v4 materials.h)         DiffuseTransmissionMaterial::GetBxDF: the reference has none (SHM_DIFFUSE_TRANSMISSION, bxdf.h)
 //   sampling.rs:347-371, filter.rs:99-105         get_camera_sample, BoxFilter::sample (the other pixel filters: filter.h)
 //   camera.rs:1003-1079, 769-792  {Perspective,Orthographic}Camera::generate_ray_differential
+//   (PBRT-v4 cameras.cpp, camera.h) SphericalCamera::GenerateRay, CameraBase::GenerateRayDifferential: the reference has no such camera (SHM_SPHERICAL_CAMERA, below)
 //   film.rs:548-574, 907-914      RgbFilm::add_sample, PixelSensor::to_sensor_rgb
 #pragma once
 #include "bxdf.h"
@@ -335,10 +336,61 @@ SHM_HD BSDF get_bsdf(const SceneView& sv, SurfaceInteraction& si, const ShmMater
     return bsdf_new(si.shading.n, si.shading.dpdu, b);
 }
 
+// SHM_SPHERICAL_CAMERA: compile PBRT-v4's SphericalCamera (SHM_CAMERA_SPHERICAL) into camera_generate_ray_differential. ON wherever nobody says otherwise (the oracle,
+// the host mirror, the leaf probe); the kernel units pass their K_SPHERICAL_CAMERA (wavefront.h), which only k_generate_spherical.hip sets: the generate kernels of a
+// scene with one of the reference's two cameras are those of a library without this one. A scene that holds one never reaches a kernel built with 0 (RenderPlan::spherical).
+#ifndef SHM_SPHERICAL_CAMERA
+#define SHM_SPHERICAL_CAMERA 1
+#endif
+
+// PBRT-v4's WrapEqualAreaSquare (util/math.h): a point outside the unit square mirrored back in, the way the octahedral map continues across its edges — a pixel filter
+// wider than the box puts film samples there at border pixels, and the auxiliary rays below step over the edge
+SHM_HD V2 wrap_equal_area_square(V2 uv) {
+    if (uv.x < 0.0f) { uv.x = -uv.x; uv.y = 1.0f - uv.y; }
+    else if (uv.x > 1.0f) { uv.x = 2.0f - uv.x; uv.y = 1.0f - uv.y; }
+    if (uv.y < 0.0f) { uv.x = 1.0f - uv.x; uv.y = -uv.y; }
+    else if (uv.y > 1.0f) { uv.x = 1.0f - uv.x; uv.y = 2.0f - uv.y; }
+    return uv;
+}
+// PBRT-v4's SphericalCamera::GenerateRay for a film point: the ray from the camera's origin, in render space. `uv0` is camera_from_raster(p_film) = (u, v, 0): the matrix
+// is diag(1 / W, 1 / H, 1, 1) for this camera (include/shimmer_hip.h, ShmCamera).
+// PBRT-v4's conventions, kept as they are (tests/test_spherical_camera.py pins them — they are not mistakes to repair): after the swap of y and z the centre of an
+// equal-area film looks along the camera's +y and the centre of an equirectangular film along its -x; row 0 of an equirectangular film is the camera's +y pole. The
+// equirectangular mapping is not wrapped: theta < 0 and phi > 2 pi, from film points outside the film, go through sin and cos as they are.
+SHM_HD Ray spherical_camera_ray(const ShmCamera& cam, V3 uv0) {
+    V3 dir;
+    if (cam.mapping == SHM_SPHERICAL_EQUIRECTANGULAR) {
+        Float theta = PI_F * uv0.y, phi = 2.0f * PI_F * uv0.x;
+        dir = spherical_direction(sin(theta), cos(theta), phi);
+    } else {
+        dir = equal_area_square_to_sphere<true>(wrap_equal_area_square(v2(uv0.x, uv0.y)));
+    }
+    Ray r;
+    r.o = v3s(0.0f);
+    r.d = v3(dir.x, dir.z, dir.y);  // swap(dir.y, dir.z)
+    return xf_ray(cam.render_from_camera, r);
+}
+
 // {Perspective,Orthographic}Camera::generate_ray_differential (camera.rs:1003-1079, 769-792) for one CameraSample; `aux`
 // (may be null) receives the auxiliary rays.
 SHM_HD Ray camera_generate_ray_differential(const ShmCamera& cam, V2 p_film, V2 p_lens, AuxRays* aux) {
     V3 p_camera = xf_point(cam.camera_from_raster, v3(p_film.x, p_film.y, 0.0f));
+    if (SHM_SPHERICAL_CAMERA && cam.kind == SHM_CAMERA_SPHERICAL) {  // no lens: p_lens is drawn and not used
+        Ray ray = spherical_camera_ray(cam, p_camera);
+        if (aux) {
+            // PBRT-v4's generic CameraBase::GenerateRayDifferential (this camera has no closed form): the ray once more 0.05 pixels along x and along y, and the
+            // finite difference scaled up to one pixel. Both in render space.
+            const Float eps = 0.05f;
+            Ray rx = spherical_camera_ray(cam, xf_point(cam.camera_from_raster, v3(p_film.x + eps, p_film.y, 0.0f)));
+            Ray ry = spherical_camera_ray(cam, xf_point(cam.camera_from_raster, v3(p_film.x, p_film.y + eps, 0.0f)));
+            aux->has = true;
+            aux->rx_o = ray.o + (rx.o - ray.o) / eps;
+            aux->rx_d = ray.d + (rx.d - ray.d) / eps;
+            aux->ry_o = ray.o + (ry.o - ray.o) / eps;
+            aux->ry_d = ray.d + (ry.d - ray.d) / eps;
+        }
+        return ray;
+    }
     Ray base;
     if (cam.kind == SHM_CAMERA_ORTHOGRAPHIC) {
         // camera.rs:769-792 returns this ray in CAMERA space: unlike generate_ray (:747-767) it never applies render_from_camera.

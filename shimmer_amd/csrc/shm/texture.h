@@ -808,13 +808,16 @@ SHM_HD Float poly7_estrin(Float x, const Float c[7]) {
     return fma(hi, x4, lo);
 }
 // math.rs:456-485. Kept as written: phi = (vp - up / r + 1) pi / 4 (PBRT-v4 has (vp - up) / r + 1).
+// AS_PBRT_V4: PBRT-v4's grouping instead, the inverse of equal_area_sphere_to_square below — for what the reference does not have and PBRT-v4 defines (the spherical
+// camera, path.h). Everything the reference has keeps the default.
+template <bool AS_PBRT_V4 = false>
 SHM_HD V3 equal_area_square_to_sphere(V2 p) {
     Float u = 2.0f * p.x - 1.0f, v = 2.0f * p.y - 1.0f;
     Float up = abs(u), vp = abs(v);
     Float signed_distance = 1.0f - (up + vp);
     Float d = abs(signed_distance);
     Float r = 1.0f - d;
-    Float phi = ((r == 0.0f) ? 1.0f : (vp - up / r + 1.0f)) * PI_F / 4.0f;
+    Float phi = ((r == 0.0f) ? 1.0f : (AS_PBRT_V4 ? (vp - up) / r + 1.0f : vp - up / r + 1.0f)) * PI_F / 4.0f;
     Float z = copysign(1.0f - sqr(r), signed_distance);
     Float cos_phi = copysign(cos(phi), u), sin_phi = copysign(sin(phi), v);
     return v3(cos_phi * r * safe_sqrt(2.0f - sqr(r)), sin_phi * r * safe_sqrt(2.0f - sqr(r)), z);

@@ -28,6 +28,12 @@
 // which k_vertex_*.hip gets for it too (get_bsdf and the class of kind 8; it draws nothing, so no *_zs_dl) — and RenderPlan::dl names that set for a scene that holds the
 // material (FlatScene::has_diffuse_transmission), as it does for one that holds a distant or spot light.
 #define SHM_DIFFUSE_TRANSMISSION K_DELTA_LIGHTS
+// K_SPHERICAL_CAMERA (a translation unit's switch): PBRT-v4's spherical camera is compiled into camera_generate_ray_differential (shm/path.h, SHM_SPHERICAL_CAMERA) only
+// where it is true, and only k_generate_spherical.hip — k_generate.inl a second time — sets it: RenderPlan::spherical names its kernels for a scene whose camera is one.
+#ifndef K_SPHERICAL_CAMERA
+#define K_SPHERICAL_CAMERA false
+#endif
+#define SHM_SPHERICAL_CAMERA K_SPHERICAL_CAMERA
 #include "shm/path.h"
 #include "shm/tri_shade.h"
 #define WF_CAT_(a, b) a##b
@@ -477,6 +483,12 @@ using GenerateKernel = void (*)(SceneView, PathArrays, const uint32_t*, uint32_t
 // K1 / K6 of the pixel filters beside the box filter (render.hip, k_generate_filtered<HAS_TEX, LEAN, ZS, FC>, k_film_weighted<W>): + the per-path filter weights (+ the constant K)
 using FilteredGenerateKernel = void (*)(SceneView, PathArrays, const uint32_t*, uint32_t, int, int, ShmRenderParams, uint32_t*, QueueState*, uint32_t, float*);
 using WeightedFilmKernel = void (*)(SceneView, PathArrays, const uint32_t*, uint32_t, int, ShmFilmPixel*, DeviceCounters*, uint32_t, const float*, float);
+// K1 of a scene whose camera is PBRT-v4's spherical one (k_generate_spherical.hip): render.hip's generate cells once more, per sampler
+struct SphericalGenerateCells {
+    GenerateKernel generate[2][2];                  // [HAS_TEX][LEAN]
+    FilteredGenerateKernel generate_filtered[2][2][2];  // [filter class: triangle, tabulated][HAS_TEX][LEAN]
+};
+WF_INTERNAL const SphericalGenerateCells& wf_generate_spherical(bool zs);
 // The kernels of one scene class: a cell of render.hip's table by geometry x image class x sampler (nullptr: no such build,
 // shm_plan::HAS_LEAN_KERNELS), of which select_kernels makes a render's set by the RenderPlan's coordinates. The plan says which of them run; the bounce loop calls them.
 struct ShadeKernels {

@@ -763,6 +763,23 @@ class SceneBuilder:
         self.camera = cam
         return rfw.reshape(4, 4)
 
+    SPHERICAL_MAPPINGS = {"equalarea": abi.SHM_SPHERICAL_EQUAL_AREA, "equirectangular": abi.SHM_SPHERICAL_EQUIRECTANGULAR}
+
+    def set_camera_spherical(self, lib, pos, look_at, up, mapping="equalarea"):
+        """PBRT-v4's SphericalCamera at `pos`, its frame from Transform::look_at as above (shm_look_at -> shm_camera_spherical). `mapping`: equalarea (the layout of
+        an ImageInfinitelight's map: a square film is an environment map) | equirectangular. Returns render_from_world like set_camera_look_at."""
+        if mapping not in self.SPHERICAL_MAPPINGS:
+            raise ValueError(f"unknown mapping for spherical camera {mapping!r} ({', '.join(self.SPHERICAL_MAPPINGS)})")
+        wfc32 = np.zeros(16, np.float32)
+        abi.check(lib, lib.shm_look_at(_fptr(_as_f32(pos)), _fptr(_as_f32(look_at)), _fptr(_as_f32(up)), _fptr(wfc32)), "shm_look_at")
+        cam = abi.ShmCamera()
+        rfw = np.zeros(16, np.float32)
+        res = (C.c_int32 * 2)(*self.film.full_resolution)
+        abi.check(lib, lib.shm_camera_spherical(_fptr(wfc32), self.SPHERICAL_MAPPINGS[mapping], res, abi.SHM_RENDER_SPACE_CAMERA_WORLD, C.byref(cam), _fptr(rfw)),
+                  "shm_camera_spherical")
+        self.camera = cam
+        return rfw.reshape(4, 4)
+
     # ---- finalize ----
     # ---- object instancing (loading/scene.rs:814-866; TransformedPrimitive, primitive.rs:136-176) ----
     def begin_object(self, name):

@@ -67,6 +67,22 @@ def _finish(b, lib, extra_lights=None, rfw=None, **extra):
     return SimpleNamespace(desc=desc, builder=b, info=info, **extra)
 
 
+def _set_camera(b, lib, camera, pos, look_at, up, fov):
+    """The generators' optional `camera=` argument REPLACES the scene's own camera (given here as pos, look_at, up, fov); absent, the description is byte for byte
+    what the generator always produced. A dict: "type" — "spherical" (PBRT-v4's SphericalCamera, with "mapping": "equalarea" | "equirectangular"), "perspective" or
+    "orthographic" —, and optionally "pos", "look_at", "up" (world space; default: the scene's own), "fov", "lens_radius", "focal_distance" (the projective two)."""
+    if camera is None:
+        return b.set_camera_look_at(lib, pos, look_at, up, fov)
+    unknown = set(camera) - {"type", "pos", "look_at", "up", "mapping", "fov", "lens_radius", "focal_distance"}
+    if unknown or camera.get("type") not in ("spherical", "perspective", "orthographic"):
+        raise ValueError(f"camera: unknown key(s) {sorted(unknown)} or type {camera.get('type')!r} (spherical, perspective, orthographic)")
+    pos, look_at, up = camera.get("pos", pos), camera.get("look_at", look_at), camera.get("up", up)
+    if camera["type"] == "spherical":
+        return b.set_camera_spherical(lib, pos, look_at, up, mapping=camera.get("mapping", "equalarea"))
+    return b.set_camera_look_at(lib, pos, look_at, up, camera.get("fov", fov), lens_radius=camera.get("lens_radius", 0.0), focal_distance=camera.get("focal_distance", 1e6),
+                                orthographic=camera["type"] == "orthographic")
+
+
 def spot_and_distant(spot_from=(0.4, 1.6, 0.6), spot_to=(0.0, 0.0, 0.0), coneangle=35.0, conedelta=10.0, spot_scale=8.0, sun_from=(1.0, 2.0, 1.5), sun_to=(0.0, 0.0, 0.0),
                      sun_scale=1.5, spot=True, distant=True):
     """An `extra_lights` argument for the generators below: PBRT-v4's spot light and / or distant light, given in WORLD space."""
@@ -116,7 +132,7 @@ def test_image(size=64, channels=3, seed=7):
 
 def cornell_box(lib, width=512, height=512, coated=False, mix=False, patches=False, patch_skew=0.0, textured=False,
                 texture_filter=None, textured_coated_ceiling=True, glass=False, emitter_reflects=False, environment=None, glass_too=False, film=None, extra_lights=None,
-                diffuse_transmission=None):
+                diffuse_transmission=None, camera=None):
     """S2 (config C2): 5 walls x 2 + 2 boxes x 5 faces x 2 + light 2 = 32 triangles.
     coated=True: the tall box becomes CoatedConductor (rough interface, Cu), the short one CoatedDiffuse with a scattering
     medium between the interfaces, the floor CoatedDiffuse with a smooth interface (SURVEY §8f-1 materials).
@@ -132,7 +148,7 @@ def cornell_box(lib, width=512, height=512, coated=False, mix=False, patches=Fal
     assert dt <= {"sheet", "textured", "mixed", "tall", "gold", "sphere", "all"}
     b = SceneBuilder()
     b.set_film(width, height, **(film or {}))
-    rfw = b.set_camera_look_at(lib, (0, 1, 3.4), (0, 1, 0), (0, 1, 0), 39.0)
+    rfw = _set_camera(b, lib, camera, (0, 1, 3.4), (0, 1, 0), (0, 1, 0), 39.0)
     if "all" in dt:
         white = b.material_diffuse_transmission(0.6, 0.15)
         red = b.material_diffuse_transmission(_two_point_spectrum(b, 0.05, 0.6), _two_point_spectrum(b, 0.0, 0.15))
@@ -420,7 +436,7 @@ def cube_sphere(n, seed=1234, amplitude=0.15, shuffle_seed=99, as_quads=False, q
     return verts, tris
 
 
-def ganesha_proxy(lib, width=1024, height=1024, n=599, with_room=True, coated=False, variant=None, floor_filter="ewa", quad_fraction=None, object_material=None, film=None, extra_lights=None):
+def ganesha_proxy(lib, width=1024, height=1024, n=599, with_room=True, coated=False, variant=None, floor_filter="ewa", quad_fraction=None, object_material=None, film=None, extra_lights=None, camera=None):
     """S3 (configs C3/C5): n=599 gives 6*599^2*2 = 4 305 612 triangles and 2 152 808 vertices.
     coated=True: the object is CoatedDiffuse (the material of the reference's Ganesha render, images/shimmer-ganesha-1.png).
     variant (round 5: the shapes a real PBRT-v4 scene mixes into its triangles; same camera, room and object):
@@ -440,7 +456,7 @@ def ganesha_proxy(lib, width=1024, height=1024, n=599, with_room=True, coated=Fa
     assert variant in (None, "patch_emitter", "one_sphere", "instanced", "environment", "textured_floor", "textured_hidden", "quads", "smooth", "mesh_emitter", "textured_object", "instance_grid")
     b = SceneBuilder()
     b.set_film(width, height, **(film or {}))
-    rfw = b.set_camera_look_at(lib, (0.0, 0.6, 4.2), (0.0, 0.0, 0.0), (0, 1, 0), 38.0)
+    rfw = _set_camera(b, lib, camera, (0.0, 0.6, 4.2), (0.0, 0.0, 0.0), (0, 1, 0), 38.0)
     obj = b.material_coated_diffuse(reflectance=0.4, roughness=0.05, thickness=0.01) if coated else b.material_diffuse(0.4)
     if object_material == "gold":  # (round 6 class probes) a rough conductor / a dispersive glass / a coated conductor object
         obj = b.material_conductor(b.spectrum_named("metal-Au-eta"), b.spectrum_named("metal-Au-k"), roughness=0.2)
@@ -572,12 +588,12 @@ def icosphere(level):
     return v.astype(np.float32), f.astype(np.uint32)
 
 
-def crown_proxy(lib, width=1000, height=1400, level=4, n_glass=64, n_gold=16, seed=4242, environment=None, film=None, extra_lights=None):
+def crown_proxy(lib, width=1000, height=1400, level=4, n_glass=64, n_gold=16, seed=4242, environment=None, film=None, extra_lights=None, camera=None):
     """S4 (config C4): dispersive smooth dielectric icospheres (BK7 eta table -> terminate_secondary), rough gold
     conductors, diffuse floor, one quad emitter; render with max_depth=32."""
     b = SceneBuilder()
     b.set_film(width, height, **(film or {}))
-    rfw = b.set_camera_look_at(lib, (0.0, 2.2, 7.5), (0.0, 1.2, 0.0), (0, 1, 0), 32.0)
+    rfw = _set_camera(b, lib, camera, (0.0, 2.2, 7.5), (0.0, 1.2, 0.0), (0, 1, 0), 32.0)
     glass = b.material_dielectric(b.spectrum_named("glass-BK7"))
     gold = b.material_conductor(b.spectrum_named("metal-Au-eta"), b.spectrum_named("metal-Au-k"), roughness=0.01)  # alpha = sqrt(0.01) = 0.1
     floor = b.material_diffuse(0.5)
@@ -624,14 +640,23 @@ def environment_image(n=32, sun=(0.3, 0.5, 0.81), sun_radiance=40.0):
     return img.astype(np.float32)
 
 
+def environment_from_probe(image):
+    """The film of an equal-area spherical camera (linear RGB, row 0 first; the camera's up = the world's +y) as the `environment=` image of the generators here, so
+    that what the probe saw in a world direction is what the map shows in that direction. The camera's swap of y and z is a REFLECTION ((x, y, z) -> (x, z, y)) and the
+    generators turn their map by a ROTATION ((x, y, z) -> (x, z, -y)); with the look-at frame's right = cross(up, dir) pointing along -x for a probe that looks down -z,
+    what is left between the two is a mirror in u: the film flipped left to right. (Negative values, which a filter with negative lobes may leave, are clamped.)"""
+    return np.ascontiguousarray(np.maximum(np.asarray(image, np.float32)[:, ::-1], 0.0))
+
+
 def three_spheres(lib, width=32, height=32, offsets=(-3.5, 0.0, 5.0), camera=(0.0, 0.0, 0.0), environment=None, film=None, extra_lights=None):
     """The reference's set_of_spheres BVH test scene (aggregate.rs:631-702): unit spheres at x = -3.5, 0, 5.
     With the default camera at the origin world == render space, as the reference's unit tests assume (rays are given
-    in render space); pass a camera position outside the spheres to render it."""
+    in render space); pass a camera position outside the spheres to render it — or, like the other generators, a dict that replaces the camera (_set_camera)."""
     b = SceneBuilder()
     b.set_film(width, height, **(film or {}))
-    cam = np.asarray(camera, np.float64)
-    rfw = b.set_camera_look_at(lib, cam, cam + np.array([0.0, 0.0, -1.0]), (0, 1, 0), 60.0)
+    spec = camera if isinstance(camera, dict) else None
+    cam = np.asarray((0.0, 0.0, 0.0) if spec is not None else camera, np.float64)
+    rfw = _set_camera(b, lib, spec, cam, cam + np.array([0.0, 0.0, -1.0]), (0, 1, 0), 60.0)
     m = b.material_diffuse(0.5)
     for x in offsets:
         rfo = np.eye(4, dtype=np.float32)
@@ -648,7 +673,7 @@ def three_spheres(lib, width=32, height=32, offsets=(-3.5, 0.0, 5.0), camera=(0.
     return _finish(b, lib, extra_lights=extra_lights, rfw=rfw, name="three spheres" + ("" if environment is None else " (environment map)"))
 
 
-def instanced_scene(lib, width=64, height=48, n_instances=5, only_object=False, baked=False, environment=None, film=None, extra_lights=None, diffuse_transmission=False):
+def instanced_scene(lib, width=64, height=48, n_instances=5, only_object=False, baked=False, environment=None, film=None, extra_lights=None, diffuse_transmission=False, camera=None):
     """Object instancing: one object definition (an icosphere with per-vertex normals, a partial sphere and a curved
     bilinear patch, three materials) placed several times with rotated, non-uniformly scaled transforms over a floor lit by a quad
     light and a point light. `only_object`: just the object's shapes at top level, untransformed, no floor. `baked`: the same
@@ -656,7 +681,7 @@ def instanced_scene(lib, width=64, height=48, n_instances=5, only_object=False, 
     rng = np.random.Generator(np.random.PCG64(77))
     b = SceneBuilder()
     b.set_film(width, height, **(film or {}))
-    rfw = b.set_camera_look_at(lib, (0.0, 2.2, 7.0), (0.0, 0.8, 0.0), (0, 1, 0), 40.0)
+    rfw = _set_camera(b, lib, camera, (0.0, 2.2, 7.0), (0.0, 0.8, 0.0), (0, 1, 0), 40.0)
     # (diffuse_transmission: the object's icosphere is PBRT-v4's diffuse transmission material instead of a DiffuseMaterial)
     mats = [b.material_diffuse_transmission(_two_point_spectrum(b, 0.3, 0.1), _two_point_spectrum(b, 0.2, 0.6)) if diffuse_transmission else b.material_diffuse(_two_point_spectrum(b, 0.7, 0.2)), b.material_conductor(b.spectrum_named("metal-Cu-eta"), b.spectrum_named("metal-Cu-k"), roughness=0.2),
             b.material_coated_diffuse(reflectance=0.5, roughness=0.1)]
