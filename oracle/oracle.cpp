@@ -1391,6 +1391,36 @@ int orc_fn_render_plan(const int32_t* in, int n, int32_t* out) {
     }
     return shm_plan::N_WS_ARRAYS;
 }
+// The traversal part of the plan (host/render_plan.hpp: TRACE_SHAPES, ScenePlan::trace_variant / trace_spill_levels, RenderPlan::trace_any_strict) over `n` rows of
+// ORC_TRACE_IN int32 (has_spheres, has_instances, patch_heavy, has_quadric_patch, max_leaf_depth, SHM_GEN_HEAVY (-1: unset), disable_reference_quirks) -> rows of
+// ORC_TRACE_OUT int32: variant, strict, then closest / any pairs of waves per SIMD, LDS stack levels, HBM spill levels and LDS bytes per workgroup, then waves, LDS
+// levels and LDS bytes of the STRICT any-hit kernel such a render's shadow rays would take (on the any-hit side's grid and spill).
+enum { ORC_TRACE_IN = 7, ORC_TRACE_OUT = 13 };
+void orc_fn_trace_plan(const int32_t* in, int n, int32_t* out) {
+    using namespace shm_plan;
+    for (int i = 0; i < n; ++i, in += ORC_TRACE_IN, out += ORC_TRACE_OUT) {
+        SceneFacts f;
+        f.has_spheres = in[0]; f.has_instances = in[1]; f.patch_heavy = in[2]; f.has_quadric_patch = in[3]; f.max_leaf_depth = in[4]; f.has_prims = true;
+        Knobs k;
+        k.gen_heavy = in[5];
+        ShmRenderParams o;
+        memset(&o, 0, sizeof(o));
+        o.disable_reference_quirks = in[6];
+        const ScenePlan sp = scene_plan(f, k);
+        const RenderPlan p = render_plan(sp, o);
+        const TraceShape *c = &TRACE_SHAPES[sp.trace_variant][RAY_CLOSEST], *a = &TRACE_SHAPES[sp.trace_variant][RAY_ANY],
+                         *st = &TRACE_SHAPES[trace_strict_variant(sp.trace_variant)][RAY_ANY];
+        const int32_t cols[ORC_TRACE_OUT] = {sp.trace_variant, p.trace_any_strict, c->waves, a->waves, c->lds_levels, a->lds_levels, sp.trace_spill_levels[RAY_CLOSEST],
+                                             sp.trace_spill_levels[RAY_ANY], trace_lds_bytes(*c), trace_lds_bytes(*a), st->waves, st->lds_levels, trace_lds_bytes(*st)};
+        memcpy(out, cols, sizeof(cols));
+    }
+}
+// a scene's own input row of orc_fn_trace_plan, less the knob and the render's option: which traversal plan a real scene gets (tests/test_gpu_parity.py)
+void orc_fn_scene_trace_facts(OrcScene* s, int32_t* out) {
+    const shm_plan::SceneFacts f = shm_plan::scene_facts(reinterpret_cast<Oracle*>(s)->flat);
+    const int32_t cols[5] = {f.has_spheres, f.has_instances, f.patch_heavy, f.has_quadric_patch, f.max_leaf_depth};
+    memcpy(out, cols, sizeof(cols));
+}
 // the workspace table's identifiers, comma-separated, in order
 const char* orc_fn_ws_array_names() {
     static std::string names;

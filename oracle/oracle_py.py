@@ -139,6 +139,8 @@ def load():
     IP32, UP32, NP = C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(abi.ShmBvhNode)
     lib.orc_fn_render_plan.restype, lib.orc_fn_render_plan.argtypes = C.c_int, [IP32, C.c_int, IP32]
     lib.orc_fn_ws_array_names.restype, lib.orc_fn_ws_array_names.argtypes = C.c_char_p, []
+    lib.orc_fn_trace_plan.restype, lib.orc_fn_trace_plan.argtypes = None, [IP32, C.c_int, IP32]
+    lib.orc_fn_scene_trace_facts.restype, lib.orc_fn_scene_trace_facts.argtypes = None, [C.c_void_p, IP32]
     lib.orc_fn_bvh_pairs.restype = C.c_int
     lib.orc_fn_bvh_pairs.argtypes = [NP, C.c_uint32, UP32, C.c_uint32, UP32, C.c_uint32, NP, UP32, UP32, C.POINTER(C.c_int), UP32, UP32, NP]
     _lib = lib
@@ -173,6 +175,23 @@ def render_plans(rows):
     res = {name: out[:, i] for i, name in enumerate(PLAN_OUT)}
     res["ws"], res["ws_names"] = out[:, PLAN_WS_COL0:PLAN_WS_COL0 + n_arrays], names
     return res
+
+
+# orc_fn_trace_plan's row layouts (oracle.cpp): the traversal part of the plan; "_closest" / "_any" by ray kind, "strict_": the STRICT any-hit kernel's row
+TRACE_IN = ["has_spheres", "has_instances", "patch_heavy", "has_quadric_patch", "max_leaf_depth", "gen_heavy_knob", "disable_reference_quirks"]
+TRACE_OUT = ["variant", "strict", "waves_closest", "waves_any", "lds_levels_closest", "lds_levels_any", "spill_levels_closest", "spill_levels_any", "lds_bytes_closest",
+             "lds_bytes_any", "strict_waves", "strict_lds_levels", "strict_lds_bytes"]
+
+
+def trace_plans(rows):
+    """The traversal part of host/render_plan.hpp over an (n, len(TRACE_IN)) int32 array: a dict of int32 columns by TRACE_OUT name."""
+    lib = load()
+    rows = np.ascontiguousarray(rows, dtype=np.int32)
+    assert rows.ndim == 2 and rows.shape[1] == len(TRACE_IN)
+    out = np.zeros((rows.shape[0], len(TRACE_OUT)), np.int32)
+    IP32 = C.POINTER(C.c_int32)
+    lib.orc_fn_trace_plan(rows.ctypes.data_as(IP32), rows.shape[0], out.ctypes.data_as(IP32))
+    return {name: out[:, i] for i, name in enumerate(TRACE_OUT)}
 
 
 def sampler_stream_zs(px, py, index, spp, rx, ry, seed, none, kinds):
@@ -246,6 +265,13 @@ class Oracle:
         out = (C.c_int32 * 10)()
         self.lib.orc_fn_scene_facts(self.handle, out)
         return dict(zip(PLAN_IN[:10], out))
+
+    def trace_plan(self, gen_heavy_knob=-1, disable_reference_quirks=False):
+        """The traversal plan of this scene (trace_plans' columns, as ints), under the SHM_GEN_HEAVY knob and the render option given."""
+        facts = (C.c_int32 * 5)()
+        self.lib.orc_fn_scene_trace_facts(self.handle, facts)
+        plan = trace_plans([list(facts) + [gen_heavy_knob, int(disable_reference_quirks)]])
+        return {name: int(col[0]) for name, col in plan.items()}
 
     def camera_ray_zs(self, px, py, index, seed, spp, none=False, disable_wavelength_jitter=False, disable_pixel_jitter=False):
         """The camera ray of a ZSobol pixel sample: a dict of o, d, lambda, pdf (float32 arrays), the filter weight and the dimension the next draw is taken from."""

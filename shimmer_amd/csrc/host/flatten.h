@@ -43,7 +43,7 @@ struct FlatScene {
     uint32_t max_leaf_depth = 0;  // deepest leaf (root = 0); bounds the traversal stack
     float scene_radius = 0.0f;
     uint64_t n_quadric_patch_prims = 0;  // primitive records that are spheres or bilinear patches (instances not counted): a scene where they are MANY runs the traversal
-                                         // kernels' five-wave instantiations (k_trace.hip, K5_GEN_HEAVY_WAVES: the parked round's registers instead of its spill code)
+                                         // kernels' five-wave instantiations (k_trace.hip, TRACE_GEN_HEAVY: the parked round's registers instead of its spill code)
     bool has_spheres = false;  // any non-triangle shape (sphere or bilinear patch): selects k_trace5<.., GEN = true> and the general-geometry shading instantiations
     bool has_layered = false;  // any Coated* material: selects the k_shade instantiation that carries LayeredBxDF
     bool has_rough_dielectric = false;  // a DielectricMaterial whose roughness is not the constant 0 (the specular / rough split of its scatter kernels)

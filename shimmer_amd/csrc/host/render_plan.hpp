@@ -1,6 +1,7 @@
 // host/render_plan.hpp — WHICH pipeline a scene and a render run, and what path workspace that needs, decided once and kept as data (plain C++17, no HIP:
 // oracle/oracle.cpp exports the two functions to tests/test_render_plan.py, which walks their whole domain).
-//   ScenePlan   at scene creation, from the class facts of the FlatScene and the environment knobs (read_knobs: the only getenv of the decisions)
+//   ScenePlan   at scene creation, from the class facts of the FlatScene and the environment knobs (read_knobs: the only getenv of the decisions); with it the
+//               traversal kernels' variant table (TRACE_SHAPES)
 //   RenderPlan  once per shm_render_wave, from the ScenePlan and the render's options
 // render.hip's select_kernels is a lookup by the RenderPlan's coordinates and its bounce loop asks the plan and nothing else; WS_ARRAYS below is the one list of
 // per-path arrays behind both the workspace budget and its allocation.
@@ -34,6 +35,7 @@ struct SceneFacts {
     bool small_tree = false, has_prims = false;             // fewer than 4096 BVH nodes / any primitive record
     uint32_t filter = SHM_FILTER_BOX;
     bool spherical_camera = false;  // PBRT-v4's spherical camera: K1 is k_generate_spherical.hip's; nothing else depends on it
+    int max_leaf_depth = 0;         // the deepest leaf of the BVH (root = 0; below 64, flatten.h): bounds the traversal stack
 };
 inline SceneFacts scene_facts(const shm_host::FlatScene& f) {
     SceneFacts s;
@@ -51,8 +53,35 @@ inline SceneFacts scene_facts(const shm_host::FlatScene& f) {
     s.has_prims = !f.prim_recs.empty();
     s.filter = f.film.filter;
     s.spherical_camera = f.camera.kind == SHM_CAMERA_SPHERICAL;
+    s.max_leaf_depth = (int)f.max_leaf_depth;
     return s;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------------------------------------------
+// The traversal kernels (k_trace.hip): ONE row per scene variant and ray kind — what the kernel is compiled with (waves per SIMD, the stack levels its LDS holds, the
+// five-wave builds' LDS save area) and, from the same row, what the scene allocates for it (the persistent grid, the HBM stack spill). A sweep edits a row;
+// tests/test_render_plan.py holds every row to the CU's LDS and every scene's stack to its tree.
+//   TRI        top-level triangles only. Closest hit at eight waves; any hit at seven (r04 sweep: 8 waves x 9 levels 65.5 ms of any-hit launches per headline frame,
+//              7 waves x 11 levels 62.8). S3: 98.5 % of the pushes land below level 9, 99.95 % below 12 (tools/sim/run_pair_sim.py); the rest goes to the HBM spill.
+//   GEN        spheres, bilinear patches or instances too: the direction, the instance slot and the parked round's live values take the closest-hit kernel past the 64
+//              registers of eight waves; seven waves (<= 72 VGPRs) cost the triangle kernel under 1 % (r04 sweep: 98.0 -> 98.7 ms).
+//   GEN_HEAVY  the same body at five waves, for scenes where the non-triangle tests are the RULE (ScenePlan::gen_heavy; the measurements: k_trace.hip, at the kernels):
+//              the five-wave share of 15 levels less the six levels' worth (12 KiB) of the save area around a quadric / patch test (trace5_body<SAVE_LDS>).
+// A workgroup is four waves, one per SIMD: `waves` per SIMD is also workgroups per CU.
+// ---------------------------------------------------------------------------------------------------------------------------------------------------------------
+enum : int { TRACE_TRI, TRACE_GEN, TRACE_GEN_HEAVY, N_TRACE };
+enum : int { RAY_CLOSEST, RAY_ANY, N_RAY };
+struct TraceShape { int waves, lds_levels, lds_save_bytes; };
+constexpr TraceShape TRACE_SHAPES[N_TRACE][N_RAY] = {
+    {{8, 9, 0}, {7, 11, 0}},
+    {{7, 11, 0}, {7, 11, 0}},
+    {{5, 15 - 6, 12 << 10}, {5, 15 - 6, 12 << 10}},
+};
+constexpr int TRACE_LDS_LEVEL_BYTES = 256 * 8;  // one stack level of a workgroup: 256 lanes x an 8-byte entry
+constexpr int trace_lds_bytes(const TraceShape& k) { return k.lds_levels * TRACE_LDS_LEVEL_BYTES + k.lds_save_bytes; }  // per workgroup
+// ShmRenderParams::disable_reference_quirks in a scene with instances: the any-hit kernels' STRICT pair (k_trace5_any_strict) — the general any-hit row, five waves for
+// a GEN_HEAVY scene and seven for every other. It runs on the grid and the spill of the scene's own any-hit row: the two must agree (the plan test holds them to it).
+constexpr int trace_strict_variant(int variant) { return variant == TRACE_GEN_HEAVY ? TRACE_GEN_HEAVY : TRACE_GEN; }
 
 // Tuning knobs (development): defaults are the measured optimum on S3. -1 / 0: not set.
 struct Knobs {
@@ -96,7 +125,9 @@ struct ScenePlan {
     bool lean_kernel = false;  // k_shade<lean> runs, direct or diverted: the workspace holds the deferred emitter hits (PathArrays::e_*, q_emit)
     bool tri_shade = false, tri_shade_plain_only = false;  // build the flat triangles' shading records (shm/tri_shade.h) / of plain DiffuseMaterials only
     // the traversal kernels (k_trace.hip)
-    bool gen_heavy = false;    // the five-wave instantiations for scenes where spheres / patches are a twelfth of the primitive records or more (K5_GEN_HEAVY_WAVES; S3 with
+    int trace_variant = TRACE_TRI;         // the row of TRACE_SHAPES (and of k_trace.hip's kernel table) this scene's rays take
+    int trace_spill_levels[N_RAY] = {1, 1};  // stack levels in the per-lane HBM spill: what the tree's depth needs beyond the row's LDS levels, and one more
+    bool gen_heavy = false;    // the five-wave instantiations for scenes where spheres / patches are a twelfth of the primitive records or more (TRACE_GEN_HEAVY; S3 with
                                // 100 / 50 / 25 / 10 % of the object's cells as patches, five against seven waves: +73 / +38 / +13 / 0 %, with ONE patch in 4.3 M triangles -7 %)
     // idle lanes before a traversal wave refills: the kernels set a ray up with the root test and six IEEE divisions (200 VALU instructions), so that fewer, fuller refills
     // win although a quarter of the lanes idle (r04 sweep on the headline frame, closest / any ms: 24: 97.4 / 62.3, 40: 96.5 / 60.9, 48: 102.1 / 63.5, 56: 119.1 / 78.1)
@@ -135,6 +166,11 @@ inline ScenePlan scene_plan(const SceneFacts& f, const Knobs& k) {
     // tree means long dependent chains per ray, which want every wave the device has (C4: 8 costs 2 %)
     p.trace_rays_per_lane = k.trace_rays_per_lane >= 0 ? k.trace_rays_per_lane : (f.small_tree ? 8 : 4);
     p.gen_heavy = f.has_spheres && (k.gen_heavy >= 0 ? k.gen_heavy != 0 : f.patch_heavy);
+    p.trace_variant = !f.has_spheres ? TRACE_TRI : (p.gen_heavy ? TRACE_GEN_HEAVY : TRACE_GEN);
+    for (int r = 0; r < N_RAY; ++r) {
+        const int beyond_lds = f.max_leaf_depth + 1 - TRACE_SHAPES[p.trace_variant][r].lds_levels;
+        p.trace_spill_levels[r] = (beyond_lds > 0 ? beyond_lds : 0) + 1;
+    }
     // at five waves a refill is cheaper to make early (24 idle lanes: S3 as patches 3 506 -> 3 685 Mray/s; profiles/r06_patch_heavy_scenes.txt)
     p.refill_min = k.refill_min ? k.refill_min : (p.gen_heavy ? 24 : 40);
     p.refill_min_any = k.refill_min_any ? k.refill_min_any : p.refill_min;
@@ -154,6 +190,7 @@ struct RenderPlan {
     // the render's hit records: 16 bytes {primitive, b0, b1, b2} where every kernel that reads them takes that form (triangle and textured scenes; with spheres / patches the
     // split form, a second record with t and phi — not with instances: a hit inside one names it in the 32-byte record); kept: double-buffered by bounce parity
     bool hit16 = false, hit_split = false, hit_kept = false;
+    bool trace_any_strict = false;  // the shadow rays take the any-hit kernels' STRICT pair: PBRT-v4's way into an instance (k_trace.hip)
     int fused_from = NEVER;        // the first bounce the fused all-materials kernel shades (staged route)
     bool split = false;            // k_split_plain runs in front of k_vertex: plain-diffuse hits -> q_lean, the rest -> q_split
     bool divert_vertex = false;    // k_vertex itself diverts plain-diffuse hits to q_lean (ShadeArgs::q_divert)
@@ -184,6 +221,7 @@ inline RenderPlan render_plan(const ScenePlan& s, const ShmRenderParams& o) {
     p.hit16 = path && (!f.has_spheres || !f.has_instances);
     p.hit_split = p.hit16 && f.has_spheres;
     p.hit_kept = p.route == ROUTE_LEAN && p.hit16 && !f.has_spheres;  // (the split form keeps its second records in the other half)
+    p.trace_any_strict = f.has_instances && o.disable_reference_quirks != 0;
     // a scene with several BxDF classes but without coated materials: ONE fused all-materials launch per bounce instead of the staged four or five, from bounce
     // `tail_fused_bounce` on. Rounds 3-4, chunks unsorted: only the late bounces paid (C4 frame 522-528 ms staged throughout, 510-512 from bounce 6, 511-513 from 8).
     // Round 5, chunks counting-sorted by material (k_shade_tail_sorted.hip): the earlier the better — C4 403.2 ms from bounce 8, 399 from 4, 388 from 2, 378 from 1,

@@ -6,7 +6,12 @@
 // far child untested — as the kernel of non-triangle scenes and the A/B partner of this one: retired in round 5, when the both-children step learned the other shapes
 // and measured 112-171 ms where that kernel took 228-278 on the same frames, profiles/r05_cliff_before.json beside r05_bench_final.json. What it established stays in the
 // comments below and in DESIGN.md section 4.)
+// WHICH entry point a scene's rays take, and at what occupancy and LDS stack depth it is compiled, is one row of host/render_plan.hpp's TRACE_SHAPES: the kernels' attributes
+// (below the body), the scene's grid and stack spill (wf_trace_prepare) and the launch (wf_launch_trace, through one table of kernel pointers) are all made from that row.
 #include "wavefront.h"
+
+using namespace shm_plan;
+static_assert(TRACE_LDS_LEVEL_BYTES == TRACE_BLOCK * 8, "a stack level is one 8-byte entry per lane of the workgroup");
 
 namespace {
 
@@ -22,8 +27,8 @@ namespace {
 //    hit writes, profiles/r01_v4; holding them in registers through select chains was measured too: slower than LDS).
 // Node and primitive visit counts equal the reference's in both modes (it is the same algorithm, node for node).
 // ---------------------------------------------------------------------------------------------
-#ifndef K3_CHUNK_MAX
-#define K3_CHUNK_MAX 1024
+#ifndef K_CHUNK_MAX
+#define K_CHUNK_MAX 1024
 #endif
 
 // v_cndmask with the per-ray sign held as a 64-bit lane mask in a SCALAR register pair (one bit per lane, rebuilt by three ballots whenever
@@ -39,11 +44,13 @@ __device__ __forceinline__ Float sel_mask(unsigned long long mask, Float if_clea
 // One-instruction max / min of three (IEEE maxNum / minNum; used only where no operand can be a NaN, see the slab test).
 __device__ __forceinline__ Float vmax3(Float a, Float b, Float c) { Float r; asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
 __device__ __forceinline__ Float vmin3(Float a, Float b, Float c) { Float r; asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
-#define K3_PARAMS SceneView sv, const uint32_t* __restrict__ queue, const uint32_t* __restrict__ n_ptr, uint32_t n_direct, uint32_t* head,                    \
+// The kernels' parameter list (wf_launch_trace fills it, in this order) and the same names as arguments: what an entry point hands to trace5_body
+#define K5_PARAMS SceneView sv, const uint32_t* __restrict__ queue, const uint32_t* __restrict__ n_ptr, uint32_t n_direct, uint32_t* head,                    \
                   const ShmRay* __restrict__ rays, ShmHit* __restrict__ hits, uint8_t* __restrict__ occluded_out, float4* __restrict__ L,                 \
                   const float4* __restrict__ contrib, DeviceCounters* counters, uint32_t* __restrict__ spill, int spill_levels, int refill_min, int leaf_min, \
-                  int queue_parts, int rays_per_lane, int hit16
-#define K3_ARGS sv, queue, n_ptr, n_direct, head, rays, hits, occluded_out, L, contrib, counters, spill, spill_levels, refill_min, leaf_min, queue_parts, rays_per_lane, hit16
+                  int queue_parts, int rays_per_lane, int hit16, const uint32_t* __restrict__ big_leaf_n, float4* gen_save, int other_min, float4* hit2
+#define K5_ARGS sv, queue, n_ptr, n_direct, head, rays, hits, occluded_out, L, contrib, counters, spill, spill_levels, refill_min, leaf_min, queue_parts, rays_per_lane, hit16, \
+                big_leaf_n, gen_save, other_min, hit2
 
 // ---------------------------------------------------------------------------------------------
 // k_trace5: the BOTH-CHILDREN step (round 4), for scenes made of triangles only. Same algorithm, node for node — the reference tests both children of
@@ -95,13 +102,7 @@ constexpr uint32_t SGN_RAY = 15u, SGN_HIT = 16u, SGN_HIT_INSIDE = 32u, SGN_INST_
 // shadows from somewhere else; tests/test_instancing.py). The outer t_max rides in the spare word of save area 0. Own instantiations (k_trace5_any_strict): the
 // reference-exact kernels are compiled without a trace of it.
 template <bool ANY, bool GEN, int LDS_N, bool SAVE_LDS = false, bool STRICT = false>
-__device__ __forceinline__ void trace5_body(const SceneView& sv, const uint32_t* __restrict__ queue, const uint32_t* __restrict__ n_ptr,
-                                            uint32_t n_direct, uint32_t* head, const ShmRay* __restrict__ rays,
-                                            ShmHit* __restrict__ hits, uint8_t* __restrict__ occluded_out,
-                                            float4* __restrict__ L, const float4* __restrict__ contrib,
-                                            DeviceCounters* counters, uint32_t* __restrict__ spill, int spill_levels,
-                                            int refill_min, int leaf_min, int queue_parts, int rays_per_lane, int hit16, const uint32_t* __restrict__ big_leaf_n,
-                                            float4* gen_save, int other_min, float4* __restrict__ hit2) {
+__device__ __forceinline__ void trace5_body(K5_PARAMS) {
     typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
     typedef __attribute__((address_space(3))) u32x2 lds_u2;
     __shared__ u32x2 lds_stack5[(TRACE_BLOCK / WAVE) * LDS_N * WAVE];
@@ -145,7 +146,7 @@ __device__ __forceinline__ void trace5_body(const SceneView& sv, const uint32_t*
     uint32_t since_other = 0u;       // GEN, wave-uniform: iterations since the wave's last round of parked work
     const uint32_t n_waves = active_blocks * (TRACE_BLOCK / WAVE);
     uint32_t chunk = n / (n_waves * 8u);
-    chunk = chunk < 64u ? 64u : (chunk > (uint32_t)K3_CHUNK_MAX ? (uint32_t)K3_CHUNK_MAX : chunk);
+    chunk = chunk < 64u ? 64u : (chunk > (uint32_t)K_CHUNK_MAX ? (uint32_t)K_CHUNK_MAX : chunk);
     chunk = (chunk + 63u) & ~63u;
     uint32_t path = 0;
     // (Measured and rejected on the refill — round 5: the next refill's queue entries fetched a refill ahead, K2 -0.8 ms, profiles/r05_refill_queue_prefetch.txt; round 6:
@@ -199,7 +200,8 @@ __device__ __forceinline__ void trace5_body(const SceneView& sv, const uint32_t*
     };
 
 #ifndef K5_OUTER_IN_REGS
-#define K5_OUTER_IN_REGS 0
+#define K5_OUTER_IN_REGS 0  // (1: the outer ray's state in registers instead of save area 0. Never built that way any more, and its branches are dead code — but taking them
+                            //  and their six variables out changes the text of the six GEN kernels: a performance change, to be made with a GPU measurement of its own)
 #endif
     // GEN: the OUTER ray's state while an instance is traversed
     V3 o_ro = v3s(0.0f), o_inv = v3s(0.0f);
@@ -280,6 +282,8 @@ __device__ __forceinline__ void trace5_body(const SceneView& sv, const uint32_t*
         t0_out = t0;
         return ok && (t1 > 0.0f);
     };
+    // the link word a lane stays pending with on a leaf of several primitives: `left` more of them, from the next slot on
+    auto next_in_leaf = [](uint32_t left, uint32_t slot) -> uint32_t { return LINK_LEAF | ((left < LINK_COUNT_MAX ? left : LINK_COUNT_MAX) << LINK_COUNT_SHIFT) | (slot + 1u); };
     auto push = [&](uint32_t link, uint32_t word1) {
         // two different store flavours, so that the compiler cannot merge them into one flat_store of a selected pointer
         if (top < st_base + LDS_N * WAVE) *top = u32x2{link, word1};
@@ -287,7 +291,7 @@ __device__ __forceinline__ void trace5_body(const SceneView& sv, const uint32_t*
         top += WAVE;
     };
 
-    // Queue partitions: the queue is cut into `queue_parts` contiguous ranges, each with its own head word (own 128-B line). A wave starts in the partition of the XCD it
+    // Queue partitions: the queue is cut into `queue_parts` (TRACE_QUEUE_PARTS) contiguous ranges, each with its own head word (TRACE_HEAD_STRIDE dwords apart: own 128-B line). A wave starts in the partition of the XCD it
     // runs on — queue order is image order (pix_group), so one XCD's L2 serves one image region's part of the BVH, and 8 head words see 1/8 of the atomics each (one word
     // saturates near 88 dequeues/us: MI355X_MICROARCH.md "dequeue") — and moves on to the next partition when its own has run dry. The chunk a wave claims with one atomic
     // is large enough that the head word sees few atomics and small enough that the last chunks balance across the resident waves.
@@ -306,18 +310,15 @@ __device__ __forceinline__ void trace5_body(const SceneView& sv, const uint32_t*
             const int n_idle = __popcll(idle);
             // GEN: a lane parked on a non-triangle test takes no node step either — the refill threshold counts the lanes that cannot, not only the idle ones (with one
             // sphere in 4.3 M triangles a parked lane waits ~190 iterations for company: 4 parked + 17 idle lanes left 32 of 64 at a node, against 37 in the triangle scene)
-#ifndef K5_REFILL_COUNTS_PARKED
-#define K5_REFILL_COUNTS_PARKED 1
-#endif
             // (... once they have waited: where parked work is frequent — every ray of an instanced object parks twice — a round comes every ~16 iterations and
             //  early refills only break its batches: S3 instanced 171 -> 182 ms when every parked lane counted)
-            const int n_unavailable = (GEN && K5_REFILL_COUNTS_PARKED && since_other > 24u) ? n_idle + __popcll(__ballot(cur >= (LINK_LEAF | LINK_OTHER))) : n_idle;
+            const int n_unavailable = (GEN && since_other > 24u) ? n_idle + __popcll(__ballot(cur >= (LINK_LEAF | LINK_OTHER))) : n_idle;
             if (!exhausted && (n_unavailable >= refill_min || idle == ~0ull)) {
                 while (w_next >= w_end && !exhausted) {
                     const uint32_t p_begin = part * part_size;
                     const uint32_t p_end = (p_begin < n) ? ((n - p_begin < part_size) ? n : p_begin + part_size) : p_begin;
                     uint32_t base = 0;
-                    if (lane == 0) base = atomicAdd(head + part * 32u, chunk);
+                    if (lane == 0) base = atomicAdd(head + part * TRACE_HEAD_STRIDE, chunk);
                     base = __builtin_amdgcn_readfirstlane(base);
                     if (base < p_end - p_begin) {
                         w_next = p_begin + base;
@@ -339,10 +340,7 @@ __device__ __forceinline__ void trace5_body(const SceneView& sv, const uint32_t*
                             path = queue ? queue[qi] : qi;
                             const float4* rp = reinterpret_cast<const float4*>(rays + path);
                             const float4 r0 = rp[0], r1 = rp[1];
-#ifndef K5_L_AT_REFILL
-#define K5_L_AT_REFILL 1  // (0: L and the contribution are loaded when the ray ends: A/B)
-#endif
-                            if (ANY && K5_L_AT_REFILL && L) {
+                            if (ANY && L) {
                                 const float4 l = L[path], c = contrib[path];
                                 l_new = make_float4(l.x + c.x, l.y + c.y, l.z + c.z, l.w + c.w);
                             }
@@ -448,7 +446,7 @@ __device__ __forceinline__ void trace5_body(const SceneView& sv, const uint32_t*
                     if (GEN && !tested) cur |= LINK_OTHER;  // no triangle: the lane parks on this slot until the wave runs its other tests
                     else if (ANY && got) cur = CUR_DONE;    // intersect_predicate returns at its first hit (aggregate.rs:160-166)
                     else if (leaf_n == 0u) cur = CUR_POP;
-                    else cur = LINK_LEAF | ((leaf_n < LINK_COUNT_MAX ? leaf_n : LINK_COUNT_MAX) << LINK_COUNT_SHIFT) | (slot + 1u);
+                    else cur = next_in_leaf(leaf_n, slot);
                 }
                 if (GEN) w_prims += (unsigned long long)__popcll(__ballot(tested));
             }
@@ -550,7 +548,7 @@ __device__ __forceinline__ void trace5_body(const SceneView& sv, const uint32_t*
                             leaf_n -= 1u;
                             if (ANY && got) cur = CUR_DONE;
                             else if (leaf_n == 0u) cur = CUR_POP;
-                            else cur = LINK_LEAF | ((leaf_n < LINK_COUNT_MAX ? leaf_n : LINK_COUNT_MAX) << LINK_COUNT_SHIFT) | (slot + 1u);
+                            else cur = next_in_leaf(leaf_n, slot);
                         }
                     }
                     CENSUS(18, __popcll(__ballot(entered)));
@@ -617,15 +615,7 @@ __device__ __forceinline__ void trace5_body(const SceneView& sv, const uint32_t*
             const bool found = (sgn & SGN_HIT) != 0u;
             if (ANY) {
                 if (occluded_out) occluded_out[path] = found ? 1 : 0;
-                if (L && !found) {
-                    if (K5_L_AT_REFILL) {
-                        L[path] = l_new;
-                    } else {
-                        float4 l = L[path], c = contrib[path];
-                        l.x += c.x; l.y += c.y; l.z += c.z; l.w += c.w;
-                        L[path] = l;
-                    }
-                }
+                if (L && !found) L[path] = l_new;
             } else if (!found) {
                 if (hit16) {
                     reinterpret_cast<float4*>(hits)[path] = make_float4(__int_as_float(-1), 0.0f, 0.0f, 0.0f);
@@ -660,83 +650,45 @@ __device__ __forceinline__ void trace5_body(const SceneView& sv, const uint32_t*
     }
 }
 
-#ifndef K5_CLOSEST_WAVES
-#define K5_CLOSEST_WAVES 8
-#endif
-#ifndef K5_ANY_WAVES
-#define K5_ANY_WAVES 7  // (r04 sweep: 8 waves x 9 levels 65.5 ms of any-hit launches per headline frame, 7 waves x 11 levels 62.8)
-#endif
-// {LDS levels of 8-byte entries, workgroups per CU}: 256 lanes x 8 B = 2 KiB per level and workgroup; 9 levels x 8 workgroups = 144 of the CU's 160 KiB
-// (S3: 98.5 % of the pushes land below level 9, 99.95 % below 12 — tools/sim/run_pair_sim.py; the rest goes to the HBM spill)
-#ifndef K5_LDS_AT_8
-#define K5_LDS_AT_8 9
-#endif
-template <int WAVES> struct K5Shape { static constexpr int LDS = (WAVES >= 8 ? K5_LDS_AT_8 : (WAVES == 7 ? 11 : (WAVES == 6 ? 13 : 15))), PER_CU = WAVES; };
-#define K5_PARAMS K3_PARAMS, const uint32_t* __restrict__ big_leaf_n, float4* gen_save, int other_min, float4* hit2
-#define K5_ARGS K3_ARGS, big_leaf_n, gen_save, other_min, hit2
+// ---- the entry points: one per row of host/render_plan.hpp's TRACE_SHAPES — occupancy, LDS stack levels and the LDS save area are the row's, and so are the grid and the
+// spill the scene allocates (wf_trace_prepare) ----
+// (__VA_ARGS__: the specialization's name — it holds commas)
+#define TRACE_KERNEL(VARIANT, RAY, STRICT, ...)                                                                                                                   \
+    template <>                                                                                                                                                   \
+    __global__ void __launch_bounds__(TRACE_BLOCK)                                                                                                                \
+    __attribute__((amdgpu_waves_per_eu(TRACE_SHAPES[VARIANT][RAY].waves, TRACE_SHAPES[VARIANT][RAY].waves))) __VA_ARGS__(K5_PARAMS) {                             \
+        trace5_body<RAY == RAY_ANY, VARIANT != TRACE_TRI, TRACE_SHAPES[VARIANT][RAY].lds_levels, TRACE_SHAPES[VARIANT][RAY].lds_save_bytes != 0, STRICT>(K5_ARGS); \
+    }
 template <bool ANY, bool GEN = false, bool HEAVY = false>
 __global__ void __launch_bounds__(TRACE_BLOCK) k_trace5(K5_PARAMS);
-template <>
-__global__ void __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(K5_CLOSEST_WAVES, K5_CLOSEST_WAVES))) k_trace5<false, false>(K5_PARAMS) {
-    trace5_body<false, false, K5Shape<K5_CLOSEST_WAVES>::LDS>(K5_ARGS);
-}
-template <>
-__global__ void __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(K5_ANY_WAVES, K5_ANY_WAVES))) k_trace5<true, false>(K5_PARAMS) {
-    trace5_body<true, false, K5Shape<K5_ANY_WAVES>::LDS>(K5_ARGS);
-}
-// scenes with spheres / bilinear patches / instances (GEN): the direction, the instance slot and the second sub-phase's live values take the closest-hit kernel past the
-// 64 registers of eight waves; seven waves (<= 72 VGPRs) cost the triangle kernel under 1 % (r04 sweep: 98.0 -> 98.7 ms)
-#ifndef K5_GEN_CLOSEST_WAVES
-#define K5_GEN_CLOSEST_WAVES 7
-#endif
-#ifndef K5_GEN_ANY_WAVES
-#define K5_GEN_ANY_WAVES 7
-#endif
-template <>
-__global__ void __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(K5_GEN_CLOSEST_WAVES, K5_GEN_CLOSEST_WAVES))) k_trace5<false, true>(K5_PARAMS) {
-    trace5_body<false, true, K5Shape<K5_GEN_CLOSEST_WAVES>::LDS>(K5_ARGS);
-}
-template <>
-__global__ void __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(K5_GEN_ANY_WAVES, K5_GEN_ANY_WAVES))) k_trace5<true, true>(K5_PARAMS) {
-    trace5_body<true, true, K5Shape<K5_GEN_ANY_WAVES>::LDS>(K5_ARGS);
-}
+TRACE_KERNEL(TRACE_TRI, RAY_CLOSEST, false, k_trace5<false, false>)
+TRACE_KERNEL(TRACE_TRI, RAY_ANY, false, k_trace5<true, false>)
+TRACE_KERNEL(TRACE_GEN, RAY_CLOSEST, false, k_trace5<false, true>)
+TRACE_KERNEL(TRACE_GEN, RAY_ANY, false, k_trace5<true, true>)
 // HEAVY (round 6): scenes where the non-triangle tests are the RULE — a quad PLY file becomes one BilinearPatch per face in the reference (shape/mesh.rs:233-256), so a real
 // scene's object is patches, not triangles. At seven waves (72 VGPRs) the parked round's arithmetic lives in spill code: 124 / 94 spilled VGPRs, 164 / 148 B of scratch per
 // lane — harmless where a round runs every 270 iterations (one sphere among 4.3 M triangles), and 0.7 TB of scratch traffic per frame where one runs every 17 (S3 as 2.15 M
 // patches: K2 263 ms, K3 171 ms against 92 / 59 for the same object as triangles). The SAME body at five waves per SIMD holds it in registers (96 VGPRs + 10 spilled / 93 + 0):
 // K2 158, K3 87 ms, 2 261 -> 3 496 Mray/s; with the refill at 24 idle lanes and the patch's fourth corner in its own record (flatten.h) K2 147, K3 77 ms, 3 736 Mray/s
-// (profiles/r06_patch_heavy_scenes.txt), with the save area around the test in LDS K2 138, K3 72 ms, 3 909 Mray/s; with few non-triangles the seven-wave build stays ahead by 3-10 % (occupancy for the node step): chosen per scene, render.hip.
-#ifndef K5_GEN_HEAVY_WAVES
-#define K5_GEN_HEAVY_WAVES 5
-#endif
-#ifndef K5_GEN_HEAVY_LDS
-#define K5_GEN_HEAVY_LDS (K5Shape<K5_GEN_HEAVY_WAVES>::LDS - 6)  // stack levels in LDS: the five-wave share (15 x 2 KB) less the 12 KB save area of trace5_body<SAVE_LDS>
-#endif
-template <>
-__global__ void __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(K5_GEN_HEAVY_WAVES, K5_GEN_HEAVY_WAVES))) k_trace5<false, true, true>(K5_PARAMS) {
-    trace5_body<false, true, K5_GEN_HEAVY_LDS, true>(K5_ARGS);
-}
-template <>
-__global__ void __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(K5_GEN_HEAVY_WAVES, K5_GEN_HEAVY_WAVES))) k_trace5<true, true, true>(K5_PARAMS) {
-    trace5_body<true, true, K5_GEN_HEAVY_LDS, true>(K5_ARGS);
-}
+// (profiles/r06_patch_heavy_scenes.txt), with the save area around the test in LDS K2 138, K3 72 ms, 3 909 Mray/s; with few non-triangles the seven-wave build stays ahead by 3-10 % (occupancy for the node step): chosen per scene (ScenePlan::trace_variant).
+TRACE_KERNEL(TRACE_GEN_HEAVY, RAY_CLOSEST, false, k_trace5<false, true, true>)
+TRACE_KERNEL(TRACE_GEN_HEAVY, RAY_ANY, false, k_trace5<true, true, true>)
 // the any-hit kernels of scenes with instances under ShmRenderParams::disable_reference_quirks (trace5_body, STRICT): seven waves, and the five-wave build for patch-heavy scenes
 template <bool HEAVY>
 __global__ void __launch_bounds__(TRACE_BLOCK) k_trace5_any_strict(K5_PARAMS);
-template <>
-__global__ void __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(K5_GEN_ANY_WAVES, K5_GEN_ANY_WAVES))) k_trace5_any_strict<false>(K5_PARAMS) {
-    trace5_body<true, true, K5Shape<K5_GEN_ANY_WAVES>::LDS, false, true>(K5_ARGS);
-}
-template <>
-__global__ void __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(K5_GEN_HEAVY_WAVES, K5_GEN_HEAVY_WAVES))) k_trace5_any_strict<true>(K5_PARAMS) {
-    trace5_body<true, true, K5_GEN_HEAVY_LDS, true, true>(K5_ARGS);
-}
+TRACE_KERNEL(trace_strict_variant(TRACE_GEN), RAY_ANY, true, k_trace5_any_strict<false>)
+TRACE_KERNEL(trace_strict_variant(TRACE_GEN_HEAVY), RAY_ANY, true, k_trace5_any_strict<true>)
+#undef TRACE_KERNEL
+using TraceKernel = void (*)(K5_PARAMS);
+constexpr TraceKernel TRACE_KERNELS[N_TRACE][N_RAY] = {
+    {k_trace5<false, false>, k_trace5<true, false>}, {k_trace5<false, true>, k_trace5<true, true>}, {k_trace5<false, true, true>, k_trace5<true, true, true>}};
+constexpr TraceKernel TRACE_KERNELS_ANY_STRICT[2] = {k_trace5_any_strict<false>, k_trace5_any_strict<true>};  // [trace_strict_variant - TRACE_GEN]
 
 // (Round 5 built and measured k_trace6 here — TWO rays per lane, each phase run for whichever slot of a lane is ready: bit-exact, 23 % fewer wave iterations, 38.3 instead of 31.4
 // lanes per VALU instruction, and 62 % more instructions per iteration for the selects that bring the chosen slot's state to each phase: K2 91 -> 133 ms, K3 58 -> 79 ms.
 // Rejected with profiles/r05_rejected_two_rays_per_lane.txt; the code left the tree in round 6 (git history: round-5 commits of k_trace.hip).)
 
-__global__ void k_reset_heads3(uint32_t* heads) { for (uint32_t i = threadIdx.x; i < 8 * 32; i += blockDim.x) heads[i] = 0; }
+__global__ void k_reset_trace_heads(uint32_t* heads) { for (uint32_t i = threadIdx.x; i < TRACE_QUEUE_PARTS * TRACE_HEAD_STRIDE; i += blockDim.x) heads[i] = 0; }
 }  // namespace
 
 void wf_trace_census() {
@@ -757,53 +709,40 @@ void wf_trace_census() {
 #endif
 }
 
+// The scene's side of its rows: the persistent grid (one workgroup per wave-per-SIMD and CU), the HBM stack spill and, for the GEN bodies, the ray-state save areas
 int wf_trace_prepare(ShmScene* s) {
     if (s->flat.nodes.size() + s->flat.instances.size() + 2 > (size_t)1 << 27) { shm_err() = "more than 2^27 BVH nodes (the traversal kernels address the node array with 32-bit byte offsets)"; return SHM_ERR_UNSUPPORTED; }
-    const bool tri_only = !s->flat.has_spheres;
-    for (int any = 0; any < 2; ++any) {
-        int lds = any ? K5Shape<K5_ANY_WAVES>::LDS : K5Shape<K5_CLOSEST_WAVES>::LDS, per_cu = any ? K5Shape<K5_ANY_WAVES>::PER_CU : K5Shape<K5_CLOSEST_WAVES>::PER_CU;
-        if (!tri_only) { lds = any ? K5Shape<K5_GEN_ANY_WAVES>::LDS : K5Shape<K5_GEN_CLOSEST_WAVES>::LDS; per_cu = any ? K5Shape<K5_GEN_ANY_WAVES>::PER_CU : K5Shape<K5_GEN_CLOSEST_WAVES>::PER_CU; }
-        if (!tri_only && s->plan.gen_heavy) { lds = K5_GEN_HEAVY_LDS; per_cu = K5Shape<K5_GEN_HEAVY_WAVES>::PER_CU; }
-        s->trace3_blocks[any] = s->n_cu * per_cu;
-        s->spill3_levels[any] = std::max(0, (int)s->flat.max_leaf_depth + 1 - lds) + 1;
-        const size_t words = (size_t)s->trace3_blocks[any] * (TRACE_BLOCK / WAVE) * (size_t)s->spill3_levels[any] * WAVE * 2u;  // (8-byte stack entries)
+    if (s->flat.instances.size() >= ((size_t)1 << 25)) { shm_err() = "more than 2^25 instances (the traversal kernels keep the instance index in 26 bits)"; return SHM_ERR_UNSUPPORTED; }
+    const int variant = s->plan.trace_variant;
+    for (int ray = 0; ray < N_RAY; ++ray) {
+        TraceSide& side = s->trace[ray];
+        side.blocks = s->n_cu * TRACE_SHAPES[variant][ray].waves;
+        side.spill_levels = s->plan.trace_spill_levels[ray];
+        const size_t lanes = (size_t)side.blocks * TRACE_BLOCK;
         void* d = nullptr;
-        if (hipMalloc(&d, words * sizeof(uint32_t)) != hipSuccess) { shm_err() = "hipMalloc of the traversal stack spill failed"; return SHM_ERR_OUT_OF_MEMORY; }
+        if (hipMalloc(&d, lanes * (size_t)side.spill_levels * 2u * sizeof(uint32_t)) != hipSuccess) { shm_err() = "hipMalloc of the traversal stack spill failed"; return SHM_ERR_OUT_OF_MEMORY; }  // (8-byte stack entries)
         s->allocs.push_back(d);
-        (any ? s->d_spill3_any : s->d_spill3) = static_cast<uint32_t*>(d);
-        if (!tri_only) {  // k_trace5<., GEN>: two 48-byte ray-state save areas per resident lane
-            if (s->flat.instances.size() >= ((size_t)1 << 25)) { shm_err() = "more than 2^25 instances (the traversal kernels keep the instance index in 26 bits)"; return SHM_ERR_UNSUPPORTED; }
+        side.d_spill = static_cast<uint32_t*>(d);
+        if (variant != TRACE_TRI) {  // trace5_body<., GEN>: two 48-byte ray-state save areas per resident lane
             void* g = nullptr;
-            if (hipMalloc(&g, (size_t)s->trace3_blocks[any] * (TRACE_BLOCK / WAVE) * 6 * WAVE * sizeof(float4)) != hipSuccess) { shm_err() = "hipMalloc of the traversal save areas failed"; return SHM_ERR_OUT_OF_MEMORY; }
+            if (hipMalloc(&g, lanes * 6 * sizeof(float4)) != hipSuccess) { shm_err() = "hipMalloc of the traversal save areas failed"; return SHM_ERR_OUT_OF_MEMORY; }
             s->allocs.push_back(g);
-            s->d_gen_save[any] = static_cast<float4*>(g);
+            side.d_gen_save = static_cast<float4*>(g);
         }
     }
     return SHM_OK;
 }
 
-int wf_launch_trace(ShmScene* s, bool any, const TraceArgs& t) {
-    uint32_t* heads = s->d_heads3 + (any ? 8 * 32 : 0);
-    uint32_t* spill = any ? s->d_spill3_any : s->d_spill3;
-    hipLaunchKernelGGL(k_reset_heads3, dim3(1), dim3(64), 0, t.stream, heads);
-    const int leaf_min = any ? s->plan.leaf_min_any : s->plan.leaf_min;
-    const bool tri_only = !s->flat.has_spheres;
-    // hit16 with the GEN kernels: the split record form (wavefront.h, load_hit_tri) — the second records follow the `capacity` first ones in the hit allocation
-    float4* const hit2 = (t.hit16 && !tri_only && t.hits) ? reinterpret_cast<float4*>(t.hits) + s->capacity : nullptr;
-#define TRACE5_KERNEL_ARGS(ANY)                                                                                                                          \
-    s->dsv, t.queue, t.n_ptr, t.n_direct, heads, t.rays, t.hits, t.occluded, t.L, t.contrib, s->d_counters, spill, s->spill3_levels[ANY],                 \
-        (ANY ? s->plan.refill_min_any : s->plan.refill_min), leaf_min, s->queue_parts, s->plan.trace_rays_per_lane, t.hit16, s->d_big_leaf_n, s->d_gen_save[ANY ? 1 : 0], \
-        (ANY ? s->plan.other_min_any : s->plan.other_min), hit2
-#define TRACE5_LAUNCH(ANY, ...) hipLaunchKernelGGL((k_trace5<ANY, __VA_ARGS__>), dim3(s->trace3_blocks[ANY]), dim3(TRACE_BLOCK), 0, t.stream, TRACE5_KERNEL_ARGS(ANY))
-    if (any && s->flat.has_instances && t.strict) {  // (the PBRT-v4 form of the shadow ray's way into an instance: its own instantiations)
-        if (s->plan.gen_heavy) hipLaunchKernelGGL((k_trace5_any_strict<true>), dim3(s->trace3_blocks[1]), dim3(TRACE_BLOCK), 0, t.stream, TRACE5_KERNEL_ARGS(1));
-        else hipLaunchKernelGGL((k_trace5_any_strict<false>), dim3(s->trace3_blocks[1]), dim3(TRACE_BLOCK), 0, t.stream, TRACE5_KERNEL_ARGS(1));
-    }
-    else if (tri_only) { if (any) TRACE5_LAUNCH(true, false); else TRACE5_LAUNCH(false, false); }
-    else if (s->plan.gen_heavy) { if (any) TRACE5_LAUNCH(true, true, true); else TRACE5_LAUNCH(false, true, true); }
-    else { if (any) TRACE5_LAUNCH(true, true); else TRACE5_LAUNCH(false, true); }
-#undef TRACE5_KERNEL_ARGS
-#undef TRACE5_LAUNCH
+// One launch through the kernel table, by the plan's coordinates: the scene's variant, the ray kind and — any hit only — the render's strictness
+int wf_launch_trace(ShmScene* s, int ray, bool any_strict, const TraceArgs& t) {
+    const TraceSide& side = s->trace[ray];
+    const ScenePlan& p = s->plan;
+    const bool any = ray == RAY_ANY;
+    const TraceKernel kernel = (any && any_strict) ? TRACE_KERNELS_ANY_STRICT[trace_strict_variant(p.trace_variant) - TRACE_GEN] : TRACE_KERNELS[p.trace_variant][ray];
+    hipLaunchKernelGGL(k_reset_trace_heads, dim3(1), dim3(64), 0, t.stream, side.d_heads);
+    hipLaunchKernelGGL(kernel, dim3(side.blocks), dim3(TRACE_BLOCK), 0, t.stream, s->dsv, t.queue, t.n_ptr, t.n_direct, side.d_heads, t.rays, t.hits, t.occluded, t.L, t.contrib,
+                       s->d_counters, side.d_spill, side.spill_levels, any ? p.refill_min_any : p.refill_min, any ? p.leaf_min_any : p.leaf_min, (int)TRACE_QUEUE_PARTS,
+                       p.trace_rays_per_lane, t.hit16, s->d_big_leaf_n, side.d_gen_save, any ? p.other_min_any : p.other_min, t.hit2);
     LAUNCH_TRY(any ? "k_trace<any>" : "k_trace<closest>");
     return SHM_OK;
 }

@@ -420,7 +420,9 @@ int upload_scene(ShmScene* s) {
     if (hipMemset(s->d_film, 0, s->n_film_pixels * sizeof(ShmFilmPixel)) != hipSuccess) { g_err = "hipMemset film"; return SHM_ERR_DEVICE; }
     if ((rc = dev_alloc<QueueState>(s, 1, &s->d_qs)) != SHM_OK) return rc;
     if ((rc = dev_alloc<DeviceCounters>(s, 1, &s->d_counters)) != SHM_OK) return rc;
-    if ((rc = dev_alloc<uint32_t>(s, 2 * 8 * 32, &s->d_heads3)) != SHM_OK) return rc;
+    uint32_t* heads = nullptr;
+    if ((rc = dev_alloc<uint32_t>(s, N_RAY * TRACE_QUEUE_PARTS * TRACE_HEAD_STRIDE, &heads)) != SHM_OK) return rc;
+    for (int ray = 0; ray < N_RAY; ++ray) s->trace[ray].d_heads = heads + ray * TRACE_QUEUE_PARTS * TRACE_HEAD_STRIDE;
     hipMemset(s->d_qs, 0, sizeof(QueueState));
     hipMemset(s->d_counters, 0, sizeof(DeviceCounters));
     return SHM_OK;
@@ -511,8 +513,8 @@ int shm_scene_create(const ShmSceneDesc* desc, int device, ShmScene** out) {
     s->lds_tables_small = wf_lds_tables(s, LDS_TABLE_BUDGET_SMALL);
     if (s->plan.tri_shade && (rc = build_tri_shade(s)) != SHM_OK) return fail(rc);
     if ((rc = wf_trace_prepare(s)) != SHM_OK) return fail(rc);
-    DBG("scene: %u nodes, depth %u, trace blocks %d / %d, spill levels %d / %d", (unsigned)s->flat.nodes.size(), s->flat.max_leaf_depth, s->trace3_blocks[0], s->trace3_blocks[1],
-        s->spill3_levels[0], s->spill3_levels[1]);
+    DBG("scene: %u nodes, depth %u, trace blocks %d / %d, spill levels %d / %d", (unsigned)s->flat.nodes.size(), s->flat.max_leaf_depth, s->trace[RAY_CLOSEST].blocks, s->trace[RAY_ANY].blocks,
+        s->trace[RAY_CLOSEST].spill_levels, s->trace[RAY_ANY].spill_levels);
     *out = s;
     return SHM_OK;
 }
@@ -726,10 +728,10 @@ static int render_batch(Render& r, const uint32_t* pixels, uint32_t n_pix) {
         hipEvent_t a = ev.get(), b = ev.get();
         hipEventRecord(a, s->stream);
         const bool first_lean = p.lean_first && bounce == 0;  // (the identity queue was not written: K2 takes slot = queue index, k_shade knows the constants)
-        TraceArgs closest{.stream = s->stream, .rays = s->pa.ray, .hits = s->pa.hit, .hit16 = (int)s->pa.hit16};
+        TraceArgs closest{.stream = s->stream, .rays = s->pa.ray, .hits = s->pa.hit, .hit16 = (int)s->pa.hit16, .hit2 = const_cast<float4*>(s->pa.hit2)};
         if (first_lean) closest.n_direct = total;
         else { closest.queue = s->d_q_active[cur]; closest.n_ptr = &s->d_qs->n_active[cur]; }
-        if ((rc = wf_launch_trace(s, false, closest)) != SHM_OK) return rc;
+        if ((rc = wf_launch_trace(s, RAY_CLOSEST, false, closest)) != SHM_OK) return rc;
         hipEventRecord(b, s->stream);
         r.ev_closest.push_back({a, b});
         if (overlap && k3_done) hipStreamWaitEvent(s->stream, k3_done, 0);  // shade(b) touches L and refills the shadow buffers
@@ -750,8 +752,8 @@ static int render_batch(Render& r, const uint32_t* pixels, uint32_t n_pix) {
             }
             hipEventRecord(c, any_stream);
             const TraceArgs shadow{.stream = any_stream, .queue = s->d_q_shadow, .n_ptr = &s->d_qs->n_shadow[sh], .rays = s->pa.shadow_ray, .L = s->pa.L,
-                                   .contrib = s->pa.shadow_contrib, .strict = params->disable_reference_quirks != 0};
-            if ((rc = wf_launch_trace(s, true, shadow)) != SHM_OK) return rc;
+                                   .contrib = s->pa.shadow_contrib};
+            if ((rc = wf_launch_trace(s, RAY_ANY, p.trace_any_strict, shadow)) != SHM_OK) return rc;
             hipEventRecord(d, any_stream);
             r.ev_any.push_back({c, d});
             k3_done = d;
@@ -912,11 +914,11 @@ static int trace_device_impl(ShmScene* s, bool any, const void* rays_dev, uint32
     for (int r = 0; r < repeat; ++r) {
         hipEvent_t a = ev.get(), b = ev.get();
         hipEventRecord(a, s->stream);
-        // (strict = false: the reference-exact any-hit kernels, whatever the scene's last render used)
+        // (not strict: the reference-exact any-hit kernels, whatever the scene's last render used; 32-byte hit records)
         TraceArgs t{.stream = s->stream, .n_direct = n, .rays = (const ShmRay*)rays_dev};
         if (any) t.occluded = (uint8_t*)out_dev;
         else t.hits = (ShmHit*)out_dev;
-        const int rc = wf_launch_trace(s, any, t);
+        const int rc = wf_launch_trace(s, any ? RAY_ANY : RAY_CLOSEST, false, t);
         if (rc != SHM_OK) return rc;
         hipEventRecord(b, s->stream);
         evs.push_back({a, b});

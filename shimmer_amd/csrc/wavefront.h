@@ -78,6 +78,8 @@ static inline bool dbg_on() { static int v = -1; if (v < 0) v = getenv("SHM_DEBU
 constexpr int WAVE = 64;
 constexpr int TRACE_BLOCK = 256;  // 4 waves per workgroup
 constexpr int SHADE_BLOCK = 128;
+// The traversal queue's partitions — one per XCD, with stealing — and the dwords between their head words: one 128-B line each (k_trace.hip)
+constexpr uint32_t TRACE_QUEUE_PARTS = 8, TRACE_HEAD_STRIDE = 32;
 
 // The DEVICE copy of a BVH node (host/bvh_pairs.hpp lays the tree out by sibling pairs and rewrites `offset` into a link word; the ABI's array and the
 // oracle's keep the reference's fields): everything a traversal step needs to go on from a node without reading it again —
@@ -333,6 +335,15 @@ using namespace wf;
 // ---------------------------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------------------------
+// One side of the traversal kernels' state, closest hit [RAY_CLOSEST] / any hit [RAY_ANY] — the any-hit kernel may run beside the closest-hit one (second stream):
+// sized by wf_trace_prepare from the scene's row of shm_plan::TRACE_SHAPES
+struct TraceSide {
+    int blocks = 0;                // the persistent grid
+    int spill_levels = 1;          // stack levels beyond the kernel's LDS levels (ScenePlan::trace_spill_levels) ...
+    uint32_t* d_spill = nullptr;   // ... per resident lane, in HBM
+    float4* d_gen_save = nullptr;  // trace5_body<., GEN> (scenes with spheres / patches / instances): per resident lane two 48-byte areas for the ray state
+    uint32_t* d_heads = nullptr;   // the queue's head words: [TRACE_QUEUE_PARTS][TRACE_HEAD_STRIDE]
+};
 struct ShmScene {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -362,23 +373,16 @@ struct ShmScene {
     size_t tiles_capacity = 0;
     std::vector<uint64_t> tile_bitmap;  // host scratch of the disjointness check in shm_render_wave
     int n_cu = 256;
-    // tuned traversal (k_trace5; the field names date from the retired one-node-step kernels)
-    int trace3_blocks[2] = {0, 0};   // persistent grid of the closest-hit [0] / any-hit [1] entry point this scene uses (k_trace.hip: K5Shape)
-    int spill3_levels[2] = {1, 1};   // stack levels beyond the entry point's LDS levels (HBM spill)
-    uint32_t* d_spill3 = nullptr;
+    TraceSide trace[shm_plan::N_RAY];
+    uint32_t* d_big_leaf_n = nullptr;  // n_prims by first primitive slot, only in scenes with a leaf of >= 7 primitives (LINK_COUNT_MAX: the link word holds smaller counts)
     LdsTables lds_tables = {};        // the small tables the shading kernels stage in LDS within the full budget (render.hip: wf_lds_tables)
     LdsTables lds_tables_small = {};  // ... within the 1.5 KB the material-sorted triangle vertex kernel has to spare
     uint32_t* d_q_emit = nullptr;      // paths of the current fused-kernel launch that hit an emitter (k_emit_jobs)
-    uint32_t* d_big_leaf_n = nullptr;  // n_prims by first primitive slot, only in scenes with a leaf of >= 7 primitives (LINK_COUNT_MAX: the link word holds smaller counts)
     float4* d_rw = nullptr;          // RandomWalk: (le, f cos) per depth per path, 2 * (max_depth + 1) * capacity float4
     size_t rw_floats4 = 0;
-    uint32_t* d_spill3_any = nullptr;  // the any-hit kernel may run concurrently with the closest-hit one (second stream)
-    float4* d_gen_save[2] = {nullptr, nullptr};  // k_trace5<., GEN> (scenes with spheres / patches / instances): per resident lane two 48-byte areas for the ray state (closest, any)
     hipStream_t stream2 = nullptr;
     hipStream_t stream_cls[4] = {nullptr, nullptr, nullptr, nullptr};  // staged shading: the scatter kernels of the 2nd .. 4th BxDF class of a bounce run beside the first one's
     uint32_t pix_group = 1024;      // path-slot order [tile][sample][pixel in tile] (>= n_pix would be sample-major; swept in round 1: profiles/r01_*)
-    int queue_parts = 8;           // the traversal queue's partitions, one per XCD with stealing
-    uint32_t* d_heads3 = nullptr;  // [2 (closest, any)][8 partitions][32 dwords: one 128-B line per head word]
     std::vector<hipEvent_t> events;
     struct DistState* dist = nullptr;  // multi-GPU state (dist.hip): communicator, this rank's tile shard, the gather plan
     uint32_t n_tri_shade_records = 0;   // the flat triangles' shading records built at scene creation (shm/tri_shade.h; shm_scene_shading_records) ...
@@ -406,8 +410,8 @@ struct EventPool {
 WF_INTERNAL LdsTables wf_lds_tables(const ShmScene* s, uint32_t budget);  // render.hip: which small tables fit `budget` bytes of LDS
 WF_INTERNAL void wf_trace_census();  // k_trace.hip: prints the per-phase lane census of a -DK5_CENSUS development build (a no-op otherwise)
 WF_INTERNAL void wf_layered_census();  // k_scatter_layered_staged_tri.hip: the same for a -DLJ_CENSUS build of the staged LayeredBxDF kernel
-WF_INTERNAL int wf_trace_prepare(ShmScene* s);  // grid sizes + stack spill buffers of the two traversal kernels (at scene creation)
-// k_trace.hip: BvhAggregate::intersect (any = false) / intersect_predicate (any = true) over a queue of path slots, or over slots 0 .. n_direct - 1 without one
+WF_INTERNAL int wf_trace_prepare(ShmScene* s);  // ShmScene::trace: grid sizes, stack spill and save areas of the scene's two traversal kernels (at scene creation)
+// k_trace.hip: BvhAggregate::intersect (RAY_CLOSEST) / intersect_predicate (RAY_ANY) over a queue of path slots, or over slots 0 .. n_direct - 1 without one
 struct TraceArgs {
     hipStream_t stream;
     const uint32_t* queue = nullptr;  // the path slots to trace, and their count (on the device)
@@ -418,10 +422,11 @@ struct TraceArgs {
     uint8_t* occluded = nullptr;      // any hit: one flag per ray, or
     float4* L = nullptr;              // ... `contrib` added to L where the ray is unoccluded
     const float4* contrib = nullptr;
-    int hit16 = 0;                    // the render's compact hit records (PathArrays::hit16)
-    bool strict = false;              // any hit in scenes with instances: PBRT-v4's way into an instance (ShmRenderParams::disable_reference_quirks; k_trace5_any_strict)
+    int hit16 = 0;                    // the render's compact hit records (PathArrays::hit16) ...
+    float4* hit2 = nullptr;           // ... and, in their split form, the second records (PathArrays::hit2)
 };
-WF_INTERNAL int wf_launch_trace(ShmScene* s, bool any, const TraceArgs& t);
+// (any_strict: RenderPlan::trace_any_strict — the any-hit kernels with PBRT-v4's way into an instance; the public trace entry points keep the reference-exact ones)
+WF_INTERNAL int wf_launch_trace(ShmScene* s, int ray, bool any_strict, const TraceArgs& t);
 // shading of one path vertex of PathIntegrator::li for every entry of q_active[cur]
 struct ShadeArgs {
     hipStream_t stream;

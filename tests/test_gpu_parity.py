@@ -191,6 +191,15 @@ def test_layered_walks_of_hundreds_of_steps(env):
     assert sg["rays_any"] > 1000  # (next-event estimation ran: the f and pdf walks too)
 
 
+TRACE_TRI, TRACE_GEN, TRACE_GEN_HEAVY = 0, 1, 2  # host/render_plan.hpp: the rows of the traversal kernels' table
+
+
+def _spilling_kernels(orc, gen_heavy_knob=-1):
+    """The (variant, ray kind) pairs whose HBM stack spill this scene really sizes from its depth (host/render_plan.hpp through the oracle: no GPU): two levels or more."""
+    plan = orc.trace_plan(gen_heavy_knob=gen_heavy_knob)
+    return {(plan["variant"], kind) for kind in ("closest", "any") if plan[f"spill_levels_{kind}"] >= 2}
+
+
 @pytest.mark.parametrize("other_min", ["16", "1", "64"])
 def test_trace_tree_shapes_and_parked_tests(env, monkeypatch, other_min):
     """The traversal kernels (k_trace5 / k_trace5<., GEN>: the both-children step) against the oracle's scalar loop — hit records, occlusion flags and all four visit
@@ -206,8 +215,10 @@ def test_trace_tree_shapes_and_parked_tests(env, monkeypatch, other_min):
             [scenes.instanced_scene(lib, 32, 24), scenes.three_spheres(lib, 32, 24, camera=(0.75, 0.5, 9.0)), scenes.cornell_box(lib, 32, 32, patches=True),
              scenes.ganesha_proxy(lib, 32, 32, n=64, variant="instanced"), scenes.ganesha_proxy(lib, 32, 32, n=24, variant="patch_emitter"),
              scenes.random_scene(lib, 3), scenes.random_scene(lib, 11)]
+    spilling = set()
     for sc in cases:
         gpu, orc = render.Renderer(lib, sc.desc, 0), oracle_py.Oracle(sc.desc)
+        spilling |= _spilling_kernels(orc)
         for seed, tmax, aim in ((5, np.inf, 0.5), (6, 2.5, 0.9)):
             rays = _rays(sc, 40000, seed, tmax, toward_centre=aim)
             hg, sg = gpu.trace(rays)
@@ -225,6 +236,8 @@ def test_trace_tree_shapes_and_parked_tests(env, monkeypatch, other_min):
             assert st[k] == so[k], (sc.name, k)
         gpu.close()
         orc.close()
+    # the case list holds a tree deeper than the LDS stack levels for both ray kinds of the triangle and the general kernels (the five-wave ones: the next test)
+    assert spilling >= {(v, kind) for v in (TRACE_TRI, TRACE_GEN) for kind in ("closest", "any")}
 
 
 @pytest.mark.parametrize("heavy", ["0", "1"])
@@ -236,8 +249,10 @@ def test_both_occupancies_of_the_general_traversal_kernels(env, monkeypatch, hea
     monkeypatch.setenv("SHM_GEN_HEAVY", heavy)
     cases = [(scenes.ganesha_proxy(lib, 64, 64, n=32, variant="quads"), 6, 5), (scenes.ganesha_proxy(lib, 48, 48, n=24, quad_fraction=0.3, coated=True), 4, 5),
              (scenes.cornell_box(lib, 48, 48, patches=True), 6, 5), (scenes.three_spheres(lib, 48, 32, camera=(0.75, 0.5, 9.0)), 4, 5), (scenes.instanced_scene(lib, 48, 36), 4, 6)]
+    spilling = set()
     for sc, spp, depth in cases:
         gpu, orc = render.Renderer(lib, sc.desc, 0), oracle_py.Oracle(sc.desc)
+        spilling |= _spilling_kernels(orc, gen_heavy_knob=int(heavy))
         rays = _rays(sc, 20000, 5)
         hg, sg = gpu.trace(rays)
         ho, so = orc.trace(rays)
@@ -261,6 +276,8 @@ def test_both_occupancies_of_the_general_traversal_kernels(env, monkeypatch, hea
             for k in ("paths", "rays_closest", "rays_any", "nodes_closest", "tris_closest", "nodes_any", "tris_any"):
                 assert stg[k] == sto[k], (sc.name, k)
         gpu.close(); orc.close()
+    # ... and at the occupancy forced here, a tree deeper than the kernels' LDS stack levels for both ray kinds (the STRICT pair runs on the any-hit side's spill)
+    assert spilling >= {(TRACE_GEN_HEAVY if heavy == "1" else TRACE_GEN, kind) for kind in ("closest", "any")}
 
 
 def test_trace_edge_cases(env):

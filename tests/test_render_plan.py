@@ -11,7 +11,10 @@ What is asserted, per combination:
 some render of that scene touches it — for the auxiliary rays, rng0 / pixel0 and filter_weight. The staging arrays (bx, the class queues, q_lean, q_split) and the
 lean kernel's e_* / q_emit are allocated by scene CLASS, as before the plan existed: every non-lean scene keeps them, also a scene whose every bounce the fused
 all-materials kernel shades (SHM_TAIL_FUSED_BOUNCE=0 without coated materials). There the assertion is the safety half — touched implies present — and
-test_staging_arrays_follow_the_scene_class pins the rule itself."""
+test_staging_arrays_follow_the_scene_class pins the rule itself.
+
+The traversal part of the plan — which row of the kernel table a scene's rays take, and the stack that row and the scene's tree need — is walked separately, through
+orc_fn_trace_plan (the tests at the end): the variant and strictness rules, the stack bound against the deepest leaf, and every row's LDS against the compute unit's."""
 import itertools
 import sys
 from pathlib import Path
@@ -187,3 +190,72 @@ def test_routes_and_hit_record_forms(plans):
     fused = q["fused_from"] != NEVER
     assert not np.any(fused & (((i["classes"] >> 3) & 1 != 0) | (i["force_diffuse"] != 0) | (q["route"] != ROUTE_STAGED)))
     assert np.array_equal(q["fused_from"][fused], np.where(i["tail_fused_bounce"][fused] < 0, NEVER, i["tail_fused_bounce"][fused]))
+
+
+# ---- the traversal part of the plan (TRACE_SHAPES, ScenePlan::trace_variant / trace_spill_levels, RenderPlan::trace_any_strict) through orc_fn_trace_plan ----
+TRACE_TRI, TRACE_GEN, TRACE_GEN_HEAVY = 0, 1, 2
+CU_LDS_BYTES = 160 << 10  # MI355X: the LDS of one compute unit
+STACK_LEVEL_BYTES = 256 * 8  # one stack level of a four-wave workgroup: 256 lanes x an 8-byte entry
+
+
+@pytest.fixture(scope="module")
+def trace_plans():
+    """Every scene the traversal plan can see: spheres x instances x patch-heavy x quadric / patch x the deepest leaf 0 .. 63 (flatten_scene refuses deeper trees) x
+    SHM_GEN_HEAVY (unset / 0 / 1) x disable_reference_quirks. 6 144 rows."""
+    rows = np.array(list(itertools.product((0, 1), (0, 1), (0, 1), (0, 1), range(64), (-1, 0, 1), (0, 1))), np.int32)
+    q = oracle_py.trace_plans(rows)
+    q["in"] = {n: rows[:, i] for i, n in enumerate(oracle_py.TRACE_IN)}
+    return q
+
+
+def test_trace_variant_and_strictness_follow_their_rules(trace_plans):
+    q, i = trace_plans, trace_plans["in"]
+    assert len(q["variant"]) == 2 * 2 * 2 * 2 * 64 * 3 * 2
+    heavy = (i["has_spheres"] != 0) & np.where(i["gen_heavy_knob"] >= 0, i["gen_heavy_knob"] != 0, i["patch_heavy"] != 0)
+    assert np.array_equal(q["variant"], np.where(i["has_spheres"] == 0, TRACE_TRI, np.where(heavy, TRACE_GEN_HEAVY, TRACE_GEN)))
+    assert set(np.unique(q["variant"])) == {TRACE_TRI, TRACE_GEN, TRACE_GEN_HEAVY}
+    assert np.array_equal(q["strict"] != 0, (i["has_instances"] != 0) & (i["disable_reference_quirks"] != 0))
+
+
+def test_trace_stack_holds_the_deepest_leaf(trace_plans):
+    """The stack a kernel gets — its LDS levels and the HBM spill sized at scene creation — against the tree: a ray's stack holds at most one entry per level it
+    descended, and the spill keeps one level beyond that. The STRICT any-hit kernels run on the any-hit side's spill: held to the same bound with their own LDS levels."""
+    q, i = trace_plans, trace_plans["in"]
+    depth = i["max_leaf_depth"]
+    for kind in ("closest", "any"):
+        lds, spill = q[f"lds_levels_{kind}"], q[f"spill_levels_{kind}"]
+        assert np.array_equal(spill, np.maximum(0, depth + 1 - lds) + 1)
+        assert np.all(lds + spill >= depth + 2) and spill.min() >= 1
+    assert np.all(q["strict_lds_levels"] + q["spill_levels_any"] >= depth + 2)
+
+
+def test_trace_rows_fit_the_lds_of_a_compute_unit(trace_plans):
+    """Per variant and ray kind: waves per SIMD — one four-wave workgroup each — x (stack levels + save area) within the CU's 160 KiB."""
+    q = trace_plans
+    seen = set()
+    for kind in ("closest", "any", "strict"):
+        waves, levels, lds = (q[f"strict_{c}"] for c in ("waves", "lds_levels", "lds_bytes")) if kind == "strict" else (q[f"{c}_{kind}"] for c in ("waves", "lds_levels", "lds_bytes"))
+        save = lds - levels * STACK_LEVEL_BYTES
+        assert set(np.unique(save)) <= {0, 12 << 10}
+        assert np.array_equal(save != 0, q["variant"] == TRACE_GEN_HEAVY)
+        assert np.all(waves * lds <= CU_LDS_BYTES) and waves.min() >= 1 and levels.min() >= 1
+        seen |= set(zip(q["variant"].tolist(), [kind] * len(waves), waves.tolist(), levels.tolist()))
+    # the table itself, as data: every (variant, ray kind) has ONE row, whatever the scene's depth, flags and knobs
+    rows = {(v, k): (w, l) for v, k, w, l in seen}
+    assert len(rows) == len(seen) == 9
+    assert rows[TRACE_TRI, "closest"] == (8, 9) and rows[TRACE_TRI, "any"] == (7, 11)
+    assert rows[TRACE_GEN, "closest"] == rows[TRACE_GEN, "any"] == (7, 11)
+    assert rows[TRACE_GEN_HEAVY, "closest"] == rows[TRACE_GEN_HEAVY, "any"] == (5, 9)
+
+
+def test_strict_kernels_take_the_general_any_hit_row(trace_plans):
+    """k_trace5_any_strict<heavy> is compiled from the GEN / GEN_HEAVY any-hit row, and launched on the grid and spill of the scene's own any-hit row: wherever a
+    render can be strict, the two rows are one."""
+    q = trace_plans
+    gen_any = {v: (int(q["waves_any"][q["variant"] == v][0]), int(q["lds_levels_any"][q["variant"] == v][0]), int(q["lds_bytes_any"][q["variant"] == v][0]))
+               for v in (TRACE_GEN, TRACE_GEN_HEAVY)}
+    want = np.array([gen_any[TRACE_GEN_HEAVY if v == TRACE_GEN_HEAVY else TRACE_GEN] for v in q["variant"]], np.int32)
+    assert np.array_equal(np.stack([q["strict_waves"], q["strict_lds_levels"], q["strict_lds_bytes"]], axis=1), want)
+    s = q["strict"] != 0
+    assert s.any()
+    assert np.array_equal(q["strict_waves"][s], q["waves_any"][s]) and np.array_equal(q["strict_lds_levels"][s], q["lds_levels_any"][s])

@@ -24,15 +24,11 @@ FLAGS = "--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -ffp-con
         "-fno-gpu-flush-denormals-to-zero -Wno-unused-result -Wno-unused-value -gline-tables-only".split()
 
 
-MARKS3 = [("setup", "template <bool ANY, bool TRI_ONLY, int LDS_N>"), ("refill", "// ---- refill idle lanes"),
-          ("node_step (load + slab test)", "// ---- one uniform node step"), ("leaf-mark / push", "// the three outcomes as selects"),
-          ("leaf_phase", "// ---- postponed leaf phase"), ("pop", "// ---- pop: a lane that missed"),
-          ("retire", "// ---- retire finished rays"), ("epilogue", "unsigned long long w_prims = c_prims;"), ("end", "#define K3_PARAMS")]
-MARKS5 = [("setup", "template <bool ANY, bool GEN, int LDS_N>"), ("refill (+ root test)", "// ---- refill idle lanes"),
+MARKS5 = [("setup", "template <bool ANY, bool GEN, int LDS_N"), ("refill (+ root test)", "// ---- refill idle lanes"),
           ("pair_step (2 x (load + slab test) + push)", "// ---- one uniform step: every lane that stands"),
           ("leaf_phase", "// ---- postponed leaf phase: lanes standing"), ("other_phase (GEN: sphere / patch / instance)", "// ---- GEN: the parked non-triangle tests"),
           ("pop", "// ---- pop: a lane whose two children"),
-          ("retire", "// ---- retire finished rays"), ("epilogue", "unsigned long long wn = c_nodes;"), ("end", "#ifndef K5_CLOSEST_WAVES")]  # (MARKS3: the retired one-node-step body; profiles/r03_k_trace3_isa*.txt were made with it)
+          ("retire", "// ---- retire finished rays"), ("epilogue", "unsigned long long wn = c_nodes;"), ("end", "// ---- the entry points: one per row")]  # (the profiles of round 3 were made with the marks of the retired one-node-step body)
 
 
 def sections_of(src_lines, marks, first_line=0):
@@ -80,9 +76,9 @@ def main():
         m = re.match(r'\s*\.file\s+(\d+)\s+"([^"]*)"(?:\s+"([^"]*)")?', l)
         if m:
             files[int(m.group(1))] = m.group(3) or m.group(2)
-    lines_out = [f"# static instruction census of the traversal kernels by section of trace5_body / trace3_body (tools/isa_sections.py; hipcc {' '.join(FLAGS[:3])} ...)"]
-    for label, want, secs in (("k_trace5<closest> (both-children step)", "k_trace5ILb0ELb0EE", secs5), ("k_trace5<any>", "k_trace5ILb1ELb0EE", secs5),
-                              ("k_trace5<closest, GEN> (scenes with spheres / patches / instances)", "k_trace5ILb0ELb1EE", secs5), ("k_trace5<any, GEN>", "k_trace5ILb1ELb1EE", secs5)):
+    lines_out = [f"# static instruction census of the traversal kernels by section of trace5_body (tools/isa_sections.py; hipcc {' '.join(FLAGS[:3])} ...)"]
+    for label, want, secs in (("k_trace5<closest> (both-children step)", "k_trace5ILb0ELb0ELb0EE", secs5), ("k_trace5<any>", "k_trace5ILb1ELb0ELb0EE", secs5),
+                              ("k_trace5<closest, GEN> (scenes with spheres / patches / instances)", "k_trace5ILb0ELb1ELb0EE", secs5), ("k_trace5<any, GEN>", "k_trace5ILb1ELb1ELb0EE", secs5)):
         start = next(i for i, l in enumerate(asm) if re.match(r"^_ZN.*" + want + r".*:", l))
         end = next(i for i in range(start, len(asm)) if asm[i].strip().startswith(".Lfunc_end"))
         counts = defaultdict(lambda: defaultdict(int))
