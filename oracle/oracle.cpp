@@ -1415,6 +1415,24 @@ void orc_fn_trace_plan(const int32_t* in, int n, int32_t* out) {
         memcpy(out, cols, sizeof(cols));
     }
 }
+// The shading launchers' serving rule (host/render_plan.hpp: serving_build) as data: out[family][geo][img] = {geo', img'} of the build that serves the cell, {-1, -1}
+// where none does; N_FAM * N_GEO * N_IMG * 2 int32. Returns N_FAM; orc_fn_shade_family_names: the families, comma-separated, in the enum's order.
+int orc_fn_shade_serving(int32_t* out) {
+    using namespace shm_plan;
+    for (int f = 0; f < N_FAM; ++f)
+        for (int g = 0; g < N_GEO; ++g)
+            for (int i = 0; i < N_IMG; ++i) {
+                const ShadeBuild b = serving_build(f, g, i);
+                *out++ = b.geo; *out++ = b.img;
+            }
+    return N_FAM;
+}
+const char* orc_fn_shade_family_names() {
+    using namespace shm_plan;
+    static_assert(FAM_LEAN == 0 && FAM_LEAN_DIVERTED == 1 && FAM_FUSED_ALL == 2 && FAM_VERTEX == 3 && FAM_SCATTER_DIFFUSE == 4 && FAM_SCATTER_CONDUCTOR == 5 &&
+                  FAM_SCATTER_DIELECTRIC == 6 && FAM_SCATTER_LAYERED == 7 && FAM_SCATTER_LAYERED_ONEPASS == 8 && FAM_SIMPLE == 9 && FAM_RANDOMWALK == 10 && N_FAM == 11, "the names' order");
+    return "LEAN,LEAN_DIVERTED,FUSED_ALL,VERTEX,SCATTER_DIFFUSE,SCATTER_CONDUCTOR,SCATTER_DIELECTRIC,SCATTER_LAYERED,SCATTER_LAYERED_ONEPASS,SIMPLE,RANDOMWALK";
+}
 // a scene's own input row of orc_fn_trace_plan, less the knob and the render's option: which traversal plan a real scene gets (tests/test_gpu_parity.py)
 void orc_fn_scene_trace_facts(OrcScene* s, int32_t* out) {
     const shm_plan::SceneFacts f = shm_plan::scene_facts(reinterpret_cast<Oracle*>(s)->flat);

@@ -141,6 +141,8 @@ def load():
     lib.orc_fn_ws_array_names.restype, lib.orc_fn_ws_array_names.argtypes = C.c_char_p, []
     lib.orc_fn_trace_plan.restype, lib.orc_fn_trace_plan.argtypes = None, [IP32, C.c_int, IP32]
     lib.orc_fn_scene_trace_facts.restype, lib.orc_fn_scene_trace_facts.argtypes = None, [C.c_void_p, IP32]
+    lib.orc_fn_shade_serving.restype, lib.orc_fn_shade_serving.argtypes = C.c_int, [IP32]
+    lib.orc_fn_shade_family_names.restype, lib.orc_fn_shade_family_names.argtypes = C.c_char_p, []
     lib.orc_fn_bvh_pairs.restype = C.c_int
     lib.orc_fn_bvh_pairs.argtypes = [NP, C.c_uint32, UP32, C.c_uint32, UP32, C.c_uint32, NP, UP32, UP32, C.POINTER(C.c_int), UP32, UP32, NP]
     _lib = lib
@@ -192,6 +194,16 @@ def trace_plans(rows):
     IP32 = C.POINTER(C.c_int32)
     lib.orc_fn_trace_plan(rows.ctypes.data_as(IP32), rows.shape[0], out.ctypes.data_as(IP32))
     return {name: out[:, i] for i, name in enumerate(TRACE_OUT)}
+
+
+def shade_serving():
+    """The shading launchers' serving rule (host/render_plan.hpp, serving_build): (the families' names in the enum's order, an int32 array [family][geo][img][2] —
+    the (geo, img) of the build that serves the cell, (-1, -1) where none does)."""
+    lib = load()
+    names = lib.orc_fn_shade_family_names().decode().split(",")
+    out = np.full((len(names), 2, 3, 2), -2, np.int32)
+    assert lib.orc_fn_shade_serving(out.ctypes.data_as(C.POINTER(C.c_int32))) == len(names)
+    return names, out
 
 
 def sampler_stream_zs(px, py, index, spp, rx, ry, seed, none, kinds):

@@ -22,8 +22,32 @@ enum : int { IMG_NONE, IMG_TEX, IMG_ENV, N_IMG };  // no image / image textures 
 enum : int { FLT_BOX, FLT_TRIANGLE, FLT_TABULATED, FLT_TABULATED_SIGNED, N_FLT };
 enum : int { ROUTE_LEAN, ROUTE_STAGED, ROUTE_SIMPLE, ROUTE_RANDOM_WALK };
 constexpr int NEVER = 1 << 30;  // a bounce no render reaches (max_depth <= 254)
-// The table's null cells, by image class: the textured classes have no lean kernel (direct or diverted) and no k_generate<., LEAN>. render.hip holds its table to this.
+// The table's null cells, by image class: the textured classes have no lean kernel (direct or diverted) and no k_generate<., LEAN>. serving_build (below) goes by it; render.hip holds
+// its k_generate cells to it.
 constexpr bool HAS_LEAN_KERNELS[N_IMG] = {true, false, true};
+// The shading launchers by family (wavefront.h: wf_shade<FAMILY, GEO, IMG, ZS, DL>), and the ONE rule for which build of a family serves a cell of the table. A build
+// goes by the coordinates of the cell it was written for; a family with fewer builds than cells has some of them serve several:
+//   LEAN, LEAN_DIVERTED      k_shade<lean>, over the whole queue / over q_lean: a build per cell that has lean kernels, none for the textured class
+//   FUSED_ALL                the material-sorted fused all-materials kernel: a build per cell
+//   VERTEX, SCATTER + class  staged shading (SCATTER_LAYERED: the dense per-wave stages): a build per geometry without textures and under an environment map; ONE textured
+//                            build, <TRI_ONLY = false, HAS_TEX = true>, for both geometries: (GEN, TEX)
+//   SCATTER_LAYERED_ONEPASS  the LayeredBxDF class in one pass per vertex: as above, but no K_ENV_LIGHT build — it runs under options.force_diffuse, where the image
+//                            class is never env (render_plan, below): the env cells get the build without the light
+//   SIMPLE, RANDOMWALK       the other integrators: one build of every material and shape kind for every cell, filed under (GEN, TEX)
+// 44 builds in all (tests/test_render_plan.py counts them); render.hip computes its table from this function and a build that is missing fails the link.
+enum : int { FAM_LEAN, FAM_LEAN_DIVERTED, FAM_FUSED_ALL, FAM_VERTEX, FAM_SCATTER, FAM_SCATTER_DIFFUSE = FAM_SCATTER + CLS_DIFFUSE, FAM_SCATTER_CONDUCTOR = FAM_SCATTER + CLS_CONDUCTOR,
+              FAM_SCATTER_DIELECTRIC = FAM_SCATTER + CLS_DIELECTRIC, FAM_SCATTER_LAYERED = FAM_SCATTER + CLS_LAYERED, FAM_SCATTER_LAYERED_ONEPASS, FAM_SIMPLE, FAM_RANDOMWALK, N_FAM };
+constexpr int scatter_class(int family) { return family == FAM_SCATTER_LAYERED_ONEPASS ? CLS_LAYERED : family - FAM_SCATTER; }  // the queue a SCATTER family works through
+struct ShadeBuild { int geo, img; };
+constexpr ShadeBuild NO_BUILD = {-1, -1};
+constexpr bool has_build(const ShadeBuild& b) { return b.geo >= 0; }
+constexpr ShadeBuild serving_build(int family, int geo, int img) {
+    if (family == FAM_LEAN || family == FAM_LEAN_DIVERTED) return HAS_LEAN_KERNELS[img] ? ShadeBuild{geo, img} : NO_BUILD;
+    if (family == FAM_FUSED_ALL) return {geo, img};
+    if (family == FAM_SIMPLE || family == FAM_RANDOMWALK) return {GEO_GEN, IMG_TEX};
+    if (img == IMG_TEX) return {GEO_GEN, IMG_TEX};
+    return {geo, family == FAM_SCATTER_LAYERED_ONEPASS ? IMG_NONE : img};
+}
 
 // What flatten_scene found, as far as a decision reads it
 struct SceneFacts {

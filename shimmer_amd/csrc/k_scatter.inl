@@ -406,15 +406,19 @@ __global__ void __launch_bounds__(SHADE2_BLOCK) K_SHADE_ATTR k_scatter_nonspecul
 }
 }  // namespace
 
-#define WF_SCATTER_LAUNCH(CLASS, TRI, TEX)                                                                                                      \
+using namespace shm_plan;  // (the builds' coordinates: GEO_*, IMG_*, FAM_*)
+// KERNEL (k_scatter or one of its two halves) of a build (GEO, IMG) (wavefront.h: build_tri_only, build_has_tex) over the queue of CLASS, on BLOCKS workgroups
+#define WF_SCATTER_LAUNCH_SUB(GEO, IMG, CLASS, KERNEL, BLOCKS)                                                                                   \
     do {                                                                                                                                        \
-        hipLaunchKernelGGL((k_scatter<CLASS, TRI, TEX>), dim3(a.blocks), dim3(SHADE2_BLOCK), 0, a.stream, s->dsv, s->pa, s->d_q_scatter[CLASS], \
-                           s->d_q_active[a.cur ^ 1], s->d_q_shadow, s->d_qs, a.cur, a.params, a.shadow_parity, s->lds_tables);                                \
-        LAUNCH_TRY("k_scatter");                                                                                                                \
-    } while (0)
-#define WF_SCATTER_LAUNCH_SUB(KERNEL, BLOCKS, CLASS, TRI, TEX)                                                                                   \
-    do {                                                                                                                                        \
-        hipLaunchKernelGGL((KERNEL<CLASS, TRI, TEX>), dim3(BLOCKS), dim3(SHADE2_BLOCK), 0, a.stream, s->dsv, s->pa, s->d_q_scatter[CLASS],         \
+        hipLaunchKernelGGL((KERNEL<CLASS, build_tri_only(GEO), build_has_tex(IMG)>), dim3(BLOCKS), dim3(SHADE2_BLOCK), 0, a.stream, s->dsv, s->pa, s->d_q_scatter[CLASS], \
                            s->d_q_active[a.cur ^ 1], s->d_q_shadow, s->d_qs, a.cur, a.params, a.shadow_parity, s->lds_tables);                                \
         LAUNCH_TRY(#KERNEL);                                                                                                                    \
     } while (0)
+#define WF_SCATTER_LAUNCH(GEO, IMG, CLASS) WF_SCATTER_LAUNCH_SUB(GEO, IMG, CLASS, k_scatter, a.blocks)
+// A SCATTER family's launcher of one build: its coordinates, its queue (shm_plan::scatter_class) and the kernel's class from the same tokens
+#define WF_SCATTER_STUB(FAMILY, GEO, IMG)                                                                                                       \
+    template <> int wf_shade<FAMILY, GEO, IMG, K_ZSOBOL, K_DELTA_LIGHTS>(ShmScene* s, const ShadeArgs& a) {                                     \
+        WF_ENV_UNIT_CHECK(IMG);                                                                                                                 \
+        WF_SCATTER_LAUNCH(GEO, IMG, scatter_class(FAMILY));                                                                                     \
+        return SHM_OK;                                                                                                                          \
+    }

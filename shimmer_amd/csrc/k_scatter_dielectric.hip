@@ -6,24 +6,23 @@
 // material table holds a dielectric that can be rough) by the general kernel; each skips the other's entries.
 // (one body for the three launchers, which names the kernels in the order they are instantiated in — the order of the code object, on which the compiler's register
 //  allocation depends: named scene class by scene class, the rough-dielectric kernels spilled other SGPR counts)
-static int launch_dielectric(ShmScene* s, const ShadeArgs& a, bool tri_only, bool has_tex) {
+#define WF_DIELECTRIC_LAUNCH(KERNEL, BLOCKS)                                                                          \
+    do {                                                                                                              \
+        if (img == IMG_TEX) WF_SCATTER_LAUNCH_SUB(GEO_GEN, IMG_TEX, CLASS_DIELECTRIC, KERNEL, BLOCKS);                \
+        else if (geo == GEO_TRI) WF_SCATTER_LAUNCH_SUB(GEO_TRI, IMG_NONE, CLASS_DIELECTRIC, KERNEL, BLOCKS);          \
+        else WF_SCATTER_LAUNCH_SUB(GEO_GEN, IMG_NONE, CLASS_DIELECTRIC, KERNEL, BLOCKS);                              \
+    } while (0)
+static int launch_dielectric(ShmScene* s, const ShadeArgs& a, int geo, int img) {
     if (a.params.force_diffuse != 0 || a.params.regularize != 0) {
-        if (has_tex) WF_SCATTER_LAUNCH(CLASS_DIELECTRIC, false, true);
-        else if (tri_only) WF_SCATTER_LAUNCH(CLASS_DIELECTRIC, true, false);
-        else WF_SCATTER_LAUNCH(CLASS_DIELECTRIC, false, false);
+        WF_DIELECTRIC_LAUNCH(k_scatter, a.blocks);
         return SHM_OK;
     }
-    const int spec_blocks = s->n_cu * 4;
-    if (has_tex) WF_SCATTER_LAUNCH_SUB(k_scatter_specular, spec_blocks, CLASS_DIELECTRIC, false, true);
-    else if (tri_only) WF_SCATTER_LAUNCH_SUB(k_scatter_specular, spec_blocks, CLASS_DIELECTRIC, true, false);
-    else WF_SCATTER_LAUNCH_SUB(k_scatter_specular, spec_blocks, CLASS_DIELECTRIC, false, false);
-    if (s->flat.has_rough_dielectric) {
-        if (has_tex) WF_SCATTER_LAUNCH_SUB(k_scatter_nonspecular, a.blocks, CLASS_DIELECTRIC, false, true);
-        else if (tri_only) WF_SCATTER_LAUNCH_SUB(k_scatter_nonspecular, a.blocks, CLASS_DIELECTRIC, true, false);
-        else WF_SCATTER_LAUNCH_SUB(k_scatter_nonspecular, a.blocks, CLASS_DIELECTRIC, false, false);
-    }
+    WF_DIELECTRIC_LAUNCH(k_scatter_specular, s->n_cu * 4);
+    if (s->flat.has_rough_dielectric) WF_DIELECTRIC_LAUNCH(k_scatter_nonspecular, a.blocks);
     return SHM_OK;
 }
-template <> int wf_launch_scatter_dielectric_tex<K_ZSOBOL, K_DELTA_LIGHTS>(ShmScene* s, const ShadeArgs& a) { return launch_dielectric(s, a, false, true); }
-template <> int wf_launch_scatter_dielectric_tri<K_ZSOBOL, K_DELTA_LIGHTS>(ShmScene* s, const ShadeArgs& a) { return launch_dielectric(s, a, true, false); }
-template <> int wf_launch_scatter_dielectric_gen<K_ZSOBOL, K_DELTA_LIGHTS>(ShmScene* s, const ShadeArgs& a) { return launch_dielectric(s, a, false, false); }
+#define WF_DIELECTRIC_STUB(GEO, IMG) \
+    template <> int wf_shade<FAM_SCATTER_DIELECTRIC, GEO, IMG, K_ZSOBOL, K_DELTA_LIGHTS>(ShmScene* s, const ShadeArgs& a) { WF_ENV_UNIT_CHECK(IMG); return launch_dielectric(s, a, GEO, IMG); }
+WF_DIELECTRIC_STUB(GEO_GEN, IMG_TEX)
+WF_DIELECTRIC_STUB(GEO_TRI, IMG_NONE)
+WF_DIELECTRIC_STUB(GEO_GEN, IMG_NONE)

@@ -4,20 +4,21 @@
 #include "k_scatter.inl"
 
 // (one body for both launchers, as in k_scatter_dielectric.hip)
-static int launch_dielectric(ShmScene* s, const ShadeArgs& a, bool tri_only) {
+#define WF_DIELECTRIC_LAUNCH(KERNEL, BLOCKS)                                                                          \
+    do {                                                                                                              \
+        if (geo == GEO_TRI) WF_SCATTER_LAUNCH_SUB(GEO_TRI, IMG_ENV, CLASS_DIELECTRIC, KERNEL, BLOCKS);                \
+        else WF_SCATTER_LAUNCH_SUB(GEO_GEN, IMG_ENV, CLASS_DIELECTRIC, KERNEL, BLOCKS);                               \
+    } while (0)
+static int launch_dielectric(ShmScene* s, const ShadeArgs& a, int geo) {
     if (a.params.regularize != 0) {
-        if (tri_only) WF_SCATTER_LAUNCH(CLASS_DIELECTRIC, true, false);
-        else WF_SCATTER_LAUNCH(CLASS_DIELECTRIC, false, false);
+        WF_DIELECTRIC_LAUNCH(k_scatter, a.blocks);
         return SHM_OK;
     }
-    const int spec_blocks = s->n_cu * 4;
-    if (tri_only) WF_SCATTER_LAUNCH_SUB(k_scatter_specular, spec_blocks, CLASS_DIELECTRIC, true, false);
-    else WF_SCATTER_LAUNCH_SUB(k_scatter_specular, spec_blocks, CLASS_DIELECTRIC, false, false);
-    if (s->flat.has_rough_dielectric) {
-        if (tri_only) WF_SCATTER_LAUNCH_SUB(k_scatter_nonspecular, a.blocks, CLASS_DIELECTRIC, true, false);
-        else WF_SCATTER_LAUNCH_SUB(k_scatter_nonspecular, a.blocks, CLASS_DIELECTRIC, false, false);
-    }
+    WF_DIELECTRIC_LAUNCH(k_scatter_specular, s->n_cu * 4);
+    if (s->flat.has_rough_dielectric) WF_DIELECTRIC_LAUNCH(k_scatter_nonspecular, a.blocks);
     return SHM_OK;
 }
-template <> int wf_launch_scatter_dielectric_tri_env<K_ZSOBOL, K_DELTA_LIGHTS>(ShmScene* s, const ShadeArgs& a) { return launch_dielectric(s, a, true); }
-template <> int wf_launch_scatter_dielectric_gen_env<K_ZSOBOL, K_DELTA_LIGHTS>(ShmScene* s, const ShadeArgs& a) { return launch_dielectric(s, a, false); }
+#define WF_DIELECTRIC_STUB(GEO) \
+    template <> int wf_shade<FAM_SCATTER_DIELECTRIC, GEO, IMG_ENV, K_ZSOBOL, K_DELTA_LIGHTS>(ShmScene* s, const ShadeArgs& a) { WF_ENV_UNIT_CHECK(IMG_ENV); return launch_dielectric(s, a, GEO); }
+WF_DIELECTRIC_STUB(GEO_TRI)
+WF_DIELECTRIC_STUB(GEO_GEN)

@@ -2,5 +2,5 @@
 #define K_ENV_LIGHT true
 #include "k_scatter.inl"
 
-template <> int wf_launch_scatter_diffuse_tri_env<K_ZSOBOL, K_DELTA_LIGHTS>(ShmScene* s, const ShadeArgs& a) { WF_SCATTER_LAUNCH(CLASS_DIFFUSE, true, false); return SHM_OK; }
-template <> int wf_launch_scatter_diffuse_gen_env<K_ZSOBOL, K_DELTA_LIGHTS>(ShmScene* s, const ShadeArgs& a) { WF_SCATTER_LAUNCH(CLASS_DIFFUSE, false, false); return SHM_OK; }
+WF_SCATTER_STUB(FAM_SCATTER_DIFFUSE, GEO_TRI, IMG_ENV)
+WF_SCATTER_STUB(FAM_SCATTER_DIFFUSE, GEO_GEN, IMG_ENV)

@@ -467,9 +467,13 @@ __global__ void __launch_bounds__(SHADE2_BLOCK) K_SHADE_ATTR k_scatter_layered(S
 
 }  // namespace
 
-#define WF_SCATTER_LAYERED_LAUNCH(TRI, TEX)                                                                                                          \
-    do {                                                                                                                                             \
-        hipLaunchKernelGGL((k_scatter_layered<TRI, TEX>), dim3(a.blocks), dim3(SHADE2_BLOCK), 0, a.stream, s->dsv, s->pa, s->d_q_scatter[CLASS_LAYERED], \
+using namespace shm_plan;  // (the builds' coordinates: GEO_*, IMG_*, FAM_*)
+// FAM_SCATTER_LAYERED of one build (GEO, IMG): the launcher's coordinates and the kernel's class (wavefront.h: build_tri_only, build_has_tex) from the same tokens
+#define WF_SCATTER_LAYERED_STUB(GEO, IMG)                                                                                                            \
+    template <> int wf_shade<FAM_SCATTER_LAYERED, GEO, IMG, K_ZSOBOL, K_DELTA_LIGHTS>(ShmScene* s, const ShadeArgs& a) {                             \
+        WF_ENV_UNIT_CHECK(IMG);                                                                                                                      \
+        hipLaunchKernelGGL((k_scatter_layered<build_tri_only(GEO), build_has_tex(IMG)>), dim3(a.blocks), dim3(SHADE2_BLOCK), 0, a.stream, s->dsv, s->pa, s->d_q_scatter[CLASS_LAYERED], \
                            s->d_q_active[a.cur ^ 1], s->d_q_shadow, s->d_qs, a.cur, a.params, a.shadow_parity, s->lds_tables_small);                   \
         LAUNCH_TRY("k_scatter_layered");                                                                                                             \
-    } while (0)
+        return SHM_OK;                                                                                                                               \
+    }

@@ -4,7 +4,4 @@
 #define SHM_BASE_BXDF_CALL SHM_HD_NOINLINE  // the walks call the interface BxDFs instead of inlining them ~30 times
 #include "k_scatter.inl"
 
-template <> int wf_launch_scatter_layered_gen<K_ZSOBOL, K_DELTA_LIGHTS>(ShmScene* s, const ShadeArgs& a) {
-    WF_SCATTER_LAUNCH(CLASS_LAYERED, false,false);
-    return SHM_OK;
-}
+WF_SCATTER_STUB(FAM_SCATTER_LAYERED_ONEPASS, GEO_GEN, IMG_NONE)

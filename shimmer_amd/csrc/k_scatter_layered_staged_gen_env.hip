@@ -5,7 +5,4 @@
 #define K_ENV_LIGHT true
 #include "k_scatter_layered.inl"
 
-template <> int wf_launch_scatter_layered_staged_gen_env<K_ZSOBOL, K_DELTA_LIGHTS>(ShmScene* s, const ShadeArgs& a) {
-    WF_SCATTER_LAYERED_LAUNCH(false, false);
-    return SHM_OK;
-}
+WF_SCATTER_LAYERED_STUB(GEO_GEN, IMG_ENV)

@@ -3,7 +3,4 @@
 #define SHM_BASE_BXDF_CALL SHM_HD_NOINLINE  // the walks call the interface BxDFs instead of inlining them ~30 times
 #include "k_scatter_layered.inl"
 
-template <> int wf_launch_scatter_layered_staged_tex<K_ZSOBOL, K_DELTA_LIGHTS>(ShmScene* s, const ShadeArgs& a) {
-    WF_SCATTER_LAYERED_LAUNCH(false, true);
-    return SHM_OK;
-}
+WF_SCATTER_LAYERED_STUB(GEO_GEN, IMG_TEX)

@@ -3,10 +3,7 @@
 #define SHM_BASE_BXDF_CALL SHM_HD_NOINLINE  // the walks call the interface BxDFs instead of inlining them ~30 times
 #include "k_scatter_layered.inl"
 
-template <> int wf_launch_scatter_layered_staged_tri<K_ZSOBOL, K_DELTA_LIGHTS>(ShmScene* s, const ShadeArgs& a) {
-    WF_SCATTER_LAYERED_LAUNCH(true, false);
-    return SHM_OK;
-}
+WF_SCATTER_LAYERED_STUB(GEO_TRI, IMG_NONE)
 
 #if !K_ZSOBOL && !K_DELTA_LIGHTS  // (once in the library)
 // development build (-DLJ_CENSUS=1): what the four stages did, printed at scene destruction

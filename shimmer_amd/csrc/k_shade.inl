@@ -457,12 +457,15 @@ __global__ void __launch_bounds__(SHADE2_BLOCK) k_emit_jobs(SceneView sv, PathAr
 }  // namespace
 
 
-#define WF_EMIT_JOBS_LAUNCH(CTX_AS_HIT)                                                                                                      \
+using namespace shm_plan;  // (the builds' coordinates: GEO_*, IMG_*, FAM_*)
+// The launches below read a build's (GEO, IMG) (wavefront.h: build_tri_only, build_has_tex, build_env_light), and the stubs at the end define the launchers from the
+// same tokens: a unit writes WF_SHADE_LEAN_STUBS(GEO_GEN, IMG_ENV) and gets the specializations at those coordinates, launching that class's kernels.
+#define WF_EMIT_JOBS_LAUNCH(GEO, CTX_AS_HIT)                                                                                                 \
     do {                                                                                                                                     \
-        hipLaunchKernelGGL((k_emit_jobs<true, false>), dim3(s->n_cu * 4), dim3(SHADE2_BLOCK), 0, a.stream, s->dsv, s->pa, s->d_q_emit, s->d_qs, (CTX_AS_HIT)); \
+        hipLaunchKernelGGL((k_emit_jobs<build_tri_only(GEO), false>), dim3(s->n_cu * 4), dim3(SHADE2_BLOCK), 0, a.stream, s->dsv, s->pa, s->d_q_emit, s->d_qs, (CTX_AS_HIT)); \
         LAUNCH_TRY("k_emit_jobs");                                                                                                           \
     } while (0)
-#define WF_SHADE_LAUNCH(KERNEL)                                                                                                              \
+#define WF_SHADE_LAUNCH(KERNEL, CTX_AS_HIT_FLAG)                                                                                             \
     do {                                                                                                                                     \
         hipLaunchKernelGGL(KERNEL, dim3(s->n_cu * K_SHADE_LEAN_WAVES), dim3(SHADE2_BLOCK), 0, a.stream, s->dsv, s->pa, s->d_q_active[a.cur], s->d_q_active[a.cur ^ 1], \
                            s->d_q_shadow, s->d_qs, a.cur, a.params, s->d_counters, a.shadow_parity, (const uint32_t*)nullptr, s->d_q_emit, s->lds_tables, a.first_bounce | (CTX_AS_HIT_FLAG)); \
@@ -474,3 +477,29 @@ __global__ void __launch_bounds__(SHADE2_BLOCK) k_emit_jobs(SceneView sv, PathAr
                            s->d_q_shadow, s->d_qs, a.cur, a.params, s->d_counters, a.shadow_parity, (const uint32_t*)&s->d_qs->n_lean, s->d_q_emit, s->lds_tables, 0); \
         LAUNCH_TRY("k_shade (diverted)");                                                                                                    \
     } while (0)
+// k_shade<HAS_LAYERED = false, TRI_ONLY, HAS_TEX, DIFFUSE_ONLY, EMIT_INLINE, SORT_CHUNK, ENV_LIGHT> of a build: the lean kernel defers its emitter hits (k_emit_jobs),
+// the fused all-materials one handles them inline and sorts its chunks by material
+#define WF_K_SHADE_LEAN(GEO, IMG) k_shade<false, build_tri_only(GEO), build_has_tex(IMG), true, false, false, build_env_light(IMG)>
+#define WF_K_SHADE_FUSED_ALL(GEO, IMG) k_shade<false, build_tri_only(GEO), build_has_tex(IMG), false, true, true, build_env_light(IMG)>
+// FAM_LEAN and FAM_LEAN_DIVERTED of one build. A triangle scene that runs the kernel alone leaves a vertex's hit record, not its LightSampleContext, for the next
+// vertex's emitter MIS weight (ctx_as_hit; round 4 A/B: DESIGN.md section 6) — the 16-byte hit-record forms need triangle hits: with spheres, patches or instances the
+// records are the 32-byte ShmHit (t, phi, instance) and the vertex leaves its context. k_emit_jobs: emission of the vertices that hit an emitter, before K3 adds this
+// bounce's shadow contributions. The diverted launcher works through the queue k_vertex or the split pass diverted plain-diffuse hits to (a scene that also holds other
+// materials): for those vertices the fused kernel beats the staged pair — no parameter block to write and read back ("staged shading").
+#define WF_SHADE_LEAN_STUBS(GEO, IMG)                                                                                                        \
+    template <> int wf_shade<FAM_LEAN, GEO, IMG, K_ZSOBOL, K_DELTA_LIGHTS>(ShmScene* s, const ShadeArgs& a) {                      \
+        constexpr int ctx_as_hit = build_tri_only(GEO) ? 1 : 0;                                                                              \
+        WF_SHADE_LAUNCH((WF_K_SHADE_LEAN(GEO, IMG)), (ctx_as_hit << 1) | ((ctx_as_hit && a.hit_kept) ? 4 : 0));                              \
+        WF_EMIT_JOBS_LAUNCH(GEO, ctx_as_hit);                                                                                                \
+        return SHM_OK;                                                                                                                       \
+    }                                                                                                                                        \
+    template <> int wf_shade<FAM_LEAN_DIVERTED, GEO, IMG, K_ZSOBOL, K_DELTA_LIGHTS>(ShmScene* s, const ShadeArgs& a) {             \
+        WF_SHADE_LAUNCH_DIVERTED((WF_K_SHADE_LEAN(GEO, IMG)));                                                                               \
+        WF_EMIT_JOBS_LAUNCH(GEO, 0);                                                                                                         \
+        return SHM_OK;                                                                                                                       \
+    }
+#define WF_SHADE_FUSED_ALL_STUB(GEO, IMG)                                                                                                    \
+    template <> int wf_shade<FAM_FUSED_ALL, GEO, IMG, K_ZSOBOL, K_DELTA_LIGHTS>(ShmScene* s, const ShadeArgs& a) {                 \
+        WF_SHADE_LAUNCH((WF_K_SHADE_FUSED_ALL(GEO, IMG)), 0);                                                                                \
+        return SHM_OK;                                                                                                                       \
+    }

@@ -289,13 +289,15 @@ __global__ void __launch_bounds__(SHADE_BLOCK) k_fold_randomwalk(PathArrays pa, 
 #endif
 }  // namespace
 
-template <> int wf_launch_shade_simple<K_ZSOBOL, K_DELTA_LIGHTS>(ShmScene* s, const ShadeArgs& a) {
+using namespace shm_plan;
+// (one build each, of every material and shape kind, for every scene class: filed under (GEO_GEN, IMG_TEX), shm_plan::serving_build)
+template <> int wf_shade<FAM_SIMPLE, GEO_GEN, IMG_TEX, K_ZSOBOL, K_DELTA_LIGHTS>(ShmScene* s, const ShadeArgs& a) {
     hipLaunchKernelGGL(k_shade_simple, dim3(a.blocks), dim3(SHADE2_BLOCK), 0, a.stream, s->dsv, s->pa, s->d_q_active[a.cur], s->d_q_active[a.cur ^ 1],
                        s->d_q_shadow, s->d_qs, a.cur, a.params, a.shadow_parity);
     LAUNCH_TRY("k_shade_simple");
     return SHM_OK;
 }
-template <> int wf_launch_shade_randomwalk<K_ZSOBOL, K_DELTA_LIGHTS>(ShmScene* s, const ShadeArgs& a) {
+template <> int wf_shade<FAM_RANDOMWALK, GEO_GEN, IMG_TEX, K_ZSOBOL, K_DELTA_LIGHTS>(ShmScene* s, const ShadeArgs& a) {
     hipLaunchKernelGGL(k_shade_randomwalk, dim3(a.blocks), dim3(SHADE2_BLOCK), 0, a.stream, s->dsv, s->pa, s->d_q_active[a.cur], s->d_q_active[a.cur ^ 1],
                        s->d_qs, a.cur, a.params, s->d_rw, a.cap_eff);
     LAUNCH_TRY("k_shade_randomwalk");

@@ -6,9 +6,4 @@
 #endif
 #include "k_shade.inl"
 
-template <> int wf_launch_shade_tail_sorted<K_ZSOBOL, K_DELTA_LIGHTS>(ShmScene* s, const ShadeArgs& a) {
-#define CTX_AS_HIT_FLAG 0
-    WF_SHADE_LAUNCH((k_shade<false, true, false, false, true, true>));
-#undef CTX_AS_HIT_FLAG
-    return SHM_OK;
-}
+WF_SHADE_FUSED_ALL_STUB(GEO_TRI, IMG_NONE)

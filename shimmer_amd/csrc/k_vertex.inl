@@ -251,17 +251,28 @@ __global__ void __launch_bounds__(SHADE2_BLOCK) __attribute__((amdgpu_waves_per_
 
 }  // namespace
 
-#define WF_VERTEX_LAUNCH_W3(TRI, TEX, SORT)                                                                                                    \
+using namespace shm_plan;  // (the builds' coordinates: GEO_*, IMG_*, FAM_*)
+// k_vertex of a build (GEO, IMG) (wavefront.h: build_tri_only, build_has_tex). Chunks are always material-sorted (a one-material scene pays the counting sort's pass
+// over its chunk: the unsorted instantiations left the library in round 6).
+#define WF_VERTEX_LAUNCH_W3(GEO, IMG)                                                                                                          \
     do {                                                                                                                                       \
-        hipLaunchKernelGGL((k_vertex_w3<TRI, TEX, SORT>), dim3(a.blocks * 3 / 2), dim3(SHADE2_BLOCK), 0, a.stream, s->dsv, s->pa, a.q_in ? a.q_in : s->d_q_active[a.cur], \
+        hipLaunchKernelGGL((k_vertex_w3<build_tri_only(GEO), build_has_tex(IMG), true>), dim3(a.blocks * 3 / 2), dim3(SHADE2_BLOCK), 0, a.stream, s->dsv, s->pa, a.q_in ? a.q_in : s->d_q_active[a.cur], \
                            s->d_q_scatter[0], s->d_q_scatter[1], s->d_q_scatter[2], s->d_q_scatter[3], s->d_qs, a.cur, a.params,               \
                            a.q_divert, s->lds_tables_small, a.n_in);           \
         LAUNCH_TRY("k_vertex_w3");                                                                                                             \
     } while (0)
-#define WF_VERTEX_LAUNCH(TRI, TEX, SORT)                                                                                                       \
+#define WF_VERTEX_LAUNCH(GEO, IMG)                                                                                                             \
     do {                                                                                                                                       \
-        hipLaunchKernelGGL((k_vertex<TRI, TEX, SORT>), dim3(a.blocks), dim3(SHADE2_BLOCK), 0, a.stream, s->dsv, s->pa, a.q_in ? a.q_in : s->d_q_active[a.cur],          \
+        hipLaunchKernelGGL((k_vertex<build_tri_only(GEO), build_has_tex(IMG), true>), dim3(a.blocks), dim3(SHADE2_BLOCK), 0, a.stream, s->dsv, s->pa, a.q_in ? a.q_in : s->d_q_active[a.cur],          \
                            s->d_q_scatter[0], s->d_q_scatter[1], s->d_q_scatter[2], s->d_q_scatter[3], s->d_qs, a.cur, a.params,               \
                            a.q_divert, s->lds_tables, a.n_in);                                 \
         LAUNCH_TRY("k_vertex");                                                                                                                \
     } while (0)
+// FAM_VERTEX of one build, launched by LAUNCH (one of the two above): the launcher's coordinates and the kernel's class from the same tokens. k_vertex draws nothing:
+// <., ZS = false, .> serves both samplers.
+#define WF_VERTEX_STUB(LAUNCH, GEO, IMG)                                                                                                       \
+    template <> int wf_shade<FAM_VERTEX, GEO, IMG, false, K_DELTA_LIGHTS>(ShmScene* s, const ShadeArgs& a) {                                   \
+        WF_ENV_UNIT_CHECK(IMG);                                                                                                                \
+        LAUNCH(GEO, IMG);                                                                                                                      \
+        return SHM_OK;                                                                                                                         \
+    }

@@ -3,11 +3,5 @@
 #define K_ENV_LIGHT true
 #include "k_vertex.inl"
 
-int WF_DL_NAME(wf_launch_vertex_tri_env)(ShmScene* s, const ShadeArgs& a) {
-    WF_VERTEX_LAUNCH_W3(true, false, true);
-    return SHM_OK;
-}
-int WF_DL_NAME(wf_launch_vertex_gen_env)(ShmScene* s, const ShadeArgs& a) {
-    WF_VERTEX_LAUNCH(false, false, true);
-    return SHM_OK;
-}
+WF_VERTEX_STUB(WF_VERTEX_LAUNCH_W3, GEO_TRI, IMG_ENV)
+WF_VERTEX_STUB(WF_VERTEX_LAUNCH, GEO_GEN, IMG_ENV)

@@ -193,34 +193,32 @@ using namespace shm_plan;
 // Which kernels a scene runs: one cell per geometry x image class x sampler x extended build (DL: the *_dl builds, wavefront.h K_DELTA_LIGHTS).
 // WHICH cell a render takes, and which of its launchers run, is the RenderPlan's (host/render_plan.hpp); the staged pipeline replaced the fused general kernels of
 // round 1 everywhere but in the lean class (round-2 A/B, same box: coated S3 1 208 -> 1 724 Mray/s, textured Cornell 768 -> 906, crown-proxy C4 1 758 -> 1 735).
+// The table is computed: a cell's launcher of a family is the build shm_plan::serving_build names for it (host/render_plan.hpp — the rule, walked by
+// tests/test_render_plan.py), null where it names none. (k_vertex draws nothing: its <., ZS = false, .> builds serve both samplers.)
+template <int FAMILY, int GEO, int IMG, bool ZS, bool DL>
+constexpr ShadeFn shade_fn() {
+    constexpr ShadeBuild b = serving_build(FAMILY, GEO, IMG);
+    if constexpr (has_build(b)) return wf_shade<FAMILY, b.geo, b.img, ZS && FAMILY != FAM_VERTEX, DL>;
+    else return nullptr;
+}
+// K1 by image class, [LEAN]: the textured class has no k_generate<., LEAN> (HAS_LEAN_KERNELS; cells_match_plan below)
+template <bool ZS>
+constexpr GenerateKernel generate_cells[N_IMG][2] = {
+    {k_generate<false, false, ZS>, k_generate<false, true, ZS>}, {k_generate<true, false, ZS>, nullptr}, {k_generate<false, false, ZS>, k_generate<false, true, ZS>}};
+template <int GEO, int IMG, bool ZS, bool DL>
+constexpr ShadeKernels shade_cell = {
+    .generate = {generate_cells<ZS>[IMG][0], generate_cells<ZS>[IMG][1]},
+    .lean = shade_fn<FAM_LEAN, GEO, IMG, ZS, DL>(), .lean_diverted = shade_fn<FAM_LEAN_DIVERTED, GEO, IMG, ZS, DL>(),
+    .fused_all = shade_fn<FAM_FUSED_ALL, GEO, IMG, ZS, DL>(), .vertex = shade_fn<FAM_VERTEX, GEO, IMG, ZS, DL>(),
+    .scatter = {shade_fn<FAM_SCATTER + CLASS_DIFFUSE, GEO, IMG, ZS, DL>(), shade_fn<FAM_SCATTER + CLASS_CONDUCTOR, GEO, IMG, ZS, DL>(),
+                shade_fn<FAM_SCATTER + CLASS_DIELECTRIC, GEO, IMG, ZS, DL>(), shade_fn<FAM_SCATTER + CLASS_LAYERED, GEO, IMG, ZS, DL>()},
+    .scatter_layered_onepass = shade_fn<FAM_SCATTER_LAYERED_ONEPASS, GEO, IMG, ZS, DL>(),
+    .simple = shade_fn<FAM_SIMPLE, GEO, IMG, ZS, DL>(), .randomwalk = shade_fn<FAM_RANDOMWALK, GEO, IMG, ZS, DL>()};
+static_assert(GEO_TRI == 0 && GEO_GEN == 1 && IMG_NONE == 0 && IMG_TEX == 1 && IMG_ENV == 2 && CLASS_LAYERED == CLS_LAYERED, "the order of shade_cells' initializer");
 template <bool ZS, bool DL>
 constexpr ShadeKernels shade_cells[N_GEO][N_IMG] = {
-    {{.generate = {k_generate<false, false, ZS>, k_generate<false, true, ZS>}, .lean = wf_launch_shade_lean<ZS, DL>, .lean_diverted = wf_launch_shade_lean_diverted<ZS, DL>,
-      .fused_all = wf_launch_shade_tail_sorted<ZS, DL>, .vertex = DL ? wf_launch_vertex_tri_dl : wf_launch_vertex_tri,
-      .scatter = {wf_launch_scatter_diffuse_tri<ZS, DL>, wf_launch_scatter_conductor_tri<ZS, DL>, wf_launch_scatter_dielectric_tri<ZS, DL>, wf_launch_scatter_layered_staged_tri<ZS, DL>},
-      .scatter_layered_onepass = wf_launch_scatter_layered_tri<ZS, DL>, .simple = wf_launch_shade_simple<ZS, DL>, .randomwalk = wf_launch_shade_randomwalk<ZS, DL>},
-     {.generate = {k_generate<true, false, ZS>, nullptr}, .lean = nullptr, .lean_diverted = nullptr,
-      .fused_all = wf_launch_shade_fused_tex<ZS, DL>, .vertex = DL ? wf_launch_vertex_tex_dl : wf_launch_vertex_tex,
-      .scatter = {wf_launch_scatter_diffuse_tex<ZS, DL>, wf_launch_scatter_conductor_tex<ZS, DL>, wf_launch_scatter_dielectric_tex<ZS, DL>, wf_launch_scatter_layered_staged_tex<ZS, DL>},
-      .scatter_layered_onepass = wf_launch_scatter_layered_tex<ZS, DL>, .simple = wf_launch_shade_simple<ZS, DL>, .randomwalk = wf_launch_shade_randomwalk<ZS, DL>},
-     {.generate = {k_generate<false, false, ZS>, k_generate<false, true, ZS>}, .lean = wf_launch_shade_lean_env<ZS, DL>, .lean_diverted = wf_launch_shade_lean_env_diverted<ZS, DL>,
-      .fused_all = wf_launch_shade_tail_sorted_env<ZS, DL>, .vertex = DL ? wf_launch_vertex_tri_env_dl : wf_launch_vertex_tri_env,
-      .scatter = {wf_launch_scatter_diffuse_tri_env<ZS, DL>, wf_launch_scatter_conductor_tri_env<ZS, DL>, wf_launch_scatter_dielectric_tri_env<ZS, DL>, wf_launch_scatter_layered_staged_tri_env<ZS, DL>},
-      .scatter_layered_onepass = wf_launch_scatter_layered_tri<ZS, DL>,  // (no K_ENV_LIGHT build: the one-pass kernel runs under force_diffuse, where img is never env)
-      .simple = wf_launch_shade_simple<ZS, DL>, .randomwalk = wf_launch_shade_randomwalk<ZS, DL>}},
-    {{.generate = {k_generate<false, false, ZS>, k_generate<false, true, ZS>}, .lean = wf_launch_shade_lean_gen<ZS, DL>, .lean_diverted = wf_launch_shade_lean_gen_diverted<ZS, DL>,
-      .fused_all = wf_launch_shade_fused_gen<ZS, DL>, .vertex = DL ? wf_launch_vertex_gen_dl : wf_launch_vertex_gen,
-      .scatter = {wf_launch_scatter_diffuse_gen<ZS, DL>, wf_launch_scatter_conductor_gen<ZS, DL>, wf_launch_scatter_dielectric_gen<ZS, DL>, wf_launch_scatter_layered_staged_gen<ZS, DL>},
-      .scatter_layered_onepass = wf_launch_scatter_layered_gen<ZS, DL>, .simple = wf_launch_shade_simple<ZS, DL>, .randomwalk = wf_launch_shade_randomwalk<ZS, DL>},
-     {.generate = {k_generate<true, false, ZS>, nullptr}, .lean = nullptr, .lean_diverted = nullptr,
-      .fused_all = wf_launch_shade_fused_gen_tex<ZS, DL>, .vertex = DL ? wf_launch_vertex_tex_dl : wf_launch_vertex_tex,
-      .scatter = {wf_launch_scatter_diffuse_tex<ZS, DL>, wf_launch_scatter_conductor_tex<ZS, DL>, wf_launch_scatter_dielectric_tex<ZS, DL>, wf_launch_scatter_layered_staged_tex<ZS, DL>},
-      .scatter_layered_onepass = wf_launch_scatter_layered_tex<ZS, DL>, .simple = wf_launch_shade_simple<ZS, DL>, .randomwalk = wf_launch_shade_randomwalk<ZS, DL>},
-     {.generate = {k_generate<false, false, ZS>, k_generate<false, true, ZS>}, .lean = wf_launch_shade_lean_gen_env<ZS, DL>, .lean_diverted = wf_launch_shade_lean_gen_env_diverted<ZS, DL>,
-      .fused_all = wf_launch_shade_fused_gen_env<ZS, DL>, .vertex = DL ? wf_launch_vertex_gen_env_dl : wf_launch_vertex_gen_env,
-      .scatter = {wf_launch_scatter_diffuse_gen_env<ZS, DL>, wf_launch_scatter_conductor_gen_env<ZS, DL>, wf_launch_scatter_dielectric_gen_env<ZS, DL>, wf_launch_scatter_layered_staged_gen_env<ZS, DL>},
-      .scatter_layered_onepass = wf_launch_scatter_layered_gen<ZS, DL>,  // (as above)
-      .simple = wf_launch_shade_simple<ZS, DL>, .randomwalk = wf_launch_shade_randomwalk<ZS, DL>}},
+    {shade_cell<GEO_TRI, IMG_NONE, ZS, DL>, shade_cell<GEO_TRI, IMG_TEX, ZS, DL>, shade_cell<GEO_TRI, IMG_ENV, ZS, DL>},
+    {shade_cell<GEO_GEN, IMG_NONE, ZS, DL>, shade_cell<GEO_GEN, IMG_TEX, ZS, DL>, shade_cell<GEO_GEN, IMG_ENV, ZS, DL>},
 };
 // ... and per pixel-filter class (FLT_TRIANGLE ..: [flt - 1]) x sampler: K1 and K6 of the filters that are not the box filter; the generate kernels as [HAS_TEX][LEAN]
 struct FilterKernels {
@@ -262,18 +260,16 @@ static ShadeKernels select_kernels(const RenderPlan& p) {
     }
     return k;
 }
-// (the table's null cells are the ones host/render_plan.hpp exports as HAS_LEAN_KERNELS, which its validation and tests/test_render_plan.py go by. Behind select_kernels,
-//  in its order: the check must not be the first use of the tables — that moved k_generate's instantiations within the code object and changed their text)
+// (the launchers' null cells follow from HAS_LEAN_KERNELS by construction — serving_build reads it; what stays written by hand are K1's, held to it here. Behind
+//  select_kernels, in its order: the check must not be the first use of the tables — that moved k_generate's instantiations within the code object and changed their text)
 template <bool ZS, bool DL>
 constexpr bool cells_match_plan() {
     for (int g = 0; g < N_GEO; ++g)
-        for (int i = 0; i < N_IMG; ++i) {
-            const ShadeKernels& c = shade_cells<ZS, DL>[g][i];
-            if ((c.lean != nullptr) != HAS_LEAN_KERNELS[i] || (c.lean_diverted != nullptr) != HAS_LEAN_KERNELS[i] || (c.generate[1] != nullptr) != HAS_LEAN_KERNELS[i]) return false;
-        }
+        for (int i = 0; i < N_IMG; ++i)
+            if ((shade_cells<ZS, DL>[g][i].generate[1] != nullptr) != HAS_LEAN_KERNELS[i]) return false;
     return true;
 }
-static_assert(cells_match_plan<true, true>() && cells_match_plan<false, true>() && cells_match_plan<true, false>() && cells_match_plan<false, false>(), "shade_cells vs HAS_LEAN_KERNELS");
+static_assert(cells_match_plan<true, true>() && cells_match_plan<false, true>() && cells_match_plan<true, false>() && cells_match_plan<false, false>(), "k_generate<., LEAN> vs HAS_LEAN_KERNELS");
 // ... and the one validation behind it: every launcher the plan will call is there
 static bool kernels_complete(const ShadeKernels& k, const ScenePlan& sp, const RenderPlan& p) {
     bool ok = p.flt != FLT_BOX ? k.generate_filtered[p.lean_first ? 1 : 0] != nullptr : k.generate[p.lean_first ? 1 : 0] != nullptr;

@@ -18,7 +18,7 @@
 #include "host/render_plan.hpp"
 // K_DELTA_LIGHTS (a translation unit's switch, like K_ZSOBOL below): PBRT-v4's distant and spot lights are compiled into a unit's light sampling only where it is true
 // (shm/path.h, SHM_DELTA_LIGHTS). The Makefile compiles every unit that samples lights once more with it into *_dl (and *_zs_dl) objects, whose kernels carry a _dl
-// suffix and whose launchers are the <., true> specializations (WF_SAMPLED_LAUNCHER); the render's plan (host/render_plan.hpp, RenderPlan::dl) names that set for a scene that holds such a light
+// suffix and whose launchers are the <., DL = true> specializations of wf_shade (below); the render's plan (host/render_plan.hpp, RenderPlan::dl) names that set for a scene that holds such a light
 // (FlatScene::has_directed_lights). Without the switch the two branches fold away: the kernels of every other scene are those of a build without the lights.
 #ifndef K_DELTA_LIGHTS
 #define K_DELTA_LIGHTS false
@@ -36,6 +36,7 @@
 #define SHM_SPHERICAL_CAMERA K_SPHERICAL_CAMERA
 #include "shm/path.h"
 #include "shm/tri_shade.h"
+// (the kernels' names: the *_dl builds' carry the suffix after the sampler's, k_*.inl)
 #define WF_CAT_(a, b) a##b
 #define WF_CAT(a, b) WF_CAT_(a, b)
 #if K_DELTA_LIGHTS
@@ -123,7 +124,7 @@ struct alignas(64) PathRec {
 static_assert(sizeof(PathRec) == 64, "PathRec is one half cache line");
 // K_ZSOBOL (a translation unit's switch, like K_ENV_LIGHT): the Makefile compiles every unit whose kernels draw twice, the second time with K_ZSOBOL
 // true into *_zs objects whose kernels carry a _zs suffix (k_shade.inl, k_scatter.inl, k_scatter_layered.inl, k_shade_other.hip) and whose launchers are the
-// <true> specializations (WF_SAMPLED_LAUNCHER, below). select_kernels (render.hip) picks the set from ShmRenderParams::sampler, so the sampler is a compile-time constant of every kernel: with the independent
+// <., ZS = true, .> specializations of wf_shade (below). select_kernels (render.hip) picks the set from ShmRenderParams::sampler, so the sampler is a compile-time constant of every kernel: with the independent
 // sampler the ZSobol code folds away and the kernels are those of a build without it (tools/kernel_resources.py).
 #ifndef K_ZSOBOL
 #define K_ZSOBOL false
@@ -441,48 +442,32 @@ struct ShadeArgs {
     const uint32_t* n_in = nullptr;
     uint32_t* q_divert = nullptr;    // k_vertex: where it diverts the hits on plain diffuse materials (RenderPlan::divert_vertex: q_lean), null: nowhere
 };
-// Every shading launcher launches ONE scene-class variant of its kernel: geometry (tri: top-level triangles only, gen: spheres / patches / instances too) x image
-// class (none, tex: image textures — ray differentials, MIP filtering —, env: an ImageInfinitelight alone, the K_ENV_LIGHT units). render.hip puts them in one table,
-// ShadeKernels by (geometry, image class, sampler, extended build); a render's RenderPlan (host/render_plan.hpp) holds the coordinates and select_kernels looks them up.
+// Every shading launcher launches ONE build of its family's kernel for ONE scene class: geometry (GEO_TRI: top-level triangles only, GEO_GEN: spheres / patches /
+// instances too) x image class (IMG_NONE, IMG_TEX: image textures — ray differentials, MIP filtering —, IMG_ENV: an ImageInfinitelight alone, the K_ENV_LIGHT units).
+// They are the explicit specializations of ONE template, addressed by coordinates: the family (shm_plan::FAM_*, host/render_plan.hpp), the build's scene class, the
+// sampler and the extended build. Each kernel unit defines <., K_ZSOBOL, K_DELTA_LIGHTS> of the builds it holds — the Makefile compiles the units that draw and sample
+// lights four times (K_ZSOBOL x K_DELTA_LIGHTS) and k_vertex_*.hip, which draws nothing, twice: it defines <., false, K_DELTA_LIGHTS> for both samplers. Which build
+// serves which cell is shm_plan::serving_build, from which render.hip computes its table (ShadeKernels by geometry, image class, sampler, extended build); a render's
+// RenderPlan holds the coordinates and select_kernels looks them up. The template has no definition: a build the rule names and no unit defines is a link error
+// (an undefined hidden symbol) whose name spells the coordinates.
+//   FAM_LEAN, FAM_LEAN_DIVERTED  k_shade<lean> (k_shade_lean*.hip): all-diffuse scenes without textures — every hit of the queue — / the hits k_vertex or the split pass diverted
+//   FAM_FUSED_ALL                the material-sorted fused all-materials kernel (k_shade_tail_sorted*.hip, k_shade_fused_*.hip): scenes without coated materials
+//   FAM_VERTEX                   staged shading (k_vertex_*.hip): the hit half of a vertex (interaction, emission + MIS, get_bsdf with its texture evaluation -> BxDF parameter
+//                                block, pushed to the queue of its BxDF class); its K_DELTA_LIGHTS build knows the diffuse transmission material
+//   FAM_SCATTER + class          ... then per class the scattering half (k_scatter_*.hip: NEE, sample_f, RR); the LayeredBxDF class as dense per-wave stages
+//                                (k_scatter_layered.inl): every render but options.force_diffuse ...
+//   FAM_SCATTER_LAYERED_ONEPASS  ... and in one pass per vertex (k_scatter.inl), which has force_diffuse's code
+//   FAM_SIMPLE, FAM_RANDOMWALK   the other integrators (k_shade_other.hip): one kernel each for every scene class
 using ShadeFn = int (*)(ShmScene*, const ShadeArgs&);
-// The units whose kernels draw and sample lights are compiled four times (K_ZSOBOL x K_DELTA_LIGHTS, Makefile): each defines its launchers as the specialization
-// <K_ZSOBOL, K_DELTA_LIGHTS> of one template, so that the table names all four builds and a missing one is a link error (an undefined hidden symbol).
-#define WF_SAMPLED_LAUNCHER(name)                                                    \
-    template <bool ZS, bool DL> int name(ShmScene* s, const ShadeArgs& a);           \
-    template <> WF_INTERNAL int name<false, false>(ShmScene* s, const ShadeArgs& a); \
-    template <> WF_INTERNAL int name<true, false>(ShmScene* s, const ShadeArgs& a);  \
-    template <> WF_INTERNAL int name<false, true>(ShmScene* s, const ShadeArgs& a);  \
-    template <> WF_INTERNAL int name<true, true>(ShmScene* s, const ShadeArgs& a)
-// the fused kernel k_shade<lean> (k_shade_lean*.hip): all-diffuse scenes without textures — every hit of the queue — and the hits k_vertex or the split pass diverted
-WF_SAMPLED_LAUNCHER(wf_launch_shade_lean); WF_SAMPLED_LAUNCHER(wf_launch_shade_lean_gen); WF_SAMPLED_LAUNCHER(wf_launch_shade_lean_env); WF_SAMPLED_LAUNCHER(wf_launch_shade_lean_gen_env);
-WF_SAMPLED_LAUNCHER(wf_launch_shade_lean_diverted); WF_SAMPLED_LAUNCHER(wf_launch_shade_lean_gen_diverted); WF_SAMPLED_LAUNCHER(wf_launch_shade_lean_env_diverted);
-WF_SAMPLED_LAUNCHER(wf_launch_shade_lean_gen_env_diverted);
-// the material-sorted fused all-materials kernel (k_shade_tail_sorted*.hip, k_shade_fused_*.hip): scenes without coated materials
-WF_SAMPLED_LAUNCHER(wf_launch_shade_tail_sorted); WF_SAMPLED_LAUNCHER(wf_launch_shade_fused_gen); WF_SAMPLED_LAUNCHER(wf_launch_shade_fused_tex);
-WF_SAMPLED_LAUNCHER(wf_launch_shade_fused_gen_tex); WF_SAMPLED_LAUNCHER(wf_launch_shade_tail_sorted_env); WF_SAMPLED_LAUNCHER(wf_launch_shade_fused_gen_env);
-// staged shading (k_vertex_*.hip, k_scatter_*.hip): the hit half of a vertex (interaction, emission + MIS, get_bsdf with its texture evaluation -> BxDF parameter
-// block, pushed to the queue of its BxDF class), then per class the scattering half (NEE, sample_f, RR). k_vertex draws nothing: one build serves both samplers.
-WF_INTERNAL int wf_launch_vertex_tri(ShmScene* s, const ShadeArgs& a); WF_INTERNAL int wf_launch_vertex_gen(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_vertex_tex(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_vertex_tri_env(ShmScene* s, const ShadeArgs& a); WF_INTERNAL int wf_launch_vertex_gen_env(ShmScene* s, const ShadeArgs& a);
-// ... and a second one, K_DELTA_LIGHTS, knows the diffuse transmission material (the *_dl objects of k_vertex_*.hip)
-WF_INTERNAL int wf_launch_vertex_tri_dl(ShmScene* s, const ShadeArgs& a); WF_INTERNAL int wf_launch_vertex_gen_dl(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_vertex_tex_dl(ShmScene* s, const ShadeArgs& a);
-WF_INTERNAL int wf_launch_vertex_tri_env_dl(ShmScene* s, const ShadeArgs& a); WF_INTERNAL int wf_launch_vertex_gen_env_dl(ShmScene* s, const ShadeArgs& a);
-WF_SAMPLED_LAUNCHER(wf_launch_scatter_diffuse_tri); WF_SAMPLED_LAUNCHER(wf_launch_scatter_diffuse_gen); WF_SAMPLED_LAUNCHER(wf_launch_scatter_diffuse_tex);
-WF_SAMPLED_LAUNCHER(wf_launch_scatter_diffuse_tri_env); WF_SAMPLED_LAUNCHER(wf_launch_scatter_diffuse_gen_env);
-WF_SAMPLED_LAUNCHER(wf_launch_scatter_conductor_tri); WF_SAMPLED_LAUNCHER(wf_launch_scatter_conductor_gen); WF_SAMPLED_LAUNCHER(wf_launch_scatter_conductor_tex);
-WF_SAMPLED_LAUNCHER(wf_launch_scatter_conductor_tri_env); WF_SAMPLED_LAUNCHER(wf_launch_scatter_conductor_gen_env);
-WF_SAMPLED_LAUNCHER(wf_launch_scatter_dielectric_tri); WF_SAMPLED_LAUNCHER(wf_launch_scatter_dielectric_gen); WF_SAMPLED_LAUNCHER(wf_launch_scatter_dielectric_tex);
-WF_SAMPLED_LAUNCHER(wf_launch_scatter_dielectric_tri_env); WF_SAMPLED_LAUNCHER(wf_launch_scatter_dielectric_gen_env);
-// the LayeredBxDF class as dense per-wave stages (k_scatter_layered.inl): every render but options.force_diffuse ...
-WF_SAMPLED_LAUNCHER(wf_launch_scatter_layered_staged_tri); WF_SAMPLED_LAUNCHER(wf_launch_scatter_layered_staged_gen); WF_SAMPLED_LAUNCHER(wf_launch_scatter_layered_staged_tex);
-WF_SAMPLED_LAUNCHER(wf_launch_scatter_layered_staged_tri_env); WF_SAMPLED_LAUNCHER(wf_launch_scatter_layered_staged_gen_env);
-// ... and in one pass per vertex (k_scatter.inl), which has force_diffuse's code
-WF_SAMPLED_LAUNCHER(wf_launch_scatter_layered_tri); WF_SAMPLED_LAUNCHER(wf_launch_scatter_layered_gen); WF_SAMPLED_LAUNCHER(wf_launch_scatter_layered_tex);
-// the other integrators (k_shade_other.hip): one kernel each for every scene class
-WF_SAMPLED_LAUNCHER(wf_launch_shade_simple); WF_SAMPLED_LAUNCHER(wf_launch_shade_randomwalk);
-WF_INTERNAL int wf_launch_fold_randomwalk(ShmScene* s, hipStream_t stream, uint32_t cap_eff, uint32_t total);
+template <int FAMILY, int GEO, int IMG, bool ZS, bool DL> WF_INTERNAL int wf_shade(ShmScene* s, const ShadeArgs& a);
+// A build's coordinates as its kernels' template parameters: the stubs of the kernel units (WF_*_STUB, k_*.inl) take (GEO, IMG) and derive these, so that a launcher's
+// place in the table and the kernel it launches cannot disagree. (The one textured build of the staged families is (GEO_GEN, IMG_TEX): TRI_ONLY = false.)
+constexpr bool build_tri_only(int geo) { return geo == shm_plan::GEO_TRI; }
+constexpr bool build_has_tex(int img) { return img == shm_plan::IMG_TEX; }
+constexpr bool build_env_light(int img) { return img == shm_plan::IMG_ENV; }
+// (the units that compile the environment light in by their switch, not by a template parameter: an env build belongs in a K_ENV_LIGHT unit, and no other does)
+#define WF_ENV_UNIT_CHECK(IMG) static_assert(build_env_light(IMG) == (K_ENV_LIGHT), "an IMG_ENV build is a K_ENV_LIGHT unit's, and such a unit holds no other")
+WF_INTERNAL int wf_launch_fold_randomwalk(ShmScene* s, hipStream_t stream, uint32_t cap_eff, uint32_t total);  // k_shade_other.hip: RandomWalk's sum over depths, after the last bounce
 // K1 (render.hip, k_generate<HAS_TEX, LEAN, ZS>)
 using GenerateKernel = void (*)(SceneView, PathArrays, const uint32_t*, uint32_t, int, int, ShmRenderParams, uint32_t*, QueueState*, uint32_t);
 // K1 / K6 of the pixel filters beside the box filter (render.hip, k_generate_filtered<HAS_TEX, LEAN, ZS, FC>, k_film_weighted<W>): + the per-path filter weights (+ the constant K)

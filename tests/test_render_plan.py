@@ -14,7 +14,10 @@ all-materials kernel shades (SHM_TAIL_FUSED_BOUNCE=0 without coated materials). 
 test_staging_arrays_follow_the_scene_class pins the rule itself.
 
 The traversal part of the plan — which row of the kernel table a scene's rays take, and the stack that row and the scene's tree need — is walked separately, through
-orc_fn_trace_plan (the tests at the end): the variant and strictness rules, the stack bound against the deepest leaf, and every row's LDS against the compute unit's."""
+orc_fn_trace_plan: the variant and strictness rules, the stack bound against the deepest leaf, and every row's LDS against the compute unit's.
+
+The shading launchers' serving rule — which build of a launcher family serves which cell of render.hip's table (serving_build; the table is computed from it) — is
+walked through orc_fn_shade_serving (the tests at the end): its shape, its 44 builds, and that every launcher a plan of the domain above would call is served."""
 import itertools
 import sys
 from pathlib import Path
@@ -259,3 +262,76 @@ def test_strict_kernels_take_the_general_any_hit_row(trace_plans):
     s = q["strict"] != 0
     assert s.any()
     assert np.array_equal(q["strict_waves"][s], q["waves_any"][s]) and np.array_equal(q["strict_lds_levels"][s], q["lds_levels_any"][s])
+
+
+# ---- the shading launchers' serving rule (serving_build: family x geo x img -> the build that serves the cell) through orc_fn_shade_serving ----
+GEO_TRI, GEO_GEN = 0, 1
+FAMILY_BUILDS = {"LEAN": 4, "LEAN_DIVERTED": 4, "FUSED_ALL": 6, "VERTEX": 5, "SCATTER_DIFFUSE": 5, "SCATTER_CONDUCTOR": 5, "SCATTER_DIELECTRIC": 5, "SCATTER_LAYERED": 5,
+                 "SCATTER_LAYERED_ONEPASS": 3, "SIMPLE": 1, "RANDOMWALK": 1}
+
+
+@pytest.fixture(scope="module")
+def serving():
+    names, table = oracle_py.shade_serving()
+    return {name: table[f] for f, name in enumerate(names)}  # [geo][img] -> (geo', img')
+
+
+def test_serving_rule_names_builds_that_serve_themselves(serving):
+    assert list(serving) == list(FAMILY_BUILDS)
+    for name, t in serving.items():
+        assert t.shape == (2, 3, 2)
+        for g, i in itertools.product(range(2), range(3)):
+            bg, bi = (int(v) for v in t[g, i])
+            if (bg, bi) == (-1, -1):
+                continue
+            assert 0 <= bg < 2 and 0 <= bi < 3, (name, g, i)
+            assert tuple(t[bg, bi]) == (bg, bi), (name, g, i)  # a build serves the cell it is named after
+
+
+def test_serving_rule_has_the_44_builds(serving):
+    builds = {name: {tuple(int(v) for v in t[g, i]) for g, i in itertools.product(range(2), range(3))} - {(-1, -1)} for name, t in serving.items()}
+    assert {name: len(b) for name, b in builds.items()} == FAMILY_BUILDS
+    assert sum(len(b) for b in builds.values()) == 44
+
+
+def test_serving_rule_is_null_exactly_where_there_is_no_lean_kernel(serving, plans):
+    (q,) = plans.values()
+    has_lean = [int(q["has_lean_none"][0]), int(q["has_lean_tex"][0]), int(q["has_lean_env"][0])]
+    assert has_lean == [1, 0, 1]
+    for name, t in serving.items():
+        for g, i in itertools.product(range(2), range(3)):
+            null = tuple(t[g, i]) == (-1, -1)
+            assert null == (name in ("LEAN", "LEAN_DIVERTED") and not has_lean[i]), (name, g, i)
+            if name in ("LEAN", "LEAN_DIVERTED") and not null:
+                assert tuple(t[g, i]) == (g, i)  # its own build
+
+
+def test_one_pass_layered_family_has_no_env_build(serving):
+    t = serving["SCATTER_LAYERED_ONEPASS"]
+    assert not np.any(t[:, :, 1] == IMG_ENV)
+    for g in range(2):
+        assert tuple(t[g, IMG_ENV]) == (g, IMG_NONE)  # the env cells: the build without the light, of the same geometry
+        assert tuple(t[g, IMG_TEX]) == (GEO_GEN, IMG_TEX)
+
+
+def test_every_launcher_a_plan_calls_has_a_serving_build(serving, plans):
+    """render.hip's kernels_complete on the plan's columns: select_kernels takes the lean launchers at (geo, img_lean), everything else at (geo, img), and puts the
+    one-pass LayeredBxDF launcher in the class's place where the plan says so."""
+    served = {name: t[:, :, 0] >= 0 for name, t in serving.items()}  # [geo][img]
+    for q in plans.values():
+        i = q["in"]
+        geo, img, img_lean = q["geo"], q["img"], q["img_lean"]
+        at = lambda name, im: served[name][geo, im]
+        staged0 = (q["route"] == ROUTE_STAGED) & (q["fused_from"] > 0)  # RenderPlan::staged_bounce(0)
+        missing = (q["route"] == ROUTE_LEAN) & ~at("LEAN", img_lean)
+        missing |= (q["route"] == ROUTE_SIMPLE) & ~at("SIMPLE", img)
+        missing |= (q["route"] == ROUTE_RANDOM_WALK) & ~at("RANDOMWALK", img)
+        missing |= (q["route"] == ROUTE_STAGED) & (q["fused_from"] != NEVER) & ~at("FUSED_ALL", img)
+        missing |= staged0 & ~at("VERTEX", img)
+        missing |= staged0 & (q["drain_lean"] != 0) & ~at("LEAN_DIVERTED", img_lean)
+        for c, name in enumerate(("SCATTER_DIFFUSE", "SCATTER_CONDUCTOR", "SCATTER_DIELECTRIC")):
+            missing |= staged0 & ((i["classes"] >> c) & 1 != 0) & ~at(name, img)
+        layered = np.where(q["layered_onepass"] != 0, at("SCATTER_LAYERED_ONEPASS", img), at("SCATTER_LAYERED", img))
+        missing |= staged0 & ((i["classes"] >> 3) & 1 != 0) & ~layered
+        assert not missing.any()
+        assert staged0.any() and (q["route"] == ROUTE_LEAN).any() and (q["drain_lean"] != 0).any()
