@@ -1427,6 +1427,17 @@ int orc_fn_shade_serving(int32_t* out) {
             }
     return N_FAM;
 }
+// K1's and K6's rule (host/render_plan.hpp: has_generate_build, generate_filter_class, film_weight) as data: out[tex][lean][flt] = {a k_generate build exists, the filter
+// class it is compiled for, where k_film takes the sample's weight from}; 2 * 2 * N_FLT * 3 int32. Returns N_FLT.
+int orc_fn_generate_rule(int32_t* out) {
+    using namespace shm_plan;
+    for (int tex = 0; tex < 2; ++tex)
+        for (int lean = 0; lean < 2; ++lean)
+            for (int flt = 0; flt < N_FLT; ++flt) {
+                *out++ = has_generate_build(tex != 0, lean != 0); *out++ = generate_filter_class(flt); *out++ = film_weight(flt);
+            }
+    return N_FLT;
+}
 const char* orc_fn_shade_family_names() {
     using namespace shm_plan;
     static_assert(FAM_LEAN == 0 && FAM_LEAN_DIVERTED == 1 && FAM_FUSED_ALL == 2 && FAM_VERTEX == 3 && FAM_SCATTER_DIFFUSE == 4 && FAM_SCATTER_CONDUCTOR == 5 &&

@@ -143,6 +143,7 @@ def load():
     lib.orc_fn_scene_trace_facts.restype, lib.orc_fn_scene_trace_facts.argtypes = None, [C.c_void_p, IP32]
     lib.orc_fn_shade_serving.restype, lib.orc_fn_shade_serving.argtypes = C.c_int, [IP32]
     lib.orc_fn_shade_family_names.restype, lib.orc_fn_shade_family_names.argtypes = C.c_char_p, []
+    lib.orc_fn_generate_rule.restype, lib.orc_fn_generate_rule.argtypes = C.c_int, [IP32]
     lib.orc_fn_bvh_pairs.restype = C.c_int
     lib.orc_fn_bvh_pairs.argtypes = [NP, C.c_uint32, UP32, C.c_uint32, UP32, C.c_uint32, NP, UP32, UP32, C.POINTER(C.c_int), UP32, UP32, NP]
     _lib = lib
@@ -204,6 +205,21 @@ def shade_serving():
     out = np.full((len(names), 2, 3, 2), -2, np.int32)
     assert lib.orc_fn_shade_serving(out.ctypes.data_as(C.POINTER(C.c_int32))) == len(names)
     return names, out
+
+
+# the plan's pixel-filter classes (host/render_plan.hpp, FLT_*), K1's filter classes (shm/filter.h, FILTER_CLASS_*) and K6's weight sources (FILM_WEIGHT_*), in their enums' order
+FLT = ["BOX", "TRIANGLE", "TABULATED", "TABULATED_SIGNED"]
+FILTER_CLASS = ["BOX", "TRIANGLE", "TABULATED"]
+FILM_WEIGHT = ["ONE", "CONSTANT", "PER_SAMPLE"]
+
+
+def generate_rule():
+    """K1's and K6's rule (host/render_plan.hpp: has_generate_build, generate_filter_class, film_weight): an int32 array [tex][lean][flt][3] —
+    {a k_generate build exists, its filter class (an index into FILTER_CLASS), the film weight's source (an index into FILM_WEIGHT)}."""
+    lib = load()
+    out = np.full((2, 2, len(FLT), 3), -2, np.int32)
+    assert lib.orc_fn_generate_rule(out.ctypes.data_as(C.POINTER(C.c_int32))) == len(FLT)
+    return out
 
 
 def sampler_stream_zs(px, py, index, spp, rx, ry, seed, none, kinds):

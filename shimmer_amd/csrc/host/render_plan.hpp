@@ -3,7 +3,8 @@
 //   ScenePlan   at scene creation, from the class facts of the FlatScene and the environment knobs (read_knobs: the only getenv of the decisions); with it the
 //               traversal kernels' variant table (TRACE_SHAPES)
 //   RenderPlan  once per shm_render_wave, from the ScenePlan and the render's options
-// render.hip's select_kernels is a lookup by the RenderPlan's coordinates and its bounce loop asks the plan and nothing else; WS_ARRAYS below is the one list of
+// render.hip's select_kernels is a lookup by the RenderPlan's coordinates, K1's launcher (wf_generate, k_generate.inl) and K6's (launch_film) go by the same coordinates
+// and the rule below serving_build, and the bounce loop asks the plan and nothing else; WS_ARRAYS below is the one list of
 // per-path arrays behind both the workspace budget and its allocation.
 #pragma once
 #include <stdint.h>
@@ -22,8 +23,8 @@ enum : int { IMG_NONE, IMG_TEX, IMG_ENV, N_IMG };  // no image / image textures 
 enum : int { FLT_BOX, FLT_TRIANGLE, FLT_TABULATED, FLT_TABULATED_SIGNED, N_FLT };
 enum : int { ROUTE_LEAN, ROUTE_STAGED, ROUTE_SIMPLE, ROUTE_RANDOM_WALK };
 constexpr int NEVER = 1 << 30;  // a bounce no render reaches (max_depth <= 254)
-// The table's null cells, by image class: the textured classes have no lean kernel (direct or diverted) and no k_generate<., LEAN>. serving_build (below) goes by it; render.hip holds
-// its k_generate cells to it.
+// The table's null cells, by image class: the textured classes have no lean kernel (direct or diverted) and no k_generate<., LEAN>. serving_build and has_generate_build
+// (below) go by it.
 constexpr bool HAS_LEAN_KERNELS[N_IMG] = {true, false, true};
 // The shading launchers by family (wavefront.h: wf_shade<FAMILY, GEO, IMG, ZS, DL>), and the ONE rule for which build of a family serves a cell of the table. A build
 // goes by the coordinates of the cell it was written for; a family with fewer builds than cells has some of them serve several:
@@ -48,6 +49,14 @@ constexpr ShadeBuild serving_build(int family, int geo, int img) {
     if (img == IMG_TEX) return {GEO_GEN, IMG_TEX};
     return {geo, family == FAM_SCATTER_LAYERED_ONEPASS ? IMG_NONE : img};
 }
+// K1 and K6 by the plan's coordinates: the one rule behind k_generate.inl's table (wf_generate) and render.hip's launch_film.
+//   the filter class K1 is compiled for (shm/filter.h): both tabulated classes of the plan run the one tabulated kernel — the sign rides in the weight it leaves
+constexpr int generate_filter_class(int flt) { return flt == FLT_BOX ? shm::FILTER_CLASS_BOX : (flt == FLT_TRIANGLE ? shm::FILTER_CLASS_TRIANGLE : shm::FILTER_CLASS_TABULATED); }
+//   where K6 takes a sample's weight from: it is 1 (box, triangle) / the one constant K that heads the scene's table (gaussian) / +-K per path slot, as K1 left it (Mitchell, sinc)
+enum : int { FILM_WEIGHT_ONE, FILM_WEIGHT_CONSTANT, FILM_WEIGHT_PER_SAMPLE };
+constexpr int film_weight(int flt) { return flt == FLT_TABULATED ? FILM_WEIGHT_CONSTANT : (flt == FLT_TABULATED_SIGNED ? FILM_WEIGHT_PER_SAMPLE : FILM_WEIGHT_ONE); }
+//   which K1 builds exist, per camera, sampler and filter class: <HAS_TEX, LEAN> unless LEAN in a class without lean kernels — 3 x 3 filter classes = 9, 36 in all
+constexpr bool has_generate_build(bool tex, bool lean) { return !lean || HAS_LEAN_KERNELS[tex ? IMG_TEX : IMG_NONE]; }
 
 // What flatten_scene found, as far as a decision reads it
 struct SceneFacts {
@@ -223,7 +232,7 @@ struct RenderPlan {
     // table coordinates
     int geo = GEO_TRI, img = IMG_NONE, img_lean = IMG_NONE, img_generate = IMG_NONE, flt = FLT_BOX;
     bool zs = false, dl = false;
-    bool spherical = false;        // the generate kernels of k_generate_spherical.hip, in the same cells (HAS_TEX x LEAN x sampler x filter class)
+    bool spherical = false;        // K1's launcher is k_generate_spherical.hip's, wf_generate<true>: the same cells (HAS_TEX x LEAN x sampler x filter class)
     bool film_per_sample = false;  // k_film_weighted reads the per-path weights k_generate_filtered left
     // overlap policy
     uint64_t overlap_paths = 0;       // a batch below this many paths runs K3(b) beside K2(b+1) and the class scatter kernels beside each other ...
@@ -277,7 +286,7 @@ inline RenderPlan render_plan(const ScenePlan& s, const ShmRenderParams& o) {
     // k_generate and k_film; the others their own K1 / K6 pair
     if (f.filter != SHM_FILTER_BOX && o.disable_pixel_jitter == 0)
         p.flt = f.filter == SHM_FILTER_TRIANGLE ? FLT_TRIANGLE : (shm::filter_weight_is_signed(f.filter) ? FLT_TABULATED_SIGNED : FLT_TABULATED);
-    p.film_per_sample = p.flt == FLT_TABULATED_SIGNED;
+    p.film_per_sample = film_weight(p.flt) == FILM_WEIGHT_PER_SAMPLE;
     // Small batches are tail-dominated (the last rays of a persistent traversal launch take ~0.5 ms whatever its size): there K3 of bounce b runs on a second stream
     // beside K2 of bounce b+1 and the next shade launch waits for both. Large batches (the 1-GPU headline frame) keep everything on one stream.
     // (a scene shaded by the diverted fused kernel AND the LayeredBxDF scatter kernel runs in this mode at any batch size: its any-hit share is large and its
@@ -294,7 +303,7 @@ inline const char* render_plan_error(const ScenePlan& s, const RenderPlan& p) {
     if (p.dl != s.f.extended) return "internal: the kernel set does not match the scene's delta lights / materials";
     if (p.spherical != s.f.spherical_camera) return "internal: the generate kernels do not match the scene's camera";
     if ((p.route == ROUTE_LEAN || p.drain_lean) && !HAS_LEAN_KERNELS[p.img_lean]) return "internal: the plan calls a lean kernel of a textured class";
-    if (p.lean_first && !HAS_LEAN_KERNELS[p.img_generate]) return "internal: the plan calls k_generate<HAS_TEX, LEAN>";
+    if (p.lean_first && !has_generate_build(p.img_generate == IMG_TEX, true)) return "internal: the plan calls k_generate<HAS_TEX, LEAN>";
     return nullptr;
 }
 

@@ -1,19 +1,16 @@
-// k_generate.inl — K1, the camera rays of one batch: generate_paths and its kernels k_generate (box filter) / k_generate_filtered (the other pixel filters).
-// Included inside a namespace by two units: render.hip (the reference's perspective and orthographic cameras: its kernels know nothing else) and
-// k_generate_spherical.hip (K_SPHERICAL_CAMERA, wavefront.h: the same kernels with PBRT-v4's spherical camera compiled into the leaf, for scenes whose camera is one).
-// ---------------------------------------------------------------------------------------------
-// K1: camera rays for one batch. Path slots are ordered [pixel group][sample][pixel in group] with groups of `pix_group`
-// consecutive pixels of the tile-ordered pixel list (pix_group >= n_pix is the plain sample-major order
-// slot = s_local * n_pix + p_local; pix_group = 64 keeps all samples of one 8x8 tile adjacent in the queues, so that a
-// wave's private queue range, and an XCD's queue partition, is a compact image region).
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t slot_of(uint32_t p_local, uint32_t s_local, uint32_t n_pix, uint32_t n_samples, uint32_t pix_group) {
-    uint32_t g = p_local / pix_group;
-    uint32_t g0 = g * pix_group;
-    uint32_t pg = min(pix_group, n_pix - g0);
-    return g0 * n_samples + s_local * pg + (p_local - g0);
-}
+// k_generate.inl — K1, the camera rays of one batch: generate_paths, its kernels k_generate (box filter) / k_generate_filtered (the other pixel filters), and the unit's
+// one launcher, wf_generate<K_SPHERICAL_CAMERA> (wavefront.h). Included behind wavefront.h by two units: render.hip (the reference's perspective and orthographic
+// cameras: its kernels know nothing else) and k_generate_spherical.hip (K_SPHERICAL_CAMERA: the same kernels with PBRT-v4's spherical camera compiled into the leaf, for
+// scenes whose camera is one). Which kernels a unit holds is not written here: the table at the end is computed from shm_plan::has_generate_build (host/render_plan.hpp).
+#include <array>
 
+namespace {
+#if K_SPHERICAL_CAMERA
+namespace spherical {  // (the spherical unit's kernels carry the camera in their names: a profile or a disassembly tells the two units' apart)
+#endif
+// ---------------------------------------------------------------------------------------------
+// K1: camera rays for one batch, one path slot per lane (slot_of, wavefront.h, is the slots' order).
+// ---------------------------------------------------------------------------------------------
 // HAS_TEX: scenes that bind image textures carry the camera ray's auxiliary rays (a compile-time switch: with a run-time pointer the
 // auxiliary-ray record lived in scratch memory, 52 B of stores per path, in every scene)
 // FC: the pixel filter's class (shm/filter.h). filter_table: the tabulated class's table (the block's copy in LDS); filter_weight: where a filter whose weight differs
@@ -111,4 +108,60 @@ __global__ void __launch_bounds__(SHADE_BLOCK) k_generate_filtered(SceneView sv,
     } else {
         generate_paths<HAS_TEX, LEAN, ZS, FC>(sv, pa, pixels, n_pix, sample_begin, n_samples, params, q_active, qs, pix_group, nullptr, nullptr);
     }
+}
+// The unit's kernels by the plan's coordinates, [ZS ? 0 : 1][filter class][HAS_TEX][LEAN]: a cell launches its kernel where shm_plan::has_generate_build says there is one and
+// is null elsewhere. The box filter's kernel and the others' differ by the filter_weight argument.
+using GenerateLaunch = void (*)(ShmScene*, const GenerateArgs&);
+template <bool HAS_TEX, bool LEAN, bool ZS, int FC>
+void launch_generate(ShmScene* s, const GenerateArgs& a) {
+    const uint32_t total = a.n_pix * (uint32_t)a.n_samples;
+    auto launch = [&](auto kernel, auto... more) {
+        hipLaunchKernelGGL(kernel, dim3((total + SHADE_BLOCK - 1) / SHADE_BLOCK), dim3(SHADE_BLOCK), 0, a.stream, s->dsv, s->pa, a.pixels, a.n_pix, a.sample_begin, a.n_samples,
+                           a.params, s->d_q_active[0], s->d_qs, s->pix_group, more...);
+    };
+    if constexpr (FC == FILTER_CLASS_BOX) launch(k_generate<HAS_TEX, LEAN, ZS>);
+    else launch(k_generate_filtered<HAS_TEX, LEAN, ZS, FC>, s->d_filter_weight);
+}
+template <bool HAS_TEX, bool LEAN, bool ZS, int FC>
+constexpr GenerateLaunch generate_cell() {
+    if constexpr (shm_plan::has_generate_build(HAS_TEX, LEAN)) return launch_generate<HAS_TEX, LEAN, ZS, FC>;
+    else return nullptr;
+}
+using GenerateClassCells = std::array<std::array<GenerateLaunch, 2>, 2>;  // [HAS_TEX][LEAN]
+using GenerateSamplerCells = std::array<GenerateClassCells, 3>;           // [filter class]
+template <bool ZS, int FC>
+constexpr GenerateClassCells generate_class_cells = {{{generate_cell<false, false, ZS, FC>(), generate_cell<false, true, ZS, FC>()},
+                                                      {generate_cell<true, false, ZS, FC>(), generate_cell<true, true, ZS, FC>()}}};
+static_assert(FILTER_CLASS_BOX == 0 && FILTER_CLASS_TRIANGLE == 1 && FILTER_CLASS_TABULATED == 2, "the order of generate_sampler_cells' initializer");
+template <bool ZS>
+constexpr GenerateSamplerCells generate_sampler_cells = {generate_class_cells<ZS, FILTER_CLASS_BOX>, generate_class_cells<ZS, FILTER_CLASS_TRIANGLE>, generate_class_cells<ZS, FILTER_CLASS_TABULATED>};
+// The order in which the cells are first named is the order of the kernels in the unit's code object, and that order is part of a ZSobol kernel's text: it calls
+// shm::zsobol_bits, which heads the code object, by its distance. So the tables name ZSobol first, [ZS ? 0 : 1], and render.hip's unit, whose table once began with the box
+// filter's row of both samplers, still names that row first (profiles/generate_launcher.md). A change that may alter the kernels' text can drop both.
+#if !K_SPHERICAL_CAMERA
+constexpr std::array<GenerateClassCells, 2> generate_box_cells_first = {generate_class_cells<true, FILTER_CLASS_BOX>, generate_class_cells<false, FILTER_CLASS_BOX>};
+#endif
+constexpr std::array<GenerateSamplerCells, 2> generate_table = {generate_sampler_cells<true>, generate_sampler_cells<false>};
+// (an initializer with a cell left out would leave a null behind: the table is held to the rule here, not at the first render)
+constexpr bool generate_table_is_the_rule() {
+    for (int zs = 0; zs < 2; ++zs)
+        for (int fc = 0; fc < 3; ++fc)
+            for (int tex = 0; tex < 2; ++tex)
+                for (int lean = 0; lean < 2; ++lean)
+                    if ((generate_table[zs][fc][tex][lean] != nullptr) != shm_plan::has_generate_build(tex != 0, lean != 0)) return false;
+    return true;
+}
+static_assert(generate_table_is_the_rule(), "k_generate.inl: the table lacks a build shm_plan::has_generate_build names, or holds one it does not name");
+#if K_SPHERICAL_CAMERA
+}  // namespace spherical
+using namespace spherical;
+#endif
+}  // namespace
+
+template <> int wf_generate<K_SPHERICAL_CAMERA>(ShmScene* s, const GenerateArgs& a) {
+    const GenerateLaunch launch = generate_table[a.zs ? 0 : 1][shm_plan::generate_filter_class(a.flt)][a.tex ? 1 : 0][a.lean ? 1 : 0];
+    if (!launch) { shm_err() = "internal: the render plan calls a k_generate build that does not exist"; return SHM_ERR_INTERNAL; }
+    launch(s, a);
+    LAUNCH_TRY("k_generate");
+    return SHM_OK;
 }

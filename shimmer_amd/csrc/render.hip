@@ -2,7 +2,7 @@
 //
 // Replaces the tile-parallel loop of the reference (paths relative to /root/reference/src):
 //   integrator.rs:226-322  ImageTileIntegrator::render      -> shm_render / shm_render_device / shm_render_wave (host loop below)
-//   integrator.rs:326-396  evaluate_pixel_sample            -> K1 k_generate
+//   integrator.rs:326-396  evaluate_pixel_sample            -> K1 (wf_generate: the generate units)
 //   aggregate.rs:71-139    BvhAggregate::intersect          -> K2 k_trace5<false, GEN> (persistent waves, LDS stack, both children per step)
 //   aggregate.rs:141-203   BvhAggregate::intersect_predicate-> K3 k_trace5<true, GEN>
 //   integrator.rs:772-892  PathIntegrator::li loop body     -> K4+K5 k_shade<HAS_LAYERED, TRI_ONLY> (one path vertex per launch)
@@ -38,9 +38,6 @@ __global__ void k_expand_tiles(const ShmTile* tiles, const uint32_t* tile_offset
     for (int x = tl.x0; x < tl.x1; ++x)
         for (int y = tl.y0; y < tl.y1; ++y) pixels[k++] = (uint32_t)x | ((uint32_t)y << 16);
 }
-
-// K1 (k_generate.inl): generate_paths, k_generate and k_generate_filtered for the reference's two cameras — this unit is built without K_SPHERICAL_CAMERA (wavefront.h)
-#include "k_generate.inl"
 
 // Scene creation: the shading records of the flat triangles (shm/tri_shade.h), one thread per primitive slot. The record is what triangle_interaction + get_bsdf — the
 // code the shading kernels would run at every hit on the slot — leave behind; the slot's PrimRec::pad[1] says that it is there.
@@ -111,10 +108,10 @@ __global__ void __launch_bounds__(SHADE2_BLOCK) k_split_plain(SceneView sv, Path
 // K6: RgbFilm::add_sample for every sample of the batch, per pixel in sample order (f64 sums are
 // order dependent; the reference adds samples of a pixel in increasing sample_index).
 // ---------------------------------------------------------------------------------------------
-// W: where a sample's filter weight comes from. FILM_WEIGHT_ONE: it is 1 (box, triangle; every filter under options.disable_pixel_jitter); FILM_WEIGHT_CONSTANT: the one
-// constant `weight_k` of the scene's table (gaussian: still accumulated as K, so that weight_sum is spp * K as in the oracle); FILM_WEIGHT_PER_SAMPLE: +-K as k_generate_filtered
-// left it per path slot (Mitchell, sinc).
-enum : int { FILM_WEIGHT_ONE, FILM_WEIGHT_CONSTANT, FILM_WEIGHT_PER_SAMPLE };
+// W: where a sample's filter weight comes from (shm_plan::film_weight, host/render_plan.hpp). FILM_WEIGHT_ONE: it is 1 (box, triangle; every filter under
+// options.disable_pixel_jitter); FILM_WEIGHT_CONSTANT: the one constant `weight_k` of the scene's table (gaussian: still accumulated as K, so that weight_sum is spp * K
+// as in the oracle); FILM_WEIGHT_PER_SAMPLE: +-K as K1 left it per path slot (Mitchell, sinc).
+using namespace shm_plan;
 template <int W>
 __device__ __forceinline__ void film_add_samples(const SceneView& sv, const PathArrays& pa, const uint32_t* pixels, uint32_t n_pix, int n_samples, ShmFilmPixel* film,
                                                  DeviceCounters* counters, uint32_t pix_group, const float* filter_weight, float weight_k) {
@@ -155,6 +152,11 @@ __global__ void __launch_bounds__(SHADE_BLOCK) k_film_weighted(SceneView sv, Pat
 
 }  // namespace
 
+// K1 for the reference's two cameras, perspective and orthographic: this unit is built without K_SPHERICAL_CAMERA, so the .inl defines wf_generate<false> here (wavefront.h).
+// (Not yet a unit of its own like the spherical camera's: the ZSobol kernels call shm::zsobol_bits at the head of the code object by its distance, which is part of their
+//  text, and only this unit's kernels in front of them keep that distance what it was — profiles/generate_launcher.md.)
+#include "k_generate.inl"
+
 namespace {
 
 template <typename T>
@@ -189,7 +191,6 @@ static uint64_t max_batch_paths() {
     return max_cap;
 }
 
-using namespace shm_plan;
 // Which kernels a scene runs: one cell per geometry x image class x sampler x extended build (DL: the *_dl builds, wavefront.h K_DELTA_LIGHTS).
 // WHICH cell a render takes, and which of its launchers run, is the RenderPlan's (host/render_plan.hpp); the staged pipeline replaced the fused general kernels of
 // round 1 everywhere but in the lean class (round-2 A/B, same box: coated S3 1 208 -> 1 724 Mray/s, textured Cornell 768 -> 906, crown-proxy C4 1 758 -> 1 735).
@@ -201,13 +202,8 @@ constexpr ShadeFn shade_fn() {
     if constexpr (has_build(b)) return wf_shade<FAMILY, b.geo, b.img, ZS && FAMILY != FAM_VERTEX, DL>;
     else return nullptr;
 }
-// K1 by image class, [LEAN]: the textured class has no k_generate<., LEAN> (HAS_LEAN_KERNELS; cells_match_plan below)
-template <bool ZS>
-constexpr GenerateKernel generate_cells[N_IMG][2] = {
-    {k_generate<false, false, ZS>, k_generate<false, true, ZS>}, {k_generate<true, false, ZS>, nullptr}, {k_generate<false, false, ZS>, k_generate<false, true, ZS>}};
 template <int GEO, int IMG, bool ZS, bool DL>
 constexpr ShadeKernels shade_cell = {
-    .generate = {generate_cells<ZS>[IMG][0], generate_cells<ZS>[IMG][1]},
     .lean = shade_fn<FAM_LEAN, GEO, IMG, ZS, DL>(), .lean_diverted = shade_fn<FAM_LEAN_DIVERTED, GEO, IMG, ZS, DL>(),
     .fused_all = shade_fn<FAM_FUSED_ALL, GEO, IMG, ZS, DL>(), .vertex = shade_fn<FAM_VERTEX, GEO, IMG, ZS, DL>(),
     .scatter = {shade_fn<FAM_SCATTER + CLASS_DIFFUSE, GEO, IMG, ZS, DL>(), shade_fn<FAM_SCATTER + CLASS_CONDUCTOR, GEO, IMG, ZS, DL>(),
@@ -220,59 +216,18 @@ constexpr ShadeKernels shade_cells[N_GEO][N_IMG] = {
     {shade_cell<GEO_TRI, IMG_NONE, ZS, DL>, shade_cell<GEO_TRI, IMG_TEX, ZS, DL>, shade_cell<GEO_TRI, IMG_ENV, ZS, DL>},
     {shade_cell<GEO_GEN, IMG_NONE, ZS, DL>, shade_cell<GEO_GEN, IMG_TEX, ZS, DL>, shade_cell<GEO_GEN, IMG_ENV, ZS, DL>},
 };
-// ... and per pixel-filter class (FLT_TRIANGLE ..: [flt - 1]) x sampler: K1 and K6 of the filters that are not the box filter; the generate kernels as [HAS_TEX][LEAN]
-struct FilterKernels {
-    FilteredGenerateKernel generate[2][2];
-    WeightedFilmKernel film;  // (null: k_film, weight 1)
-};
-template <bool ZS>
-constexpr FilterKernels filter_cells[N_FLT - 1] = {
-    {{{k_generate_filtered<false, false, ZS, FILTER_CLASS_TRIANGLE>, k_generate_filtered<false, true, ZS, FILTER_CLASS_TRIANGLE>}, {k_generate_filtered<true, false, ZS, FILTER_CLASS_TRIANGLE>, nullptr}}, nullptr},
-    {{{k_generate_filtered<false, false, ZS, FILTER_CLASS_TABULATED>, k_generate_filtered<false, true, ZS, FILTER_CLASS_TABULATED>}, {k_generate_filtered<true, false, ZS, FILTER_CLASS_TABULATED>, nullptr}},
-     k_film_weighted<FILM_WEIGHT_CONSTANT>},
-    {{{k_generate_filtered<false, false, ZS, FILTER_CLASS_TABULATED>, k_generate_filtered<false, true, ZS, FILTER_CLASS_TABULATED>}, {k_generate_filtered<true, false, ZS, FILTER_CLASS_TABULATED>, nullptr}},
-     k_film_weighted<FILM_WEIGHT_PER_SAMPLE>},
-};
-// A render's kernels: a lookup by the plan's coordinates
+// A render's shading launchers: a lookup by the plan's coordinates (K1's launcher, wf_generate, and K6's, launch_film below, take the coordinates themselves)
 static ShadeKernels select_kernels(const RenderPlan& p) {
     const ShadeKernels(&cells)[N_GEO][N_IMG] = p.dl ? (p.zs ? shade_cells<true, true> : shade_cells<false, true>) : (p.zs ? shade_cells<true, false> : shade_cells<false, false>);
     ShadeKernels k = cells[p.geo][p.img];
     k.lean = cells[p.geo][p.img_lean].lean;
     k.lean_diverted = cells[p.geo][p.img_lean].lean_diverted;
-    k.generate[0] = cells[p.geo][p.img_generate].generate[0];
-    k.generate[1] = cells[p.geo][p.img_generate].generate[1];
-    k.generate_filtered[0] = k.generate_filtered[1] = nullptr;
-    k.film_weighted = nullptr;
-    if (p.flt != FLT_BOX) {
-        const FilterKernels& fk = (p.zs ? filter_cells<true> : filter_cells<false>)[p.flt - 1];
-        k.generate_filtered[0] = fk.generate[p.img_generate == IMG_TEX ? 1 : 0][0];
-        k.generate_filtered[1] = fk.generate[p.img_generate == IMG_TEX ? 1 : 0][1];
-        k.film_weighted = fk.film;
-    }
     if (p.layered_onepass) k.scatter[CLASS_LAYERED] = k.scatter_layered_onepass;
-    if (p.spherical) {  // PBRT-v4's spherical camera: the same cells of k_generate_spherical.hip; nothing after K1 knows the camera
-        const SphericalGenerateCells& sc = wf_generate_spherical(p.zs);
-        const int tex = p.img_generate == IMG_TEX ? 1 : 0;
-        for (int lean = 0; lean < 2; ++lean) {
-            k.generate[lean] = sc.generate[tex][lean];
-            k.generate_filtered[lean] = p.flt != FLT_BOX ? sc.generate_filtered[p.flt == FLT_TRIANGLE ? 0 : 1][tex][lean] : nullptr;
-        }
-    }
     return k;
 }
-// (the launchers' null cells follow from HAS_LEAN_KERNELS by construction — serving_build reads it; what stays written by hand are K1's, held to it here. Behind
-//  select_kernels, in its order: the check must not be the first use of the tables — that moved k_generate's instantiations within the code object and changed their text)
-template <bool ZS, bool DL>
-constexpr bool cells_match_plan() {
-    for (int g = 0; g < N_GEO; ++g)
-        for (int i = 0; i < N_IMG; ++i)
-            if ((shade_cells<ZS, DL>[g][i].generate[1] != nullptr) != HAS_LEAN_KERNELS[i]) return false;
-    return true;
-}
-static_assert(cells_match_plan<true, true>() && cells_match_plan<false, true>() && cells_match_plan<true, false>() && cells_match_plan<false, false>(), "k_generate<., LEAN> vs HAS_LEAN_KERNELS");
-// ... and the one validation behind it: every launcher the plan will call is there
+// ... and the one validation behind it: every launcher the plan will call is there (the null cells follow from HAS_LEAN_KERNELS by construction — serving_build reads it)
 static bool kernels_complete(const ShadeKernels& k, const ScenePlan& sp, const RenderPlan& p) {
-    bool ok = p.flt != FLT_BOX ? k.generate_filtered[p.lean_first ? 1 : 0] != nullptr : k.generate[p.lean_first ? 1 : 0] != nullptr;
+    bool ok = true;
     if (p.route == ROUTE_LEAN) ok = ok && k.lean;
     if (p.route == ROUTE_SIMPLE) ok = ok && k.simple;
     if (p.route == ROUTE_RANDOM_WALK) ok = ok && k.randomwalk;
@@ -282,6 +237,20 @@ static bool kernels_complete(const ShadeKernels& k, const ScenePlan& sp, const R
         for (int c = 0; c < N_BXDF_CLASSES; ++c) ok = ok && (!sp.f.has_class[c] || k.scatter[c]);
     }
     return ok;
+}
+// K6 of a batch: the film kernel that takes a sample's weight from where the render's filter class leaves it (shm_plan::film_weight)
+static int launch_film(ShmScene* s, const RenderPlan& p, const uint32_t* pixels, uint32_t n_pix, int n_samples) {
+    auto launch = [&](auto kernel, auto... more) {
+        hipLaunchKernelGGL(kernel, dim3((n_pix + SHADE_BLOCK - 1) / SHADE_BLOCK), dim3(SHADE_BLOCK), 0, s->stream, s->dsv, s->pa, pixels, n_pix, n_samples, s->d_film, s->d_counters,
+                           s->pix_group, more...);
+    };
+    switch (film_weight(p.flt)) {  // (the weighted kernels' two arguments: the per-path weights, and the constant K that heads the scene's filter table)
+        case FILM_WEIGHT_CONSTANT: launch(k_film_weighted<FILM_WEIGHT_CONSTANT>, s->d_filter_weight, s->flat.dist_data[0]); break;
+        case FILM_WEIGHT_PER_SAMPLE: launch(k_film_weighted<FILM_WEIGHT_PER_SAMPLE>, s->d_filter_weight, s->flat.dist_data[0]); break;
+        default: launch(k_film); break;
+    }
+    LAUNCH_TRY("k_film");
+    return SHM_OK;
 }
 // The batch limit on THIS device right now: SHM_BATCH_PATHS, bounded by 80 % of the memory that is free (plus what the
 // current workspace already holds), so that a GPU shared with other allocations degrades to more batches, not to an error.
@@ -691,19 +660,13 @@ static int shade_vertex(Render& r, const ShadeArgs& sa, int bounce, bool overlap
 static int render_batch(Render& r, const uint32_t* pixels, uint32_t n_pix) {
     ShmScene* s = r.s;
     const RenderPlan& p = r.plan;
-    const ShadeKernels& k = r.k;
     const ShmRenderParams* params = r.params;
     EventPool& ev = r.ev;
     int rc;
     const uint32_t total = n_pix * (uint32_t)r.n_samples;
     BatchHitState hits{s, p};
-    if (p.flt != FLT_BOX)
-        hipLaunchKernelGGL(k.generate_filtered[p.lean_first ? 1 : 0], dim3((total + SHADE_BLOCK - 1) / SHADE_BLOCK), dim3(SHADE_BLOCK), 0, s->stream, s->dsv, s->pa, pixels, n_pix,
-                           r.sample_begin, r.n_samples, *params, s->d_q_active[0], s->d_qs, s->pix_group, s->d_filter_weight);
-    else
-        hipLaunchKernelGGL(k.generate[p.lean_first ? 1 : 0], dim3((total + SHADE_BLOCK - 1) / SHADE_BLOCK), dim3(SHADE_BLOCK), 0, s->stream, s->dsv, s->pa, pixels, n_pix,
-                           r.sample_begin, r.n_samples, *params, s->d_q_active[0], s->d_qs, s->pix_group);
-    LAUNCH_TRY("k_generate");
+    const GenerateArgs ga{s->stream, pixels, n_pix, r.sample_begin, r.n_samples, *params, p.img_generate == IMG_TEX, p.lean_first, p.zs, p.flt};
+    if ((rc = (p.spherical ? wf_generate<true> : wf_generate<false>)(s, ga)) != SHM_OK) return rc;
     int cur = 0;
     // K3 of bounce b on a second stream beside K2 of bounce b+1 — they are independent: K3 reads the shadow buffers and adds into L, K2 reads the extension rays and
     // writes hit records — and the next shade launch waits for both: where the plan's overlap policy says so (small batches; late bounces)
@@ -767,13 +730,7 @@ static int render_batch(Render& r, const uint32_t* pixels, uint32_t n_pix) {
     if (overlap && k3_done) hipStreamWaitEvent(s->stream, k3_done, 0);  // the film reads L
     if (p.route == ROUTE_RANDOM_WALK)
         if ((rc = wf_launch_fold_randomwalk(s, s->stream, r.cap_eff, total)) != SHM_OK) return rc;
-    if (k.film_weighted)  // (the weight: the constant K that heads the scene's filter table, with its sign per path slot where the filter has negative lobes)
-        hipLaunchKernelGGL(k.film_weighted, dim3((n_pix + SHADE_BLOCK - 1) / SHADE_BLOCK), dim3(SHADE_BLOCK), 0, s->stream, s->dsv, s->pa, pixels, n_pix, r.n_samples,
-                           s->d_film, s->d_counters, s->pix_group, s->d_filter_weight, s->flat.dist_data[0]);
-    else
-        hipLaunchKernelGGL(k_film, dim3((n_pix + SHADE_BLOCK - 1) / SHADE_BLOCK), dim3(SHADE_BLOCK), 0, s->stream, s->dsv, s->pa, pixels, n_pix, r.n_samples,
-                           s->d_film, s->d_counters, s->pix_group);
-    LAUNCH_TRY("k_film");
+    if ((rc = launch_film(s, p, pixels, n_pix, r.n_samples)) != SHM_OK) return rc;
     if (ev.failed) { g_err = "hipEventCreate failed"; return SHM_ERR_DEVICE; }
     return SHM_OK;
 }

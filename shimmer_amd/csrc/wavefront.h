@@ -1,7 +1,7 @@
 // wavefront.h — shared declarations of the gfx950 wavefront path tracer behind include/shimmer_hip.h: path state (SoA in HBM), queue
 // bookkeeping, the scene object, and the launchers each kernel translation unit exports. WHICH of them a scene and a render run is decided in
 // host/render_plan.hpp (ScenePlan at scene creation, RenderPlan per render: pure C++, tested on the CPU); render.hip looks the launchers up and calls them. The kernels are split over several .hip files
-// (k_trace.hip, k_shade_*.hip, render.hip) so that they compile in parallel; nothing here is exported from the library.
+// (k_trace.hip, k_generate_spherical.hip, k_shade_*.hip, render.hip) so that they compile in parallel; nothing here is exported from the library.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -29,7 +29,8 @@
 // material (FlatScene::has_diffuse_transmission), as it does for one that holds a distant or spot light.
 #define SHM_DIFFUSE_TRANSMISSION K_DELTA_LIGHTS
 // K_SPHERICAL_CAMERA (a translation unit's switch): PBRT-v4's spherical camera is compiled into camera_generate_ray_differential (shm/path.h, SHM_SPHERICAL_CAMERA) only
-// where it is true, and only k_generate_spherical.hip — k_generate.inl a second time — sets it: RenderPlan::spherical names its kernels for a scene whose camera is one.
+// where it is true, and only k_generate_spherical.hip — k_generate.inl beside render.hip's — sets it: its launcher is wf_generate<true> (below), which
+// RenderPlan::spherical names for a scene whose camera is one.
 #ifndef K_SPHERICAL_CAMERA
 #define K_SPHERICAL_CAMERA false
 #endif
@@ -318,6 +319,16 @@ __device__ __forceinline__ uint32_t queue_push_slot(uint32_t* counter, bool pred
     uint32_t rank = (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
     return base + rank;
 }
+// A path's slot in a batch, shared by K1 (k_generate.inl), which fills the slots, and K6 (k_film, render.hip), which reads them back per pixel in sample order: slots are
+// ordered [pixel group][sample][pixel in group] with groups of `pix_group` consecutive pixels of the tile-ordered pixel list (pix_group >= n_pix is the plain sample-major
+// order slot = s_local * n_pix + p_local; pix_group = 64 keeps all samples of one 8x8 tile adjacent in the queues, so that a wave's private queue range, and an XCD's
+// queue partition, is a compact image region).
+__device__ __forceinline__ uint32_t slot_of(uint32_t p_local, uint32_t s_local, uint32_t n_pix, uint32_t n_samples, uint32_t pix_group) {
+    uint32_t g = p_local / pix_group;
+    uint32_t g0 = g * pix_group;
+    uint32_t pg = min(pix_group, n_pix - g0);
+    return g0 * n_samples + s_local * pg + (p_local - g0);
+}
 __device__ __forceinline__ Spec ld_spec(const float4& f) { Spec s; s.v[0] = f.x; s.v[1] = f.y; s.v[2] = f.z; s.v[3] = f.w; return s; }
 __device__ __forceinline__ float4 st_spec(const Spec& s) { return make_float4(s.v[0], s.v[1], s.v[2], s.v[3]); }
 constexpr int SHADE2_BLOCK = 256;
@@ -468,23 +479,23 @@ constexpr bool build_env_light(int img) { return img == shm_plan::IMG_ENV; }
 // (the units that compile the environment light in by their switch, not by a template parameter: an env build belongs in a K_ENV_LIGHT unit, and no other does)
 #define WF_ENV_UNIT_CHECK(IMG) static_assert(build_env_light(IMG) == (K_ENV_LIGHT), "an IMG_ENV build is a K_ENV_LIGHT unit's, and such a unit holds no other")
 WF_INTERNAL int wf_launch_fold_randomwalk(ShmScene* s, hipStream_t stream, uint32_t cap_eff, uint32_t total);  // k_shade_other.hip: RandomWalk's sum over depths, after the last bounce
-// K1 (render.hip, k_generate<HAS_TEX, LEAN, ZS>)
-using GenerateKernel = void (*)(SceneView, PathArrays, const uint32_t*, uint32_t, int, int, ShmRenderParams, uint32_t*, QueueState*, uint32_t);
-// K1 / K6 of the pixel filters beside the box filter (render.hip, k_generate_filtered<HAS_TEX, LEAN, ZS, FC>, k_film_weighted<W>): + the per-path filter weights (+ the constant K)
-using FilteredGenerateKernel = void (*)(SceneView, PathArrays, const uint32_t*, uint32_t, int, int, ShmRenderParams, uint32_t*, QueueState*, uint32_t, float*);
-using WeightedFilmKernel = void (*)(SceneView, PathArrays, const uint32_t*, uint32_t, int, ShmFilmPixel*, DeviceCounters*, uint32_t, const float*, float);
-// K1 of a scene whose camera is PBRT-v4's spherical one (k_generate_spherical.hip): render.hip's generate cells once more, per sampler
-struct SphericalGenerateCells {
-    GenerateKernel generate[2][2];                  // [HAS_TEX][LEAN]
-    FilteredGenerateKernel generate_filtered[2][2][2];  // [filter class: triangle, tabulated][HAS_TEX][LEAN]
+// K1, the camera rays of one batch (k_generate.inl): ONE launcher per unit that holds the kernels — <false>: render.hip, the reference's perspective and orthographic
+// cameras; <true>: k_generate_spherical.hip — addressed by the plan's coordinates: image textures (the camera rays' auxiliary rays: RenderPlan::img_generate == IMG_TEX),
+// bounce 0 on known constants (lean_first), the sampler and the pixel filter's class (FLT_*). Which (tex, lean) builds exist, and the class a FLT_* runs, is
+// shm_plan::has_generate_build / generate_filter_class (host/render_plan.hpp); like wf_shade the template has no definition.
+struct GenerateArgs {
+    hipStream_t stream;
+    const uint32_t* pixels;
+    uint32_t n_pix;
+    int sample_begin, n_samples;
+    ShmRenderParams params;
+    bool tex, lean, zs;
+    int flt;
 };
-WF_INTERNAL const SphericalGenerateCells& wf_generate_spherical(bool zs);
-// The kernels of one scene class: a cell of render.hip's table by geometry x image class x sampler (nullptr: no such build,
-// shm_plan::HAS_LEAN_KERNELS), of which select_kernels makes a render's set by the RenderPlan's coordinates. The plan says which of them run; the bounce loop calls them.
+template <bool SPHERICAL> WF_INTERNAL int wf_generate(ShmScene* s, const GenerateArgs& a);
+// The shading launchers of one scene class: a cell of render.hip's table by geometry x image class x sampler x extended build (nullptr: no such
+// build, shm_plan::serving_build), of which select_kernels makes a render's set by the RenderPlan's coordinates. The plan says which of them run; the bounce loop calls them.
 struct ShadeKernels {
-    GenerateKernel generate[2];       // [LEAN]: bounce 0 on known constants (ShadeArgs::first_bounce)
-    FilteredGenerateKernel generate_filtered[2];  // ... of a scene whose pixel filter is not the box filter (null: `generate`), and the film kernel that applies
-    WeightedFilmKernel film_weighted;             // its weights (null: k_film, weight 1) — select_kernels fills the three from the scene's filter class
     ShadeFn lean, lean_diverted;      // k_shade<lean>: the whole queue of an all-diffuse scene / the hits k_vertex or the split pass diverted
     ShadeFn fused_all;                // the material-sorted fused all-materials kernel
     ShadeFn vertex;                   // staged shading: the hit half ...

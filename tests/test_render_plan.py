@@ -17,7 +17,10 @@ The traversal part of the plan — which row of the kernel table a scene's rays 
 orc_fn_trace_plan: the variant and strictness rules, the stack bound against the deepest leaf, and every row's LDS against the compute unit's.
 
 The shading launchers' serving rule — which build of a launcher family serves which cell of render.hip's table (serving_build; the table is computed from it) — is
-walked through orc_fn_shade_serving (the tests at the end): its shape, its 44 builds, and that every launcher a plan of the domain above would call is served."""
+walked through orc_fn_shade_serving: its shape, its 44 builds, and that every launcher a plan of the domain above would call is served.
+
+K1's and K6's rule — which camera-ray kernel builds exist, the filter class a plan's FLT_* runs, and where the film kernel takes a sample's weight from — is walked
+through orc_fn_generate_rule (the tests at the end): its fixed points, its 36 builds, and that every plan of the domain lands on a build that exists."""
 import itertools
 import sys
 from pathlib import Path
@@ -335,3 +338,44 @@ def test_every_launcher_a_plan_calls_has_a_serving_build(serving, plans):
         missing |= staged0 & ((i["classes"] >> 3) & 1 != 0) & ~layered
         assert not missing.any()
         assert staged0.any() and (q["route"] == ROUTE_LEAN).any() and (q["drain_lean"] != 0).any()
+
+
+# ---- K1's and K6's rule (has_generate_build, generate_filter_class, film_weight: the plan's coordinates -> the camera-ray kernel and the film kernel) through orc_fn_generate_rule ----
+FLT_BOX, FLT_TRIANGLE, FLT_TABULATED, FLT_TABULATED_SIGNED = (oracle_py.FLT.index(n) for n in ("BOX", "TRIANGLE", "TABULATED", "TABULATED_SIGNED"))
+
+
+@pytest.fixture(scope="module")
+def generate_rule():
+    t = oracle_py.generate_rule()  # [tex][lean][flt] -> (exists, filter class, film weight)
+    assert t.shape == (2, 2, 4, 3) and t.min() >= 0
+    return t
+
+
+def test_generate_rule_fixed_points(generate_rule):
+    t = generate_rule
+    for tex, lean in itertools.product(range(2), range(2)):  # the filter class and the film weight go by the plan's filter class alone
+        assert [oracle_py.FILTER_CLASS[c] for c in t[tex, lean, :, 1]] == ["BOX", "TRIANGLE", "TABULATED", "TABULATED"]
+        assert [oracle_py.FILM_WEIGHT[w] for w in t[tex, lean, :, 2]] == ["ONE", "ONE", "CONSTANT", "PER_SAMPLE"]
+        assert len(set(t[tex, lean, :, 0])) == 1  # ... and whether a build exists by (tex, lean) alone
+
+
+def test_generate_rule_has_the_36_builds(generate_rule, plans):
+    t = generate_rule
+    builds = {(tex, lean, int(t[tex, lean, flt, 1])) for tex, lean, flt in itertools.product(range(2), range(2), range(4)) if t[tex, lean, flt, 0]}
+    assert len(builds) == 9 and len(builds) * 2 * 2 == 36  # x camera (perspective / orthographic, spherical) x sampler
+    empty = {(tex, lean) for tex, lean in itertools.product(range(2), range(2)) if not t[tex, lean, :, 0].any()}
+    assert empty == {(1, 1)}  # lean with image textures, and nothing else: the textured class has no lean kernels
+    (q,) = plans.values()
+    assert bool(t[1, 1, 0, 0]) == bool(q["has_lean_tex"][0]) and bool(t[0, 1, 0, 0]) == bool(q["has_lean_none"][0])  # read from HAS_LEAN_KERNELS
+
+
+def test_every_plan_lands_on_a_generate_build_and_its_film_kernel(generate_rule, plans):
+    t = generate_rule
+    for name, q in plans.items():
+        i = q["in"]
+        assert not np.any(q["img_generate"] == IMG_ENV)
+        tex, lean, flt = (q["img_generate"] == IMG_TEX).astype(int), (q["lean_first"] != 0).astype(int), q["flt"]
+        assert t[tex, lean, flt, 0].all()
+        assert np.array_equal(q["film_per_sample"] != 0, t[tex, lean, flt, 2] == oracle_py.FILM_WEIGHT.index("PER_SAMPLE"))
+        assert not np.any((flt != FLT_BOX) & ((i["disable_pixel_jitter"] != 0) | (name == "BOX")))
+        assert set(np.unique(flt)) == {"BOX": {FLT_BOX}, "TRIANGLE": {FLT_BOX, FLT_TRIANGLE}, "GAUSSIAN": {FLT_BOX, FLT_TABULATED}, "MITCHELL": {FLT_BOX, FLT_TABULATED_SIGNED}}[name]
