@@ -6,6 +6,7 @@
     python examples/render_scene.py textured | checkerboard | coated | patches | instanced | environment | ganesha | crown | spotlit | fuzz:13
     python examples/render_scene.py diffuse_transmission | translucent   (PBRT-v4's diffuse transmission material: the scene file / the builder)
     python examples/render_scene.py cornell --camera spherical [--mapping equirectangular]   (PBRT-v4's spherical camera in place of the scene's own)
+    python examples/render_scene.py disk_and_cylinder | quadrics     (PBRT-v4's disk and cylinder: examples/scenes/disk_and_cylinder.pbrt / the builder)
     python examples/render_scene.py cornell_probe                    (examples/scenes/cornell_probe.pbrt: an equal-area probe in the middle of the Cornell box)
 
 Everything goes through the C ABI of include/shimmer_hip.h (shimmer_amd/abi.py is the ctypes binding): scene description ->
@@ -25,7 +26,7 @@ from shimmer_amd import abi, render, scenes  # noqa: E402
 
 
 def make_scene(lib, name, w, h, film=None, camera=None):
-    if camera is not None and (name in ("checkerboard", "diffuse_transmission", "cornell_probe") or name.startswith(("procedural", "fuzz:"))):
+    if camera is not None and (name in ("checkerboard", "diffuse_transmission", "cornell_probe", "disk_and_cylinder") or name.startswith(("procedural", "fuzz:"))):
         raise SystemExit(f"--camera does not apply to {name}: a scene file has its own camera, and the procedural and fuzz generators take none")
     if name == "cornell":
         return scenes.cornell_box(lib, w, h, camera=camera, film=film)
@@ -36,10 +37,11 @@ def make_scene(lib, name, w, h, film=None, camera=None):
         return scenes.cornell_box(lib, w, h, camera=camera, textured=True, film=film)
     if name == "coated":
         return scenes.cornell_box(lib, w, h, camera=camera, coated=True, film=film)
-    if name in ("checkerboard", "diffuse_transmission", "cornell_probe"):
+    if name in ("checkerboard", "diffuse_transmission", "cornell_probe", "disk_and_cylinder"):
         # scene FILES through the C++ front end (their own film size; --filter is the file's): PBRT-v4's procedural textures (examples/scenes/checkerboard.pbrt); a back-lit
         # sheet of PBRT-v4's diffuse transmission material in the Cornell box (examples/scenes/diffuse_transmission.pbrt: the extended *_dl kernels); PBRT-v4's
         # spherical camera as an equal-area probe in the middle of the box (examples/scenes/cornell_probe.pbrt; the file's camera: --camera does not apply)
+        # ; PBRT-v4's disk and cylinder as a lamp post whose emitter is a disk (examples/scenes/disk_and_cylinder.pbrt: the extended kernels and k_trace_quadrics.hip's)
         import ctypes as C
         from types import SimpleNamespace
         out = C.POINTER(abi.ShmPbrtScene)()
@@ -51,6 +53,8 @@ def make_scene(lib, name, w, h, film=None, camera=None):
         return scenes.cornell_box(lib, w, h, camera=camera, film=film, diffuse_transmission="sheet tall")
     if name in ("procedural", "procedural-general", "procedural-coated"):  # the same textures through the Python builder (scenes.procedural_cornell)
         return scenes.procedural_cornell(lib, w, h, which={"procedural": "checker", "procedural-general": "general", "procedural-coated": "coated"}[name], film=film)
+    if name == "quadrics":  # the same shapes through the Python builder (scenes.quadric_scene)
+        return scenes.quadric_scene(lib, "glass", w, h, film=film)
     if name == "patches":
         return scenes.cornell_box(lib, w, h, camera=camera, patches=True, film=film)
     if name == "instanced":

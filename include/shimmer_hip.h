@@ -27,7 +27,7 @@ extern "C" {
 
 /* Enum values added WITHOUT a version step are additive: no struct changes size or layout and a caller built against the earlier header never passes them.
  * Under version 10 these are SHM_TEXMAP_POINT3D, SHM_FLOATTEX_CHECKERBOARD .. SHM_FLOATTEX_BILERP, the mapping-only ShmImageTexture record (n_levels == 0) and
- * SHM_MATERIAL_DIFFUSE_TRANSMISSION. */
+ * SHM_MATERIAL_DIFFUSE_TRANSMISSION, and SHM_QUADRIC_DISK / SHM_QUADRIC_CYLINDER in ShmSphere::quadric (a byte of its padding). */
 #define SHM_ABI_VERSION 10
 
 /* The library is built with -fvisibility=hidden; only these entry points are exported. */
@@ -89,14 +89,21 @@ typedef struct ShmBilinearPatchMesh {
     uint8_t pad[6];
 } ShmBilinearPatchMesh;
 
-/* Sphere (src/shape/sphere.rs:27-38); matrices row-major m[r][c] as SquareMatrix<4>. */
+/* Sphere (src/shape/sphere.rs:27-38); matrices row-major m[r][c] as SquareMatrix<4>.
+ * The record also carries PBRT-v4's two other quadrics with the sphere's hit record {t_hit, p_obj, phi} (the reference has neither): `quadric` says which. They stay
+ * SHM_SHAPE_SPHERE primitives, and a zeroed byte (the former pad: every scene written before it had a name) is a sphere.
+ *   SHM_QUADRIC_DISK      radius; z_min == z_max = the height; theta_z_min = the inner radius, 0 <= inner < radius; theta_z_max = 0; phi_max in radians, in (0, 2 pi]
+ *   SHM_QUADRIC_CYLINDER  radius; z_min < z_max; theta_z_min = theta_z_max = 0; phi_max in radians, in (0, 2 pi]
+ * shm_scene_create answers any other kind with SHM_ERR_UNSUPPORTED and a field outside these ranges with SHM_ERR_INVALID_ARGUMENT. */
+enum { SHM_QUADRIC_SPHERE = 0, SHM_QUADRIC_DISK = 1, SHM_QUADRIC_CYLINDER = 2 };
 typedef struct ShmSphere {
     float radius, z_min, z_max, theta_z_min, theta_z_max, phi_max;
     float render_from_object[16];
     float object_from_render[16];
     uint8_t reverse_orientation;
     uint8_t transform_swaps_handedness;
-    uint8_t pad[6];
+    uint8_t quadric;   /* SHM_QUADRIC_* */
+    uint8_t pad[5];
 } ShmSphere;
 
 enum { SHM_SHAPE_TRIANGLE = 0, SHM_SHAPE_SPHERE = 1, SHM_SHAPE_BILINEAR_PATCH = 2,

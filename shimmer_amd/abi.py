@@ -21,6 +21,7 @@ SHM_MATERIAL_COATED_DIFFUSE, SHM_MATERIAL_COATED_CONDUCTOR, SHM_MATERIAL_MIX = 4
 SHM_MATERIAL_DIFFUSE_TRANSMISSION = 8  # (7 is reserved: rejected with SHM_ERR_UNSUPPORTED)
 SHM_LIGHT_POINT, SHM_LIGHT_DIFFUSE_AREA, SHM_LIGHT_UNIFORM_INFINITE, SHM_LIGHT_IMAGE_INFINITE = 0, 1, 2, 3
 SHM_LIGHT_DISTANT, SHM_LIGHT_SPOT = 4, 5  # PBRT-v4's DistantLight / SpotLight (ABI v10)
+SHM_QUADRIC_SPHERE, SHM_QUADRIC_DISK, SHM_QUADRIC_CYLINDER = 0, 1, 2  # ShmSphere.quadric: PBRT-v4's disk and cylinder ride in the sphere's record
 SHM_SPECTRUM_IMAGE_TEXTURE, SHM_SPECTRUM_TEXTURE_NODE = 6, 7
 SHM_SPECTEX_LEAF, SHM_SPECTEX_SCALED, SHM_SPECTEX_MIX, SHM_SPECTEX_DIRECTION_MIX = 0, 1, 2, 3
 SHM_TEXMAP_UV, SHM_TEXMAP_SPHERICAL, SHM_TEXMAP_CYLINDRICAL, SHM_TEXMAP_PLANAR = 0, 1, 2, 3
@@ -67,7 +68,7 @@ class ShmSphere(C.Structure):
     _fields_ = [("radius", C.c_float), ("z_min", C.c_float), ("z_max", C.c_float), ("theta_z_min", C.c_float),
                 ("theta_z_max", C.c_float), ("phi_max", C.c_float), ("render_from_object", C.c_float * 16),
                 ("object_from_render", C.c_float * 16), ("reverse_orientation", C.c_uint8),
-                ("transform_swaps_handedness", C.c_uint8), ("pad", C.c_uint8 * 6)]
+                ("transform_swaps_handedness", C.c_uint8), ("quadric", C.c_uint8), ("pad", C.c_uint8 * 5)]
 
 
 class ShmPrimitive(C.Structure):

@@ -35,6 +35,7 @@ struct FlatScene {
                                                 // spot_cos_theta), zeros otherwise: SceneView::light_prim_recs
     bool has_diffuse_transmission = false;  // a SHM_MATERIAL_DIFFUSE_TRANSMISSION: selects the same kernels (shm/bxdf.h, SHM_DIFFUSE_TRANSMISSION)
     bool has_directed_lights = false;  // a SHM_LIGHT_DISTANT or SHM_LIGHT_SPOT: selects the *_dl shading kernels (wavefront.h, K_DELTA_LIGHTS)
+    bool has_quadric_kinds = false;    // a sphere record that is a disk or a cylinder (ShmSphere::quadric): selects the same shading kernels and k_trace_quadrics.hip's traversal kernels (shm/shapes.h, SHM_QUADRICS)
     std::vector<uint32_t> infinite_lights;
     std::vector<float> spectrum_data;
     std::vector<float> sensor_r, sensor_g, sensor_b;
@@ -260,6 +261,24 @@ inline int flatten_scene(const ShmSceneDesc* d, FlatScene& out, std::string& err
     out.nodes.assign(d->nodes, d->nodes + d->n_nodes);
     out.primitives.assign(d->primitives, d->primitives + d->n_primitives);
     out.spheres.assign(d->spheres, d->spheres + (d->spheres ? d->n_spheres : 0));
+    // PBRT-v4's disk and cylinder in the sphere's record (ShmSphere::quadric; shm/shapes.h): a record of a kind nobody knows, or one outside its kind's ranges, is named here
+    for (const ShmSphere& q : out.spheres) {
+        if (q.quadric == SHM_QUADRIC_SPHERE) continue;
+        if (q.quadric > SHM_QUADRIC_CYLINDER) { err = "unsupported quadric kind (sphere, disk, cylinder)"; return SHM_ERR_UNSUPPORTED; }
+        const char* what = q.quadric == SHM_QUADRIC_DISK ? "disk" : "cylinder";
+        bool finite = std::isfinite(q.radius) && std::isfinite(q.z_min) && std::isfinite(q.z_max) && std::isfinite(q.theta_z_min) && std::isfinite(q.theta_z_max) && std::isfinite(q.phi_max);
+        for (int k = 0; k < 16; ++k) finite = finite && std::isfinite(q.render_from_object[k]) && std::isfinite(q.object_from_render[k]);
+        if (!finite) { err = std::string(what) + ": a field is not finite"; return SHM_ERR_INVALID_ARGUMENT; }
+        if (!(q.radius > 0.0f)) { err = std::string(what) + ": the radius must be positive"; return SHM_ERR_INVALID_ARGUMENT; }
+        if (q.quadric == SHM_QUADRIC_DISK && (q.z_min != q.z_max || !(q.theta_z_min >= 0.0f && q.theta_z_min < q.radius) || q.theta_z_max != 0.0f)) {
+            err = "disk: need z_min == z_max (the height), 0 <= inner radius (theta_z_min) < radius and theta_z_max == 0"; return SHM_ERR_INVALID_ARGUMENT;
+        }
+        if (q.quadric == SHM_QUADRIC_CYLINDER && (!(q.z_min < q.z_max) || q.theta_z_min != 0.0f || q.theta_z_max != 0.0f)) {
+            err = "cylinder: need z_min < z_max and theta_z_min == theta_z_max == 0"; return SHM_ERR_INVALID_ARGUMENT;
+        }
+        if (!(q.phi_max > 0.0f && q.phi_max <= 2.0f * shm::PI_F)) { err = std::string(what) + ": phi_max must lie in (0, 2 pi]"; return SHM_ERR_INVALID_ARGUMENT; }
+        out.has_quadric_kinds = true;
+    }
     out.materials.assign(d->materials, d->materials + d->n_materials);
     out.lights.assign(d->lights, d->lights + (d->lights ? d->n_lights : 0));
     out.spectrum_data.assign(d->spectrum_data, d->spectrum_data + (d->spectrum_data ? d->n_spectrum_floats : 0));

@@ -11,7 +11,7 @@
 // CoordSysTransform ReverseOrientation Camera (perspective / orthographic / spherical) Film (rgb) Sampler PixelFilter (box gaussian mitchell sinc triangle) Integrator Option
 // WorldBegin AttributeBegin/End Attribute (per-target default parameters) Material MakeNamedMaterial NamedMaterial Texture (float / spectrum: constant scale mix
 // directionmix imagemap) AreaLightSource (diffuse) LightSource (point, infinite: uniform or an environment image) Shape (trianglemesh
-// bilinearmesh sphere plymesh) ObjectBegin/End ObjectInstance Include; spectra as "spectrum" samples / named tables / files, "blackbody",
+// bilinearmesh sphere disk cylinder plymesh) ObjectBegin/End ObjectInstance Include; spectra as "spectrum" samples / named tables / files, "blackbody",
 // and "rgb" through the sRGB rgb2spec table (the `.spec` file the reference loads); PNG images (the only format the reference reads,
 // host/image_io.hpp) for textures, normal maps and environment lights. What the reference itself leaves todo!() or this backend does not
 // take (media, Import, portals, animated transforms, other colour spaces) is reported as SHM_ERR_UNSUPPORTED with the line number, never
@@ -842,6 +842,12 @@ private:
             const float radius = ps.one_float("radius", 1.0f);
             a_->add_sphere(radius, ps.one_float("zmin", -radius), ps.one_float("zmax", radius), ps.one_float("phimax", 360.0f), rfo, reverse, (uint32_t)gs_.material,
                            gs_.area_light, object_);
+        } else if (type == "disk") {  // PBRT-v4 Disk::Create
+            a_->add_disk(ps.one_float("height", 0.0f), ps.one_float("radius", 1.0f), ps.one_float("innerradius", 0.0f), ps.one_float("phimax", 360.0f), rfo, reverse,
+                         (uint32_t)gs_.material, gs_.area_light, object_);
+        } else if (type == "cylinder") {  // PBRT-v4 Cylinder::Create
+            a_->add_cylinder(ps.one_float("radius", 1.0f), ps.one_float("zmin", -1.0f), ps.one_float("zmax", 1.0f), ps.one_float("phimax", 360.0f), rfo, reverse,
+                             (uint32_t)gs_.material, gs_.area_light, object_);
         } else if (type == "trianglemesh") {  // triangle.rs:55-140
             const std::vector<float> P = ps.floats("P");
             std::vector<int> vi = ps.ints("indices");
@@ -890,7 +896,7 @@ private:
                 a_->add_patch_mesh(std::move(m), (uint32_t)gs_.material, gs_.area_light, object_);
             }
         } else {
-            fail(tk.where(line) + ": shape \"" + type + "\" is not supported by this backend (sphere, trianglemesh, bilinearmesh, plymesh)", SHM_ERR_UNSUPPORTED);
+            fail(tk.where(line) + ": shape \"" + type + "\" is not supported by this backend (sphere, disk, cylinder, trianglemesh, bilinearmesh, plymesh)", SHM_ERR_UNSUPPORTED);
         }
     }
     std::string resolve(const std::string& f) const { return (f.empty() || f[0] == '/' || base_dir_.empty()) ? f : base_dir_ + "/" + f; }

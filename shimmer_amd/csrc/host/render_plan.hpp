@@ -62,7 +62,8 @@ constexpr bool has_generate_build(bool tex, bool lean) { return !lean || HAS_LEA
 struct SceneFacts {
     bool has_class[N_CLS] = {false, false, false, false};
     bool diffuse_only = true, has_material_textures = false, has_image_light = false, has_spheres = false, has_instances = false;
-    bool extended = false;         // a distant or spot light or a diffuse transmission material: the *_dl builds (wavefront.h, K_DELTA_LIGHTS) and no others
+    bool extended = false;         // a distant or spot light, a diffuse transmission material or a disk / cylinder: the *_dl builds (wavefront.h, K_DELTA_LIGHTS) and no others
+    bool has_quadric_kinds = false;  // a disk or a cylinder (ShmSphere::quadric): the traversal kernels of k_trace_quadrics.hip (and `extended`: the shading kernels that know the shapes)
     bool has_plain_diffuse = false, plain_quarter = false;  // primitives on a plain DiffuseMaterial: any / a quarter or more by count or by surface area
     bool patch_heavy = false, has_quadric_patch = false;    // spheres / bilinear patches: a twelfth of the primitive records or more / any
     bool small_tree = false, has_prims = false;             // fewer than 4096 BVH nodes / any primitive record
@@ -75,7 +76,8 @@ inline SceneFacts scene_facts(const shm_host::FlatScene& f) {
     for (int c = 0; c < N_CLS; ++c) s.has_class[c] = f.has_class[c];
     s.diffuse_only = f.diffuse_only; s.has_material_textures = f.has_material_textures; s.has_image_light = f.has_image_light;
     s.has_spheres = f.has_spheres; s.has_instances = f.has_instances;
-    s.extended = f.has_directed_lights || f.has_diffuse_transmission;
+    s.has_quadric_kinds = f.has_quadric_kinds;
+    s.extended = f.has_directed_lights || f.has_diffuse_transmission || f.has_quadric_kinds;
     s.has_plain_diffuse = f.n_plain_diffuse_prims > 0;
     // (round 6: ... or a quarter of the SURFACE AREA — hits fall by area, not by count: a textured 4.3 M-triangle object in a plain room of 14 triangles sent every wall and
     //  floor hit through the textured class: 2 796 -> 3 127 Mray/s with the pass, profiles/r06_textured_object.txt)
@@ -277,8 +279,8 @@ inline RenderPlan render_plan(const ScenePlan& s, const ShmRenderParams& o) {
     // (k_generate writes the camera rays' auxiliary rays where the workspace holds them — under force_diffuse an env-only scene has none)
     p.img_generate = s.tex_ws ? IMG_TEX : IMG_NONE;
     p.zs = o.sampler == SHM_SAMPLER_ZSOBOL;
-    // (the *_dl builds for a scene with a distant or spot light or a diffuse transmission material, in every class: a kernel built without them would sample the lights as
-    //  area lights and shade the material as a CoatedConductor. This is the only place the set is chosen.)
+    // (the *_dl builds for a scene with a distant or spot light, a diffuse transmission material or a disk / cylinder, in every class: a kernel built without them would
+    //  sample the lights as area lights, shade the material as a CoatedConductor and the shapes as spheres. This is the only place the set is chosen.)
     p.dl = f.extended;
     // (the generate kernels that know PBRT-v4's spherical camera, for a scene whose camera is one and for no other: every other kernel would read it as a perspective camera)
     p.spherical = f.spherical_camera;

@@ -552,6 +552,49 @@ public:
         }
         prims.push_back(pr);
     }
+    // PBRT-v4's Disk and Cylinder (the reference has neither): quadrics in the sphere's record (ShmSphere::quadric), SHM_SHAPE_SPHERE primitives like it. The bounds are
+    // render_from_object of the object-space box (-r, -r, z_min) .. (r, r, z_max) — a disk's z_min == z_max is its height — through the sphere's eight corners.
+    void add_quadric(uint8_t kind, float radius, float z_min, float z_max, float inner, float phi_max_deg, const Xf& render_from_object, bool reverse, uint32_t material,
+                     const Emission& em, uint32_t owner) {
+        ShmSphere s;
+        memset(&s, 0, sizeof(s));
+        auto clampf = [](float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); };
+        s.quadric = kind;
+        s.radius = radius;
+        s.z_min = z_min;
+        s.z_max = z_max;
+        s.theta_z_min = inner;
+        s.phi_max = (3.14159265358979323846f / 180.0f) * clampf(phi_max_deg, 0.0f, 360.0f);
+        memcpy(s.render_from_object, render_from_object.m.m, sizeof(float) * 16);
+        memcpy(s.object_from_render, render_from_object.inv.m, sizeof(float) * 16);
+        s.reverse_orientation = reverse ? 1 : 0;
+        s.transform_swaps_handedness = swaps_handedness(render_from_object.m) ? 1 : 0;
+        spheres.push_back(s);
+        Prim pr{SHM_SHAPE_SPHERE, (uint32_t)spheres.size() - 1, material, -1, owner, {0}};
+        for (int k = 0; k < 3; ++k) { pr.b[k] = INFINITY; pr.b[3 + k] = -INFINITY; }
+        for (int c = 0; c < 8; ++c) {
+            const V3 q = shm::v3(c & 1 ? radius : -radius, c & 2 ? radius : -radius, c & 4 ? s.z_max : s.z_min);
+            const M4& m = render_from_object.m;
+            const float p[3] = {m.m[0][0] * q.x + m.m[0][1] * q.y + m.m[0][2] * q.z + m.m[0][3], m.m[1][0] * q.x + m.m[1][1] * q.y + m.m[1][2] * q.z + m.m[1][3],
+                                m.m[2][0] * q.x + m.m[2][1] * q.y + m.m[2][2] * q.z + m.m[2][3]};
+            for (int k = 0; k < 3; ++k) { pr.b[k] = std::min(pr.b[k], p[k]); pr.b[3 + k] = std::max(pr.b[3 + k], p[k]); }
+        }
+        if (em.on) {
+            // Disk::Area = phi_max (r^2 - inner^2) / 2, Cylinder::Area = (z_max - z_min) r phi_max (shm/shapes.h, quadric_area: the same operations)
+            const float area = kind == SHM_QUADRIC_DISK ? s.phi_max * (s.radius * s.radius - inner * inner) * 0.5f : (s.z_max - s.z_min) * s.radius * s.phi_max;
+            pr.light = area_light((uint32_t)prims.size(), area, em.L, em.scale, em.two_sided);
+            if (em.power > 0.0f) lights.back().scale *= em.power / ((em.two_sided ? 2.0f : 1.0f) * area * 3.14159265358979323846f);
+        }
+        prims.push_back(pr);
+    }
+    void add_disk(float height, float radius, float inner_radius, float phi_max_deg, const Xf& render_from_object, bool reverse, uint32_t material, const Emission& em,
+                  uint32_t owner) {
+        add_quadric(SHM_QUADRIC_DISK, radius, height, height, inner_radius, phi_max_deg, render_from_object, reverse, material, em, owner);
+    }
+    void add_cylinder(float radius, float z_min_in, float z_max_in, float phi_max_deg, const Xf& render_from_object, bool reverse, uint32_t material, const Emission& em,
+                      uint32_t owner) {
+        add_quadric(SHM_QUADRIC_CYLINDER, radius, std::min(z_min_in, z_max_in), std::max(z_min_in, z_max_in), 0.0f, phi_max_deg, render_from_object, reverse, material, em, owner);
+    }
 
     // ---- the flattened description (owns every array desc points to) ----
     struct Built {

@@ -11,6 +11,7 @@
 //                                 SurfaceInteraction (quirk 6), apply_ray
 //   interaction.rs:68-85,100-135,379-405  offset_ray_origin, SurfaceInteraction::new, set_shading_geometry
 //   ray.rs:53-99                  offset_ray_origin, spawn_ray, spawn_ray_to_both_offset
+//   (PBRT-v4 shapes.h / shapes.cpp) Disk, Cylinder: the reference has neither shape (SHM_QUADRICS, below; DESIGN.md "Disk and cylinder")
 #pragma once
 #include "sampling.h"
 #include "../../../include/shimmer_hip.h"
@@ -452,9 +453,18 @@ struct QuadricIntersection {
     V3 p_obj;
     Float phi;
 };
+// SHM_QUADRICS: compile PBRT-v4's disk and cylinder (ShmSphere::quadric = SHM_QUADRIC_DISK / SHM_QUADRIC_CYLINDER) into the sphere's six functions below, each of which
+// hands such a record to its quadric_* twin at the end of this file. ON wherever nobody says otherwise (the oracle, the host mirror, the probe library); a kernel unit
+// says so by its K_QUADRICS (wavefront.h): without it the branch folds away, and the kernels of every scene without such a shape are those of a build without them.
+#ifndef SHM_QUADRICS
+#define SHM_QUADRICS 1
+#endif
+SHM_HD bool quadric_basic_intersect(const ShmSphere& s, V3 ro, V3 rd, Float t_max, QuadricIntersection& out);
+SHM_HD SurfaceInteraction quadric_interaction(const ShmSphere& s, const QuadricIntersection& isect, V3 wo);
 
 // shape/sphere.rs:95-196
 SHM_HD bool sphere_basic_intersect(const ShmSphere& s, V3 ro, V3 rd, Float t_max, QuadricIntersection& out) {
+    if (SHM_QUADRICS && s.quadric != 0) return quadric_basic_intersect(s, ro, rd, t_max, out);
     P3i oi = xf_point_i(s.object_from_render, p3i_exact(ro));
     P3i di = xf_vector_i(s.object_from_render, p3i_exact(rd));
     Interval a = iv_sqr(di.x) + iv_sqr(di.y) + iv_sqr(di.z);
@@ -504,6 +514,7 @@ SHM_HD bool sphere_basic_intersect(const ShmSphere& s, V3 ro, V3 rd, Float t_max
 
 // shape/sphere.rs:198-271
 SHM_HD SurfaceInteraction sphere_interaction(const ShmSphere& s, const QuadricIntersection& isect, V3 wo, bool strict = false) {
+    if (SHM_QUADRICS && s.quadric != 0) return quadric_interaction(s, isect, wo);
     V3 p_hit = isect.p_obj;
     Float phi = isect.phi;
     Float u = phi / s.phi_max;
@@ -650,9 +661,17 @@ SHM_HD Float triangle_pdf_with_context(const TriangleData& tr, const ShapeSample
     return pdf;
 }
 
-SHM_HD Float sphere_area(const ShmSphere& s) { return s.phi_max * s.radius * (s.z_max - s.z_min); }  // sphere.rs:301-303
+SHM_HD Float quadric_area(const ShmSphere& s);
+SHM_HD ShapeSample quadric_sample(const ShmSphere& s, V2 u);
+SHM_HD_NOINLINE bool quadric_sample_with_context(const ShmSphere& s, const ShapeSampleContext& ctx, V2 u, ShapeSample& out);
+SHM_HD_NOINLINE Float quadric_pdf_with_context(const ShmSphere& s, const ShapeSampleContext& ctx, V3 wi);
+SHM_HD Float sphere_area(const ShmSphere& s) {  // sphere.rs:301-303
+    if (SHM_QUADRICS && s.quadric != 0) return quadric_area(s);
+    return s.phi_max * s.radius * (s.z_max - s.z_min);
+}
 // sphere.rs:305-337
 SHM_HD ShapeSample sphere_sample(const ShmSphere& s, V2 u) {
+    if (SHM_QUADRICS && s.quadric != 0) return quadric_sample(s, u);
     V3 p_obj = v3s(0.0f) + sample_uniform_sphere(u) * s.radius;
     p_obj = p_obj * (s.radius / distance(p_obj, v3s(0.0f)));
     V3 p_obj_error = gamma(5) * abs3(p_obj);
@@ -667,6 +686,7 @@ SHM_HD ShapeSample sphere_sample(const ShmSphere& s, V2 u) {
 }
 // sphere.rs:339-422
 SHM_HD bool sphere_sample_with_context(const ShmSphere& s, const ShapeSampleContext& ctx, V2 u, ShapeSample& out) {
+    if (SHM_QUADRICS && s.quadric != 0) return quadric_sample_with_context(s, ctx, u, out);
     V3 p_center = xf_point(s.render_from_object, v3s(0.0f));
     V3 p_origin = offset_ray_origin(ctx.pi, ctx.n, p_center - ctx.p());
     if (distance_squared(p_origin, p_center) <= sqr(s.radius)) {
@@ -706,6 +726,7 @@ SHM_HD bool sphere_sample_with_context(const ShmSphere& s, const ShapeSampleCont
 }
 // sphere.rs:424-457 (quirk 1: 2.90 and the double division are the reference's)
 SHM_HD Float sphere_pdf_with_context(const ShmSphere& s, const ShapeSampleContext& ctx, V3 wi, bool strict = false) {
+    if (SHM_QUADRICS && s.quadric != 0) return quadric_pdf_with_context(s, ctx, wi);
     V3 p_center = xf_point(s.render_from_object, v3s(0.0f));
     V3 p_origin = offset_ray_origin(ctx.pi, ctx.n, p_center - ctx.p());
     if (distance_squared(p_origin, p_center) <= s.radius * s.radius) {
@@ -723,6 +744,168 @@ SHM_HD Float sphere_pdf_with_context(const ShmSphere& s, const ShapeSampleContex
     Float one_minus_cos_theta_max = 1.0f - cos_theta_max;
     if (sin2_theta_max < 0.00068523f) one_minus_cos_theta_max = sin2_theta_max / 2.0f;
     return 1.0f / ((strict ? 2.0f : 2.90f) * PI_F * one_minus_cos_theta_max);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Disk and cylinder (PBRT-v4 shapes.h / shapes.cpp; the reference has neither): the two other quadrics with the sphere's hit record, in the sphere's record.
+//   disk      radius, z_min == z_max = the height, theta_z_min = the inner radius; the normal is the object's +z
+//   cylinder  radius, z_min < z_max; the normal points away from the axis
+// Nothing here depends on the reference-quirks switch: there is no reference behaviour to keep, so an interaction goes to render space the way PBRT-v4's
+// Transform::operator()(SurfaceInteraction) takes it (xf_surface_interaction's strict form) and a density is the area density over |n . wi| / distance^2, whatever the render asks for.
+// Deviation from PBRT-v4: Disk::Sample draws from the WHOLE disk whatever innerradius and phimax are; quadric_sample draws from the annulus sector the shape is.
+// ---------------------------------------------------------------------------------------------
+SHM_HD bool quadric_clipped(const ShmSphere& s, V3 p_hit, Float phi) { return p_hit.z < s.z_min || p_hit.z > s.z_max || phi > s.phi_max; }  // (the cylinder's)
+SHM_HD bool quadric_basic_intersect(const ShmSphere& s, V3 ro, V3 rd, Float t_max, QuadricIntersection& out) {
+    P3i oi = xf_point_i(s.object_from_render, p3i_exact(ro));
+    P3i di = xf_vector_i(s.object_from_render, p3i_exact(rd));
+    if (s.quadric == SHM_QUADRIC_DISK) {  // Disk::BasicIntersect, on the midpoints
+        const V3 o = oi.mid(), d = di.mid();
+        if (d.z == 0.0f) return false;  // a ray in (or parallel to) the disk's plane
+        const Float t_shape_hit = (s.z_min - o.z) / d.z;
+        if (!(t_shape_hit > 0.0f && t_shape_hit < t_max)) return false;
+        V3 p_hit = o + t_shape_hit * d;
+        const Float dist2 = sqr(p_hit.x) + sqr(p_hit.y);
+        if (!(dist2 <= sqr(s.radius) && dist2 >= sqr(s.theta_z_min))) return false;
+        Float phi = atan2(p_hit.y, p_hit.x);
+        if (phi < 0.0f) phi += 2.0f * PI_F;
+        if (phi > s.phi_max) return false;
+        out.t_hit = t_shape_hit;
+        out.p_obj = p_hit;
+        out.phi = phi;
+        return true;
+    }
+    // Cylinder::BasicIntersect: the sphere's interval arithmetic in x and y
+    Interval a = iv_sqr(di.x) + iv_sqr(di.y);
+    Interval b = 2.0f * (di.x * oi.x + di.y * oi.y);
+    Interval c = iv_sqr(oi.x) + iv_sqr(oi.y) - iv_sqr(iv(s.radius));
+    if (!(a.low > 0.0f)) return false;  // a ray parallel to the axis: a's interval holds 0, and the divisions below would be by it
+    Interval f = b / (2.0f * a);
+    Interval vx = oi.x - f * di.x, vy = oi.y - f * di.y;
+    Interval len = iv_sqrt(iv_sqr(vx) + iv_sqr(vy));
+    Interval discrim = 4.0f * a * (iv(s.radius) + len) * (iv(s.radius) - len);
+    if (discrim.low < 0.0f) return false;
+    Interval root_discrim = iv_sqrt(discrim);
+    Interval q;
+    if (b.midpoint() < 0.0f) q = -0.5f * (b - root_discrim);
+    else q = -0.5f * (b + root_discrim);
+    Interval t0 = q / a;
+    Interval t1 = c / q;
+    if (t0.low > t1.low) { Interval tmp = t0; t0 = t1; t1 = tmp; }
+    if (t0.high > t_max || t1.low <= 0.0f) return false;
+    Interval t_shape_hit = t0;
+    if (t_shape_hit.low <= 0.0f) {
+        t_shape_hit = t1;
+        if (t_shape_hit.high > t_max) return false;
+    }
+    V3 p_hit = oi.mid() + t_shape_hit.midpoint() * di.mid();
+    Float hit_rad = sqrt(sqr(p_hit.x) + sqr(p_hit.y));
+    p_hit.x *= s.radius / hit_rad;
+    p_hit.y *= s.radius / hit_rad;
+    Float phi = atan2(p_hit.y, p_hit.x);
+    if (phi < 0.0f) phi += 2.0f * PI_F;
+    if (quadric_clipped(s, p_hit, phi)) {
+        if (t_shape_hit == t1) return false;
+        if (t1.high > t_max) return false;
+        t_shape_hit = t1;
+        p_hit = oi.mid() + t_shape_hit.midpoint() * di.mid();
+        hit_rad = sqrt(sqr(p_hit.x) + sqr(p_hit.y));
+        p_hit.x *= s.radius / hit_rad;
+        p_hit.y *= s.radius / hit_rad;
+        phi = atan2(p_hit.y, p_hit.x);
+        if (phi < 0.0f) phi += 2.0f * PI_F;
+        if (quadric_clipped(s, p_hit, phi)) return false;
+    }
+    out.t_hit = t_shape_hit.midpoint();
+    out.p_obj = p_hit;
+    out.phi = phi;
+    return true;
+}
+// Disk::InteractionFromIntersection / Cylinder::InteractionFromIntersection
+SHM_HD SurfaceInteraction quadric_interaction(const ShmSphere& s, const QuadricIntersection& isect, V3 wo) {
+    V3 p_hit = isect.p_obj;
+    const Float u = isect.phi / s.phi_max;
+    const V3 dpdu = v3(-s.phi_max * p_hit.y, s.phi_max * p_hit.x, 0.0f);
+    const bool flip_normal = (s.reverse_orientation != 0) ^ (s.transform_swaps_handedness != 0);
+    const V3 wo_object = xf_vector(s.object_from_render, wo);
+    Float v;
+    V3 dpdv, dndu, dndv, p_error;
+    if (s.quadric == SHM_QUADRIC_DISK) {
+        const Float r_hit = sqrt(sqr(p_hit.x) + sqr(p_hit.y));
+        v = (s.radius - r_hit) / (s.radius - s.theta_z_min);
+        dpdv = v3(p_hit.x, p_hit.y, 0.0f) * (s.theta_z_min - s.radius) / r_hit;
+        dndu = v3s(0.0f);
+        dndv = v3s(0.0f);
+        p_hit.z = s.z_min;  // "refine disk intersection point"
+        p_error = v3s(0.0f);
+    } else {
+        v = (p_hit.z - s.z_min) / (s.z_max - s.z_min);
+        dpdv = v3(0.0f, 0.0f, s.z_max - s.z_min);
+        const V3 d2pduu = -s.phi_max * s.phi_max * v3(p_hit.x, p_hit.y, 0.0f);
+        const V3 d2pduv = v3s(0.0f), d2pdvv = v3s(0.0f);
+        // the Weingarten equations, as the sphere has them
+        const Float e1 = dot(dpdu, dpdu), f1 = dot(dpdu, dpdv), g1 = dot(dpdv, dpdv);
+        const V3 n = normalize(cross(dpdu, dpdv));
+        const Float e = dot(n, d2pduu), f = dot(n, d2pduv), g = dot(n, d2pdvv);
+        const Float egf2 = difference_of_products(e1, g1, f1, f1);
+        const Float env_egf2 = (egf2 == 0.0f) ? 0.0f : 1.0f / egf2;
+        dndu = (f * f1 - e * g1) * env_egf2 * dpdu + (e * f1 - f * e1) * env_egf2 * dpdv;
+        dndv = (g * f1 - f * g1) * env_egf2 * dpdu + (f * f1 - g * e1) * env_egf2 * dpdv;
+        p_error = gamma(3) * abs3(v3(p_hit.x, p_hit.y, 0.0f));
+    }
+    SurfaceInteraction si = surface_interaction_new(p3i_from_value_and_error(p_hit, p_error), v2(u, v), wo_object, dpdu, dpdv, dndu, dndv, flip_normal);
+    return xf_surface_interaction(s.render_from_object, s.object_from_render, si, true);
+}
+SHM_HD Float quadric_area(const ShmSphere& s) {
+    if (s.quadric == SHM_QUADRIC_DISK) return s.phi_max * (sqr(s.radius) - sqr(s.theta_z_min)) * 0.5f;
+    return (s.z_max - s.z_min) * s.radius * s.phi_max;
+}
+// Disk::Sample (of the annulus sector: the deviation above) / Cylinder::Sample
+SHM_HD ShapeSample quadric_sample(const ShmSphere& s, V2 u) {
+    const Float phi = u.y * s.phi_max;
+    V3 p_obj, p_obj_error, n_obj;
+    if (s.quadric == SHM_QUADRIC_DISK) {
+        const Float rho = sqrt(lerp(u.x, sqr(s.theta_z_min), sqr(s.radius)));
+        p_obj = v3(rho * cos(phi), rho * sin(phi), s.z_min);
+        p_obj_error = v3s(0.0f);
+        n_obj = v3(0.0f, 0.0f, 1.0f);
+    } else {
+        const Float z = lerp(u.x, s.z_min, s.z_max);
+        p_obj = v3(s.radius * cos(phi), s.radius * sin(phi), z);
+        const Float hit_rad = sqrt(sqr(p_obj.x) + sqr(p_obj.y));
+        p_obj.x *= s.radius / hit_rad;
+        p_obj.y *= s.radius / hit_rad;
+        p_obj_error = gamma(3) * abs3(v3(p_obj.x, p_obj.y, 0.0f));
+        n_obj = v3(p_obj.x, p_obj.y, 0.0f);
+    }
+    V3 n = normalize(xf_normal(s.object_from_render, n_obj));  // render_from_object applied to a normal: the transpose of its inverse
+    if (s.reverse_orientation) n = -n;
+    ShapeSample ss;
+    ss.pi = xf_point_i(s.render_from_object, p3i_from_value_and_error(p_obj, p_obj_error));
+    ss.n = n;
+    ss.pdf = 1.0f / quadric_area(s);
+    return ss;
+}
+// the area sample as a solid-angle one, like the inside-the-sphere branch of sphere_sample_with_context
+// (SHM_HD_NOINLINE, this one and the density below: real calls on the device. Inlined into light_sample_li / light_pdf_li they doubled the sphere branch's code in every
+//  extended shading kernel, and the lean general one went from three waves per SIMD to two: profiles/quadrics.md)
+SHM_HD_NOINLINE bool quadric_sample_with_context(const ShmSphere& s, const ShapeSampleContext& ctx, V2 u, ShapeSample& out) {
+    ShapeSample ss = quadric_sample(s, u);
+    V3 wi = ss.pi.mid() - ctx.p();
+    if (length_squared(wi) == 0.0f) return false;
+    wi = normalize(wi);
+    ss.pdf /= abs_dot(ss.n, -wi) / distance_squared(ctx.p(), ss.pi.mid());
+    if (!is_finite(ss.pdf)) return false;
+    out = ss;
+    return true;
+}
+SHM_HD_NOINLINE Float quadric_pdf_with_context(const ShmSphere& s, const ShapeSampleContext& ctx, V3 wi) {
+    V3 o = offset_ray_origin(ctx.pi, ctx.n, wi);
+    QuadricIntersection qi;
+    if (!quadric_basic_intersect(s, o, wi, infinity(), qi)) return 0.0f;
+    SurfaceInteraction isect = quadric_interaction(s, qi, -wi);
+    Float pdf = (1.0f / quadric_area(s)) / (abs_dot(isect.n, -wi) / distance_squared(ctx.p(), isect.p()));
+    if (!is_finite(pdf)) return 0.0f;
+    return pdf;
 }
 
 }  // namespace shm

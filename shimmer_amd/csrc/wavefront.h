@@ -12,6 +12,17 @@
 #include <string>
 #include <vector>
 
+// K_QUADRICS (a translation unit's switch; it follows K_DELTA_LIGHTS, below, unless the unit sets it): PBRT-v4's disk and cylinder (shm/shapes.h, SHM_QUADRICS:
+// ShmSphere::quadric) are compiled into a unit's sphere code only where it is true — the *_dl builds, which RenderPlan::dl names for a scene that holds one
+// (FlatScene::has_quadric_kinds), and k_trace_quadrics.hip: k_trace.hip's general traversal kernels a second time (k_trace.inl), which wf_launch_trace takes for such a
+// scene. Every other unit's sphere code is that of a build without the shapes. (Up here: host/flatten.h brings shm/shapes.h in.)
+#ifndef K_DELTA_LIGHTS
+#define K_DELTA_LIGHTS false
+#endif
+#ifndef K_QUADRICS
+#define K_QUADRICS K_DELTA_LIGHTS
+#endif
+#define SHM_QUADRICS K_QUADRICS
 #include "host/flatten.h"
 #include "shm/bvh_link.h"
 #include "host/bvh_pairs.hpp"

@@ -718,6 +718,45 @@ class SceneBuilder:
         self._n_prims += 1
         return prim_index
 
+    # PBRT-v4's disk and cylinder (the reference has neither): quadrics in the sphere's record, told apart by ShmSphere.quadric; still SHM_SHAPE_SPHERE primitives, and
+    # prim_bounds' sphere box — (-r, -r, z_min) .. (r, r, z_max) through render_from_object — is theirs too (a disk's z_min == z_max is its height)
+    def _add_quadric(self, kind, radius, z_min, z_max, inner, phi_max, area, material, render_from_object, reverse_orientation, emission, emission_scale, two_sided):
+        rfo = IDENTITY if render_from_object is None else _as_f32(render_from_object, (4, 4))
+        ofr = np.linalg.inv(rfo.astype(np.float64)).astype(np.float32)
+        s = abi.ShmSphere()
+        s.quadric = kind
+        s.radius, s.z_min, s.z_max = float(f32(radius)), float(f32(z_min)), float(f32(z_max))
+        s.theta_z_min, s.theta_z_max = float(f32(inner)), 0.0
+        s.phi_max = float(f32(np.pi / 180.0) * f32(np.clip(phi_max, 0, 360)))
+        s.render_from_object[:] = [float(x) for x in rfo.ravel()]
+        s.object_from_render[:] = [float(x) for x in ofr.ravel()]
+        s.reverse_orientation = int(reverse_orientation)
+        s.transform_swaps_handedness = int(np.linalg.det(rfo[:3, :3].astype(np.float64)) < 0)
+        self.spheres.append(s)
+        prim_index = self._n_prims
+        li = -1
+        if emission is not None:
+            li = self._area_light(prim_index, float(area(s)), emission, emission_scale, two_sided)
+        self.prims.append(np.array([[abi.SHM_SHAPE_SPHERE, len(self.spheres) - 1, material, li]], np.int64))
+        self.owners.append(self._object)
+        self._n_prims += 1
+        return prim_index
+
+    def add_disk(self, radius, material, height=0.0, inner_radius=0.0, phi_max=360.0, render_from_object=None, reverse_orientation=False,
+                 emission=None, emission_scale=1.0, two_sided=False):
+        """PBRT-v4's Shape "disk": the annulus inner_radius <= rho <= radius of the plane z = height, its normal +z in object space. Area phi_max (r^2 - inner^2) / 2."""
+        return self._add_quadric(abi.SHM_QUADRIC_DISK, radius, height, height, inner_radius, phi_max,
+                                 lambda s: f32(f32(s.phi_max) * f32(f32(f32(s.radius) * f32(s.radius)) - f32(f32(s.theta_z_min) * f32(s.theta_z_min)))) * f32(0.5),
+                                 material, render_from_object, reverse_orientation, emission, emission_scale, two_sided)
+
+    def add_cylinder(self, radius, material, z_min=-1.0, z_max=1.0, phi_max=360.0, render_from_object=None, reverse_orientation=False,
+                     emission=None, emission_scale=1.0, two_sided=False):
+        """PBRT-v4's Shape "cylinder": radius around the object's z axis between z_min and z_max (ordered here), its normal pointing outwards. Area (z_max - z_min) r phi_max."""
+        lo, hi = min(z_min, z_max), max(z_min, z_max)
+        return self._add_quadric(abi.SHM_QUADRIC_CYLINDER, radius, lo, hi, 0.0, phi_max,
+                                 lambda s: f32(f32(f32(s.z_max) - f32(s.z_min)) * f32(s.radius)) * f32(s.phi_max),
+                                 material, render_from_object, reverse_orientation, emission, emission_scale, two_sided)
+
     # ---- camera / film ----
     # PixelFilter: name -> (SHM_FILTER_*, PBRT-v4's default radius, its default parameters: sigma | B, C | tau)
     FILTERS = {"box": (abi.SHM_FILTER_BOX, 0.5, ()), "gaussian": (abi.SHM_FILTER_GAUSSIAN, 1.5, (0.5,)), "mitchell": (abi.SHM_FILTER_MITCHELL, 2.0, (1.0 / 3.0, 1.0 / 3.0)),

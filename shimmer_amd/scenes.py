@@ -442,6 +442,7 @@ def ganesha_proxy(lib, width=1024, height=1024, n=599, with_room=True, coated=Fa
     variant (round 5: the shapes a real PBRT-v4 scene mixes into its triangles; same camera, room and object):
       "patch_emitter"  the window emitter is ONE bilinear patch — what a quad face of a PLY file becomes (shape/shape.rs:119-134, shape/mesh.rs:233-256)
       "one_sphere"     a diffuse sphere stands on the floor beside the object (shape/sphere.rs)
+      "one_disk", "one_cylinder"  PBRT-v4's disk (hovering where that sphere's centre is) / cylinder (standing where it stands) in its place
       "instanced"      the object is an object definition placed once through a TransformedPrimitive (primitive.rs:136-176)
       "textured_floor" the ground plane's reflectance is an image texture (EWA-filtered, repeated): ONE textured material among plain ones
       "mesh_emitter"   (round 6) the window emitter tessellated into 64 x 64 x 2 = 8 192 emissive triangles: one DiffuseAreaLight per triangle (light.rs:632-684), the uniform
@@ -453,7 +454,7 @@ def ganesha_proxy(lib, width=1024, height=1024, n=599, with_room=True, coated=Fa
       "quads"          (round 6) the object's 6 n^2 cells as bilinear patches instead of 12 n^2 triangles: what a quad PLY file becomes in the reference
       "environment"    no room and no window: the object on its ground plane under an ImageInfinitelight (light.rs:805-981) — escaped rays look the map up, next-event
                        estimation samples its (compensated) piecewise-constant distribution"""
-    assert variant in (None, "patch_emitter", "one_sphere", "instanced", "environment", "textured_floor", "textured_hidden", "quads", "smooth", "mesh_emitter", "textured_object", "instance_grid")
+    assert variant in (None, "patch_emitter", "one_sphere", "instanced", "environment", "textured_floor", "textured_hidden", "quads", "smooth", "mesh_emitter", "textured_object", "instance_grid", "one_disk", "one_cylinder")
     b = SceneBuilder()
     b.set_film(width, height, **(film or {}))
     rfw = _set_camera(b, lib, camera, (0.0, 0.6, 4.2), (0.0, 0.0, 0.0), (0, 1, 0), 38.0)
@@ -514,6 +515,13 @@ def ganesha_proxy(lib, width=1024, height=1024, n=599, with_room=True, coated=Fa
         rfo = np.eye(4, dtype=np.float32)
         rfo[:3, 3] = _to_render(np.array([[0.7, -0.8, 1.7]], np.float32), rfw)[0]  # (in front of the object, to the right: in the camera's view)
         b.add_sphere(0.45, wall, render_from_object=rfo)
+    if variant in ("one_disk", "one_cylinder"):  # PBRT-v4's disk / cylinder where "one_sphere" has its sphere: the extended kernels and k_trace_quadrics.hip's on the S3 frame
+        rfo = np.array([[1, 0, 0, 0], [0, 0, 1, 0], [0, -1, 0, 0], [0, 0, 0, 1]], np.float32)  # the shape's +z is the world's +y
+        rfo[:3, 3] = _to_render(np.array([[0.7, -0.8 if variant == "one_disk" else -1.25, 1.7]], np.float32), rfw)[0]
+        if variant == "one_disk":
+            b.add_disk(0.45, wall, render_from_object=rfo)
+        else:
+            b.add_cylinder(0.45, wall, z_min=0.0, z_max=0.9, render_from_object=rfo)
     if variant == "textured_hidden":  # (development: a textured material nobody sees — the textured class's fixed cost)
         tm = b.material_diffuse(b.add_image_texture(test_image(64, 3), filter="bilinear", wrap="repeat"))
         p, vi = _quad((-0.1, -50.0, -0.1), (-0.1, -50.0, 0.1), (0.1, -50.0, 0.1), (0.1, -50.0, -0.1))
@@ -896,3 +904,96 @@ def random_scene(lib, seed, width=40, height=32, film=None, extra_lights=None):
         b.light_image_infinite(environment_image(int(trng.choice([8, 16])), sun=tuple(trng.normal(size=3)), sun_radiance=float(trng.uniform(5, 60))),
                                scale=float(trng.uniform(0.002, 0.01)), render_from_light=rot)
     return _finish(b, lib, extra_lights=extra_lights, rfw=rfw, name=f"random scene {seed}")
+
+
+def disk_and_cylinder(emissive_disk=True, glass_cylinder=False):
+    """An `extra_lights`-style argument for the generators above — it is called at the same place, with (builder, render_from_world) — that appends SHAPES: PBRT-v4's
+    disk and cylinder, given in WORLD space around the origin (a sector of an annulus lying flat at y = 0.3, an upright partial cylinder of radius 0.25 beside it) and,
+    with `emissive_disk`, a small one-sided disk emitter above them that shines downwards. Their lights come after the scene's own."""
+    def add(b, rfw):
+        rfw = np.asarray(rfw, np.float32).reshape(4, 4)
+        up = np.array([[1, 0, 0, 0], [0, 0, 1, 0], [0, -1, 0, 0], [0, 0, 0, 1]], np.float32)  # the object's +z is the world's +y
+        down = np.array([[1, 0, 0, 0], [0, 0, -1, 0], [0, 1, 0, 0], [0, 0, 0, 1]], np.float32)  # ... the world's -y
+        def place(rot, x, y, z):
+            m = rot.copy()
+            m[:3, 3] = (x, y, z)
+            return (rfw @ m).astype(np.float32)
+        b.add_disk(0.4, b.material_diffuse(0.6), height=0.0, inner_radius=0.15, phi_max=300.0, render_from_object=place(up, -0.45, 0.3, 0.2))
+        cyl_m = b.material_dielectric(1.5) if glass_cylinder else b.material_conductor(b.spectrum_named("metal-Cu-eta"), b.spectrum_named("metal-Cu-k"), roughness=0.3)
+        b.add_cylinder(0.25, cyl_m, z_min=0.0, z_max=0.7, phi_max=360.0 if glass_cylinder else 250.0, render_from_object=place(up, 0.45, 0.0, 0.1))
+        if emissive_disk:
+            b.add_disk(0.3, b.material_diffuse(0.0), render_from_object=place(down, 0.0, 1.6, 0.3), emission=blackbody_dense(5000.0), emission_scale=6.0)
+    return add
+
+
+def quadric_scene(lib, variant="lean", width=40, height=32, film=None, n_disks=96, as_spheres=False):
+    """PBRT-v4's disk and cylinder (ShmSphere.quadric) in one small scene per scene class the general kernels serve. A floor of two triangles with a disk lying ON a
+    triangle pair of the same centroid (a BVH leaf that holds a quadric together with triangles), an upright cylinder, a tilted and non-uniformly scaled annulus sector,
+    a mirrored disk and a one-sided disk emitter overhead. `variant`:
+      "lean"         every material a DiffuseMaterial
+      "glass"        the cylinder is smooth glass: the material-sorted fused kernel
+      "coated"       the floor a coated diffuse material: the staged LayeredBxDF kernels
+      "textured"     the lying disk carries an image texture by its (u, v)
+      "environment"  an environment map beside the emitter
+      "instances"    a cylinder and a disk inside an object that is instanced three times, one cylinder at top level
+      "many_disks"   `n_disks` small disks over the floor: quadrics are a twelfth of the primitive records or more, the five-wave traversal row
+    `as_spheres`: the same records with quadric = 0 (what a build without the shapes would render) — for tests that the byte is read."""
+    assert variant in ("lean", "glass", "coated", "textured", "environment", "instances", "many_disks")
+    b = SceneBuilder()
+    b.set_film(width, height, **(film or {}))
+    rfw = np.asarray(b.set_camera_look_at(lib, (0.0, 1.5, 3.5), (0.0, 0.5, 0.0), (0, 1, 0), 38.0), np.float32).reshape(4, 4)
+    up = np.array([[1, 0, 0, 0], [0, 0, 1, 0], [0, -1, 0, 0], [0, 0, 0, 1]], np.float64)    # object +z -> world +y
+    down = np.array([[1, 0, 0, 0], [0, 0, -1, 0], [0, 1, 0, 0], [0, 0, 0, 1]], np.float64)  # object +z -> world -y
+
+    def place(m, at):
+        m = np.array(m, np.float64)
+        m[:3, 3] = at
+        return (rfw.astype(np.float64) @ m).astype(np.float32)
+
+    grey = b.material_diffuse(0.55)
+    floor_m = b.material_coated_diffuse(reflectance=0.5, roughness=0.1) if variant == "coated" else b.material_diffuse(_two_point_spectrum(b, 0.3, 0.6))
+    p, vi = _quad((-3, 0, -3), (-3, 0, 3), (3, 0, 3), (3, 0, -3))
+    b.add_mesh(_to_render(p, rfw), vi, floor_m)
+    # a square plate as two triangles, each with the square's own bounding box, and the disk inscribed in it: three primitives with ONE centroid, which the builder
+    # leaves in one leaf (aggregate.rs:345-356) — every coordinate a dyadic fraction, so that the three boxes are the same floats
+    p, vi = _quad((-0.5, 0.25, -0.5), (-0.5, 0.25, 0.5), (0.5, 0.25, 0.5), (0.5, 0.25, -0.5))
+    b.add_mesh(_to_render(p, rfw), vi, grey)
+    if variant == "textured":
+        disk_m = b.material_diffuse(b.add_image_texture(test_image(16, 3), filter="bilinear"))
+    else:
+        disk_m = b.material_diffuse(_two_point_spectrum(b, 0.7, 0.2))
+    b.add_disk(0.5, disk_m, inner_radius=0.125, render_from_object=place(up, (0.0, 0.25, 0.0)))
+    cyl_m = b.material_dielectric(1.5) if variant == "glass" else grey
+    b.add_cylinder(0.25, cyl_m, z_min=0.0, z_max=0.8, phi_max=360.0 if variant == "glass" else 280.0, render_from_object=place(up, (0.9, 0.0, -0.2)))
+    tilt = up.copy()
+    c, s = np.cos(0.6), np.sin(0.6)
+    tilt[:3, :3] = np.array([[c, -s, 0], [s, c, 0], [0, 0, 1]]) @ up[:3, :3] @ np.diag([1.3, 0.7, 1.0])
+    b.add_disk(0.45, grey, height=0.1, inner_radius=0.2, phi_max=250.0, render_from_object=place(tilt, (-0.95, 0.5, -0.1)))
+    mirror = up.copy()
+    mirror[:3, :3] = up[:3, :3] @ np.diag([-1.0, 1.0, 1.0])
+    b.add_disk(0.3, grey, render_from_object=place(mirror, (0.2, 0.7, -0.9)), reverse_orientation=True)
+    b.add_disk(0.35, b.material_diffuse(0.0), render_from_object=place(down, (0.0, 2.2, 0.2)), emission=blackbody_dense(5500.0), emission_scale=9.0)
+    if variant == "environment":
+        rot = np.array([[1, 0, 0, 0], [0, 0, 1, 0], [0, -1, 0, 0], [0, 0, 0, 1]], np.float32)
+        b.light_image_infinite(environment_image(16), scale=0.3, render_from_light=rot)
+    if variant == "instances":
+        b.begin_object("post")
+        b.add_cylinder(0.12, grey, z_min=0.0, z_max=0.6, render_from_object=up.astype(np.float32))
+        cap = up.copy()
+        cap[:3, 3] = (0.0, 0.6, 0.0)
+        b.add_disk(0.2, disk_m, render_from_object=cap.astype(np.float32))
+        b.end_object()
+        for k, (x, z, sy) in enumerate(((-1.5, 0.6, 1.0), (1.5, 0.7, 1.4), (0.3, 1.2, 0.7))):
+            m = np.diag([1.0, sy, 1.0, 1.0])
+            a = 0.5 * k
+            m[:3, :3] = np.array([[np.cos(a), 0, np.sin(a)], [0, 1, 0], [-np.sin(a), 0, np.cos(a)]]) @ m[:3, :3]
+            b.add_instance("post", place(m, (x, 0.0, z)))
+    if variant == "many_disks":
+        rng = np.random.Generator(np.random.PCG64(5))
+        for _ in range(n_disks):
+            b.add_disk(float(rng.uniform(0.05, 0.12)), grey, inner_radius=float(rng.uniform(0.0, 0.04)), phi_max=float(rng.uniform(120.0, 360.0)),
+                       render_from_object=place(up, (rng.uniform(-1.6, 1.6), rng.uniform(0.05, 0.5), rng.uniform(-1.2, 1.2))))
+    if as_spheres:
+        for s in b.spheres:
+            s.quadric = abi.SHM_QUADRIC_SPHERE
+    return _finish(b, lib, rfw=rfw, name=f"disks and cylinders ({variant})" + (" as spheres" if as_spheres else ""))

@@ -16,6 +16,8 @@ CONFIGS = [
     ("S3 headline ganesha 1024x1024x256", lambda: scenes.ganesha_proxy(lib, 1024, 1024), 256, 5),
     ("S3p ganesha, patch emitter 1024x1024x256", lambda: scenes.ganesha_proxy(lib, 1024, 1024, variant="patch_emitter"), 256, 5),
     ("S3s ganesha + one sphere 1024x1024x256", lambda: scenes.ganesha_proxy(lib, 1024, 1024, variant="one_sphere"), 256, 5),
+    ("S3d ganesha + one disk 1024x1024x256", lambda: scenes.ganesha_proxy(lib, 1024, 1024, variant="one_disk"), 256, 5),
+    ("S3y ganesha + one cylinder 1024x1024x256", lambda: scenes.ganesha_proxy(lib, 1024, 1024, variant="one_cylinder"), 256, 5),
     ("S3i ganesha instanced 1024x1024x256", lambda: scenes.ganesha_proxy(lib, 1024, 1024, variant="instanced"), 256, 5),
     ("S3ig ganesha as 4 x 4 x 4 instances of one small definition 1024x1024x256", lambda: scenes.ganesha_proxy(lib, 1024, 1024, variant="instance_grid"), 256, 5),
     ("S3q ganesha as 2.15 M bilinear patches (a quad PLY) 1024x1024x256", lambda: scenes.ganesha_proxy(lib, 1024, 1024, variant="quads"), 256, 5),
