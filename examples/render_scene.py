@@ -101,6 +101,7 @@ def main():
     ap.add_argument("--quirks-off", action="store_true",
                     help="ShmRenderParams::disable_reference_quirks: PBRT-v4's forms of the reference's deviations (emitter sampling, instancing, ...: DESIGN.md section 2) "
                          "instead of the reference-exact default")
+    ap.add_argument("--aovs", action="store_true", help="also write the G-buffer pass's albedo, normal (shading) and position images beside the beauty, as PFM")
     ap.add_argument("-o", "--output", default="")
     args = ap.parse_args()
     lib = abi.load_library()
@@ -127,6 +128,13 @@ def main():
     ldr = np.where(ldr <= 0.0031308, 12.92 * ldr, 1.055 * np.power(ldr, 1 / 2.4) - 0.055)
     write_png(os.path.splitext(out)[0] + ".png", (ldr * 255 + 0.5).astype(np.uint8))
     print("wrote", out, "and", os.path.splitext(out)[0] + ".png")
+    if args.aovs:  # the G-buffer pass of the same frame: what a denoiser takes beside the beauty
+        aov = render.render_gbuffer(lib, sc.desc, p, matrix=render.SRGB_FROM_XYZ, renderer=r)
+        stem = os.path.splitext(out)[0]
+        for name, key in (("albedo", "albedo"), ("normal", "ns"), ("position", "p")):
+            a = np.ascontiguousarray(aov[key], np.float32)
+            abi.check(lib, lib.shm_write_pfm(f"{stem}.{name}.pfm".encode(), a.ctypes.data_as(abi.c_float_p), w, h), "shm_write_pfm")
+        print("wrote", ", ".join(f"{stem}.{n}.pfm" for n in ("albedo", "normal", "position")), f"(coverage {float(aov['coverage'].mean()):.3f})")
     r.close()
 
 

@@ -590,6 +590,56 @@ SHM_API int shm_trace_closest_device(ShmScene* scene, const void* rays_dev, uint
 SHM_API int shm_trace_any_device(ShmScene* scene, const void* rays_dev, uint32_t n, void* occluded_dev, int repeat,
                          ShmStats* stats);
 
+/* ---- the G-buffer pass: first-hit guide images for a denoiser ------------------------------------------
+ * A pass of its own beside the render, after PBRT-v4's GBufferFilm / VisibleSurface: for sample i of a pixel it traces exactly the camera ray the
+ * render's sample i traces (same sampler, seed, jitter options, pixel filter, camera and ray-differential scale; no further sampler dimension is drawn)
+ * and adds what the first hit shows to the pixel's sums with the sample's filter weight w, negative lobes included:
+ *   an escaped ray   w to weight_sum only;
+ *   a hit            w to weight_sum and weight_hit, and w * value to p (the hit point), n (the geometric normal, facing the camera ray's origin side:
+ *                    negated where dot(n, -d) < 0), ns (the shading normal the BSDF is built on, after bump and normal maps, flipped the same way), uv, and
+ *                    albedo: BSDF::rho_hd(-d) over 16 fixed sample points at the camera sample's wavelengths, weighted by the sensor's three response
+ *                    curves WITHOUT the film's imaging ratio and clamp (exposure does not scale an albedo); force_diffuse and regularize are ignored.
+ * A pixel's samples are added in increasing sample index, in double precision: the sums are deterministic, and a split into waves or into disjoint tile
+ * sets gives the same bits as one call. The pass touches neither the film nor anything a later render reads. */
+typedef struct ShmGBufferPixel {
+    double p[3], n[3], ns[3], uv[2], albedo[3];
+    double weight_hit, weight_sum;
+} ShmGBufferPixel;   /* 128 bytes */
+enum {
+    SHM_GBUFFER_SPACE_RENDER = 0,  /* p, n, ns in render space */
+    SHM_GBUFFER_SPACE_CAMERA = 1   /* p through camera_from_render as a point, n and ns as normals (not renormalised) */
+};
+/* The device G-buffer: pixel_bounds-sized, allocated by the first of these calls and freed by shm_scene_destroy. */
+SHM_API int shm_gbuffer_clear(ShmScene* scene);
+/* Samples [sample_begin, sample_end) of the given tiles into the device G-buffer (+=). Blocking; stats may be NULL. The tiles are validated as
+ * shm_render_wave validates them; an unknown `space` returns SHM_ERR_INVALID_ARGUMENT. */
+SHM_API int shm_gbuffer_render_wave(ShmScene* scene, const ShmRenderParams* params, uint32_t space, const ShmTile* tiles, uint32_t n_tiles,
+                                    int32_t sample_begin, int32_t sample_end, ShmStats* stats);
+/* Copy the device G-buffer to a caller-allocated pixel_bounds-sized row-major array. */
+SHM_API int shm_gbuffer_read(ShmScene* scene, ShmGBufferPixel* out);
+/* clear + all params->samples_per_pixel samples + read. */
+SHM_API int shm_render_gbuffer(ShmScene* scene, const ShmRenderParams* params, uint32_t space, const ShmTile* tiles, uint32_t n_tiles,
+                               ShmGBufferPixel* out, ShmStats* stats);
+/* The pass's CPU twin (no GPU needed): the same shared arithmetic on the host, one sample at a time, for tests and for hosts that trace themselves.
+ * pixels_xy: n (x, y) pairs; sample_index: n indices.
+ *   shm_gbuffer_camera_rays   the rays the pass traces for those samples.
+ *   shm_gbuffer_samples_host  given the closest hits of those rays (ShmHit records, as shm_trace_closest returns them), 16 doubles per sample in
+ *                             ShmGBufferPixel's order: what the sample adds to its pixel's sums.
+ *   shm_gbuffer_rho_host      12 floats per sample: the spectral rho_hd[4] behind the albedo and the wavelengths[4] and pdfs[4] it is weighted with
+ *                             (zeros for an escaped ray). */
+SHM_API int shm_gbuffer_camera_rays(const ShmSceneDesc* desc, const ShmRenderParams* params, const int32_t* pixels_xy, const int32_t* sample_index,
+                                    uint32_t n, ShmRay* out);
+SHM_API int shm_gbuffer_samples_host(const ShmSceneDesc* desc, const ShmRenderParams* params, uint32_t space, const int32_t* pixels_xy,
+                                     const int32_t* sample_index, const ShmHit* hits, uint32_t n, double* out);
+SHM_API int shm_gbuffer_rho_host(const ShmSceneDesc* desc, const ShmRenderParams* params, const int32_t* pixels_xy, const int32_t* sample_index,
+                                 const ShmHit* hits, uint32_t n, float* out);
+/* W_c: the sum of the 471-entry table of sensor channel c (1 nm steps), in double — a surface of rho = 1 has an expected albedo sum / W_c of 1. */
+SHM_API int shm_gbuffer_white(const ShmSceneDesc* desc, double white[3]);
+/* The sums as images, 15 floats per pixel: p[3], n[3], ns[3], uv[2] — each sum / weight_hit —, albedo[3] = (M a) / (M W) per channel with a the albedo sums
+ * / weight_hit, W = `white` and M = output_rgb_from_sensor_rgb (row-major 3x3; NULL: the identity), and coverage = weight_hit / weight_sum. A pixel whose
+ * weight_hit is 0 gets zeros. */
+SHM_API int shm_gbuffer_resolve(const ShmGBufferPixel* pixels, uint64_t n, const double white[3], const float* output_rgb_from_sensor_rgb, float* out15);
+
 /* ---- multi-GPU (ABI v7) -------------------------------------------------------------------------------------------
  * Pixels are independent and tile ownership is exclusive (the reference's one parallel region, integrator.rs:242-304, relies on that
  * for its unsynchronised film writes), so the frame shards by tiles with the scene replicated per GPU and NO collective while

@@ -209,6 +209,14 @@ class ShmHit(C.Structure):
                 ("phi", C.c_float), ("instance", C.c_uint32), ("pad", C.c_uint32)]
 
 
+class ShmGBufferPixel(C.Structure):
+    """A pixel of the G-buffer pass: filter-weighted sums over the samples whose camera ray hit (weight_hit) of all samples (weight_sum)."""
+    _fields_ = [("p", C.c_double * 3), ("n", C.c_double * 3), ("ns", C.c_double * 3), ("uv", C.c_double * 2), ("albedo", C.c_double * 3),
+                ("weight_hit", C.c_double), ("weight_sum", C.c_double)]
+
+
+SHM_GBUFFER_SPACE_RENDER, SHM_GBUFFER_SPACE_CAMERA = 0, 1
+assert C.sizeof(ShmGBufferPixel) == 128
 assert C.sizeof(ShmMaterial) == 64 + 4 * 32 + 48 and C.sizeof(ShmFloatTexture) == 48 and C.sizeof(ShmBvhNode) == 32 and C.sizeof(ShmRay) == 32 and C.sizeof(ShmHit) == 32 and C.sizeof(ShmFilmPixel) == 32
 
 class ShmPbrtScene(C.Structure):
@@ -254,6 +262,18 @@ EXPORTS = {
     "shm_trace_any": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(ShmStats)]),
     "shm_trace_closest_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.POINTER(ShmStats)]),
     "shm_trace_any_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.POINTER(ShmStats)]),
+    "shm_gbuffer_clear": (C.c_int, [C.c_void_p]),
+    "shm_gbuffer_render_wave": (C.c_int, [C.c_void_p, C.POINTER(ShmRenderParams), C.c_uint32, C.POINTER(ShmTile), C.c_uint32, C.c_int32, C.c_int32,
+                                          C.POINTER(ShmStats)]),
+    "shm_gbuffer_read": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "shm_render_gbuffer": (C.c_int, [C.c_void_p, C.POINTER(ShmRenderParams), C.c_uint32, C.POINTER(ShmTile), C.c_uint32, C.c_void_p, C.POINTER(ShmStats)]),
+    "shm_gbuffer_camera_rays": (C.c_int, [C.POINTER(ShmSceneDesc), C.POINTER(ShmRenderParams), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_uint32, C.c_void_p]),
+    "shm_gbuffer_samples_host": (C.c_int, [C.POINTER(ShmSceneDesc), C.POINTER(ShmRenderParams), C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p,
+                                           C.c_uint32, C.POINTER(C.c_double)]),
+    "shm_gbuffer_rho_host": (C.c_int, [C.POINTER(ShmSceneDesc), C.POINTER(ShmRenderParams), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_uint32,
+                                       c_float_p]),
+    "shm_gbuffer_white": (C.c_int, [C.POINTER(ShmSceneDesc), C.POINTER(C.c_double)]),
+    "shm_gbuffer_resolve": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_double), c_float_p, c_float_p]),
     "shm_last_error": (C.c_char_p, []),
     "shm_device_count": (C.c_int, []),
     "shm_bvh_build": (C.c_int, [c_float_p, C.c_uint32, C.c_int, C.POINTER(ShmBvhNode), c_u32_p, c_u32_p]),

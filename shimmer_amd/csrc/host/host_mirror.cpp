@@ -29,6 +29,8 @@
 
 #include "../../../include/shimmer_hip.h"
 #include "../shm/path.h"  // camera_generate_ray_differential for CameraBase::find_minimum_differentials (host use only)
+#include "../shm/gbuffer.h"  // the G-buffer pass's CPU twin, at the end of this file
+#include "flatten.h"
 
 extern "C" __attribute__((visibility("hidden"))) void shm_set_last_error(const char* msg);  // shimmer_hip.hip
 
@@ -789,6 +791,149 @@ void shm_ply_free(ShmPlyMesh* m) {
     if (!m) return;
     free(m->p); free(m->n); free(m->uv); free(m->tri_indices); free(m->quad_indices); free(m->face_indices);
     memset(m, 0, sizeof(*m));
+}
+
+}  // extern "C"
+
+// ---- the G-buffer pass's CPU twin (include/shimmer_hip.h, shm_gbuffer_*) ---------------------------------
+// The scene is flattened as shm_scene_create flattens it (host/flatten.h) and read in place through FlatScene::view(); the camera ray is K1's generate_camera_ray and a
+// sample's record is shm::gbuffer_sample — the function k_gbuffer.hip runs on the device. No switch of the shared headers is set in this unit: every extension is on.
+namespace {
+struct GBufferHost {
+    shm_host::FlatScene flat;
+    shm::SceneView sv;
+    bool tex = false;
+    uint32_t zs = 0u;
+};
+int gbuffer_host_open(const ShmSceneDesc* desc, const ShmRenderParams* params, GBufferHost& g) {
+    if (!desc || !params) return SHM_ERR_INVALID_ARGUMENT;
+    if (params->sampler > SHM_SAMPLER_ZSOBOL || params->sampler_randomization > SHM_SAMPLER_RANDOMIZE_NONE) { shm_set_last_error("unknown sampler or sampler randomization"); return SHM_ERR_INVALID_ARGUMENT; }
+    std::string err;
+    const int rc = shm_host::flatten_scene(desc, g.flat, err);
+    if (rc != SHM_OK) { shm_set_last_error(err.c_str()); return rc; }
+    g.sv = g.flat.view();
+    g.sv.quirks_off = params->disable_reference_quirks ? 1u : 0u;
+    g.tex = g.flat.has_material_textures;  // (the scenes whose camera rays carry auxiliary rays: ScenePlan::tex_ws)
+    if (params->sampler == SHM_SAMPLER_ZSOBOL)
+        g.zs = shm::zsobol_config(params->samples_per_pixel, g.flat.film.full_resolution[0], g.flat.film.full_resolution[1], params->sampler_randomization == SHM_SAMPLER_RANDOMIZE_NONE);
+    g.sv.zsobol = g.zs;
+    return SHM_OK;
+}
+// sample `index` of pixel (px, py): the ray K1 writes, its wavelengths, filter weight and (scenes with material textures) auxiliary rays
+shm::Ray gbuffer_host_ray(const GBufferHost& g, const ShmRenderParams& params, int px, int py, int index, shm::Wavelengths& lambda, shm::Float& weight, shm::AuxRays& aux) {
+    shm::Rng rng = shm::sampler_start_pixel_sample(px, py, index, params.seed, g.zs);
+    aux = shm::aux_none();
+    return shm::generate_camera_ray(g.sv, px, py, rng, params.disable_wavelength_jitter != 0, params.disable_pixel_jitter != 0, lambda, weight, g.tex ? &aux : nullptr,
+                                    params.samples_per_pixel);
+}
+shm::Hit gbuffer_host_hit(const ShmHit& h) {
+    shm::Hit hit;
+    hit.prim = h.prim; hit.t = h.t; hit.b0 = h.b0; hit.b1 = h.b1; hit.b2 = h.b2; hit.phi = h.phi; hit.inst = (int32_t)h.instance - 1;
+    return hit;
+}
+bool gbuffer_host_hit_ok(const GBufferHost& g, const ShmHit& h) {
+    return h.prim < 0 || ((size_t)h.prim < g.flat.prim_recs.size() && (size_t)h.instance <= g.flat.prim_recs.size());
+}
+}  // namespace
+
+extern "C" {
+
+int shm_gbuffer_camera_rays(const ShmSceneDesc* desc, const ShmRenderParams* params, const int32_t* pixels_xy, const int32_t* sample_index, uint32_t n, ShmRay* out) {
+    if (!pixels_xy || !sample_index || !out) return SHM_ERR_INVALID_ARGUMENT;
+    GBufferHost g;
+    const int rc = gbuffer_host_open(desc, params, g);
+    if (rc != SHM_OK) return rc;
+    for (uint32_t i = 0; i < n; ++i) {
+        shm::Wavelengths lambda;
+        shm::Float w;
+        shm::AuxRays aux;
+        const shm::Ray r = gbuffer_host_ray(g, *params, pixels_xy[2 * i], pixels_xy[2 * i + 1], sample_index[i], lambda, w, aux);
+        out[i].o[0] = r.o.x; out[i].o[1] = r.o.y; out[i].o[2] = r.o.z;
+        out[i].d[0] = r.d.x; out[i].d[1] = r.d.y; out[i].d[2] = r.d.z;
+        out[i].t_max = shm::infinity();
+        out[i].pad = 0.0f;
+    }
+    return SHM_OK;
+}
+
+int shm_gbuffer_samples_host(const ShmSceneDesc* desc, const ShmRenderParams* params, uint32_t space, const int32_t* pixels_xy, const int32_t* sample_index,
+                             const ShmHit* hits, uint32_t n, double* out) {
+    if (!pixels_xy || !sample_index || !hits || !out || space > SHM_GBUFFER_SPACE_CAMERA) return SHM_ERR_INVALID_ARGUMENT;
+    GBufferHost g;
+    const int rc = gbuffer_host_open(desc, params, g);
+    if (rc != SHM_OK) return rc;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (!gbuffer_host_hit_ok(g, hits[i])) { shm_set_last_error("a hit names a primitive the scene does not hold"); return SHM_ERR_INVALID_ARGUMENT; }
+        shm::Wavelengths lambda;
+        shm::Float w;
+        shm::AuxRays aux;
+        const shm::Ray r = gbuffer_host_ray(g, *params, pixels_xy[2 * i], pixels_xy[2 * i + 1], sample_index[i], lambda, w, aux);
+        shm::Float rec[shm::GBUFFER_SAMPLE_FLOATS];
+        const shm::Hit hit = gbuffer_host_hit(hits[i]);
+        if (g.tex) shm::gbuffer_sample<true>(g.sv, r.d, aux, hit, lambda, *params, space, rec);
+        else shm::gbuffer_sample<false>(g.sv, r.d, aux, hit, lambda, *params, space, rec);
+        double* sums = out + 16ull * i;
+        for (int k = 0; k < 16; ++k) sums[k] = 0.0;
+        shm::gbuffer_add_sample(sums, rec, w);
+    }
+    return SHM_OK;
+}
+
+int shm_gbuffer_rho_host(const ShmSceneDesc* desc, const ShmRenderParams* params, const int32_t* pixels_xy, const int32_t* sample_index, const ShmHit* hits, uint32_t n,
+                         float* out) {
+    if (!pixels_xy || !sample_index || !hits || !out) return SHM_ERR_INVALID_ARGUMENT;
+    GBufferHost g;
+    const int rc = gbuffer_host_open(desc, params, g);
+    if (rc != SHM_OK) return rc;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (!gbuffer_host_hit_ok(g, hits[i])) { shm_set_last_error("a hit names a primitive the scene does not hold"); return SHM_ERR_INVALID_ARGUMENT; }
+        float* o = out + 12ull * i;
+        for (int k = 0; k < 12; ++k) o[k] = 0.0f;
+        if (hits[i].prim < 0) continue;
+        shm::Wavelengths lambda;
+        shm::Float w;
+        shm::AuxRays aux;
+        const shm::Ray r = gbuffer_host_ray(g, *params, pixels_xy[2 * i], pixels_xy[2 * i + 1], sample_index[i], lambda, w, aux);
+        const shm::Hit hit = gbuffer_host_hit(hits[i]);
+        const shm::GBufferSurface s = g.tex ? shm::gbuffer_surface<true>(g.sv, r.d, aux, hit, lambda, *params) : shm::gbuffer_surface<false>(g.sv, r.d, aux, hit, lambda, *params);
+        for (int k = 0; k < 4; ++k) { o[k] = s.rho.v[k]; o[4 + k] = s.lambda.lambda[k]; o[8 + k] = s.lambda.pdf[k]; }
+    }
+    return SHM_OK;
+}
+
+int shm_gbuffer_white(const ShmSceneDesc* desc, double white[3]) {
+    if (!desc || !white || !desc->film.sensor_r_bar || !desc->film.sensor_g_bar || !desc->film.sensor_b_bar) return SHM_ERR_INVALID_ARGUMENT;
+    const float* tables[3] = {desc->film.sensor_r_bar, desc->film.sensor_g_bar, desc->film.sensor_b_bar};
+    for (int c = 0; c < 3; ++c) {
+        double s = 0.0;
+        for (int i = 0; i < 471; ++i) s += (double)tables[c][i];
+        white[c] = s;
+    }
+    return SHM_OK;
+}
+
+int shm_gbuffer_resolve(const ShmGBufferPixel* pixels, uint64_t n, const double white[3], const float* m, float* out15) {
+    if (!pixels || !white || !out15) return SHM_ERR_INVALID_ARGUMENT;
+    const float identity[9] = {1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f};
+    if (!m) m = identity;
+    double mw[3];
+    for (int r = 0; r < 3; ++r) mw[r] = (double)m[3 * r] * white[0] + (double)m[3 * r + 1] * white[1] + (double)m[3 * r + 2] * white[2];
+    for (uint64_t i = 0; i < n; ++i) {
+        const ShmGBufferPixel& g = pixels[i];
+        float* o = out15 + 15ull * i;
+        for (int k = 0; k < 15; ++k) o[k] = 0.0f;
+        if (g.weight_hit == 0.0) continue;
+        const double inv = 1.0 / g.weight_hit;
+        for (int k = 0; k < 3; ++k) { o[k] = (float)(g.p[k] * inv); o[3 + k] = (float)(g.n[k] * inv); o[6 + k] = (float)(g.ns[k] * inv); }
+        o[9] = (float)(g.uv[0] * inv); o[10] = (float)(g.uv[1] * inv);
+        const double a[3] = {g.albedo[0] * inv, g.albedo[1] * inv, g.albedo[2] * inv};
+        for (int r = 0; r < 3; ++r) {
+            const double ma = (double)m[3 * r] * a[0] + (double)m[3 * r + 1] * a[1] + (double)m[3 * r + 2] * a[2];
+            o[11 + r] = mw[r] != 0.0 ? (float)(ma / mw[r]) : 0.0f;
+        }
+        o[14] = g.weight_sum != 0.0 ? (float)(g.weight_hit / g.weight_sum) : 0.0f;
+    }
+    return SHM_OK;
 }
 
 }  // extern "C"

@@ -858,6 +858,129 @@ int shm_render(ShmScene* s, const ShmRenderParams* params, const ShmTile* tiles,
     return SHM_OK;
 }
 
+// ---- the G-buffer pass: K1 as a render's, the scene's own closest-hit launch, then k_gbuffer.hip's two kernels ----
+// the device G-buffer, pixel_bounds-sized and zeroed: made by the first call that needs it (shm_scene_destroy frees it with the scene's other allocations)
+static int ensure_gbuffer(ShmScene* s) {
+    if (s->d_gbuffer) return SHM_OK;
+    int rc;
+    if ((rc = dev_alloc<ShmGBufferPixel>(s, s->n_film_pixels, &s->d_gbuffer)) != SHM_OK) return rc;
+    if (hipMemset(s->d_gbuffer, 0, s->n_film_pixels * sizeof(ShmGBufferPixel)) != hipSuccess) { s->d_gbuffer = nullptr; g_err = "hipMemset of the G-buffer"; return SHM_ERR_DEVICE; }
+    return SHM_OK;
+}
+
+int shm_gbuffer_clear(ShmScene* s) {
+    if (!s) return SHM_ERR_INVALID_ARGUMENT;
+    HIP_TRY(hipSetDevice(s->device));
+    int rc;
+    if ((rc = ensure_gbuffer(s)) != SHM_OK) return rc;
+    HIP_TRY(hipMemsetAsync(s->d_gbuffer, 0, s->n_film_pixels * sizeof(ShmGBufferPixel), s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return SHM_OK;
+}
+
+int shm_gbuffer_read(ShmScene* s, ShmGBufferPixel* out) {
+    if (!s || !out) return SHM_ERR_INVALID_ARGUMENT;
+    HIP_TRY(hipSetDevice(s->device));
+    int rc;
+    if ((rc = ensure_gbuffer(s)) != SHM_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipMemcpy(out, s->d_gbuffer, s->n_film_pixels * sizeof(ShmGBufferPixel), hipMemcpyDeviceToHost));
+    return SHM_OK;
+}
+
+int shm_gbuffer_render_wave(ShmScene* s, const ShmRenderParams* params, uint32_t space, const ShmTile* tiles, uint32_t n_tiles, int32_t sample_begin, int32_t sample_end,
+                            ShmStats* stats) {
+    if (!s || !params || !tiles || n_tiles == 0 || sample_end <= sample_begin) { g_err = "invalid render arguments"; return SHM_ERR_INVALID_ARGUMENT; }
+    if (space > SHM_GBUFFER_SPACE_CAMERA) { g_err = "unknown G-buffer space"; return SHM_ERR_INVALID_ARGUMENT; }
+    if (params->sampler > SHM_SAMPLER_ZSOBOL || params->sampler_randomization > SHM_SAMPLER_RANDOMIZE_NONE) { g_err = "unknown sampler or sampler randomization"; return SHM_ERR_INVALID_ARGUMENT; }
+    const uint32_t zsobol = zsobol_config(params->samples_per_pixel, s->flat.film.full_resolution[0], s->flat.film.full_resolution[1],
+                                          params->sampler_randomization == SHM_SAMPLER_RANDOMIZE_NONE);
+    if (params->sampler == SHM_SAMPLER_ZSOBOL && (sample_begin < 0 || (int64_t)sample_end > (int64_t)1 << zsobol_log2spp(zsobol))) {
+        g_err = "zsobol: sample index outside [0, 2^ceil(log2(samples_per_pixel)))";
+        return SHM_ERR_INVALID_ARGUMENT;
+    }
+    HIP_TRY(hipSetDevice(s->device));
+    int rc;
+    uint64_t n_pixels = 0;
+    if ((rc = build_pixel_list(s, tiles, n_tiles, &n_pixels)) != SHM_OK) return rc;
+    if ((rc = ensure_gbuffer(s)) != SHM_OK) return rc;
+    s->dsv.quirks_off = params->disable_reference_quirks ? 1u : 0u;
+    s->dsv.zsobol = zsobol;
+    // the camera rays are the path integrator's, whatever integrator the parameters name: its plan gives K1's coordinates, the filter weight's source and the workspace a
+    // render of this scene would ask for — so that a render before or after this pass finds the workspace it left
+    ShmRenderParams as_path = *params;
+    as_path.integrator = SHM_INTEGRATOR_PATH;
+    as_path.force_diffuse = 0;
+    const RenderPlan p = render_plan(s->plan, as_path);
+    const int n_samples = sample_end - sample_begin;
+    const uint64_t n_paths = n_pixels * (uint64_t)n_samples;
+    if ((rc = ensure_workspace(s, n_paths, p.route == ROUTE_STAGED)) != SHM_OK) return rc;
+    uint32_t pix_per_batch = s->capacity / (uint32_t)n_samples;
+    if (pix_per_batch == 0) { g_err = "spp-wave larger than the path workspace"; return SHM_ERR_INVALID_ARGUMENT; }
+    if (pix_per_batch > 64) pix_per_batch &= ~63u;
+    EventPool ev{s};
+    hipEvent_t e_begin = ev.get(), e_end = ev.get();
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_closest;
+    HIP_TRY(hipEventRecord(e_begin, s->stream));
+    for (uint64_t p0 = 0; p0 < n_pixels; p0 += pix_per_batch) {
+        const uint32_t* pixels = s->d_pixels + p0;
+        const uint32_t n_pix = (uint32_t)std::min<uint64_t>(pix_per_batch, n_pixels - p0);
+        const uint32_t total = n_pix * (uint32_t)n_samples;
+        const bool tex = p.img_generate == IMG_TEX;
+        const GenerateArgs ga{s->stream, pixels, n_pix, sample_begin, n_samples, *params, tex, false, p.zs, p.flt};
+        if ((rc = (p.spherical ? wf_generate<true> : wf_generate<false>)(s, ga)) != SHM_OK) return rc;
+        hipEvent_t a = ev.get(), b = ev.get();
+        hipEventRecord(a, s->stream);
+        // (K1 left the identity queue: the batch's slots in order, 32-byte hit records)
+        const TraceArgs closest{.stream = s->stream, .n_direct = total, .rays = s->pa.ray, .hits = s->pa.hit};
+        if ((rc = wf_launch_trace(s, RAY_CLOSEST, false, closest)) != SHM_OK) return rc;
+        hipEventRecord(b, s->stream);
+        ev_closest.push_back({a, b});
+        const GBufferArgs gb{s->stream, pixels, n_pix, n_samples, *params, tex, space, film_weight(p.flt)};
+        if ((rc = wf_launch_gbuffer(s, gb)) != SHM_OK) return rc;
+    }
+    if (ev.failed) { g_err = "hipEventCreate failed"; return SHM_ERR_DEVICE; }
+    HIP_TRY(hipEventRecord(e_end, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipGetLastError());
+    if (stats) {
+        DeviceCounters c;
+        HIP_TRY(hipMemcpy(&c, s->d_counters, sizeof(c), hipMemcpyDeviceToHost));
+        stats->paths += n_paths;
+        stats->rays_closest += c.rays_closest;
+        stats->nodes_closest += c.nodes_closest;
+        stats->tris_closest += c.tris_closest;
+        float ms = 0.0f;
+        hipEventElapsedTime(&ms, e_begin, e_end);
+        stats->ms_total += ms;
+        double mc = 0.0;
+        for (auto& e : ev_closest) { float m = 0.0f; hipEventElapsedTime(&m, e.first, e.second); mc += m; }
+        stats->ms_trace_closest += mc;
+        stats->ms_shade += (double)ms - mc;  // K1 and the pass's two kernels
+        stats->launches_closest += (uint32_t)ev_closest.size();
+    }
+    return SHM_OK;
+}
+
+int shm_render_gbuffer(ShmScene* s, const ShmRenderParams* params, uint32_t space, const ShmTile* tiles, uint32_t n_tiles, ShmGBufferPixel* out, ShmStats* stats) {
+    if (!s || !params || !out || params->samples_per_pixel < 1) { g_err = "invalid render arguments"; return SHM_ERR_INVALID_ARGUMENT; }
+    if (stats) memset(stats, 0, sizeof(*stats));
+    int rc = shm_gbuffer_clear(s);
+    if (rc != SHM_OK) return rc;
+    // every sample of a pixel in one launch where the workspace holds them, in waves of 64 otherwise: the sums do not depend on the split
+    uint64_t n_pixels = 0;
+    for (uint32_t t = 0; tiles && t < n_tiles; ++t) n_pixels += (uint64_t)std::max(0, tiles[t].x1 - tiles[t].x0) * (uint64_t)std::max(0, tiles[t].y1 - tiles[t].y0);
+    ShmRenderParams as_path = *params;
+    as_path.integrator = SHM_INTEGRATOR_PATH;
+    as_path.force_diffuse = 0;
+    const bool staged = render_plan(s->plan, as_path).route == ROUTE_STAGED;
+    const int spp = params->samples_per_pixel;
+    const int wave = (int)std::min<uint64_t>(std::max<uint64_t>(64, n_pixels ? workspace_cap(s, staged) / n_pixels : 64), 1u << 20);
+    for (int begin = 0; begin < spp; begin += wave)
+        if ((rc = shm_gbuffer_render_wave(s, params, space, tiles, n_tiles, begin, std::min(spp, begin + wave), stats)) != SHM_OK) return rc;
+    return shm_gbuffer_read(s, out);
+}
+
 static int trace_device_impl(ShmScene* s, bool any, const void* rays_dev, uint32_t n, void* out_dev, int repeat, ShmStats* stats) {
     if (!s || !rays_dev || !out_dev || n == 0 || repeat < 1) { g_err = "invalid trace arguments"; return SHM_ERR_INVALID_ARGUMENT; }
     HIP_TRY(hipSetDevice(s->device));

@@ -1006,6 +1006,23 @@ SHM_HD void bsdf_force_diffuse(BSDF& b, V3 wo_render, Float uc, V2 u2) {
     d.r = r;
     b.bxdf = d;
 }
+// BSDF::rho_hd(wo, uc[n], u2[n]) (bsdf.rs:99-102 -> bxdf.rs:49-71) itself: the n-sample estimate of the hemispherical-directional reflectance, the samples added in
+// order — the statement above with a loop around it (the G-buffer pass's albedo, shm/gbuffer.h, with n = 16). bsdf_force_diffuse keeps its own one-sample statement
+// of it: calling through this function, with n = 1 as an argument or as a template argument, gave the same films and other instructions in every kernel that
+// holds force_diffuse's code (tools/kernel_isa_diff.py: 1 000 to 1 600 instructions fewer in k_shade_simple and k_shade_randomwalk), and those kernels are held to
+// what they were.
+SHM_HD Spec bsdf_rho_hd(const BSDF& b, V3 wo_render, const Float* uc, const V2* u2, int n) {
+    V3 wo = b.shading_frame.to_local(wo_render);
+    Spec r = spec_const(0.0f);
+    if (wo.z != 0.0f) {
+        for (int i = 0; i < n; ++i) {
+            BSDFSample bs;
+            if (bxdf_sample_f(b.bxdf, wo, uc[i], u2[i], REFLTRANS_ALL, bs) && bs.pdf > 0.0f) r = r + bs.f * abs_cos_theta(bs.wi) / bs.pdf;
+        }
+        r = r / (Float)n;
+    }
+    return r;
+}
 SHM_HD Float bsdf_pdf(const BSDF& b, V3 wo_render, V3 wi_render, uint32_t sample_flags) {  // bsdf.rs:84-97
     V3 wo = b.shading_frame.to_local(wo_render);
     V3 wi = b.shading_frame.to_local(wi_render);

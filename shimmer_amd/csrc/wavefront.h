@@ -410,6 +410,7 @@ struct ShmScene {
     struct DistState* dist = nullptr;  // multi-GPU state (dist.hip): communicator, this rank's tile shard, the gather plan
     uint32_t n_tri_shade_records = 0;   // the flat triangles' shading records built at scene creation (shm/tri_shade.h; shm_scene_shading_records) ...
     double tri_shade_build_ms = 0.0;    // ... and the wall-clock time that took
+    ShmGBufferPixel* d_gbuffer = nullptr;  // the G-buffer pass's sums, pixel_bounds-sized: allocated by the first shm_gbuffer_* call (render.hip), null in a scene that never asks
 };
 // dist.hip: releases s->dist (RCCL communicator included); called by shm_scene_destroy
 __attribute__((visibility("hidden"))) void wf_dist_release(ShmScene* s);
@@ -504,6 +505,20 @@ struct GenerateArgs {
     int flt;
 };
 template <bool SPHERICAL> WF_INTERNAL int wf_generate(ShmScene* s, const GenerateArgs& a);
+// k_gbuffer.hip: the G-buffer pass behind K1 and the closest-hit launch of a batch — k_gbuffer<tex> per path slot (shm/gbuffer.h; the slot's record goes where the
+// path's CtxRec lives, which no kernel of this pass reads), then k_gbuffer_accumulate per pixel into ShmScene::d_gbuffer, in sample order. `film_weight`: where a
+// sample's filter weight comes from (shm_plan::FILM_WEIGHT_*), as for K6.
+struct GBufferArgs {
+    hipStream_t stream;
+    const uint32_t* pixels;
+    uint32_t n_pix;
+    int n_samples;
+    ShmRenderParams params;
+    bool tex;
+    uint32_t space;
+    int film_weight;
+};
+WF_INTERNAL int wf_launch_gbuffer(ShmScene* s, const GBufferArgs& a);
 // The shading launchers of one scene class: a cell of render.hip's table by geometry x image class x sampler x extended build (nullptr: no such
 // build, shm_plan::serving_build), of which select_kernels makes a render's set by the RenderPlan's coordinates. The plan says which of them run; the bounce loop calls them.
 struct ShadeKernels {

@@ -181,6 +181,31 @@ class Renderer:
         stats = self.render_waves(params, tile_indices)
         return self.read_film(), stats
 
+    # ---- the G-buffer pass (include/shimmer_hip.h "the G-buffer pass") ----
+    def gbuffer_clear(self):
+        abi.check(self.lib, self.lib.shm_gbuffer_clear(self.handle), "shm_gbuffer_clear")
+
+    def gbuffer_wave(self, params, sample_begin, sample_end, space=abi.SHM_GBUFFER_SPACE_RENDER, tile_indices=None):
+        """Samples [sample_begin, sample_end) of the tiles into the device G-buffer (+=); returns the stats dict."""
+        tiles, n = self._tile_subset(tile_indices)
+        stats = abi.ShmStats()
+        abi.check(self.lib, self.lib.shm_gbuffer_render_wave(self.handle, C.byref(params), space, tiles, n, sample_begin, sample_end, C.byref(stats)),
+                  "shm_gbuffer_render_wave")
+        return stats.as_dict()
+
+    def read_gbuffer(self):
+        g = np.zeros((self.height, self.width), dtype=GBUFFER_DTYPE)
+        abi.check(self.lib, self.lib.shm_gbuffer_read(self.handle, g.ctypes.data_as(C.c_void_p)), "shm_gbuffer_read")
+        return g
+
+    def gbuffer(self, params, space=abi.SHM_GBUFFER_SPACE_RENDER, tile_indices=None):
+        """shm_render_gbuffer: clear, every sample, read back. Returns (the sums as a GBUFFER_DTYPE array, stats)."""
+        tiles, n = self._tile_subset(tile_indices)
+        stats = abi.ShmStats()
+        g = np.zeros((self.height, self.width), dtype=GBUFFER_DTYPE)
+        abi.check(self.lib, self.lib.shm_render_gbuffer(self.handle, C.byref(params), space, tiles, n, g.ctypes.data_as(C.c_void_p), C.byref(stats)), "shm_render_gbuffer")
+        return g, stats.as_dict()
+
     def trace(self, rays, any_hit=False):
         """Bring-up entry: rays = structured/float32 array (n, 8) [o,d,t_max,pad]. Returns hits (n,8 view) or occluded bytes."""
         rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
@@ -196,6 +221,40 @@ class Renderer:
 
 
 HIT_DTYPE = np.dtype([("prim", "<i4"), ("t", "<f4"), ("b0", "<f4"), ("b1", "<f4"), ("b2", "<f4"), ("phi", "<f4"), ("instance", "<u4"), ("pad", "<u4")])
+
+
+GBUFFER_DTYPE = np.dtype([("p", "<f8", (3,)), ("n", "<f8", (3,)), ("ns", "<f8", (3,)), ("uv", "<f8", (2,)), ("albedo", "<f8", (3,)), ("weight_hit", "<f8"),
+                          ("weight_sum", "<f8")])
+assert GBUFFER_DTYPE.itemsize == C.sizeof(abi.ShmGBufferPixel)
+
+
+def gbuffer_white(lib, desc):
+    """W_c of the scene's sensor (shm_gbuffer_white): what an albedo sum of a rho = 1 surface averages to, per channel."""
+    w = (C.c_double * 3)()
+    abi.check(lib, lib.shm_gbuffer_white(C.byref(desc), w), "shm_gbuffer_white")
+    return np.array(w[:], np.float64)
+
+
+def gbuffer_resolve(lib, gbuffer, white, matrix=None):
+    """shm_gbuffer_resolve: the G-buffer's sums as a dict of float32 images p, n, ns (.., 3), uv (.., 2), albedo (.., 3) and coverage (..)."""
+    g = np.ascontiguousarray(gbuffer, dtype=GBUFFER_DTYPE)
+    w = (C.c_double * 3)(*[float(x) for x in white])
+    m = None if matrix is None else np.ascontiguousarray(matrix, dtype=np.float32)
+    out = np.empty(g.shape + (15,), np.float32)
+    abi.check(lib, lib.shm_gbuffer_resolve(g.ctypes.data_as(C.c_void_p), g.size, w, None if m is None else m.ctypes.data_as(abi.c_float_p),
+                                           out.ctypes.data_as(abi.c_float_p)), "shm_gbuffer_resolve")
+    return {"p": out[..., 0:3], "n": out[..., 3:6], "ns": out[..., 6:9], "uv": out[..., 9:11], "albedo": out[..., 11:14], "coverage": out[..., 14]}
+
+
+def render_gbuffer(lib, desc, params, device=0, space=abi.SHM_GBUFFER_SPACE_RENDER, matrix=None, renderer=None):
+    """The G-buffer pass of a scene as images: first-hit p, n, ns, uv, albedo and coverage (numpy float32), from a scene created for the call or from `renderer`."""
+    r = renderer or Renderer(lib, desc, device=device)
+    try:
+        g, _ = r.gbuffer(params, space=space)
+    finally:
+        if renderer is None:
+            r.close()
+    return gbuffer_resolve(lib, g, gbuffer_white(lib, desc), matrix)
 
 
 def film_tensor(renderer, device=None):
