@@ -102,6 +102,8 @@ def main():
                     help="ShmRenderParams::disable_reference_quirks: PBRT-v4's forms of the reference's deviations (emitter sampling, instancing, ...: DESIGN.md section 2) "
                          "instead of the reference-exact default")
     ap.add_argument("--aovs", action="store_true", help="also write the G-buffer pass's albedo, normal (shading) and position images beside the beauty, as PFM")
+    ap.add_argument("--denoise", action="store_true", help="run the G-buffer pass and the denoiser (DESIGN.md section 4j) on the frame and write <name>.denoised.pfm and .png "
+                                                           "beside the beauty")
     ap.add_argument("-o", "--output", default="")
     args = ap.parse_args()
     lib = abi.load_library()
@@ -124,9 +126,12 @@ def main():
     out = args.output or f"{args.scene.replace(':', '_')}.pfm"
     img = np.ascontiguousarray(img, np.float32)
     abi.check(lib, lib.shm_write_pfm(out.encode(), img.ctypes.data_as(abi.c_float_p), w, h), "shm_write_pfm")
-    ldr = np.clip(img * args.exposure, 0.0, 1.0)
-    ldr = np.where(ldr <= 0.0031308, 12.92 * ldr, 1.055 * np.power(ldr, 1 / 2.4) - 0.055)
-    write_png(os.path.splitext(out)[0] + ".png", (ldr * 255 + 0.5).astype(np.uint8))
+    def write_ldr(path, image):
+        ldr = np.clip(image * args.exposure, 0.0, 1.0)
+        ldr = np.where(ldr <= 0.0031308, 12.92 * ldr, 1.055 * np.power(ldr, 1 / 2.4) - 0.055)
+        write_png(path, (ldr * 255 + 0.5).astype(np.uint8))
+
+    write_ldr(os.path.splitext(out)[0] + ".png", img)
     print("wrote", out, "and", os.path.splitext(out)[0] + ".png")
     if args.aovs:  # the G-buffer pass of the same frame: what a denoiser takes beside the beauty
         aov = render.render_gbuffer(lib, sc.desc, p, matrix=render.SRGB_FROM_XYZ, renderer=r)
@@ -135,6 +140,14 @@ def main():
             a = np.ascontiguousarray(aov[key], np.float32)
             abi.check(lib, lib.shm_write_pfm(f"{stem}.{name}.pfm".encode(), a.ctypes.data_as(abi.c_float_p), w, h), "shm_write_pfm")
         print("wrote", ", ".join(f"{stem}.{n}.pfm" for n in ("albedo", "normal", "position")), f"(coverage {float(aov['coverage'].mean()):.3f})")
+    if args.denoise:  # the film is still on the device; the pass fills the G-buffer the filter is guided by (a second pass after --aovs's gives the same sums)
+        r.gbuffer(p)
+        den, ms = r.denoise(return_ms=True)
+        dimg = np.ascontiguousarray(render.film_get_image(lib, den, render.SRGB_FROM_XYZ), np.float32)
+        stem = os.path.splitext(out)[0]
+        abi.check(lib, lib.shm_write_pfm(f"{stem}.denoised.pfm".encode(), dimg.ctypes.data_as(abi.c_float_p), w, h), "shm_write_pfm")
+        write_ldr(f"{stem}.denoised.png", dimg)
+        print(f"wrote {stem}.denoised.pfm and {stem}.denoised.png (denoiser: {ms:.3f} ms)")
     r.close()
 
 

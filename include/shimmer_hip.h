@@ -640,6 +640,40 @@ SHM_API int shm_gbuffer_white(const ShmSceneDesc* desc, double white[3]);
  * weight_hit is 0 gets zeros. */
 SHM_API int shm_gbuffer_resolve(const ShmGBufferPixel* pixels, uint64_t n, const double white[3], const float* output_rgb_from_sensor_rgb, float* out15);
 
+/* ---- the denoiser: an edge-avoiding a-trous filter over the film, guided by the G-buffer ------------------
+ * A single-frame wavelet filter after Dammertz et al. 2010 with SVGF's weights and its spatial variance estimate: the film's sensor RGB c = rgb_sum / weight_sum is divided
+ * by an effective albedo a_eff (the G-buffer's albedo over shm_gbuffer_white, blended towards 1 by the coverage weight_hit / weight_sum; a channel below albedo_floor is left as it is: a_eff = 1),
+ * filtered `iterations` times with a 5x5 B3 spline whose taps stand 2^i pixels apart in iteration i — each tap weighted by the normals' agreement (sigma_normal), the
+ * tap's angle off the pixel's tangent plane (sigma_plane) and the luminance difference against the locally estimated standard deviation (sigma_luminance; +inf: not at
+ * all) — and multiplied by a_eff again. A pixel without a usable guide (weight_sum <= 0, weight_hit <= 0, a zero shading normal, anything non-finite: escaped rays, a
+ * pixel whose negative filter lobes outweigh the rest) passes through — its result is c, bit for bit — and no other pixel reads it. Taps outside the film are skipped.
+ * The result is a ShmFilmPixel array: rgb_sum the denoised sensor RGB, weight_sum 1 (0 where the film's was 0), so shm_film_get_image takes it as it takes a film.
+ * Device and CPU twin run the same header (shm/denoise.h) and give the same bits. */
+typedef struct ShmDenoiseParams {
+    uint32_t iterations;      /* 0..8; 0: the result is c for every pixel */
+    uint32_t demodulate;      /* 0: a_eff = 1 */
+    float sigma_luminance;    /* > 0, +inf allowed */
+    float sigma_normal;       /* > 0 */
+    float sigma_plane;        /* > 0 */
+    float albedo_floor;       /* in (0, 1]: the least effective albedo a channel is divided by */
+    uint32_t reserved[2];
+} ShmDenoiseParams;
+/* 5 iterations, demodulate 1, sigma_luminance 1.5, sigma_normal 128, sigma_plane 0.1, albedo_floor 0.01 */
+SHM_API int shm_denoise_default_params(ShmDenoiseParams* out);
+/* The device film and the device G-buffer into a device result; neither input is written. Blocking; ms_out (may be NULL) receives the HIP-event time of the kernels.
+ * The first call allocates the filter's planes (80 bytes per pixel) and the result, which shm_scene_destroy frees. SHM_ERR_INVALID_ARGUMENT, with the cause in
+ * shm_last_error(): no G-buffer wave has run on the scene since its creation or since the last shm_gbuffer_clear; iterations > 8; a sigma that is NaN or <= 0;
+ * albedo_floor outside (0, 1]. */
+SHM_API int shm_denoise_device(ShmScene* scene, const ShmDenoiseParams* params, double* ms_out);
+/* Copy the last result to a caller-allocated pixel_bounds-sized row-major array (SHM_ERR_INVALID_ARGUMENT before the first shm_denoise_device). */
+SHM_API int shm_denoise_read(ShmScene* scene, ShmFilmPixel* out);
+/* shm_denoise_device + shm_denoise_read */
+SHM_API int shm_denoise(ShmScene* scene, const ShmDenoiseParams* params, ShmFilmPixel* out, double* ms_out);
+/* The CPU twin (no GPU needed): the same arithmetic on the host, from read-back buffers (shm_film_read, shm_gbuffer_read) and shm_gbuffer_white's W. `out` must not
+ * overlap the inputs. */
+SHM_API int shm_denoise_host(const ShmFilmPixel* film, const ShmGBufferPixel* gbuffer, int32_t width, int32_t height, const double white[3],
+                             const ShmDenoiseParams* params, ShmFilmPixel* out);
+
 /* ---- multi-GPU (ABI v7) -------------------------------------------------------------------------------------------
  * Pixels are independent and tile ownership is exclusive (the reference's one parallel region, integrator.rs:242-304, relies on that
  * for its unsynchronised film writes), so the frame shards by tiles with the scene replicated per GPU and NO collective while

@@ -217,6 +217,15 @@ class ShmGBufferPixel(C.Structure):
 
 SHM_GBUFFER_SPACE_RENDER, SHM_GBUFFER_SPACE_CAMERA = 0, 1
 assert C.sizeof(ShmGBufferPixel) == 128
+
+
+class ShmDenoiseParams(C.Structure):
+    """The denoiser's parameters (include/shimmer_hip.h); shm_denoise_default_params fills one."""
+    _fields_ = [("iterations", C.c_uint32), ("demodulate", C.c_uint32), ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float), ("sigma_plane", C.c_float),
+                ("albedo_floor", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
+assert C.sizeof(ShmDenoiseParams) == 32
 assert C.sizeof(ShmMaterial) == 64 + 4 * 32 + 48 and C.sizeof(ShmFloatTexture) == 48 and C.sizeof(ShmBvhNode) == 32 and C.sizeof(ShmRay) == 32 and C.sizeof(ShmHit) == 32 and C.sizeof(ShmFilmPixel) == 32
 
 class ShmPbrtScene(C.Structure):
@@ -274,6 +283,11 @@ EXPORTS = {
                                        c_float_p]),
     "shm_gbuffer_white": (C.c_int, [C.POINTER(ShmSceneDesc), C.POINTER(C.c_double)]),
     "shm_gbuffer_resolve": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_double), c_float_p, c_float_p]),
+    "shm_denoise_default_params": (C.c_int, [C.POINTER(ShmDenoiseParams)]),
+    "shm_denoise_device": (C.c_int, [C.c_void_p, C.POINTER(ShmDenoiseParams), C.POINTER(C.c_double)]),
+    "shm_denoise_read": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "shm_denoise": (C.c_int, [C.c_void_p, C.POINTER(ShmDenoiseParams), C.c_void_p, C.POINTER(C.c_double)]),
+    "shm_denoise_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(ShmDenoiseParams), C.c_void_p]),
     "shm_last_error": (C.c_char_p, []),
     "shm_device_count": (C.c_int, []),
     "shm_bvh_build": (C.c_int, [c_float_p, C.c_uint32, C.c_int, C.POINTER(ShmBvhNode), c_u32_p, c_u32_p]),

@@ -30,6 +30,7 @@
 #include "../../../include/shimmer_hip.h"
 #include "../shm/path.h"  // camera_generate_ray_differential for CameraBase::find_minimum_differentials (host use only)
 #include "../shm/gbuffer.h"  // the G-buffer pass's CPU twin, at the end of this file
+#include "../shm/denoise.h"  // the denoiser's, behind it
 #include "flatten.h"
 
 extern "C" __attribute__((visibility("hidden"))) void shm_set_last_error(const char* msg);  // shimmer_hip.hip
@@ -937,3 +938,43 @@ int shm_gbuffer_resolve(const ShmGBufferPixel* pixels, uint64_t n, const double 
 }
 
 }  // extern "C"
+
+// ---- the denoiser's CPU twin (include/shimmer_hip.h, shm_denoise_host) ------------------------------------
+// shm/denoise.h's pixel functions over the whole film, pass by pass as k_denoise.hip launches them: prepare, variance (where sigma_luminance is finite), one a-trous pass per
+// iteration from one copy of plane A into the other, finish.
+extern "C" int shm_denoise_host(const ShmFilmPixel* film, const ShmGBufferPixel* gbuffer, int32_t width, int32_t height, const double white[3], const ShmDenoiseParams* params,
+                                ShmFilmPixel* out) {
+    if (!film || !gbuffer || !white || !params || !out || width < 1 || height < 1) { shm_set_last_error("denoise: a null argument or an empty film"); return SHM_ERR_INVALID_ARGUMENT; }
+    const shm::DenoiseConfig k{params->iterations, params->demodulate, params->sigma_luminance, params->sigma_normal, params->sigma_plane, params->albedo_floor};
+    if (const char* why = shm::denoise_params_error(k)) { shm_set_last_error(why); return SHM_ERR_INVALID_ARGUMENT; }
+    const size_t n = (size_t)width * (size_t)height;
+    std::vector<shm::DnF4> A[2], B, C, D;
+    int cur = 0;
+    if (k.iterations > 0) {
+        A[0].resize(n); A[1].resize(n); B.resize(n); C.resize(n); D.resize(n);
+        const shm::Float wf[3] = {(shm::Float)white[0], (shm::Float)white[1], (shm::Float)white[2]};
+        for (size_t q = 0; q < n; ++q)
+            shm::denoise_prepare_pixel(reinterpret_cast<const double*>(film + q), reinterpret_cast<const double*>(gbuffer + q), wf, k, A[0][q], B[q], C[q], D[q]);
+        if (!shm::is_inf(k.sigma_luminance)) {
+            std::vector<shm::Float> var(n);
+            for (int y = 0; y < height; ++y)
+                for (int x = 0; x < width; ++x) {
+                    const shm::DenoiseGlobalTaps taps{A[0].data(), B.data(), C.data(), x, y, width, height, 1, false};
+                    var[(size_t)y * width + x] = shm::denoise_variance_pixel(taps, k);
+                }
+            for (size_t q = 0; q < n; ++q) A[0][q].w = var[q];
+        }
+        for (uint32_t i = 0; i < k.iterations; ++i, cur ^= 1)
+            for (int y = 0; y < height; ++y)
+                for (int x = 0; x < width; ++x) {
+                    const shm::DenoiseGlobalTaps taps{A[cur].data(), B.data(), C.data(), x, y, width, height, 1 << i, true};
+                    A[cur ^ 1][(size_t)y * width + x] = shm::denoise_atrous_pixel(taps, k);
+                }
+    }
+    for (size_t q = 0; q < n; ++q) {
+        const bool valid = k.iterations > 0 && C[q].w != 0.0f;
+        const shm::DnF4 zero = shm::dn_f4(0.0f, 0.0f, 0.0f, 0.0f);
+        shm::denoise_finish_pixel(reinterpret_cast<const double*>(film + q), valid, valid ? A[cur][q] : zero, valid ? D[q] : zero, reinterpret_cast<double*>(out + q));
+    }
+    return SHM_OK;
+}

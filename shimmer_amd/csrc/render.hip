@@ -875,6 +875,7 @@ int shm_gbuffer_clear(ShmScene* s) {
     if ((rc = ensure_gbuffer(s)) != SHM_OK) return rc;
     HIP_TRY(hipMemsetAsync(s->d_gbuffer, 0, s->n_film_pixels * sizeof(ShmGBufferPixel), s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
+    s->gbuffer_filled = false;
     return SHM_OK;
 }
 
@@ -959,6 +960,7 @@ int shm_gbuffer_render_wave(ShmScene* s, const ShmRenderParams* params, uint32_t
         stats->ms_shade += (double)ms - mc;  // K1 and the pass's two kernels
         stats->launches_closest += (uint32_t)ev_closest.size();
     }
+    s->gbuffer_filled = true;
     return SHM_OK;
 }
 

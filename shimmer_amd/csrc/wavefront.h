@@ -411,6 +411,10 @@ struct ShmScene {
     uint32_t n_tri_shade_records = 0;   // the flat triangles' shading records built at scene creation (shm/tri_shade.h; shm_scene_shading_records) ...
     double tri_shade_build_ms = 0.0;    // ... and the wall-clock time that took
     ShmGBufferPixel* d_gbuffer = nullptr;  // the G-buffer pass's sums, pixel_bounds-sized: allocated by the first shm_gbuffer_* call (render.hip), null in a scene that never asks
+    bool gbuffer_filled = false;           // a G-buffer wave has run since the scene was made or the G-buffer last cleared: what the denoiser asks for its guides
+    float4* d_denoise = nullptr;           // the denoiser's planes (k_denoise.hip: five float4 per pixel) and, behind them, its result — made by the first shm_denoise_device
+    ShmFilmPixel* d_denoised = nullptr;
+    bool denoised = false;                 // d_denoised holds a result
 };
 // dist.hip: releases s->dist (RCCL communicator included); called by shm_scene_destroy
 __attribute__((visibility("hidden"))) void wf_dist_release(ShmScene* s);

@@ -206,6 +206,16 @@ class Renderer:
         abi.check(self.lib, self.lib.shm_render_gbuffer(self.handle, C.byref(params), space, tiles, n, g.ctypes.data_as(C.c_void_p), C.byref(stats)), "shm_render_gbuffer")
         return g, stats.as_dict()
 
+    # ---- the denoiser (include/shimmer_hip.h "the denoiser") ----
+    def denoise(self, dparams=None, return_ms=False):
+        """shm_denoise: the device film filtered under the device G-buffer's guidance (a G-buffer pass must have run), read back as a FILM_DTYPE array whose
+        rgb_sum is the denoised sensor RGB and whose weight_sum is 1 — what film_get_image takes. dparams: an abi.ShmDenoiseParams (None: the defaults)."""
+        d = dparams if dparams is not None else make_denoise_params(self.lib)
+        out = np.zeros((self.height, self.width), dtype=FILM_DTYPE)
+        ms = C.c_double(0.0)
+        abi.check(self.lib, self.lib.shm_denoise(self.handle, C.byref(d), out.ctypes.data_as(C.c_void_p), C.byref(ms)), "shm_denoise")
+        return (out, float(ms.value)) if return_ms else out
+
     def trace(self, rays, any_hit=False):
         """Bring-up entry: rays = structured/float32 array (n, 8) [o,d,t_max,pad]. Returns hits (n,8 view) or occluded bytes."""
         rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
@@ -255,6 +265,47 @@ def render_gbuffer(lib, desc, params, device=0, space=abi.SHM_GBUFFER_SPACE_REND
         if renderer is None:
             r.close()
     return gbuffer_resolve(lib, g, gbuffer_white(lib, desc), matrix)
+
+
+def make_denoise_params(lib, **overrides):
+    """shm_denoise_default_params, with any of iterations, demodulate, sigma_luminance, sigma_normal, sigma_plane, albedo_floor set by keyword."""
+    d = abi.ShmDenoiseParams()
+    abi.check(lib, lib.shm_denoise_default_params(C.byref(d)), "shm_denoise_default_params")
+    for k, v in overrides.items():
+        if k not in ("iterations", "demodulate", "sigma_luminance", "sigma_normal", "sigma_plane", "albedo_floor"):
+            raise TypeError(f"make_denoise_params: no parameter {k!r}")
+        setattr(d, k, v)
+    return d
+
+
+def denoise_host(lib, film, gbuffer, white, dparams=None):
+    """shm_denoise_host, the denoiser's CPU twin: (H, W) FILM_DTYPE and GBUFFER_DTYPE arrays (Renderer.read_film / read_gbuffer, or made in numpy) and gbuffer_white's
+    W into the FILM_DTYPE result Renderer.denoise gives for the same inputs, bit for bit. No GPU needed."""
+    f = np.ascontiguousarray(film, dtype=FILM_DTYPE)
+    g = np.ascontiguousarray(gbuffer, dtype=GBUFFER_DTYPE)
+    if f.ndim != 2 or g.shape != f.shape:
+        raise ValueError("denoise_host: film and gbuffer must be (height, width) arrays of one shape")
+    d = dparams if dparams is not None else make_denoise_params(lib)
+    w = (C.c_double * 3)(*[float(x) for x in white])
+    out = np.zeros(f.shape, dtype=FILM_DTYPE)
+    abi.check(lib, lib.shm_denoise_host(f.ctypes.data_as(C.c_void_p), g.ctypes.data_as(C.c_void_p), f.shape[1], f.shape[0], w, C.byref(d), out.ctypes.data_as(C.c_void_p)),
+              "shm_denoise_host")
+    return out
+
+
+def render_denoised(lib, desc, params, dparams=None, device=0, matrix=None, renderer=None):
+    """Render, G-buffer pass and denoiser in one call, from a scene created for it or from `renderer`. Returns a dict: "film" and "denoised" (FILM_DTYPE), "noisy" and
+    "image" (their film_get_image under `matrix`: float32 (H, W, 3)), "gbuffer" (GBUFFER_DTYPE), "stats" (the render's) and "denoise_ms" (the filter's HIP-event time)."""
+    r = renderer or Renderer(lib, desc, device=device)
+    try:
+        film, stats = r.render(params)
+        g, _ = r.gbuffer(params)
+        den, ms = r.denoise(dparams, return_ms=True)
+    finally:
+        if renderer is None:
+            r.close()
+    return {"film": film, "denoised": den, "noisy": film_get_image(lib, film, matrix), "image": film_get_image(lib, den, matrix), "gbuffer": g, "stats": stats,
+            "denoise_ms": ms}
 
 
 def film_tensor(renderer, device=None):
