@@ -121,6 +121,7 @@ constexpr int trace_strict_variant(int variant) { return variant == TRACE_GEN_HE
 // Tuning knobs (development): defaults are the measured optimum on S3. -1 / 0: not set.
 struct Knobs {
     int split_pass = -1, gen_heavy = -1, tri_shade = -1;  // SHM_SPLIT_PASS, SHM_GEN_HEAVY, SHM_TRI_SHADE: 0 / 1
+    int shade_prefetch = -1;                              // SHM_SHADE_PREFETCH: 0 / 1
     int tail_fused_bounce = 0;                            // SHM_TAIL_FUSED_BOUNCE (negative = never)
     int trace_rays_per_lane = -1;                         // SHM_TRACE_RAYS_PER_LANE, 0 .. 4096
     int refill_min = 0, refill_min_any = 0, leaf_min = 0, leaf_min_any = 0, other_min = 0, other_min_any = 0;  // SHM_REFILL_MIN .. SHM_OTHER_MIN_ANY, 1 .. 64
@@ -131,6 +132,7 @@ inline Knobs read_knobs() {
     auto flag = [](const char* name, int& out) { if (const char* e = getenv(name)) out = atoi(e) != 0 ? 1 : 0; };
     auto lanes = [](const char* name, int& out) { if (const char* e = getenv(name)) { const int v = atoi(e); if (v >= 1 && v <= 64) out = v; } };
     flag("SHM_SPLIT_PASS", k.split_pass); flag("SHM_GEN_HEAVY", k.gen_heavy); flag("SHM_TRI_SHADE", k.tri_shade);
+    flag("SHM_SHADE_PREFETCH", k.shade_prefetch);
     if (const char* e = getenv("SHM_TAIL_FUSED_BOUNCE")) { const int v = atoi(e); k.tail_fused_bounce = v >= 0 ? v : NEVER; }
     if (const char* e = getenv("SHM_TRACE_RAYS_PER_LANE")) { const int v = atoi(e); if (v >= 0 && v <= 4096) k.trace_rays_per_lane = v; }
     lanes("SHM_REFILL_MIN", k.refill_min); lanes("SHM_REFILL_MIN_ANY", k.refill_min_any); lanes("SHM_LEAF_MIN", k.leaf_min); lanes("SHM_LEAF_MIN_ANY", k.leaf_min_any);
@@ -159,6 +161,8 @@ struct ScenePlan {
     bool first_bounce = false; // a render's bounce 0 may run on known constants (k_generate<., LEAN>, ShadeArgs::first_bounce): the workspace holds rng0 / pixel0
     bool lean_kernel = false;  // k_shade<lean> runs, direct or diverted: the workspace holds the deferred emitter hits (PathArrays::e_*, q_emit)
     bool tri_shade = false, tri_shade_plain_only = false;  // build the flat triangles' shading records (shm/tri_shade.h) / of plain DiffuseMaterials only
+    bool shade_prefetch = true;  // k_shade<lean> fetches the next vertex's queue entry and hit record while it shades this one (k_shade.inl, K_SHADE_PREFETCH); SHM_SHADE_PREFETCH=0:
+                                 // the same kernel loads them where it needs them (the A/B instrument: films and counters cannot differ)
     // the traversal kernels (k_trace.hip)
     int trace_variant = TRACE_TRI;         // the row of TRACE_SHAPES (and of k_trace.hip's kernel table) this scene's rays take
     int trace_spill_levels[N_RAY] = {1, 1};  // stack levels in the per-lane HBM spill: what the tree's depth needs beyond the row's LDS levels, and one more
@@ -197,6 +201,7 @@ inline ScenePlan scene_plan(const SceneFacts& f, const Knobs& k) {
     const bool vertex_reads = !f.has_material_textures && !p.lean && !p.fused_from_0;
     p.tri_shade = !f.has_spheres && f.has_prims && (lean_reads || vertex_reads) && k.tri_shade != 0;
     p.tri_shade_plain_only = f.has_material_textures;
+    p.shade_prefetch = k.shade_prefetch != 0;
     // a shallow tree means short rays, and short rays want fewer, fuller waves (C2's 63-node box: 15.5 -> 15.1 ms per frame at 8 rays per lane); a deep
     // tree means long dependent chains per ray, which want every wave the device has (C4: 8 costs 2 %)
     p.trace_rays_per_lane = k.trace_rays_per_lane >= 0 ? k.trace_rays_per_lane : (f.small_tree ? 8 : 4);

@@ -27,6 +27,17 @@ namespace {
 #ifndef K_SHADE_NEE_LAST
 #define K_SHADE_NEE_LAST 1  // next-event estimation evaluated at the end of the vertex (0: where the reference's text has it: A/B)
 #endif
+// The lean triangle instantiation (TRI_ONLY && !HAS_TEX && !ENV_LIGHT && !SORT_CHUNK, compact hit records) walks a chain of dependent gathers per vertex: queue entry ->
+// hit record -> ray, wavelengths, flags -> the primitive record's `valid` word -> primitive record + shading record, five round trips before the first arithmetic. The
+// PREFETCH instantiation of that kernel (renders with compact hit records in scenes with the shading-record table only: the launcher chooses) has a lane carry its NEXT vertex's path and 16-byte hit record and the queue entry of the one after across the vertex (six VGPRs),
+// fetched while this vertex is shaded: a vertex starts with hit.prim known and sends its ray, wavelength, primitive-record and shading-record loads in one round trip.
+// Only loads move: films and counters are what they were. 0 compiles the instantiation out (A/B); ScenePlan::shade_prefetch (SHM_SHADE_PREFETCH=0) launches the plain
+// one of the same build.
+#ifndef K_SHADE_PREFETCH
+#define K_SHADE_PREFETCH 1
+#endif
+// (Measured on top of it and not kept: the rest of the path's record — beta, p_b / eta_scale, sampler state, pixel — fetched with its first sector and held, nine VGPRs, 153
+//  in all, instead of load_rng / load_beta / load_pb_eta where they are used: 0.6 ms of a 227 ms frame, inside the runs' spread. profiles/no_slp_pack.md)
 
 // ---------------------------------------------------------------------------------------------
 // K4+K5: one path vertex (integrator.rs:772-892 for the vertex found by K2).
@@ -48,7 +59,8 @@ namespace {
 //   — the queue is in image order, and a wave of the unsorted kernel ran at 11.5 of 64 lanes per instruction on C4's late bounces (profiles/r04_staged_C4.txt).
 //   Paths are independent and every later queue is order-agnostic: films and counters do not change.
 constexpr int SHADE_SORT_BINS = 64;
-template <bool HAS_LAYERED, bool TRI_ONLY, bool HAS_TEX = false, bool DIFFUSE_ONLY = false, bool EMIT_INLINE = true, bool SORT_CHUNK = false, bool ENV_LIGHT = false>
+template <bool HAS_LAYERED, bool TRI_ONLY, bool HAS_TEX = false, bool DIFFUSE_ONLY = false, bool EMIT_INLINE = true, bool SORT_CHUNK = false, bool ENV_LIGHT = false,
+          bool PREFETCH = false>
 __global__ void __launch_bounds__(SHADE2_BLOCK) K_SHADE_LEAN_ATTR k_shade(SceneView sv_global, PathArrays pa, const uint32_t* __restrict__ q_cur, uint32_t* __restrict__ q_next,
                                                      uint32_t* __restrict__ q_shadow, QueueState* qs, int cur, ShmRenderParams params,
                                                      DeviceCounters* counters, int shadow_parity, const uint32_t* __restrict__ n_in, uint32_t* __restrict__ q_emit,
@@ -68,6 +80,8 @@ __global__ void __launch_bounds__(SHADE2_BLOCK) K_SHADE_LEAN_ATTR k_shade(SceneV
     __shared__ uint32_t s_cnt[3], s_base[3];
     __shared__ uint32_t s_sorted[SORT_CHUNK ? SHADE_CHUNK : 1];
     __shared__ uint32_t s_bin[SORT_CHUNK ? SHADE_SORT_BINS + 1 : 1];
+    static_assert(!PREFETCH || (TRI_ONLY && !HAS_TEX && !ENV_LIGHT && !SORT_CHUNK), "the prefetch is the lean triangle instantiation's");
+    constexpr uint32_t CHUNK_VERTICES = SHADE_CHUNK / SHADE2_BLOCK;  // per lane
     for (uint32_t chunk0 = blockIdx.x * SHADE_CHUNK; chunk0 < n; chunk0 += gridDim.x * SHADE_CHUNK) {
       if (threadIdx.x == 0) { s_cnt[0] = 0; s_cnt[1] = 0; s_cnt[2] = 0; }
       if (SORT_CHUNK) {
@@ -107,16 +121,52 @@ __global__ void __launch_bounds__(SHADE2_BLOCK) K_SHADE_LEAN_ATTR k_shade(SceneV
           }
       }
       __syncthreads();
-      for (uint32_t k = 0; k < SHADE_CHUNK / SHADE2_BLOCK; ++k) {
+      // PREFETCH: path and compact hit record of the vertex a lane shades next and the queue entry of the one after (queue index + SHADE2_BLOCK each). Every index is
+      // clamped to the queue's last entry instead of guarded: the loads are unconditional, so no branch joins between them and their use a vertex later (a join makes
+      // the compiler wait for everything in flight), and what a clamped index fetched belongs to a vertex the lane does not shade (i >= n: `active` is false).
+      uint32_t pf_path = 0u, pf_queued = 0u;
+      float4 pf_hit = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      if (PREFETCH) {
+          const uint32_t i0 = min(chunk0 + threadIdx.x, n - 1u), i1 = min(chunk0 + threadIdx.x + SHADE2_BLOCK, n - 1u);  // (chunk0 < n: n >= 1)
+          if (first_bounce) { pf_path = i0; pf_queued = i1; } else { pf_path = q_cur[i0]; pf_queued = q_cur[i1]; }
+          pf_hit = reinterpret_cast<const float4*>(pa.hit)[pf_path];  // (read early: see the invariant in the loop)
+      }
+      for (uint32_t k = 0; k < CHUNK_VERTICES; ++k) {
         const uint32_t i = chunk0 + k * SHADE2_BLOCK + threadIdx.x;
         bool active = i < n;
         bool push_next = false, push_shadow = false, push_emit = false;
         uint32_t path = 0;
         if (active) {
             // first_bounce (wave-uniform; the lean class and, since round 5, every class whose bounce 0 runs this kernel): k_generate left the constants out — the queue is the identity, beta = 1, p_b = eta_scale = 1, flags = 0
-            path = SORT_CHUNK ? s_sorted[k * SHADE2_BLOCK + threadIdx.x] : (first_bounce ? i : q_cur[i]);
+            path = SORT_CHUNK ? s_sorted[k * SHADE2_BLOCK + threadIdx.x] : (PREFETCH ? pf_path : (first_bounce ? i : q_cur[i]));
             Hit hit;
-            hit = load_hit_tri(pa, path);  // (the 32-byte ShmHit, or — triangle scenes, whatever instantiation shades them: a textured triangle scene runs the general ones — the compact form)
+            float4 pf_w[4];  // (PREFETCH: the primitive record's four words and the shading record, below)
+            PrimRec pf_prim;
+            TriShadeRec pf_tsr;
+            if (PREFETCH) {
+                hit = hit_from_record16(pa, pf_hit, path);
+                // With hit.prim known from the start, the primitive record and the shading record are fetched HERE, beside the ray, the wavelengths and the flags — one
+                // round trip — instead of behind the record's `valid` word inside the branch on the hit (two more). Unconditional, like the other loads of the
+                // prefetch: an escaped ray reads slot 0 and a primitive without a record its slot's unused 48 bytes; nobody looks at either. (The launcher takes
+                // this instantiation only where the scene holds the table: SceneView::tri_shade is not null here.) Left alone the compiler sinks the loads to the
+                // branch that uses them, behind the `valid` word again: an empty asm statement in front of that branch names one word of each as an operand, and
+                // an operand of a statement that may not move keeps them above it, where the wait for the flags covers them.
+                const uint32_t slot = hit.prim < 0 ? 0u : (uint32_t)hit.prim;
+                const float4* pr4 = reinterpret_cast<const float4*>(sv.prim_recs + slot);
+                pf_w[0] = pr4[0]; pf_w[1] = pr4[1]; pf_w[2] = pr4[2]; pf_w[3] = pr4[3];
+                __builtin_memcpy(&pf_prim, pf_w, sizeof(PrimRec));
+                pf_tsr = sv.tri_shade[slot];
+                // ... and the next two vertices of this lane, before anything else of this one is fetched. INVARIANT the early read rests on: nothing in this launch
+                // writes the hit array or the queue it reads. q_cur is only read; with hit_kept the vertex leaves nothing for the next one, and without it what it
+                // leaves — its own path's entry, no other lane's — goes to `ctx`, never to `hit`; the queues written are q_next, q_shadow and q_emit. So a record read
+                // one vertex early is the record read on time. (The chunk's last vertex has no next one: it reads its own entries again, and nothing uses them.)
+                const uint32_t i2 = k + 2u < CHUNK_VERTICES ? min(i + 2u * SHADE2_BLOCK, n - 1u) : i;
+                pf_path = k + 1u < CHUNK_VERTICES ? pf_queued : path;
+                pf_hit = reinterpret_cast<const float4*>(pa.hit)[pf_path];
+                if (first_bounce) pf_queued = i2; else pf_queued = q_cur[i2];
+            } else {
+                hit = load_hit_tri(pa, path);  // (the 32-byte ShmHit, or — triangle scenes, whatever instantiation shades them: a textured triangle scene runs the general ones — the compact form)
+            }
             const float4* rp = reinterpret_cast<const float4*>(pa.ray + path);
             float4 r0 = rp[0], r1 = rp[1];
             V3 ray_d = v3(r0.w, r1.x, r1.y);
@@ -155,6 +205,8 @@ __global__ void __launch_bounds__(SHADE2_BLOCK) K_SHADE_LEAN_ATTR k_shade(SceneV
                 c.ns = v3(c2.y, c2.z, c2.w);
                 return c;
             };
+            // (PREFETCH: the record loads issued above stay there — see there)
+            if (PREFETCH) asm volatile("" : : "v"(pf_w[0].x), "v"(pf_w[1].x), "v"(pf_w[2].x), "v"(pf_w[3].x), "v"(pf_tsr.a.x), "v"(pf_tsr.b.x), "v"(pf_tsr.c.x));
             if (hit.prim < 0) {
                 // integrator.rs:776-794: escaped ray, infinite lights
                 for (uint32_t k = 0; k < sv.n_infinite_lights; ++k) {
@@ -171,14 +223,14 @@ __global__ void __launch_bounds__(SHADE2_BLOCK) K_SHADE_LEAN_ATTR k_shade(SceneV
                     }
                 }
             } else {
-                const PrimRec& prim = sv.prim_recs[hit.prim];  // (material and emitter ride in the record the interaction fetches anyway)
+                const PrimRec& prim = PREFETCH ? pf_prim : sv.prim_recs[hit.prim];  // (material and emitter ride in the record the interaction fetches anyway)
                 // a flat triangle with a shading record (shm/tri_shade.h): normal and BSDF frame are fetched, not recomputed; every other hit — none in a scene
                 // created under SHM_TRI_SHADE=0 — takes the full interaction in the same kernel. Only the lean instantiation without an environment map: beside the image
                 // light's code the record path made the lean kernel spill at three waves, and the material-sorted all-materials kernel, which spills already, spilled 42 VGPRs more.
                 constexpr bool USE_RECS = TRI_ONLY && !HAS_TEX && !ENV_LIGHT && !SORT_CHUNK;
                 const bool flat = USE_RECS && tri_shade_valid(prim);
                 TriShadeRec tsr;
-                if (flat) tsr = sv.tri_shade[hit.prim];
+                if (flat) tsr = PREFETCH ? pf_tsr : sv.tri_shade[hit.prim];
                 SurfaceInteraction si = flat ? tri_shade_interaction(prim, tsr, hit, -ray_d) : hit_interaction<TRI_ONLY>(sv, hit, -ray_d);
                 // integrator.rs:798-813: emission at the hit
                 if (!EMIT_INLINE && prim.area_light >= 0) {
@@ -481,6 +533,19 @@ using namespace shm_plan;  // (the builds' coordinates: GEO_*, IMG_*, FAM_*)
 // the fused all-materials one handles them inline and sorts its chunks by material
 #define WF_K_SHADE_LEAN(GEO, IMG) k_shade<false, build_tri_only(GEO), build_has_tex(IMG), true, false, false, build_env_light(IMG)>
 #define WF_K_SHADE_FUSED_ALL(GEO, IMG) k_shade<false, build_tri_only(GEO), build_has_tex(IMG), false, true, true, build_env_light(IMG)>
+// ... and its PREFETCH instantiation (K_SHADE_PREFETCH, above), which the triangle build without an image has, for the renders with compact hit records. It lives in a
+// unit of its own, k_shade_lean_prefetch.hip, behind wf_shade_lean_prefetch (wavefront.h): with both instantiations in ONE unit the shared leaf functions have two callers,
+// the inliner leaves some of them as real calls, and BOTH kernels spill (121 / 129 VGPRs, 788 / 820 B of scratch, against none).
+#define WF_K_SHADE_LEAN_CAN_PREFETCH(GEO, IMG) (K_SHADE_PREFETCH && build_tri_only(GEO) && !build_has_tex(IMG) && !build_env_light(IMG))
+// (the renders that take it: compact hit records, which the kernel carries across the vertex, and a scene with the shading-record table, which it reads unasked)
+#define WF_SHADE_LEAN_PREFETCHES (s->plan.shade_prefetch && s->pa.hit16 != 0u && s->dsv.tri_shade != nullptr)
+#define WF_K_SHADE_LEAN_PREFETCH k_shade<false, true, false, true, false, false, false, true>
+#define WF_SHADE_LEAN_PREFETCH_STUB()                                                                                                        \
+    template <> int wf_shade_lean_prefetch<K_ZSOBOL, K_DELTA_LIGHTS>(ShmScene* s, const ShadeArgs& a, bool diverted) {                       \
+        if (diverted) WF_SHADE_LAUNCH_DIVERTED((WF_K_SHADE_LEAN_PREFETCH));                                                                  \
+        else WF_SHADE_LAUNCH((WF_K_SHADE_LEAN_PREFETCH), 2 | (a.hit_kept ? 4 : 0));                                                          \
+        return SHM_OK;                                                                                                                       \
+    }
 // FAM_LEAN and FAM_LEAN_DIVERTED of one build. A triangle scene that runs the kernel alone leaves a vertex's hit record, not its LightSampleContext, for the next
 // vertex's emitter MIS weight (ctx_as_hit; round 4 A/B: DESIGN.md section 6) — the 16-byte hit-record forms need triangle hits: with spheres, patches or instances the
 // records are the 32-byte ShmHit (t, phi, instance) and the vertex leaves its context. k_emit_jobs: emission of the vertices that hit an emitter, before K3 adds this
@@ -489,12 +554,28 @@ using namespace shm_plan;  // (the builds' coordinates: GEO_*, IMG_*, FAM_*)
 #define WF_SHADE_LEAN_STUBS(GEO, IMG)                                                                                                        \
     template <> int wf_shade<FAM_LEAN, GEO, IMG, K_ZSOBOL, K_DELTA_LIGHTS>(ShmScene* s, const ShadeArgs& a) {                      \
         constexpr int ctx_as_hit = build_tri_only(GEO) ? 1 : 0;                                                                              \
-        WF_SHADE_LAUNCH((WF_K_SHADE_LEAN(GEO, IMG)), (ctx_as_hit << 1) | ((ctx_as_hit && a.hit_kept) ? 4 : 0));                              \
+        bool prefetched = false;                                                                                                             \
+        if constexpr (WF_K_SHADE_LEAN_CAN_PREFETCH(GEO, IMG)) {                                                                              \
+            if (WF_SHADE_LEAN_PREFETCHES) {                                                                                                  \
+                const int rc = wf_shade_lean_prefetch<K_ZSOBOL, K_DELTA_LIGHTS>(s, a, false);                                                \
+                if (rc != SHM_OK) return rc;                                                                                                 \
+                prefetched = true;                                                                                                           \
+            }                                                                                                                                \
+        }                                                                                                                                    \
+        if (!prefetched) WF_SHADE_LAUNCH((WF_K_SHADE_LEAN(GEO, IMG)), (ctx_as_hit << 1) | ((ctx_as_hit && a.hit_kept) ? 4 : 0));             \
         WF_EMIT_JOBS_LAUNCH(GEO, ctx_as_hit);                                                                                                \
         return SHM_OK;                                                                                                                       \
     }                                                                                                                                        \
     template <> int wf_shade<FAM_LEAN_DIVERTED, GEO, IMG, K_ZSOBOL, K_DELTA_LIGHTS>(ShmScene* s, const ShadeArgs& a) {             \
-        WF_SHADE_LAUNCH_DIVERTED((WF_K_SHADE_LEAN(GEO, IMG)));                                                                               \
+        bool prefetched = false;                                                                                                             \
+        if constexpr (WF_K_SHADE_LEAN_CAN_PREFETCH(GEO, IMG)) {                                                                              \
+            if (WF_SHADE_LEAN_PREFETCHES) {                                                                                                  \
+                const int rc = wf_shade_lean_prefetch<K_ZSOBOL, K_DELTA_LIGHTS>(s, a, true);                                                 \
+                if (rc != SHM_OK) return rc;                                                                                                 \
+                prefetched = true;                                                                                                           \
+            }                                                                                                                                \
+        }                                                                                                                                    \
+        if (!prefetched) WF_SHADE_LAUNCH_DIVERTED((WF_K_SHADE_LEAN(GEO, IMG)));                                                              \
         WF_EMIT_JOBS_LAUNCH(GEO, 0);                                                                                                         \
         return SHM_OK;                                                                                                                       \
     }

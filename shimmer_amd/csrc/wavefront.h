@@ -298,16 +298,21 @@ __device__ __forceinline__ SceneView stage_scene_tables_tex(const SceneView& sv,
 // the primitive of a compact hit record's first word (a miss stays negative)
 __device__ __forceinline__ int hit_prim_of(int w) { return w < 0 ? w : (int)((uint32_t)w & ~HIT_HAS_SECOND); }
 // a path's hit record as the TRI_ONLY shading kernels read it: the 32-byte ShmHit, or the compact form the render's own traversal launches write (PathArrays::hit16)
+// (the compact form from a record already in registers: k_shade<lean> fetches a vertex's record while it shades the one before, k_shade.inl)
+__device__ __forceinline__ Hit hit_from_record16(const PathArrays& pa, const float4& h, uint32_t path) {
+    Hit hit;
+    const int w = __float_as_int(h.x);
+    hit.prim = hit_prim_of(w); hit.t = 0.0f; hit.b0 = h.y; hit.b1 = h.z; hit.b2 = h.w; hit.phi = 0.0f; hit.inst = -1;
+    if (w >= 0 && ((uint32_t)w & HIT_HAS_SECOND)) {  // (the split form: a sphere / patch hit's t and phi — p_obj / (u, v) ride in b0..b2)
+        const float4 h2 = pa.hit2[path];
+        hit.t = h2.x; hit.phi = h2.y;
+    }
+    return hit;
+}
 __device__ __forceinline__ Hit load_hit_tri(const PathArrays& pa, uint32_t path) {
     Hit hit;
     if (pa.hit16) {
-        const float4 h = reinterpret_cast<const float4*>(pa.hit)[path];
-        const int w = __float_as_int(h.x);
-        hit.prim = hit_prim_of(w); hit.t = 0.0f; hit.b0 = h.y; hit.b1 = h.z; hit.b2 = h.w; hit.phi = 0.0f; hit.inst = -1;
-        if (w >= 0 && ((uint32_t)w & HIT_HAS_SECOND)) {  // (the split form: a sphere / patch hit's t and phi — p_obj / (u, v) ride in b0..b2)
-            const float4 h2 = pa.hit2[path];
-            hit.t = h2.x; hit.phi = h2.y;
-        }
+        hit = hit_from_record16(pa, reinterpret_cast<const float4*>(pa.hit)[path], path);
     } else {
         const float4* hp = reinterpret_cast<const float4*>(pa.hit + path);
         const float4 h0 = hp[0], h1 = hp[1];
@@ -487,6 +492,9 @@ struct ShadeArgs {
 //   FAM_SIMPLE, FAM_RANDOMWALK   the other integrators (k_shade_other.hip): one kernel each for every scene class
 using ShadeFn = int (*)(ShmScene*, const ShadeArgs&);
 template <int FAMILY, int GEO, int IMG, bool ZS, bool DL> WF_INTERNAL int wf_shade(ShmScene* s, const ShadeArgs& a);
+// k_shade_lean_prefetch.hip: the (GEO_TRI, IMG_NONE) lean launchers' other kernel, k_shade<lean>'s PREFETCH instantiation (k_shade.inl: K_SHADE_PREFETCH), the whole queue or
+// the diverted hits — called by those launchers for the renders that take it, and like them defined once per (sampler, extended build)
+template <bool ZS, bool DL> WF_INTERNAL int wf_shade_lean_prefetch(ShmScene* s, const ShadeArgs& a, bool diverted);
 // A build's coordinates as its kernels' template parameters: the stubs of the kernel units (WF_*_STUB, k_*.inl) take (GEO, IMG) and derive these, so that a launcher's
 // place in the table and the kernel it launches cannot disagree. (The one textured build of the staged families is (GEO_GEN, IMG_TEX): TRI_ONLY = false.)
 constexpr bool build_tri_only(int geo) { return geo == shm_plan::GEO_TRI; }

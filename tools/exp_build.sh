@@ -5,7 +5,7 @@
 set -e
 cd "$(dirname "$0")/../shimmer_amd/csrc"
 TU=$1; shift
-FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -ffp-contract=off -fno-fast-math -fhip-fp32-correctly-rounded-divide-sqrt -fno-gpu-flush-denormals-to-zero -Wno-unused-result -Wno-unused-value"
+FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -ffp-contract=off -fno-fast-math -fno-slp-vectorize -fhip-fp32-correctly-rounded-divide-sqrt -fno-gpu-flush-denormals-to-zero -Wno-unused-result -Wno-unused-value"
 mkdir -p _exp
 for SPEC in "$@"; do
   NAME=${SPEC%%:*}; DEFS=${SPEC#*:}
