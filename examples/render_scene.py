@@ -8,6 +8,7 @@
     python examples/render_scene.py cornell --camera spherical [--mapping equirectangular]   (PBRT-v4's spherical camera in place of the scene's own)
     python examples/render_scene.py disk_and_cylinder | quadrics     (PBRT-v4's disk and cylinder: examples/scenes/disk_and_cylinder.pbrt / the builder)
     python examples/render_scene.py cornell_probe                    (examples/scenes/cornell_probe.pbrt: an equal-area probe in the middle of the Cornell box)
+    python examples/render_scene.py cornell --spp 256 --adaptive 0.05 [--min-spp 16] [--batch-spp 4]   (adaptive sampling: --spp is the cap)
 
 Everything goes through the C ABI of include/shimmer_hip.h (shimmer_amd/abi.py is the ctypes binding): scene description ->
 shm_scene_create -> shm_render_device -> shm_film_read -> shm_film_get_image -> shm_write_pfm. Needs an MI355X: there is no CPU path.
@@ -104,6 +105,11 @@ def main():
     ap.add_argument("--aovs", action="store_true", help="also write the G-buffer pass's albedo, normal (shading) and position images beside the beauty, as PFM")
     ap.add_argument("--denoise", action="store_true", help="run the G-buffer pass and the denoiser (DESIGN.md section 4j) on the frame and write <name>.denoised.pfm and .png "
                                                            "beside the beauty")
+    ap.add_argument("--adaptive", type=float, default=None, metavar="THRESHOLD",
+                    help="adaptive sampling (DESIGN.md section 4k): --spp is the cap, a tile stops once every pixel's relative standard error is below THRESHOLD; also "
+                         "writes <name>.spp.pfm (the per-pixel sample count) and <name>.variance.pfm (the variance of the pixel's mean, sensor RGB) beside the beauty")
+    ap.add_argument("--min-spp", type=int, default=None, help="with --adaptive: samples every tile receives (a multiple of --batch-spp, at least twice it; default 16)")
+    ap.add_argument("--batch-spp", type=int, default=None, help="with --adaptive: samples per batch (default 4)")
     ap.add_argument("-o", "--output", default="")
     args = ap.parse_args()
     lib = abi.load_library()
@@ -115,13 +121,20 @@ def main():
     r = render.Renderer(lib, sc.desc, 0)
     p = render.make_params(seed=args.seed, spp=args.spp, max_depth=args.max_depth, integrator=args.integrator, reference_quirks=not args.quirks_off,
                            sampler=args.sampler)
+    tile_spp = None
     r.clear()
     t0 = time.perf_counter()
-    st = r.render_device(p)
+    if args.adaptive is None:
+        st = r.render_device(p)
+    else:
+        over = {k: v for k, v in (("min_spp", args.min_spp), ("batch_spp", args.batch_spp)) if v is not None}
+        aparams = render.make_adaptive_params(lib, threshold=args.adaptive, **over)
+        tile_spp, st = r.render_adaptive(p, aparams)
     dt = time.perf_counter() - t0
     film = r.read_film()
     rays = st["rays_closest"] + st["rays_any"]
-    print(f"{sc.name}: {w}x{h} x {args.spp} spp, {rays / 1e6:.1f} Mrays in {dt * 1e3:.1f} ms = {rays / dt / 1e6:.0f} Mray/s")
+    spp_text = f"{args.spp} spp" if tile_spp is None else f"{st['paths'] / (w * h):.1f} spp on average (tiles from {tile_spp.min()} to {tile_spp.max()}, cap {args.spp})"
+    print(f"{sc.name}: {w}x{h} x {spp_text}, {rays / 1e6:.1f} Mrays in {dt * 1e3:.1f} ms = {rays / dt / 1e6:.0f} Mray/s")
     img = render.film_get_image(lib, film, render.SRGB_FROM_XYZ)  # RgbFilm::get_image with an sRGB output matrix
     out = args.output or f"{args.scene.replace(':', '_')}.pfm"
     img = np.ascontiguousarray(img, np.float32)
@@ -133,6 +146,13 @@ def main():
 
     write_ldr(os.path.splitext(out)[0] + ".png", img)
     print("wrote", out, "and", os.path.splitext(out)[0] + ".png")
+    if tile_spp is not None:  # what the adaptive render measured and where it spent its samples
+        stem = os.path.splitext(out)[0]
+        count = np.ascontiguousarray(np.repeat(render.tile_spp_image(tile_spp, w, h)[..., None], 3, axis=2), np.float32)
+        var = np.ascontiguousarray(render.moments_resolve(lib, r.read_moments(), aparams.floor)["v"], np.float32)
+        for name, a in (("spp", count), ("variance", var)):
+            abi.check(lib, lib.shm_write_pfm(f"{stem}.{name}.pfm".encode(), a.ctypes.data_as(abi.c_float_p), w, h), "shm_write_pfm")
+        print(f"wrote {stem}.spp.pfm and {stem}.variance.pfm")
     if args.aovs:  # the G-buffer pass of the same frame: what a denoiser takes beside the beauty
         aov = render.render_gbuffer(lib, sc.desc, p, matrix=render.SRGB_FROM_XYZ, renderer=r)
         stem = os.path.splitext(out)[0]

@@ -656,8 +656,13 @@ typedef struct ShmDenoiseParams {
     float sigma_normal;       /* > 0 */
     float sigma_plane;        /* > 0 */
     float albedo_floor;       /* in (0, 1]: the least effective albedo a channel is divided by */
-    uint32_t reserved[2];
+    uint32_t variance_source; /* SHM_DENOISE_VARIANCE_*: where the filter's initial variance of l comes from */
+    uint32_t reserved[1];
 } ShmDenoiseParams;
+#define SHM_DENOISE_VARIANCE_SPATIAL 0u  /* the default: the 7x7 spatial estimate */
+#define SHM_DENOISE_VARIANCE_MEASURED 1u /* the moments pass's variance of the pixel's mean (adaptive sampling, below) at every valid pixel whose record holds two batches
+                                            or more — var = (mean_c(sqrt(v_c) / a_eff_c))^2 — and the spatial estimate elsewhere. SHM_ERR_INVALID_ARGUMENT on a scene
+                                            without moments */
 /* 5 iterations, demodulate 1, sigma_luminance 1.5, sigma_normal 128, sigma_plane 0.1, albedo_floor 0.01 */
 SHM_API int shm_denoise_default_params(ShmDenoiseParams* out);
 /* The device film and the device G-buffer into a device result; neither input is written. Blocking; ms_out (may be NULL) receives the HIP-event time of the kernels.
@@ -673,6 +678,64 @@ SHM_API int shm_denoise(ShmScene* scene, const ShmDenoiseParams* params, ShmFilm
  * overlap the inputs. */
 SHM_API int shm_denoise_host(const ShmFilmPixel* film, const ShmGBufferPixel* gbuffer, int32_t width, int32_t height, const double white[3],
                              const ShmDenoiseParams* params, ShmFilmPixel* out);
+
+/* ---- adaptive sampling: per-pixel moments of the film, a tile error, and a render loop that stops by it ----
+ * The moments pass only reads the device film: a batch's contribution to a pixel is the film after the batch's wave minus the film as the pass last saw it
+ * (`prev`), its mean x = d rgb_sum / d weight_sum and its weight dw = d weight_sum. Over the batches of a pixel the pass keeps West's weighted Welford
+ * recurrence per channel (mean, m2 = sum dw (x - mean)^2), the weight W and the batch count B. A batch with dw <= 0 or a non-finite mean is not counted. From a
+ * record: the per-sample variance s2 = m2 / (B - 1), the variance of the pixel's mean v = s2 / W (both 0 while B < 2), and the squared relative error
+ * e2 = mean_c(v_c) / max(mean_c(mean_c), floor)^2. A pixel is converged iff B >= min_spp / batch_spp and e2 < threshold^2 (strictly: a threshold of 0
+ * converges nothing, +inf everything with a finite e2; a NaN never converges). mean, m2, s2 and v are in SENSOR RGB: an output matrix
+ * (output_rgb_from_sensor_rgb) cannot be applied to variances without the covariances between channels, which the pass does not keep.
+ * Device and CPU twin run the same header (shm/moments.h) and give the same bits. */
+typedef struct ShmMomentsPixel {
+    double prev[4];   /* the film pixel (rgb_sum, weight_sum) as the pass last saw it */
+    double mean[3];   /* weighted mean of the batch means */
+    double m2[3];     /* sum over batches of dw (x - mean)^2 */
+    double weight;    /* W: the sum of the counted batches' dw */
+    double batches;   /* B: the counted batches */
+} ShmMomentsPixel;
+typedef struct ShmTileError {
+    uint32_t unconverged;  /* pixels of the tile that are not converged */
+    float max_e2;          /* the largest e2 among the tile's pixels, as a float; a NaN counts as +inf */
+} ShmTileError;
+typedef struct ShmAdaptiveParams {
+    int32_t min_spp;     /* samples every tile receives before it may stop: a multiple of batch_spp, at least 2 * batch_spp */
+    int32_t batch_spp;   /* samples per batch, >= 1 */
+    float threshold;     /* relative standard error below which a pixel is converged: >= 0, +inf allowed */
+    float floor;         /* > 0, finite: the least mean (film units: a lit white surface is near 1) the error is taken relative to */
+    uint32_t reserved[4];
+} ShmAdaptiveParams;
+/* min_spp 16, batch_spp 4, threshold 0.05, floor 0.01 */
+SHM_API int shm_adaptive_default_params(ShmAdaptiveParams* out);
+/* Zero every record and set its prev to the device film AS IT STANDS: after shm_film_clear or in the middle of a render, the pass counts from here. The first
+ * call allocates the records (96 bytes per pixel), which shm_scene_destroy frees. Blocking. */
+SHM_API int shm_moments_clear(ShmScene* scene);
+/* One batch: update the records of the tiles' pixels from the device film and write one ShmTileError per tile, in the tiles' order, to `out` (host memory,
+ * n_tiles entries). The tiles are held to what shm_render_wave asks (inside pixel_bounds, disjoint). Blocking. SHM_ERR_INVALID_ARGUMENT, with the cause in
+ * shm_last_error(): invalid tiles or parameters; no shm_moments_clear on the scene yet. */
+SHM_API int shm_moments_update(ShmScene* scene, const ShmTile* tiles, uint32_t n_tiles, const ShmAdaptiveParams* params, ShmTileError* out);
+/* Copy the records to a caller-allocated pixel_bounds-sized row-major array. */
+SHM_API int shm_moments_read(ShmScene* scene, ShmMomentsPixel* out);
+/* Host side (no GPU needed): 8 floats per record — v[3], s2[3], B, e2 (with `floor` as ShmAdaptiveParams::floor) — in sensor RGB (see above). */
+SHM_API int shm_moments_resolve(const ShmMomentsPixel* moments, uint64_t n, float floor, float* out8);
+/* The pass's CPU twin (no GPU needed): shm_moments_update on a read-back film (width x height, row-major, pixel_bounds (0, 0, width, height)) and records
+ * updated in place. */
+SHM_API int shm_moments_update_host(const ShmFilmPixel* film, ShmMomentsPixel* moments_in_out, int32_t width, int32_t height, const ShmTile* tiles, uint32_t n_tiles,
+                                    const ShmAdaptiveParams* params, ShmTileError* tile_error_out);
+/* A whole render that spends its samples by the measured error. params->samples_per_pixel is the CAP and the value every wave is launched with (so the
+ * ray-differential scale and ZSobol's index width are the full render's). shm_film_clear and shm_moments_clear; min_spp / batch_spp base batches over all
+ * tiles, each followed by shm_moments_update; then rounds: the tiles with unconverged > 0 and fewer samples than the cap get [spp, min(spp + batch_spp, cap))
+ * and an update, until none is left. A tile that stops never returns, and every pixel receives its samples in increasing index: a tile that stopped at s holds
+ * the bits of a plain render of [0, s). The film stays on the device (shm_film_read, the G-buffer pass and the denoiser take it as it is; pixels differ in
+ * weight_sum). tile_spp_out (may be NULL): the samples tile i received. stats (may be NULL): the waves' sums. The cap must not be below min_spp.
+ * One host synchronisation and one 8-byte-per-tile read-back per round. */
+SHM_API int shm_render_adaptive(ShmScene* scene, const ShmRenderParams* params, const ShmTile* tiles, uint32_t n_tiles, const ShmAdaptiveParams* adaptive,
+                                uint32_t* tile_spp_out, ShmStats* stats);
+/* The denoiser's CPU twin with the records beside the film: shm_denoise_host for either variance_source (shm_denoise_host itself, which has no records, refuses
+ * SHM_DENOISE_VARIANCE_MEASURED). `moments`: width x height records, as shm_moments_read gives them. */
+SHM_API int shm_denoise_host_moments(const ShmFilmPixel* film, const ShmGBufferPixel* gbuffer, const ShmMomentsPixel* moments, int32_t width, int32_t height,
+                                     const double white[3], const ShmDenoiseParams* params, ShmFilmPixel* out);
 
 /* ---- multi-GPU (ABI v7) -------------------------------------------------------------------------------------------
  * Pixels are independent and tile ownership is exclusive (the reference's one parallel region, integrator.rs:242-304, relies on that

@@ -222,10 +222,30 @@ assert C.sizeof(ShmGBufferPixel) == 128
 class ShmDenoiseParams(C.Structure):
     """The denoiser's parameters (include/shimmer_hip.h); shm_denoise_default_params fills one."""
     _fields_ = [("iterations", C.c_uint32), ("demodulate", C.c_uint32), ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float), ("sigma_plane", C.c_float),
-                ("albedo_floor", C.c_float), ("reserved", C.c_uint32 * 2)]
+                ("albedo_floor", C.c_float), ("variance_source", C.c_uint32), ("reserved", C.c_uint32 * 1)]
+
+
+SHM_DENOISE_VARIANCE_SPATIAL, SHM_DENOISE_VARIANCE_MEASURED = 0, 1
 
 
 assert C.sizeof(ShmDenoiseParams) == 32
+
+
+class ShmMomentsPixel(C.Structure):
+    """A record of the moments pass (include/shimmer_hip.h): the film pixel as last seen, West's running mean and m2 per channel, W and B."""
+    _fields_ = [("prev", C.c_double * 4), ("mean", C.c_double * 3), ("m2", C.c_double * 3), ("weight", C.c_double), ("batches", C.c_double)]
+
+
+class ShmTileError(C.Structure):
+    _fields_ = [("unconverged", C.c_uint32), ("max_e2", C.c_float)]
+
+
+class ShmAdaptiveParams(C.Structure):
+    """The adaptive render's parameters; shm_adaptive_default_params fills one."""
+    _fields_ = [("min_spp", C.c_int32), ("batch_spp", C.c_int32), ("threshold", C.c_float), ("floor", C.c_float), ("reserved", C.c_uint32 * 4)]
+
+
+assert C.sizeof(ShmMomentsPixel) == 96 and C.sizeof(ShmTileError) == 8 and C.sizeof(ShmAdaptiveParams) == 32
 assert C.sizeof(ShmMaterial) == 64 + 4 * 32 + 48 and C.sizeof(ShmFloatTexture) == 48 and C.sizeof(ShmBvhNode) == 32 and C.sizeof(ShmRay) == 32 and C.sizeof(ShmHit) == 32 and C.sizeof(ShmFilmPixel) == 32
 
 class ShmPbrtScene(C.Structure):
@@ -288,6 +308,15 @@ EXPORTS = {
     "shm_denoise_read": (C.c_int, [C.c_void_p, C.c_void_p]),
     "shm_denoise": (C.c_int, [C.c_void_p, C.POINTER(ShmDenoiseParams), C.c_void_p, C.POINTER(C.c_double)]),
     "shm_denoise_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(ShmDenoiseParams), C.c_void_p]),
+    "shm_adaptive_default_params": (C.c_int, [C.POINTER(ShmAdaptiveParams)]),
+    "shm_moments_clear": (C.c_int, [C.c_void_p]),
+    "shm_moments_update": (C.c_int, [C.c_void_p, C.POINTER(ShmTile), C.c_uint32, C.POINTER(ShmAdaptiveParams), C.c_void_p]),
+    "shm_moments_read": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "shm_moments_resolve": (C.c_int, [C.c_void_p, C.c_uint64, C.c_float, c_float_p]),
+    "shm_moments_update_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(ShmTile), C.c_uint32, C.POINTER(ShmAdaptiveParams), C.c_void_p]),
+    "shm_render_adaptive": (C.c_int, [C.c_void_p, C.POINTER(ShmRenderParams), C.POINTER(ShmTile), C.c_uint32, C.POINTER(ShmAdaptiveParams), C.POINTER(C.c_uint32),
+                                      C.POINTER(ShmStats)]),
+    "shm_denoise_host_moments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(ShmDenoiseParams), C.c_void_p]),
     "shm_last_error": (C.c_char_p, []),
     "shm_device_count": (C.c_int, []),
     "shm_bvh_build": (C.c_int, [c_float_p, C.c_uint32, C.c_int, C.POINTER(ShmBvhNode), c_u32_p, c_u32_p]),

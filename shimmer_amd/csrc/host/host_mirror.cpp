@@ -31,6 +31,7 @@
 #include "../shm/path.h"  // camera_generate_ray_differential for CameraBase::find_minimum_differentials (host use only)
 #include "../shm/gbuffer.h"  // the G-buffer pass's CPU twin, at the end of this file
 #include "../shm/denoise.h"  // the denoiser's, behind it
+#include "../shm/moments.h"  // the moments pass's, last
 #include "flatten.h"
 
 extern "C" __attribute__((visibility("hidden"))) void shm_set_last_error(const char* msg);  // shimmer_hip.hip
@@ -942,9 +943,13 @@ int shm_gbuffer_resolve(const ShmGBufferPixel* pixels, uint64_t n, const double 
 // ---- the denoiser's CPU twin (include/shimmer_hip.h, shm_denoise_host) ------------------------------------
 // shm/denoise.h's pixel functions over the whole film, pass by pass as k_denoise.hip launches them: prepare, variance (where sigma_luminance is finite), one a-trous pass per
 // iteration from one copy of plane A into the other, finish.
-extern "C" int shm_denoise_host(const ShmFilmPixel* film, const ShmGBufferPixel* gbuffer, int32_t width, int32_t height, const double white[3], const ShmDenoiseParams* params,
-                                ShmFilmPixel* out) {
+// (`moments`: the records for variance_source = measured — shm_denoise_host_moments — or null: k_denoise_variance_measured's step behind the variance pass)
+static int denoise_host_impl(const ShmFilmPixel* film, const ShmGBufferPixel* gbuffer, const ShmMomentsPixel* moments, int32_t width, int32_t height, const double white[3],
+                             const ShmDenoiseParams* params, ShmFilmPixel* out) {
     if (!film || !gbuffer || !white || !params || !out || width < 1 || height < 1) { shm_set_last_error("denoise: a null argument or an empty film"); return SHM_ERR_INVALID_ARGUMENT; }
+    if (params->variance_source > SHM_DENOISE_VARIANCE_MEASURED) { shm_set_last_error("denoise: unknown variance_source"); return SHM_ERR_INVALID_ARGUMENT; }
+    const bool measured = params->variance_source == SHM_DENOISE_VARIANCE_MEASURED;
+    if (measured && !moments) { shm_set_last_error("denoise: variance_source is measured, but the call has no moments (shm_denoise_host_moments takes them)"); return SHM_ERR_INVALID_ARGUMENT; }
     const shm::DenoiseConfig k{params->iterations, params->demodulate, params->sigma_luminance, params->sigma_normal, params->sigma_plane, params->albedo_floor};
     if (const char* why = shm::denoise_params_error(k)) { shm_set_last_error(why); return SHM_ERR_INVALID_ARGUMENT; }
     const size_t n = (size_t)width * (size_t)height;
@@ -963,6 +968,11 @@ extern "C" int shm_denoise_host(const ShmFilmPixel* film, const ShmGBufferPixel*
                     var[(size_t)y * width + x] = shm::denoise_variance_pixel(taps, k);
                 }
             for (size_t q = 0; q < n; ++q) A[0][q].w = var[q];
+            if (measured)
+                for (size_t q = 0; q < n; ++q) {
+                    const double* m = reinterpret_cast<const double*>(moments + q);
+                    if (C[q].w != 0.0f && m[11] >= 2.0) A[0][q].w = shm::denoise_measured_variance(m, D[q]);
+                }
         }
         for (uint32_t i = 0; i < k.iterations; ++i, cur ^= 1)
             for (int y = 0; y < height; ++y)
@@ -976,5 +986,52 @@ extern "C" int shm_denoise_host(const ShmFilmPixel* film, const ShmGBufferPixel*
         const shm::DnF4 zero = shm::dn_f4(0.0f, 0.0f, 0.0f, 0.0f);
         shm::denoise_finish_pixel(reinterpret_cast<const double*>(film + q), valid, valid ? A[cur][q] : zero, valid ? D[q] : zero, reinterpret_cast<double*>(out + q));
     }
+    return SHM_OK;
+}
+extern "C" int shm_denoise_host(const ShmFilmPixel* film, const ShmGBufferPixel* gbuffer, int32_t width, int32_t height, const double white[3], const ShmDenoiseParams* params,
+                                ShmFilmPixel* out) {
+    return denoise_host_impl(film, gbuffer, nullptr, width, height, white, params, out);
+}
+extern "C" int shm_denoise_host_moments(const ShmFilmPixel* film, const ShmGBufferPixel* gbuffer, const ShmMomentsPixel* moments, int32_t width, int32_t height,
+                                        const double white[3], const ShmDenoiseParams* params, ShmFilmPixel* out) {
+    if (!moments) { shm_set_last_error("denoise: no moments"); return SHM_ERR_INVALID_ARGUMENT; }
+    return denoise_host_impl(film, gbuffer, moments, width, height, white, params, out);
+}
+
+// ---- the moments pass's CPU twin and its resolve (include/shimmer_hip.h, shm_moments_update_host / shm_moments_resolve) ----
+// shm/moments.h's pixel functions over the tiles' pixels, tile by tile as k_moments_update's workgroups take them; the tile's count and maximum are order-free, so a
+// row-major walk gives what the wave's ballots and shuffles give.
+extern "C" int shm_moments_update_host(const ShmFilmPixel* film, ShmMomentsPixel* moments, int32_t width, int32_t height, const ShmTile* tiles, uint32_t n_tiles,
+                                       const ShmAdaptiveParams* params, ShmTileError* tile_error_out) {
+    if (!film || !moments || !tiles || !params || !tile_error_out || n_tiles == 0 || width < 1 || height < 1) {
+        shm_set_last_error("moments: a null argument, no tiles or an empty film");
+        return SHM_ERR_INVALID_ARGUMENT;
+    }
+    if (const char* why = shm::moments_params_error(params->min_spp, params->batch_spp, params->threshold, params->floor)) { shm_set_last_error(why); return SHM_ERR_INVALID_ARGUMENT; }
+    const int32_t pb[4] = {0, 0, width, height};
+    std::vector<uint64_t> bitmap;
+    if (const char* why = shm::moments_tiles_error(&tiles[0].x0, n_tiles, pb, bitmap)) { shm_set_last_error(why); return SHM_ERR_INVALID_ARGUMENT; }
+    const shm::MomentsConfig k{params->min_spp / params->batch_spp, params->threshold, params->floor};
+    for (uint32_t t = 0; t < n_tiles; ++t) {
+        uint32_t unconverged = 0, key = 0;
+        for (int y = tiles[t].y0; y < tiles[t].y1; ++y)
+            for (int x = tiles[t].x0; x < tiles[t].x1; ++x) {
+                const size_t q = (size_t)y * (size_t)width + (size_t)x;
+                double* m = reinterpret_cast<double*>(moments + q);
+                shm::moments_update_pixel(reinterpret_cast<const double*>(film + q), m);
+                const double e2 = shm::moments_e2(m, k.mean_floor);
+                if (!shm::moments_converged(m, e2, k)) ++unconverged;
+                key = std::max(key, shm::moments_key(shm::moments_e2_float(e2)));
+            }
+        tile_error_out[t].unconverged = unconverged;
+        tile_error_out[t].max_e2 = shm::moments_key_value(key);
+    }
+    return SHM_OK;
+}
+
+extern "C" int shm_moments_resolve(const ShmMomentsPixel* moments, uint64_t n, float floor, float* out8) {
+    if (!moments || !out8) { shm_set_last_error("moments: a null argument"); return SHM_ERR_INVALID_ARGUMENT; }
+    if (!(floor > 0.0f) || shm::is_inf(floor)) { shm_set_last_error("adaptive: floor is NaN, infinite or not above 0"); return SHM_ERR_INVALID_ARGUMENT; }
+    for (uint64_t q = 0; q < n; ++q) shm::moments_resolve_pixel(reinterpret_cast<const double*>(moments + q), floor, out8 + 8 * q);
     return SHM_OK;
 }

@@ -1,7 +1,9 @@
-// k_denoise.hip — the denoiser's four kernels and its device entry points (include/shimmer_hip.h, shm_denoise_*). The arithmetic is shm/denoise.h,
+// k_denoise.hip — the denoiser's five kernels and its device entry points (include/shimmer_hip.h, shm_denoise_*). The arithmetic is shm/denoise.h,
 // which host/host_mirror.cpp compiles a second time for the CPU twin; the kernels here only say which pixel a lane owns and where its taps come from.
 //   k_denoise_prepare    one pixel per lane: the film's and the G-buffer's double sums -> planes A (e.rgb, var), B (n.xyz, l), C (p.xyz, valid), D (a_eff.rgb)
 //   k_denoise_variance   one pixel per lane: the 7x7 moments of l -> A.w
+//   k_denoise_variance_measured   one pixel per lane, after k_denoise_variance where ShmDenoiseParams::variance_source asks: the moments pass's measured variance over A.w
+//                        at every valid pixel whose record holds two batches or more (DESIGN.md section 4k's v)
 //   k_denoise_atrous     one launch per iteration, A -> A' (ping-pong): a workgroup owns a 32x8 block of ONE of the step^2 decimated sub-lattices, on which the a-trous
 //                        filter is a dense 5x5 one. It stages the block's 36x12 halo tile of A, B and C into LDS (20.25 KiB) and every tap is a 16-byte LDS read — the
 //                        same body at every step. (The plain gather — adjacent pixels per block, every tap from global memory — was built and measured against it and
@@ -20,6 +22,7 @@ constexpr int DN_TX = 32, DN_TY = 8, DN_BLOCK = DN_TX * DN_TY;
 constexpr int DN_HALO = 2, DN_PITCH = DN_TX + 2 * DN_HALO, DN_ROWS = DN_TY + 2 * DN_HALO;
 static_assert(sizeof(ShmFilmPixel) == 4 * sizeof(double) && sizeof(ShmGBufferPixel) == 16 * sizeof(double), "the pixel functions of shm/denoise.h index the sums as doubles");
 static_assert(sizeof(DnF4) == sizeof(float4), "a plane entry is a float4");
+static_assert(sizeof(ShmMomentsPixel) == MOMENTS_DOUBLES * sizeof(double), "denoise_measured_variance indexes the record as doubles");
 
 __global__ void __launch_bounds__(DN_BLOCK) k_denoise_prepare(const ShmFilmPixel* film, const ShmGBufferPixel* gbuffer, uint32_t n, float white_r, float white_g, float white_b,
                                                               DenoiseConfig k, DnF4* A, DnF4* B, DnF4* C, DnF4* D) {
@@ -37,6 +40,14 @@ __global__ void __launch_bounds__(DN_BLOCK) k_denoise_variance(DnF4* A, const Dn
     const DenoiseGlobalTaps taps{nullptr, B, C, x, y, width, height, 1, false};
     // (the pass reads planes B and C only — DenoiseGlobalTaps::guides — and writes A.w alone)
     A[(size_t)y * (size_t)width + (size_t)x].w = denoise_variance_pixel(taps, k);
+}
+
+__global__ void __launch_bounds__(DN_BLOCK) k_denoise_variance_measured(DnF4* A, const DnF4* C, const DnF4* D, const ShmMomentsPixel* moments, uint32_t n) {
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n || C[q].w == 0.0f) return;
+    const double* m = reinterpret_cast<const double*>(moments + q);
+    if (!(m[11] >= 2.0)) return;  // fewer than two batches: the spatial estimate stays
+    A[q].w = denoise_measured_variance(m, D[q]);
 }
 
 // The LDS tile of one sub-lattice block as denoise_atrous_pixel's window: tap (i, j) is the tile entry (i, j) away; an entry outside the film was staged with valid = 0.
@@ -113,6 +124,9 @@ int shm_denoise_device(ShmScene* s, const ShmDenoiseParams* params, double* ms_o
     if (!s || !params) { shm_err() = "denoise: no scene or no parameters"; return SHM_ERR_INVALID_ARGUMENT; }
     const DenoiseConfig k{params->iterations, params->demodulate, params->sigma_luminance, params->sigma_normal, params->sigma_plane, params->albedo_floor};
     if (const char* why = denoise_params_error(k)) { shm_err() = why; return SHM_ERR_INVALID_ARGUMENT; }
+    if (params->variance_source > SHM_DENOISE_VARIANCE_MEASURED) { shm_err() = "denoise: unknown variance_source"; return SHM_ERR_INVALID_ARGUMENT; }
+    const bool measured = params->variance_source == SHM_DENOISE_VARIANCE_MEASURED;
+    if (measured && !s->d_moments) { shm_err() = "denoise: variance_source is measured, but the scene has no moments (no shm_moments_clear yet)"; return SHM_ERR_INVALID_ARGUMENT; }
     if (!s->d_gbuffer || !s->gbuffer_filled) {
         shm_err() = "denoise: the scene's G-buffer is empty (no shm_gbuffer_render_wave / shm_render_gbuffer since the scene was created or the G-buffer cleared)";
         return SHM_ERR_INVALID_ARGUMENT;
@@ -147,6 +161,10 @@ int shm_denoise_device(ShmScene* s, const ShmDenoiseParams* params, double* ms_o
         if (!is_inf(k.sigma_luminance)) {  // (nothing reads the variance otherwise but the next iteration's own)
             hipLaunchKernelGGL(k_denoise_variance, tiles, block, 0, s->stream, A[0], B, C, width, height, k);
             LAUNCH_TRY("k_denoise_variance");
+            if (measured) {
+                hipLaunchKernelGGL(k_denoise_variance_measured, linear, block, 0, s->stream, A[0], C, D, s->d_moments, (uint32_t)n);
+                LAUNCH_TRY("k_denoise_variance_measured");
+            }
         }
         for (uint32_t i = 0; i < k.iterations; ++i, cur ^= 1) {
             const int step = 1 << i;

@@ -12,6 +12,7 @@
 // pixel is skipped: nothing is added for it.
 #pragma once
 #include "fp.h"
+#include "moments.h"  // the measured variance (denoise_measured_variance, at the end)
 
 namespace shm {
 
@@ -217,6 +218,22 @@ SHM_HD void denoise_finish_pixel(const double* film, bool filtered, const DnF4& 
     if (filtered) { c[0] = A.x * D.x; c[1] = A.y * D.y; c[2] = A.z * D.z; }
     out[0] = (double)c[0]; out[1] = (double)c[1]; out[2] = (double)c[2];
     out[3] = film[3] == 0.0 ? 0.0 : 1.0;
+}
+
+// The initial variance of a valid pixel from the moments pass's record instead of the spatial estimate (ShmDenoiseParams::variance_source = measured; the caller asks
+// for B >= 2). m: a ShmMomentsPixel's twelve doubles (shm/moments.h); D: the pixel's a_eff. With sd_c = sqrt(v_c) the standard deviation of channel c of the pixel's
+// mean (0 where v_c is not above 0), the standard deviation of l = mean_c(c_c / a_c) is taken as mean_c(sd_c / a_c) — a path's three channels move together — and the
+// variance is its square.
+SHM_HD Float denoise_measured_variance(const double* m, const DnF4& D) {
+    double v[3], s2[3];
+    moments_variances(m, v, s2);
+    Float sd[3];
+    for (int c = 0; c < 3; ++c) {
+        const Float vc = (Float)v[c];
+        sd[c] = vc > 0.0f ? sqrt(vc) : 0.0f;
+    }
+    const Float sd_l = ((sd[0] / D.x + sd[1] / D.y) + sd[2] / D.z) / 3.0f;
+    return sd_l * sd_l;
 }
 
 }  // namespace shm

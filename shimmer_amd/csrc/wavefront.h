@@ -420,6 +420,10 @@ struct ShmScene {
     float4* d_denoise = nullptr;           // the denoiser's planes (k_denoise.hip: five float4 per pixel) and, behind them, its result — made by the first shm_denoise_device
     ShmFilmPixel* d_denoised = nullptr;
     bool denoised = false;                 // d_denoised holds a result
+    ShmMomentsPixel* d_moments = nullptr;  // the moments pass's records (k_moments.hip), pixel_bounds-sized: made by the first shm_moments_clear, null in a scene that never asks
+    ShmTile* d_moments_tiles = nullptr;    // that pass's own tile list and its per-tile result, one allocation in `allocs`, regrown on demand
+    ShmTileError* d_tile_error = nullptr;
+    uint32_t moments_tiles_capacity = 0;
 };
 // dist.hip: releases s->dist (RCCL communicator included); called by shm_scene_destroy
 __attribute__((visibility("hidden"))) void wf_dist_release(ShmScene* s);

@@ -216,6 +216,33 @@ class Renderer:
         abi.check(self.lib, self.lib.shm_denoise(self.handle, C.byref(d), out.ctypes.data_as(C.c_void_p), C.byref(ms)), "shm_denoise")
         return (out, float(ms.value)) if return_ms else out
 
+    # ---- adaptive sampling (include/shimmer_hip.h "adaptive sampling") ----
+    def moments_clear(self):
+        """shm_moments_clear: zero records that count from the device film as it stands."""
+        abi.check(self.lib, self.lib.shm_moments_clear(self.handle), "shm_moments_clear")
+
+    def moments_update(self, aparams, tile_indices=None, tiles=None):
+        """shm_moments_update: one batch — the film since the last call — into the records of the tiles' pixels. Returns the tiles' TILE_ERROR_DTYPE array.
+        tiles: an abi.ShmTile array of the caller's own instead of indices into the renderer's 8x8 tiling."""
+        t, n = (tiles, len(tiles)) if tiles is not None else self._tile_subset(tile_indices)
+        out = np.zeros(n, dtype=TILE_ERROR_DTYPE)
+        abi.check(self.lib, self.lib.shm_moments_update(self.handle, t, n, C.byref(aparams), out.ctypes.data_as(C.c_void_p)), "shm_moments_update")
+        return out
+
+    def read_moments(self):
+        m = np.zeros((self.height, self.width), dtype=MOMENTS_DTYPE)
+        abi.check(self.lib, self.lib.shm_moments_read(self.handle, m.ctypes.data_as(C.c_void_p)), "shm_moments_read")
+        return m
+
+    def render_adaptive(self, params, aparams, tile_indices=None):
+        """shm_render_adaptive into the device film: params.samples_per_pixel is the cap. Returns (the samples each tile received as uint32, the stats dict)."""
+        tiles, n = self._tile_subset(tile_indices)
+        stats = abi.ShmStats()
+        spp = np.zeros(n, np.uint32)
+        abi.check(self.lib, self.lib.shm_render_adaptive(self.handle, C.byref(params), tiles, n, C.byref(aparams), spp.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(stats)),
+                  "shm_render_adaptive")
+        return spp, stats.as_dict()
+
     def trace(self, rays, any_hit=False):
         """Bring-up entry: rays = structured/float32 array (n, 8) [o,d,t_max,pad]. Returns hits (n,8 view) or occluded bytes."""
         rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
@@ -268,19 +295,21 @@ def render_gbuffer(lib, desc, params, device=0, space=abi.SHM_GBUFFER_SPACE_REND
 
 
 def make_denoise_params(lib, **overrides):
-    """shm_denoise_default_params, with any of iterations, demodulate, sigma_luminance, sigma_normal, sigma_plane, albedo_floor set by keyword."""
+    """shm_denoise_default_params, with any of iterations, demodulate, sigma_luminance, sigma_normal, sigma_plane, albedo_floor, variance_source set by keyword
+    (variance_source: abi.SHM_DENOISE_VARIANCE_SPATIAL, the default, or abi.SHM_DENOISE_VARIANCE_MEASURED: the moments pass's variance)."""
     d = abi.ShmDenoiseParams()
     abi.check(lib, lib.shm_denoise_default_params(C.byref(d)), "shm_denoise_default_params")
     for k, v in overrides.items():
-        if k not in ("iterations", "demodulate", "sigma_luminance", "sigma_normal", "sigma_plane", "albedo_floor"):
+        if k not in ("iterations", "demodulate", "sigma_luminance", "sigma_normal", "sigma_plane", "albedo_floor", "variance_source"):
             raise TypeError(f"make_denoise_params: no parameter {k!r}")
         setattr(d, k, v)
     return d
 
 
-def denoise_host(lib, film, gbuffer, white, dparams=None):
+def denoise_host(lib, film, gbuffer, white, dparams=None, moments=None):
     """shm_denoise_host, the denoiser's CPU twin: (H, W) FILM_DTYPE and GBUFFER_DTYPE arrays (Renderer.read_film / read_gbuffer, or made in numpy) and gbuffer_white's
-    W into the FILM_DTYPE result Renderer.denoise gives for the same inputs, bit for bit. No GPU needed."""
+    W into the FILM_DTYPE result Renderer.denoise gives for the same inputs, bit for bit. No GPU needed. moments: a (H, W) MOMENTS_DTYPE array (Renderer.read_moments)
+    for variance_source = measured — shm_denoise_host_moments."""
     f = np.ascontiguousarray(film, dtype=FILM_DTYPE)
     g = np.ascontiguousarray(gbuffer, dtype=GBUFFER_DTYPE)
     if f.ndim != 2 or g.shape != f.shape:
@@ -288,6 +317,13 @@ def denoise_host(lib, film, gbuffer, white, dparams=None):
     d = dparams if dparams is not None else make_denoise_params(lib)
     w = (C.c_double * 3)(*[float(x) for x in white])
     out = np.zeros(f.shape, dtype=FILM_DTYPE)
+    if moments is not None:
+        m = np.ascontiguousarray(moments, dtype=MOMENTS_DTYPE)
+        if m.shape != f.shape:
+            raise ValueError("denoise_host: moments must have the film's shape")
+        abi.check(lib, lib.shm_denoise_host_moments(f.ctypes.data_as(C.c_void_p), g.ctypes.data_as(C.c_void_p), m.ctypes.data_as(C.c_void_p), f.shape[1], f.shape[0], w,
+                                                    C.byref(d), out.ctypes.data_as(C.c_void_p)), "shm_denoise_host_moments")
+        return out
     abi.check(lib, lib.shm_denoise_host(f.ctypes.data_as(C.c_void_p), g.ctypes.data_as(C.c_void_p), f.shape[1], f.shape[0], w, C.byref(d), out.ctypes.data_as(C.c_void_p)),
               "shm_denoise_host")
     return out
@@ -306,6 +342,72 @@ def render_denoised(lib, desc, params, dparams=None, device=0, matrix=None, rend
             r.close()
     return {"film": film, "denoised": den, "noisy": film_get_image(lib, film, matrix), "image": film_get_image(lib, den, matrix), "gbuffer": g, "stats": stats,
             "denoise_ms": ms}
+
+
+MOMENTS_DTYPE = np.dtype([("prev", "<f8", (4,)), ("mean", "<f8", (3,)), ("m2", "<f8", (3,)), ("weight", "<f8"), ("batches", "<f8")])
+TILE_ERROR_DTYPE = np.dtype([("unconverged", "<u4"), ("max_e2", "<f4")])
+assert MOMENTS_DTYPE.itemsize == C.sizeof(abi.ShmMomentsPixel) and TILE_ERROR_DTYPE.itemsize == C.sizeof(abi.ShmTileError)
+
+
+def make_adaptive_params(lib, **overrides):
+    """shm_adaptive_default_params (min_spp 16, batch_spp 4, threshold 0.05, floor 0.01), with any of the four set by keyword."""
+    a = abi.ShmAdaptiveParams()
+    abi.check(lib, lib.shm_adaptive_default_params(C.byref(a)), "shm_adaptive_default_params")
+    for k, v in overrides.items():
+        if k not in ("min_spp", "batch_spp", "threshold", "floor"):
+            raise TypeError(f"make_adaptive_params: no parameter {k!r}")
+        setattr(a, k, v)
+    return a
+
+
+def make_tiles(boxes):
+    """An abi.ShmTile array from (x0, y0, x1, y1) boxes: a tiling of the caller's own for Renderer.moments_update / moments_update_host."""
+    t = (abi.ShmTile * max(1, len(boxes)))()
+    for i, b in enumerate(boxes):
+        t[i] = abi.ShmTile(*[int(v) for v in b])
+    return t
+
+
+def moments_update_host(lib, film, moments, tiles, aparams, n_tiles=None):
+    """shm_moments_update_host, the moments pass's CPU twin: one batch from a (H, W) FILM_DTYPE array into a (H, W) MOMENTS_DTYPE array, IN PLACE (it must be
+    C-contiguous), over an abi.ShmTile array in film coordinates. Returns the tiles' TILE_ERROR_DTYPE array — what Renderer.moments_update gives, bit for bit."""
+    f = np.ascontiguousarray(film, dtype=FILM_DTYPE)
+    if moments.dtype != MOMENTS_DTYPE or not moments.flags.c_contiguous or f.ndim != 2 or moments.shape != f.shape:
+        raise ValueError("moments_update_host: film and moments must be C-contiguous (height, width) arrays of one shape")
+    n = len(tiles) if n_tiles is None else n_tiles
+    out = np.zeros(n, dtype=TILE_ERROR_DTYPE)
+    abi.check(lib, lib.shm_moments_update_host(f.ctypes.data_as(C.c_void_p), moments.ctypes.data_as(C.c_void_p), f.shape[1], f.shape[0], tiles, n, C.byref(aparams),
+                                               out.ctypes.data_as(C.c_void_p)), "shm_moments_update_host")
+    return out
+
+
+def moments_resolve(lib, moments, floor=0.01):
+    """shm_moments_resolve: the records as a dict of float32 images — "v" (variance of the pixel's mean) and "s2" (per-sample variance), (.., 3) in SENSOR RGB (an
+    output matrix cannot be applied to variances without covariances), "batches" and "e2" (the squared relative error the adaptive render stops by)."""
+    m = np.ascontiguousarray(moments, dtype=MOMENTS_DTYPE)
+    out = np.empty(m.shape + (8,), np.float32)
+    abi.check(lib, lib.shm_moments_resolve(m.ctypes.data_as(C.c_void_p), m.size, float(floor), out.ctypes.data_as(abi.c_float_p)), "shm_moments_resolve")
+    return {"v": out[..., 0:3], "s2": out[..., 3:6], "batches": out[..., 6], "e2": out[..., 7]}
+
+
+def render_adaptive(lib, desc, params, aparams=None, device=0, renderer=None):
+    """An adaptive render (shm_render_adaptive; params.samples_per_pixel is the cap) of a scene created for the call or of `renderer`. Returns
+    (film as FILM_DTYPE, tile_spp as uint32 per 8x8 tile in row-major tile order, moments as MOMENTS_DTYPE, stats)."""
+    r = renderer or Renderer(lib, desc, device=device)
+    try:
+        tile_spp, stats = r.render_adaptive(params, aparams if aparams is not None else make_adaptive_params(lib))
+        film, moments = r.read_film(), r.read_moments()
+    finally:
+        if renderer is None:
+            r.close()
+    return film, tile_spp, moments, stats
+
+
+def tile_spp_image(tile_spp, width, height, tile=8):
+    """The per-pixel sample count of an adaptive render: tile_spp (row-major over the renderer's `tile` x `tile` tiling) spread over its pixels, float32 (H, W)."""
+    tw, th = (width + tile - 1) // tile, (height + tile - 1) // tile
+    grid = np.asarray(tile_spp, np.float32).reshape(th, tw)
+    return np.repeat(np.repeat(grid, tile, axis=0), tile, axis=1)[:height, :width]
 
 
 def film_tensor(renderer, device=None):
