@@ -134,10 +134,8 @@ int shm_denoise_device(ShmScene* s, const ShmDenoiseParams* params, double* ms_o
     HIP_TRY(hipSetDevice(s->device));
     const size_t n = s->n_film_pixels;
     if (!s->d_denoise) {  // planes A, A', B, C, D, then the result: one allocation, the scene's to free
-        void* d = nullptr;
-        HIP_TRY(hipMalloc(&d, std::max<size_t>(n, 1) * (5 * sizeof(float4) + sizeof(ShmFilmPixel))));
-        s->allocs.push_back(d);
-        s->d_denoise = reinterpret_cast<float4*>(d);
+        int rc;
+        if ((rc = wf_scene_alloc(s, std::max<size_t>(n, 1) * (5 * sizeof(float4) + sizeof(ShmFilmPixel)), (void**)&s->d_denoise)) != SHM_OK) return rc;
         s->d_denoised = reinterpret_cast<ShmFilmPixel*>(s->d_denoise + 5 * std::max<size_t>(n, 1));
     }
     const int32_t* pb = s->flat.film.pixel_bounds;
@@ -192,10 +190,7 @@ int shm_denoise_device(ShmScene* s, const ShmDenoiseParams* params, double* ms_o
 int shm_denoise_read(ShmScene* s, ShmFilmPixel* out) {
     if (!s || !out) return SHM_ERR_INVALID_ARGUMENT;
     if (!s->denoised) { shm_err() = "denoise: nothing to read before shm_denoise_device"; return SHM_ERR_INVALID_ARGUMENT; }
-    HIP_TRY(hipSetDevice(s->device));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    HIP_TRY(hipMemcpy(out, s->d_denoised, s->n_film_pixels * sizeof(ShmFilmPixel), hipMemcpyDeviceToHost));
-    return SHM_OK;
+    return wf_read_pixels(s, s->d_denoised, sizeof(ShmFilmPixel), out);
 }
 
 int shm_denoise(ShmScene* s, const ShmDenoiseParams* params, ShmFilmPixel* out, double* ms_out) {

@@ -72,13 +72,11 @@ MomentsConfig moments_config(const ShmAdaptiveParams& p) { return MomentsConfig{
 int ensure_tile_buffers(ShmScene* s, uint32_t n_tiles) {
     if (s->moments_tiles_capacity >= n_tiles) return SHM_OK;
     if (s->d_moments_tiles) {
-        hipFree(s->d_moments_tiles);
-        s->allocs.erase(std::find(s->allocs.begin(), s->allocs.end(), (void*)s->d_moments_tiles));
+        wf_scene_free(s, s->d_moments_tiles);
         s->d_moments_tiles = nullptr; s->d_tile_error = nullptr; s->moments_tiles_capacity = 0;
     }
     void* d = nullptr;
-    if (hipMalloc(&d, (size_t)n_tiles * (sizeof(ShmTile) + sizeof(ShmTileError))) != hipSuccess) { (void)hipGetLastError(); shm_err() = "hipMalloc of the moments pass's tile list failed"; return SHM_ERR_OUT_OF_MEMORY; }
-    s->allocs.push_back(d);
+    if (wf_scene_alloc(s, (size_t)n_tiles * (sizeof(ShmTile) + sizeof(ShmTileError)), &d) != SHM_OK) { shm_err() = "hipMalloc of the moments pass's tile list failed"; return SHM_ERR_OUT_OF_MEMORY; }
     s->d_moments_tiles = reinterpret_cast<ShmTile*>(d);
     s->d_tile_error = reinterpret_cast<ShmTileError*>(s->d_moments_tiles + n_tiles);
     s->moments_tiles_capacity = n_tiles;
@@ -103,12 +101,8 @@ int shm_moments_clear(ShmScene* s) {
     if (!s) { shm_err() = "moments: no scene"; return SHM_ERR_INVALID_ARGUMENT; }
     HIP_TRY(hipSetDevice(s->device));
     const size_t n = s->n_film_pixels;
-    if (!s->d_moments) {
-        void* d = nullptr;
-        HIP_TRY(hipMalloc(&d, std::max<size_t>(n, 1) * sizeof(ShmMomentsPixel)));
-        s->allocs.push_back(d);
-        s->d_moments = reinterpret_cast<ShmMomentsPixel*>(d);
-    }
+    int rc;
+    if (!s->d_moments && (rc = wf_scene_alloc(s, std::max<size_t>(n, 1) * sizeof(ShmMomentsPixel), (void**)&s->d_moments)) != SHM_OK) return rc;
     hipLaunchKernelGGL(k_moments_clear, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, s->d_film, s->d_moments, (uint32_t)n);
     LAUNCH_TRY("k_moments_clear");
     HIP_TRY(hipStreamSynchronize(s->stream));
@@ -137,10 +131,7 @@ int shm_moments_update(ShmScene* s, const ShmTile* tiles, uint32_t n_tiles, cons
 int shm_moments_read(ShmScene* s, ShmMomentsPixel* out) {
     if (!s || !out) { shm_err() = "moments: a null argument"; return SHM_ERR_INVALID_ARGUMENT; }
     if (!s->d_moments) { shm_err() = "moments: no shm_moments_clear on this scene yet"; return SHM_ERR_INVALID_ARGUMENT; }
-    HIP_TRY(hipSetDevice(s->device));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    HIP_TRY(hipMemcpy(out, s->d_moments, s->n_film_pixels * sizeof(ShmMomentsPixel), hipMemcpyDeviceToHost));
-    return SHM_OK;
+    return wf_read_pixels(s, s->d_moments, sizeof(ShmMomentsPixel), out);
 }
 
 int shm_render_adaptive(ShmScene* s, const ShmRenderParams* params, const ShmTile* tiles, uint32_t n_tiles, const ShmAdaptiveParams* ap, uint32_t* tile_spp_out,

@@ -15,6 +15,7 @@
 // sizes stay on the device (persistent / grid-stride kernels read them), so a whole render (all fused spp-waves)
 // is enqueued on one HIP stream without host round trips. There is no CPU fallback anywhere in this file.
 #include <chrono>
+#include <functional>
 #include "wavefront.h"
 #include "host/integrator.hpp"
 
@@ -171,11 +172,7 @@ int dev_upload(ShmScene* s, const std::vector<T>& v, const T** out) {
 }
 template <typename T>
 int dev_alloc(ShmScene* s, size_t n, T** out) {
-    void* d = nullptr;
-    HIP_TRY(hipMalloc(&d, std::max<size_t>(n, 1) * sizeof(T)));
-    s->allocs.push_back(d);
-    *out = reinterpret_cast<T*>(d);
-    return SHM_OK;
+    return wf_scene_alloc(s, std::max<size_t>(n, 1) * sizeof(T), reinterpret_cast<void**>(out));
 }
 
 // Path workspace sized to the work: up to SHM_BATCH_PATHS (default 512 Mi paths: 148 GB of the 288 GB for a lean scene, bounded by 80 % of
@@ -268,6 +265,23 @@ static uint64_t workspace_cap(const ShmScene* s, bool need_staged) {
 }
 
 }  // namespace
+int wf_scene_alloc(ShmScene* s, size_t bytes, void** out) {
+    void* d = nullptr;
+    HIP_TRY(hipMalloc(&d, bytes));
+    s->allocs.push_back(d);
+    *out = d;
+    return SHM_OK;
+}
+void wf_scene_free(ShmScene* s, void* d) {
+    hipFree(d);
+    s->allocs.erase(std::find(s->allocs.begin(), s->allocs.end(), d));
+}
+int wf_read_pixels(ShmScene* s, const void* d_image, size_t bytes_per_pixel, void* out) {
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipMemcpy(out, d_image, s->n_film_pixels * bytes_per_pixel, hipMemcpyDeviceToHost));
+    return SHM_OK;
+}
 // Which of the small scene tables a kernel with `budget` bytes of LDS to spare stages there (wavefront.h, stage_scene_tables): greedily, in the enum's order.
 LdsTables wf_lds_tables(const ShmScene* s, uint32_t budget) {
     LdsTables t = {};
@@ -501,10 +515,7 @@ int shm_film_clear(ShmScene* s) {
 
 int shm_film_read(ShmScene* s, ShmFilmPixel* film_out) {
     if (!s || !film_out) return SHM_ERR_INVALID_ARGUMENT;
-    HIP_TRY(hipSetDevice(s->device));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    HIP_TRY(hipMemcpy(film_out, s->d_film, s->n_film_pixels * sizeof(ShmFilmPixel), hipMemcpyDeviceToHost));
-    return SHM_OK;
+    return wf_read_pixels(s, s->d_film, sizeof(ShmFilmPixel), film_out);
 }
 
 int shm_film_device_ptr(ShmScene* s, void** ptr_out, uint64_t* bytes_out) {
@@ -514,7 +525,7 @@ int shm_film_device_ptr(ShmScene* s, void** ptr_out, uint64_t* bytes_out) {
     return SHM_OK;
 }
 
-// ---- shm_render_wave, in parts ----
+// ---- a wave call (shm_render_wave, shm_gbuffer_render_wave), in parts ----
 // the tiles of a call: inside the film, disjoint; expanded into the pixel list on the device (s->d_pixels)
 static int build_pixel_list(ShmScene* s, const ShmTile* tiles, uint32_t n_tiles, uint64_t* n_pixels_out) {
     const int32_t* pb = s->flat.film.pixel_bounds;
@@ -589,20 +600,72 @@ static int ensure_randomwalk_records(ShmScene* s, int max_depth, uint32_t* cap_e
     }
     return SHM_OK;
 }
-// One shm_render_wave call: what its batches share
+// One wave call — shm_render_wave's or shm_gbuffer_render_wave's: what its batches share. wave_begin fills it, wave_run walks the batches, add_wave_stats reads it out.
 struct Render {
     ShmScene* s;
     const ShmRenderParams* params;
-    RenderPlan plan;
-    ShadeKernels k;
-    int sample_begin, n_samples;
-    uint32_t cap_eff;  // paths per batch
+    RenderPlan plan;      // of the parameters the entry point plans with (the G-buffer pass: gbuffer_plan_params)
+    ShadeKernels k = {};  // the film render's shading launchers (select_kernels)
+    int sample_begin = 0, n_samples = 0;
+    uint64_t n_pixels = 0;
+    uint32_t cap_eff = 0;  // paths per batch
     EventPool ev;
+    hipEvent_t e_begin = nullptr, e_end = nullptr;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_closest, ev_any, ev_shade;
     bool used_overlap = false;
-    Render(ShmScene* sc, const ShmRenderParams* prm, const RenderPlan& p, int begin, int n, uint32_t cap)
-        : s(sc), params(prm), plan(p), k(select_kernels(p)), sample_begin(begin), n_samples(n), cap_eff(cap), ev{sc} {}
+    Render(ShmScene* sc, const ShmRenderParams* prm) : s(sc), params(prm), ev{sc} {}
 };
+// (apart from wave_begin: an entry point's own argument checks stand between the two, and the order in which a call's errors are reported is part of the interface)
+static bool wave_args_ok(const ShmScene* s, const ShmRenderParams* params, const ShmTile* tiles, uint32_t n_tiles, int32_t sample_begin, int32_t sample_end) {
+    if (s && params && tiles && n_tiles != 0 && sample_end > sample_begin) return true;
+    g_err = "invalid render arguments";
+    return false;
+}
+// The head of a wave call, behind the entry point's own argument checks: the sampler's checks, the pixel list, the per-render state on the scene, the plan of
+// `plan_params` and the workspace it asks for, of at most `max_batch` paths per batch
+static int wave_begin(Render& r, const ShmRenderParams& plan_params, const ShmTile* tiles, uint32_t n_tiles, int32_t sample_begin, int32_t sample_end, uint64_t max_batch) {
+    ShmScene* s = r.s;
+    const ShmRenderParams* params = r.params;
+    if (params->sampler > SHM_SAMPLER_ZSOBOL || params->sampler_randomization > SHM_SAMPLER_RANDOMIZE_NONE) { g_err = "unknown sampler or sampler randomization"; return SHM_ERR_INVALID_ARGUMENT; }
+    // ZSobol: the per-render constants of the stream (shm/sampling.h); its sample indices are the low log2spp bits of the Morton index
+    const uint32_t zsobol = zsobol_config(params->samples_per_pixel, s->flat.film.full_resolution[0], s->flat.film.full_resolution[1],
+                                          params->sampler_randomization == SHM_SAMPLER_RANDOMIZE_NONE);
+    if (params->sampler == SHM_SAMPLER_ZSOBOL && (sample_begin < 0 || (int64_t)sample_end > (int64_t)1 << zsobol_log2spp(zsobol))) {
+        g_err = "zsobol: sample index outside [0, 2^ceil(log2(samples_per_pixel)))";
+        return SHM_ERR_INVALID_ARGUMENT;
+    }
+    HIP_TRY(hipSetDevice(s->device));
+    int rc;
+    if ((rc = build_pixel_list(s, tiles, n_tiles, &r.n_pixels)) != SHM_OK) return rc;
+    s->dsv.quirks_off = params->disable_reference_quirks ? 1u : 0u;  // SHM_REFERENCE_QUIRKS: every kernel of this wave takes s->dsv by value
+    s->dsv.zsobol = zsobol;  // (read only by the ZSobol kernels: sampler_word)
+    r.plan = render_plan(s->plan, plan_params);
+    r.sample_begin = sample_begin;
+    r.n_samples = sample_end - sample_begin;
+    const uint64_t n_paths = r.n_pixels * (uint64_t)r.n_samples;
+    if ((rc = ensure_workspace(s, std::min(n_paths, max_batch), r.plan.route == ROUTE_STAGED)) != SHM_OK) return rc;
+    r.cap_eff = (uint32_t)std::min<uint64_t>(s->capacity, max_batch);
+    return SHM_OK;
+}
+// The batches of a wave call, `batch(pixels, n_pix)` each, between the call's two events; blocks until the stream is through
+static int wave_run(Render& r, const std::function<int(const uint32_t*, uint32_t)>& batch) {
+    ShmScene* s = r.s;
+    uint32_t pix_per_batch = r.cap_eff / (uint32_t)r.n_samples;
+    if (pix_per_batch == 0) { g_err = "spp-wave larger than the path workspace"; return SHM_ERR_INVALID_ARGUMENT; }
+    if (pix_per_batch > 64) pix_per_batch &= ~63u;  // whole 8x8 tiles per wavefront
+    r.e_begin = r.ev.get();
+    r.e_end = r.ev.get();
+    HIP_TRY(hipEventRecord(r.e_begin, s->stream));
+    int rc;
+    for (uint64_t p0 = 0; p0 < r.n_pixels; p0 += pix_per_batch) {
+        if ((rc = batch(s->d_pixels + p0, (uint32_t)std::min<uint64_t>(pix_per_batch, r.n_pixels - p0))) != SHM_OK) return rc;
+        if (r.ev.failed) { g_err = "hipEventCreate failed"; return SHM_ERR_DEVICE; }
+    }
+    HIP_TRY(hipEventRecord(r.e_end, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipGetLastError());
+    return SHM_OK;
+}
 // One path vertex for every entry of q_active[cur]: the route's kernel, or — a staged bounce — the hit half, then one scattering kernel per BxDF class the scene holds,
 // each over its own material-sorted queue
 static int shade_vertex(Render& r, const ShadeArgs& sa, int bounce, bool overlap) {
@@ -730,81 +793,71 @@ static int render_batch(Render& r, const uint32_t* pixels, uint32_t n_pix) {
     if (overlap && k3_done) hipStreamWaitEvent(s->stream, k3_done, 0);  // the film reads L
     if (p.route == ROUTE_RANDOM_WALK)
         if ((rc = wf_launch_fold_randomwalk(s, s->stream, r.cap_eff, total)) != SHM_OK) return rc;
-    if ((rc = launch_film(s, p, pixels, n_pix, r.n_samples)) != SHM_OK) return rc;
-    if (ev.failed) { g_err = "hipEventCreate failed"; return SHM_ERR_DEVICE; }
-    return SHM_OK;
+    return launch_film(s, p, pixels, n_pix, r.n_samples);  // (EventPool::failed: wave_run looks after every batch)
 }
-static int add_render_stats(Render& r, hipEvent_t e_begin, hipEvent_t e_end, ShmStats* stats) {
+// A finished wave call's counters and times, added to `stats`. The two kinds of wave differ in two places, both here:
+//   paths     the film render's K6 counts them on the device (DeviceCounters::paths); the G-buffer pass runs no K6, so its wave counts them on the host (`film` = false);
+//   ms_shade  everything that is not traversal. Only a film render overlaps K3 with K2 (Render::used_overlap) and then sums its shade launches; the G-buffer pass never
+//             does, and takes the rest of the wall time: K1 and its own two kernels.
+static int add_wave_stats(Render& r, bool film, ShmStats* stats) {
     DeviceCounters c;
     HIP_TRY(hipMemcpy(&c, r.s->d_counters, sizeof(c), hipMemcpyDeviceToHost));
-    stats->paths += c.paths;
+    stats->paths += film ? c.paths : r.n_pixels * (uint64_t)r.n_samples;
     stats->rays_closest += c.rays_closest;
     stats->rays_any += c.rays_any;
     stats->nodes_closest += c.nodes_closest;
     stats->tris_closest += c.tris_closest;
     stats->nodes_any += c.nodes_any;
     stats->tris_any += c.tris_any;
-    float ms = 0.0f;
-    hipEventElapsedTime(&ms, e_begin, e_end);
-    stats->ms_total += ms;
-    double mc = 0.0, ma = 0.0;
+    float ms = 0.0f, tot = 0.0f;
+    hipEventElapsedTime(&tot, r.e_begin, r.e_end);
+    stats->ms_total += tot;
+    double mc = 0.0, ma = 0.0, msh = 0.0;
     for (auto& p : r.ev_closest) { hipEventElapsedTime(&ms, p.first, p.second); mc += ms; DBG("closest launch %.3f ms", ms); }
     for (auto& p : r.ev_any) { hipEventElapsedTime(&ms, p.first, p.second); ma += ms; DBG("any launch %.3f ms", ms); }
-    double msh = 0.0;
     for (auto& p : r.ev_shade) { hipEventElapsedTime(&ms, p.first, p.second); msh += ms; DBG("shade launch %.3f ms", ms); }
     stats->ms_trace_closest += mc;
     stats->ms_trace_any += ma;
-    float tot = 0.0f;
-    hipEventElapsedTime(&tot, e_begin, e_end);
-    // everything that is not traversal: shade + generate + film. Without overlap that is the rest of the wall time; with K3
-    // running beside K2 the kernels' own durations add up to more than the wall time, so the shade launches are summed instead.
+    // Without overlap the rest is the wall time less the traversal; with K3 running beside K2 the kernels' own durations add up to more than the wall time, so the
+    // shade launches are summed instead.
     stats->ms_shade += r.used_overlap ? msh : (double)tot - mc - ma;
     stats->launches_closest += (uint32_t)r.ev_closest.size();
     stats->launches_any += (uint32_t)r.ev_any.size();
     return SHM_OK;
 }
+// How many samples per pixel one wave call over `tiles` may take: as many as fit the path workspace in one batch, at least 64
+static int fuse_width(const ShmScene* s, const ShmRenderParams& plan_params, const ShmTile* tiles, uint32_t n_tiles) {
+    uint64_t n_pixels = 0;
+    for (uint32_t t = 0; tiles && t < n_tiles; ++t)
+        n_pixels += (uint64_t)std::max(0, tiles[t].x1 - tiles[t].x0) * (uint64_t)std::max(0, tiles[t].y1 - tiles[t].y0);
+    const bool staged = render_plan(s->plan, plan_params).route == ROUTE_STAGED;
+    return (int)std::min<uint64_t>(std::max<uint64_t>(64, n_pixels ? workspace_cap(s, staged) / n_pixels : 64), 1u << 20);
+}
+// The G-buffer pass's camera rays are the path integrator's, whatever integrator the parameters name: its plan gives K1's coordinates, the filter weight's source and
+// the workspace a render of this scene would ask for — so that a render before or after the pass finds the workspace it left
+static ShmRenderParams gbuffer_plan_params(const ShmRenderParams& params) {
+    ShmRenderParams as_path = params;
+    as_path.integrator = SHM_INTEGRATOR_PATH;
+    as_path.force_diffuse = 0;
+    return as_path;
+}
 
 int shm_render_wave(ShmScene* s, const ShmRenderParams* params, const ShmTile* tiles, uint32_t n_tiles, int32_t sample_begin,
                     int32_t sample_end, ShmStats* stats) {
-    if (!s || !params || !tiles || n_tiles == 0 || sample_end <= sample_begin) { g_err = "invalid render arguments"; return SHM_ERR_INVALID_ARGUMENT; }
+    if (!wave_args_ok(s, params, tiles, n_tiles, sample_begin, sample_end)) return SHM_ERR_INVALID_ARGUMENT;
     if (params->max_depth < 0 || params->max_depth > 254) { g_err = "max_depth out of range"; return SHM_ERR_INVALID_ARGUMENT; }
     if (params->integrator > SHM_INTEGRATOR_RANDOM_WALK) { g_err = "unknown integrator"; return SHM_ERR_UNSUPPORTED; }
-    if (params->sampler > SHM_SAMPLER_ZSOBOL || params->sampler_randomization > SHM_SAMPLER_RANDOMIZE_NONE) { g_err = "unknown sampler or sampler randomization"; return SHM_ERR_INVALID_ARGUMENT; }
-    // ZSobol: the per-render constants of the stream (shm/sampling.h); its sample indices are the low log2spp bits of the Morton index
-    const uint32_t zsobol = zsobol_config(params->samples_per_pixel, s->flat.film.full_resolution[0], s->flat.film.full_resolution[1],
-                                          params->sampler_randomization == SHM_SAMPLER_RANDOMIZE_NONE);
-    if (params->sampler == SHM_SAMPLER_ZSOBOL && (sample_begin < 0 || (int64_t)sample_end > (int64_t)1 << zsobol_log2spp(zsobol))) {
-        g_err = "zsobol: sample index outside [0, 2^ceil(log2(samples_per_pixel)))";
-        return SHM_ERR_INVALID_ARGUMENT;
-    }
-    HIP_TRY(hipSetDevice(s->device));
+    // (the random walk's batches are capped at 16 Mi paths: 32 B per depth per path beside the path state)
+    const bool random_walk = params->integrator == SHM_INTEGRATOR_RANDOM_WALK;
+    Render r(s, params);
     int rc;
-    uint64_t n_pixels = 0;
-    if ((rc = build_pixel_list(s, tiles, n_tiles, &n_pixels)) != SHM_OK) return rc;
-    s->dsv.quirks_off = params->disable_reference_quirks ? 1u : 0u;  // SHM_REFERENCE_QUIRKS: every kernel of this render takes s->dsv by value
-    s->dsv.zsobol = zsobol;  // (read only by the ZSobol kernels: sampler_word)
-    // the plan, and the workspace it needs
-    const RenderPlan p = render_plan(s->plan, *params);
-    const int n_samples = sample_end - sample_begin;
-    const bool random_walk = p.route == ROUTE_RANDOM_WALK;  // (its batches are capped at 16 Mi paths: 32 B per depth per path beside the path state)
-    const uint64_t n_paths = n_pixels * (uint64_t)n_samples;
-    if ((rc = ensure_workspace(s, random_walk ? std::min<uint64_t>(n_paths, 1ull << 24) : n_paths, p.route == ROUTE_STAGED)) != SHM_OK) return rc;
-    uint32_t cap_eff = random_walk ? std::min<uint32_t>(s->capacity, 1u << 24) : s->capacity;
-    if (random_walk && (rc = ensure_randomwalk_records(s, params->max_depth, &cap_eff)) != SHM_OK) return rc;
-    Render r(s, params, p, sample_begin, n_samples, cap_eff);
-    if (const char* e = render_plan_error(s->plan, p)) { g_err = e; return SHM_ERR_INTERNAL; }
-    if (!kernels_complete(r.k, s->plan, p)) { g_err = "internal: the render plan calls a kernel its table cell does not hold"; return SHM_ERR_INTERNAL; }
-    uint32_t pix_per_batch = cap_eff / (uint32_t)n_samples;
-    if (pix_per_batch == 0) { g_err = "spp-wave larger than the path workspace"; return SHM_ERR_INVALID_ARGUMENT; }
-    if (pix_per_batch > 64) pix_per_batch &= ~63u;  // whole 8x8 tiles per wavefront
-    hipEvent_t e_begin = r.ev.get(), e_end = r.ev.get();
-    HIP_TRY(hipEventRecord(e_begin, s->stream));
-    for (uint64_t p0 = 0; p0 < n_pixels; p0 += pix_per_batch)
-        if ((rc = render_batch(r, s->d_pixels + p0, (uint32_t)std::min<uint64_t>(pix_per_batch, n_pixels - p0))) != SHM_OK) return rc;
-    HIP_TRY(hipEventRecord(e_end, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    HIP_TRY(hipGetLastError());
-    return stats ? add_render_stats(r, e_begin, e_end, stats) : SHM_OK;
+    if ((rc = wave_begin(r, *params, tiles, n_tiles, sample_begin, sample_end, random_walk ? 1ull << 24 : ~0ull)) != SHM_OK) return rc;
+    if (random_walk && (rc = ensure_randomwalk_records(s, params->max_depth, &r.cap_eff)) != SHM_OK) return rc;
+    r.k = select_kernels(r.plan);
+    if (const char* e = render_plan_error(s->plan, r.plan)) { g_err = e; return SHM_ERR_INTERNAL; }
+    if (!kernels_complete(r.k, s->plan, r.plan)) { g_err = "internal: the render plan calls a kernel its table cell does not hold"; return SHM_ERR_INTERNAL; }
+    rc = wave_run(r, [&](const uint32_t* pixels, uint32_t n_pix) { return render_batch(r, pixels, n_pix); });
+    return rc == SHM_OK && stats ? add_wave_stats(r, true, stats) : rc;
 }
 
 int shm_render_device(ShmScene* s, const ShmRenderParams* params, const ShmTile* tiles, uint32_t n_tiles, ShmStats* stats) {
@@ -815,12 +868,8 @@ int shm_render_device(ShmScene* s, const ShmRenderParams* params, const ShmTile*
     // reference's own maximum wave size) and as many more as fit the path workspace in one batch (a rank that owns 1/8 of
     // the tiles takes all 256 spp at once), without changing a single film sum (shm_render_wave is the one-launch-per-wave entry: tests/test_gpu_parity.py holds the two against each other).
     int spp = params->samples_per_pixel;
-    uint64_t n_pixels = 0;
-    for (uint32_t t = 0; tiles && t < n_tiles; ++t)
-        n_pixels += (uint64_t)std::max(0, tiles[t].x1 - tiles[t].x0) * (uint64_t)std::max(0, tiles[t].y1 - tiles[t].y0);
     HIP_TRY(hipSetDevice(s->device));
-    const bool staged = render_plan(s->plan, *params).route == ROUTE_STAGED;
-    const int max_fuse = (int)std::min<uint64_t>(std::max<uint64_t>(64, n_pixels ? workspace_cap(s, staged) / n_pixels : 64), 1u << 20);
+    const int max_fuse = fuse_width(s, *params, tiles, n_tiles);
     int wave_start = 0, wave_end = 1, next_wave_size = 1;
     int pend_begin = 0, pend_end = 0;
     while (wave_start < spp) {
@@ -858,7 +907,8 @@ int shm_render(ShmScene* s, const ShmRenderParams* params, const ShmTile* tiles,
     return SHM_OK;
 }
 
-// ---- the G-buffer pass: K1 as a render's, the scene's own closest-hit launch, then k_gbuffer.hip's two kernels ----
+// ---- the G-buffer pass: a wave call (wave_begin / wave_run, above) whose batch is K1 as a render's, the scene's own closest-hit launch, then
+//      k_gbuffer.hip's two kernels ----
 // the device G-buffer, pixel_bounds-sized and zeroed: made by the first call that needs it (shm_scene_destroy frees it with the scene's other allocations)
 static int ensure_gbuffer(ShmScene* s) {
     if (s->d_gbuffer) return SHM_OK;
@@ -884,84 +934,36 @@ int shm_gbuffer_read(ShmScene* s, ShmGBufferPixel* out) {
     HIP_TRY(hipSetDevice(s->device));
     int rc;
     if ((rc = ensure_gbuffer(s)) != SHM_OK) return rc;
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    HIP_TRY(hipMemcpy(out, s->d_gbuffer, s->n_film_pixels * sizeof(ShmGBufferPixel), hipMemcpyDeviceToHost));
-    return SHM_OK;
+    return wf_read_pixels(s, s->d_gbuffer, sizeof(ShmGBufferPixel), out);
 }
 
 int shm_gbuffer_render_wave(ShmScene* s, const ShmRenderParams* params, uint32_t space, const ShmTile* tiles, uint32_t n_tiles, int32_t sample_begin, int32_t sample_end,
                             ShmStats* stats) {
-    if (!s || !params || !tiles || n_tiles == 0 || sample_end <= sample_begin) { g_err = "invalid render arguments"; return SHM_ERR_INVALID_ARGUMENT; }
+    if (!wave_args_ok(s, params, tiles, n_tiles, sample_begin, sample_end)) return SHM_ERR_INVALID_ARGUMENT;
     if (space > SHM_GBUFFER_SPACE_CAMERA) { g_err = "unknown G-buffer space"; return SHM_ERR_INVALID_ARGUMENT; }
-    if (params->sampler > SHM_SAMPLER_ZSOBOL || params->sampler_randomization > SHM_SAMPLER_RANDOMIZE_NONE) { g_err = "unknown sampler or sampler randomization"; return SHM_ERR_INVALID_ARGUMENT; }
-    const uint32_t zsobol = zsobol_config(params->samples_per_pixel, s->flat.film.full_resolution[0], s->flat.film.full_resolution[1],
-                                          params->sampler_randomization == SHM_SAMPLER_RANDOMIZE_NONE);
-    if (params->sampler == SHM_SAMPLER_ZSOBOL && (sample_begin < 0 || (int64_t)sample_end > (int64_t)1 << zsobol_log2spp(zsobol))) {
-        g_err = "zsobol: sample index outside [0, 2^ceil(log2(samples_per_pixel)))";
-        return SHM_ERR_INVALID_ARGUMENT;
-    }
-    HIP_TRY(hipSetDevice(s->device));
+    Render r(s, params);
     int rc;
-    uint64_t n_pixels = 0;
-    if ((rc = build_pixel_list(s, tiles, n_tiles, &n_pixels)) != SHM_OK) return rc;
+    if ((rc = wave_begin(r, gbuffer_plan_params(*params), tiles, n_tiles, sample_begin, sample_end, ~0ull)) != SHM_OK) return rc;
     if ((rc = ensure_gbuffer(s)) != SHM_OK) return rc;
-    s->dsv.quirks_off = params->disable_reference_quirks ? 1u : 0u;
-    s->dsv.zsobol = zsobol;
-    // the camera rays are the path integrator's, whatever integrator the parameters name: its plan gives K1's coordinates, the filter weight's source and the workspace a
-    // render of this scene would ask for — so that a render before or after this pass finds the workspace it left
-    ShmRenderParams as_path = *params;
-    as_path.integrator = SHM_INTEGRATOR_PATH;
-    as_path.force_diffuse = 0;
-    const RenderPlan p = render_plan(s->plan, as_path);
-    const int n_samples = sample_end - sample_begin;
-    const uint64_t n_paths = n_pixels * (uint64_t)n_samples;
-    if ((rc = ensure_workspace(s, n_paths, p.route == ROUTE_STAGED)) != SHM_OK) return rc;
-    uint32_t pix_per_batch = s->capacity / (uint32_t)n_samples;
-    if (pix_per_batch == 0) { g_err = "spp-wave larger than the path workspace"; return SHM_ERR_INVALID_ARGUMENT; }
-    if (pix_per_batch > 64) pix_per_batch &= ~63u;
-    EventPool ev{s};
-    hipEvent_t e_begin = ev.get(), e_end = ev.get();
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_closest;
-    HIP_TRY(hipEventRecord(e_begin, s->stream));
-    for (uint64_t p0 = 0; p0 < n_pixels; p0 += pix_per_batch) {
-        const uint32_t* pixels = s->d_pixels + p0;
-        const uint32_t n_pix = (uint32_t)std::min<uint64_t>(pix_per_batch, n_pixels - p0);
-        const uint32_t total = n_pix * (uint32_t)n_samples;
-        const bool tex = p.img_generate == IMG_TEX;
-        const GenerateArgs ga{s->stream, pixels, n_pix, sample_begin, n_samples, *params, tex, false, p.zs, p.flt};
+    const RenderPlan& p = r.plan;
+    const bool tex = p.img_generate == IMG_TEX;
+    rc = wave_run(r, [&](const uint32_t* pixels, uint32_t n_pix) {
+        int rc;
+        const GenerateArgs ga{s->stream, pixels, n_pix, r.sample_begin, r.n_samples, *params, tex, false, p.zs, p.flt};
         if ((rc = (p.spherical ? wf_generate<true> : wf_generate<false>)(s, ga)) != SHM_OK) return rc;
-        hipEvent_t a = ev.get(), b = ev.get();
+        hipEvent_t a = r.ev.get(), b = r.ev.get();
         hipEventRecord(a, s->stream);
         // (K1 left the identity queue: the batch's slots in order, 32-byte hit records)
-        const TraceArgs closest{.stream = s->stream, .n_direct = total, .rays = s->pa.ray, .hits = s->pa.hit};
+        const TraceArgs closest{.stream = s->stream, .n_direct = n_pix * (uint32_t)r.n_samples, .rays = s->pa.ray, .hits = s->pa.hit};
         if ((rc = wf_launch_trace(s, RAY_CLOSEST, false, closest)) != SHM_OK) return rc;
         hipEventRecord(b, s->stream);
-        ev_closest.push_back({a, b});
-        const GBufferArgs gb{s->stream, pixels, n_pix, n_samples, *params, tex, space, film_weight(p.flt)};
-        if ((rc = wf_launch_gbuffer(s, gb)) != SHM_OK) return rc;
-    }
-    if (ev.failed) { g_err = "hipEventCreate failed"; return SHM_ERR_DEVICE; }
-    HIP_TRY(hipEventRecord(e_end, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    HIP_TRY(hipGetLastError());
-    if (stats) {
-        DeviceCounters c;
-        HIP_TRY(hipMemcpy(&c, s->d_counters, sizeof(c), hipMemcpyDeviceToHost));
-        stats->paths += n_paths;
-        stats->rays_closest += c.rays_closest;
-        stats->nodes_closest += c.nodes_closest;
-        stats->tris_closest += c.tris_closest;
-        float ms = 0.0f;
-        hipEventElapsedTime(&ms, e_begin, e_end);
-        stats->ms_total += ms;
-        double mc = 0.0;
-        for (auto& e : ev_closest) { float m = 0.0f; hipEventElapsedTime(&m, e.first, e.second); mc += m; }
-        stats->ms_trace_closest += mc;
-        stats->ms_shade += (double)ms - mc;  // K1 and the pass's two kernels
-        stats->launches_closest += (uint32_t)ev_closest.size();
-    }
+        r.ev_closest.push_back({a, b});
+        const GBufferArgs gb{s->stream, pixels, n_pix, r.n_samples, *params, tex, space, film_weight(p.flt)};
+        return wf_launch_gbuffer(s, gb);
+    });
+    if (rc != SHM_OK) return rc;
     s->gbuffer_filled = true;
-    return SHM_OK;
+    return stats ? add_wave_stats(r, false, stats) : SHM_OK;
 }
 
 int shm_render_gbuffer(ShmScene* s, const ShmRenderParams* params, uint32_t space, const ShmTile* tiles, uint32_t n_tiles, ShmGBufferPixel* out, ShmStats* stats) {
@@ -970,14 +972,8 @@ int shm_render_gbuffer(ShmScene* s, const ShmRenderParams* params, uint32_t spac
     int rc = shm_gbuffer_clear(s);
     if (rc != SHM_OK) return rc;
     // every sample of a pixel in one launch where the workspace holds them, in waves of 64 otherwise: the sums do not depend on the split
-    uint64_t n_pixels = 0;
-    for (uint32_t t = 0; tiles && t < n_tiles; ++t) n_pixels += (uint64_t)std::max(0, tiles[t].x1 - tiles[t].x0) * (uint64_t)std::max(0, tiles[t].y1 - tiles[t].y0);
-    ShmRenderParams as_path = *params;
-    as_path.integrator = SHM_INTEGRATOR_PATH;
-    as_path.force_diffuse = 0;
-    const bool staged = render_plan(s->plan, as_path).route == ROUTE_STAGED;
     const int spp = params->samples_per_pixel;
-    const int wave = (int)std::min<uint64_t>(std::max<uint64_t>(64, n_pixels ? workspace_cap(s, staged) / n_pixels : 64), 1u << 20);
+    const int wave = fuse_width(s, gbuffer_plan_params(*params), tiles, n_tiles);
     for (int begin = 0; begin < spp; begin += wave)
         if ((rc = shm_gbuffer_render_wave(s, params, space, tiles, n_tiles, begin, std::min(spp, begin + wave), stats)) != SHM_OK) return rc;
     return shm_gbuffer_read(s, out);

@@ -399,7 +399,7 @@ struct ShmScene {
     ShmTile* d_tiles = nullptr;
     uint32_t* d_tile_offset = nullptr;
     size_t tiles_capacity = 0;
-    std::vector<uint64_t> tile_bitmap;  // host scratch of the disjointness check in shm_render_wave
+    std::vector<uint64_t> tile_bitmap;  // host scratch of the tiles' disjointness check: a wave call's (render.hip, build_pixel_list) and shm_moments_update's
     int n_cu = 256;
     TraceSide trace[shm_plan::N_RAY];
     uint32_t* d_big_leaf_n = nullptr;  // n_prims by first primitive slot, only in scenes with a leaf of >= 7 primitives (LINK_COUNT_MAX: the link word holds smaller counts)
@@ -445,6 +445,11 @@ struct EventPool {
 // ---- launchers exported by the kernel translation units (hidden visibility: library-internal) ----
 #define WF_INTERNAL __attribute__((visibility("hidden")))
 WF_INTERNAL LdsTables wf_lds_tables(const ShmScene* s, uint32_t budget);  // render.hip: which small tables fit `budget` bytes of LDS
+// render.hip: a device allocation the scene owns (ShmScene::allocs: shm_scene_destroy frees it), and one given back before that
+WF_INTERNAL int wf_scene_alloc(ShmScene* s, size_t bytes, void** out);
+WF_INTERNAL void wf_scene_free(ShmScene* s, void* d);
+// render.hip: a pixel_bounds-sized device image (the film, the G-buffer, the moments, the denoiser's result) read back once the render stream is through
+WF_INTERNAL int wf_read_pixels(ShmScene* s, const void* d_image, size_t bytes_per_pixel, void* out);
 WF_INTERNAL void wf_trace_census();  // k_trace.hip: prints the per-phase lane census of a -DK5_CENSUS development build (a no-op otherwise)
 WF_INTERNAL void wf_layered_census();  // k_scatter_layered_staged_tri.hip: the same for a -DLJ_CENSUS build of the staged LayeredBxDF kernel
 WF_INTERNAL int wf_trace_prepare(ShmScene* s);  // ShmScene::trace: grid sizes, stack spill and save areas of the scene's two traversal kernels (at scene creation)

@@ -4,6 +4,7 @@ RgbFilm::get_pixel_rgb (film.rs:720-738).  Multi-GPU: tiles are sharded across r
 no data-path collective while rendering) and the film rows are gathered by RCCL INSIDE libshimmer_hip.so (shm_render_sharded);
 the small collectives a host needs around it (barrier, reductions) are the library's too (Renderer.dist_*): no torch.
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -265,6 +266,26 @@ GBUFFER_DTYPE = np.dtype([("p", "<f8", (3,)), ("n", "<f8", (3,)), ("ns", "<f8", 
 assert GBUFFER_DTYPE.itemsize == C.sizeof(abi.ShmGBufferPixel)
 
 
+@contextlib.contextmanager
+def _renderer_for(lib, desc, device, renderer):
+    """`renderer`, left open, or a Renderer created for the with-block and closed behind it."""
+    r = renderer or Renderer(lib, desc, device=device)
+    try:
+        yield r
+    finally:
+        if renderer is None:
+            r.close()
+
+
+def _with_overrides(who, struct, names, overrides):
+    """`struct` with the fields `overrides` names set; a keyword outside `names` is a TypeError in `who`'s name."""
+    for k, v in overrides.items():
+        if k not in names:
+            raise TypeError(f"{who}: no parameter {k!r}")
+        setattr(struct, k, v)
+    return struct
+
+
 def gbuffer_white(lib, desc):
     """W_c of the scene's sensor (shm_gbuffer_white): what an albedo sum of a rho = 1 surface averages to, per channel."""
     w = (C.c_double * 3)()
@@ -285,12 +306,8 @@ def gbuffer_resolve(lib, gbuffer, white, matrix=None):
 
 def render_gbuffer(lib, desc, params, device=0, space=abi.SHM_GBUFFER_SPACE_RENDER, matrix=None, renderer=None):
     """The G-buffer pass of a scene as images: first-hit p, n, ns, uv, albedo and coverage (numpy float32), from a scene created for the call or from `renderer`."""
-    r = renderer or Renderer(lib, desc, device=device)
-    try:
+    with _renderer_for(lib, desc, device, renderer) as r:
         g, _ = r.gbuffer(params, space=space)
-    finally:
-        if renderer is None:
-            r.close()
     return gbuffer_resolve(lib, g, gbuffer_white(lib, desc), matrix)
 
 
@@ -299,11 +316,8 @@ def make_denoise_params(lib, **overrides):
     (variance_source: abi.SHM_DENOISE_VARIANCE_SPATIAL, the default, or abi.SHM_DENOISE_VARIANCE_MEASURED: the moments pass's variance)."""
     d = abi.ShmDenoiseParams()
     abi.check(lib, lib.shm_denoise_default_params(C.byref(d)), "shm_denoise_default_params")
-    for k, v in overrides.items():
-        if k not in ("iterations", "demodulate", "sigma_luminance", "sigma_normal", "sigma_plane", "albedo_floor", "variance_source"):
-            raise TypeError(f"make_denoise_params: no parameter {k!r}")
-        setattr(d, k, v)
-    return d
+    names = ("iterations", "demodulate", "sigma_luminance", "sigma_normal", "sigma_plane", "albedo_floor", "variance_source")
+    return _with_overrides("make_denoise_params", d, names, overrides)
 
 
 def denoise_host(lib, film, gbuffer, white, dparams=None, moments=None):
@@ -332,14 +346,10 @@ def denoise_host(lib, film, gbuffer, white, dparams=None, moments=None):
 def render_denoised(lib, desc, params, dparams=None, device=0, matrix=None, renderer=None):
     """Render, G-buffer pass and denoiser in one call, from a scene created for it or from `renderer`. Returns a dict: "film" and "denoised" (FILM_DTYPE), "noisy" and
     "image" (their film_get_image under `matrix`: float32 (H, W, 3)), "gbuffer" (GBUFFER_DTYPE), "stats" (the render's) and "denoise_ms" (the filter's HIP-event time)."""
-    r = renderer or Renderer(lib, desc, device=device)
-    try:
+    with _renderer_for(lib, desc, device, renderer) as r:
         film, stats = r.render(params)
         g, _ = r.gbuffer(params)
         den, ms = r.denoise(dparams, return_ms=True)
-    finally:
-        if renderer is None:
-            r.close()
     return {"film": film, "denoised": den, "noisy": film_get_image(lib, film, matrix), "image": film_get_image(lib, den, matrix), "gbuffer": g, "stats": stats,
             "denoise_ms": ms}
 
@@ -353,11 +363,7 @@ def make_adaptive_params(lib, **overrides):
     """shm_adaptive_default_params (min_spp 16, batch_spp 4, threshold 0.05, floor 0.01), with any of the four set by keyword."""
     a = abi.ShmAdaptiveParams()
     abi.check(lib, lib.shm_adaptive_default_params(C.byref(a)), "shm_adaptive_default_params")
-    for k, v in overrides.items():
-        if k not in ("min_spp", "batch_spp", "threshold", "floor"):
-            raise TypeError(f"make_adaptive_params: no parameter {k!r}")
-        setattr(a, k, v)
-    return a
+    return _with_overrides("make_adaptive_params", a, ("min_spp", "batch_spp", "threshold", "floor"), overrides)
 
 
 def make_tiles(boxes):
@@ -393,13 +399,9 @@ def moments_resolve(lib, moments, floor=0.01):
 def render_adaptive(lib, desc, params, aparams=None, device=0, renderer=None):
     """An adaptive render (shm_render_adaptive; params.samples_per_pixel is the cap) of a scene created for the call or of `renderer`. Returns
     (film as FILM_DTYPE, tile_spp as uint32 per 8x8 tile in row-major tile order, moments as MOMENTS_DTYPE, stats)."""
-    r = renderer or Renderer(lib, desc, device=device)
-    try:
+    with _renderer_for(lib, desc, device, renderer) as r:
         tile_spp, stats = r.render_adaptive(params, aparams if aparams is not None else make_adaptive_params(lib))
         film, moments = r.read_film(), r.read_moments()
-    finally:
-        if renderer is None:
-            r.close()
     return film, tile_spp, moments, stats
 
 

@@ -8,22 +8,22 @@ from shimmer_amd import abi, render, scenes
 
 W, H, SPP = 24, 20, 3  # not a multiple of the 8x8 tile; not a power of two
 
-# one row per scene class: name -> generator(lib, film)
+# one row per scene class: name -> generator(lib, width, height, film)
 SCENES = {
-    "cornell": lambda lib, film: scenes.cornell_box(lib, W, H, film=film),                                       # the lean class
-    "materials": lambda lib, film: scenes.cornell_box(lib, W, H, glass=True, mix=True, film=film),                # conductor, thin dielectric, coated diffuse, mix
-    "coated": lambda lib, film: scenes.cornell_box(lib, W, H, coated=True, glass_too=True, film=film),            # both coated BxDFs, smooth and rough dielectric
-    "textured": lambda lib, film: scenes.cornell_box(lib, W, H, textured=True, film=film),                        # HAS_TEX: ray differentials, bump and normal maps
-    "quadrics": lambda lib, film: scenes.quadric_scene(lib, width=W, height=H, film=film),
-    "patches": lambda lib, film: scenes.cornell_box(lib, W, H, patches=True, patch_skew=0.1, film=film),
-    "instanced": lambda lib, film: scenes.instanced_scene(lib, W, H, film=film),
-    "diffuse_transmission": lambda lib, film: scenes.cornell_box(lib, W, H, diffuse_transmission="sheet tall sphere", film=film),
-    "spherical": lambda lib, film: scenes.cornell_box(lib, W, H, camera={"type": "spherical", "pos": (0.0, 1.0, 0.5)}, film=film),
+    "cornell": lambda lib, w, h, film: scenes.cornell_box(lib, w, h, film=film),                                       # the lean class
+    "materials": lambda lib, w, h, film: scenes.cornell_box(lib, w, h, glass=True, mix=True, film=film),                # conductor, thin dielectric, coated diffuse, mix
+    "coated": lambda lib, w, h, film: scenes.cornell_box(lib, w, h, coated=True, glass_too=True, film=film),            # both coated BxDFs, smooth and rough dielectric
+    "textured": lambda lib, w, h, film: scenes.cornell_box(lib, w, h, textured=True, film=film),                        # HAS_TEX: ray differentials, bump and normal maps
+    "quadrics": lambda lib, w, h, film: scenes.quadric_scene(lib, width=w, height=h, film=film),
+    "patches": lambda lib, w, h, film: scenes.cornell_box(lib, w, h, patches=True, patch_skew=0.1, film=film),
+    "instanced": lambda lib, w, h, film: scenes.instanced_scene(lib, w, h, film=film),
+    "diffuse_transmission": lambda lib, w, h, film: scenes.cornell_box(lib, w, h, diffuse_transmission="sheet tall sphere", film=film),
+    "spherical": lambda lib, w, h, film: scenes.cornell_box(lib, w, h, camera={"type": "spherical", "pos": (0.0, 1.0, 0.5)}, film=film),
     # (the orthographic camera's rays stay in camera space, as the reference leaves them: a camera whose axes are the world's sees the room, through its back wall)
-    "orthographic": lambda lib, film: scenes.cornell_box(lib, W, H, camera={"type": "orthographic", "pos": (0.0, 1.0, -5.0), "look_at": (0.0, 1.0, 0.0)}, film=film),
-    "tilted": lambda lib, film: scenes.cornell_box(lib, W, H, camera={"type": "perspective", "pos": (0.8, 1.6, 3.2)}, film=film),  # camera space is a general rotation away
-    "fuzz1": lambda lib, film: scenes.random_scene(lib, 1, W, H, film=film),
-    "fuzz2": lambda lib, film: scenes.random_scene(lib, 2, W, H, film=film),
+    "orthographic": lambda lib, w, h, film: scenes.cornell_box(lib, w, h, camera={"type": "orthographic", "pos": (0.0, 1.0, -5.0), "look_at": (0.0, 1.0, 0.0)}, film=film),
+    "tilted": lambda lib, w, h, film: scenes.cornell_box(lib, w, h, camera={"type": "perspective", "pos": (0.8, 1.6, 3.2)}, film=film),  # camera space is a general rotation away
+    "fuzz1": lambda lib, w, h, film: scenes.random_scene(lib, 1, w, h, film=film),
+    "fuzz2": lambda lib, w, h, film: scenes.random_scene(lib, 2, w, h, film=film),
 }
 FILTERS = ("box", "gaussian", "mitchell")  # weight 1 / one constant / signed per sample
 SAMPLERS = ("independent", "zsobol")
@@ -42,8 +42,8 @@ def gpu_rows():
     return rows
 
 
-def make_scene(lib, name, filt="box"):
-    return SCENES[name](lib, None if filt == "box" else {"filter": filt})
+def make_scene(lib, name, filt="box", size=(W, H)):
+    return SCENES[name](lib, size[0], size[1], None if filt == "box" else {"filter": filt})
 
 
 def all_samples(pixel_bounds, spp):

@@ -65,6 +65,30 @@ def test_wave_split_and_tile_split_equal_one_call(gpu_lib, scene):
         r.close()
 
 
+@pytest.mark.parametrize("scene", ["cornell", "textured"])
+def test_a_batched_pass_equals_the_unbatched_one(gpu_lib, monkeypatch, scene):
+    """The pass's batch loop, more than once round: 40 x 36 x 3 = 4 320 paths against a workspace of 4 096 (SHM_BATCH_PATHS) are two batches, of 1 344 pixels (1 365
+    rounded down to whole 8 x 8 tiles) and of 96. Mitchell's signed weights are indexed by path slot, and a slot depends on its batch's pixel count; the textured box
+    runs the HAS_TEX K1 with its auxiliary rays."""
+    sc = gc.make_scene(gpu_lib, scene, "mitchell", size=(40, 36))
+    params = gc.params_for("zsobol")
+    monkeypatch.delenv("SHM_BATCH_PATHS", raising=False)
+    r = render.Renderer(gpu_lib, sc.desc)
+    try:
+        whole, _ = r.gbuffer(params)
+    finally:
+        r.close()
+    monkeypatch.setenv("SHM_BATCH_PATHS", "4096")
+    r = render.Renderer(gpu_lib, sc.desc)
+    try:
+        batched, stats = r.gbuffer(params)
+    finally:
+        r.close()
+    assert gc.gbuffer_as_rows(whole).any()
+    assert batched.tobytes() == whole.tobytes()
+    assert stats["paths"] == stats["rays_closest"] == 4320
+
+
 @pytest.mark.parametrize("scene", ["cornell", "coated", "textured"])
 def test_a_gbuffer_pass_leaves_the_beauty_render_alone(gpu_lib, scene):
     sc = gc.make_scene(gpu_lib, scene)
