@@ -9,6 +9,8 @@
 // WHICH entry point a scene's rays take, and at what occupancy and LDS stack depth it is compiled, is one row of host/render_plan.hpp's TRACE_SHAPES: the kernels' attributes
 // (below the body), the scene's grid and stack spill (wf_trace_prepare) and the launch (wf_launch_trace, through one table of kernel pointers) are all made from that row.
 // The body itself is k_trace.inl: k_trace_quadrics.hip holds the general rows a second time, with PBRT-v4's disk and cylinder in the sphere test, under the same rows.
+// Its loop is laid out for the COMMON iteration — no refill, a regular wave, a push to and a pop from LDS — to be straight-line code: the scalar unit is one per four
+// SIMDs, and that iteration issued as many scalar and branch instructions as vector ones (profiles/trace_straight.md: what each piece of control flow compiles to).
 #include "k_trace.inl"
 
 namespace {

@@ -135,7 +135,10 @@ __device__ __forceinline__ void trace5_body(K5_PARAMS) {
     unsigned long long c_census[32] = {0};
 #endif
 
-    bool exhausted = false;          // wave-uniform
+    // Wave-uniform, the triangle kernels' refill gate: the number of idle lanes that leads to the refill path. refill_min (1 .. 64, host/render_plan.hpp; the upper bound is
+    // what ends the loop, hence the min) until the queue is exhausted, then 64 — "every lane is idle" —, and 65 — which no count reaches — once the wave is through: the
+    // loop's condition.
+    int refill_at = refill_min < (int)WAVE ? refill_min : (int)WAVE;
     uint32_t w_next = 0, w_end = 0;  // wave-uniform private range of the queue
     uint32_t since_other = 0u;       // GEN, wave-uniform: iterations since the wave's last round of parked work
     const uint32_t n_waves = active_blocks * (TRACE_BLOCK / WAVE);
@@ -242,46 +245,59 @@ __device__ __forceinline__ void trace5_body(K5_PARAMS) {
         if (ANY && STRICT && area == 0) t_max = s2.w;  // (the outer ray's extent: apply_ray_inverse shortened the inner one)
     };
 
-    // Bounds3f::intersect_p_cached (bounding_box.rs:520-563) without its `t0 < t_max`: the t_max-independent part of the verdict, and t0
-    auto slab = [&](const float4 na, const float4 nb, Float& t0_out) -> bool {
+    // Bounds3f::intersect_p_cached (bounding_box.rs:520-563) without its `t0 < t_max`: the t_max-independent part of the verdict, and t0 — in three pieces, so that the
+    // node step can decide the wave's regularity ONCE, for both children (a test of m_irregular per child put the max3 / min3 side behind two taken branches per child and
+    // merged the two sides' verdicts with three scalar instructions per child — profiles/trace_straight.md).
+    struct SlabDist { Float x0, x1, y0, y1, z0, z1; };  // the six slab distances of one box, the far ones not yet times g
+    auto slab_dist = [&](const float4 na, const float4 nb) -> SlabDist {
+        SlabDist d;
+        d.x0 = (sel_mask(m_negx, na.x, na.w) - ro.x) * inv_dir.x;
+        d.x1 = (sel_mask(m_negx, na.w, na.x) - ro.x) * inv_dir.x;
+        d.y0 = (sel_mask(m_negy, na.y, nb.x) - ro.y) * inv_dir.y;
+        d.y1 = (sel_mask(m_negy, nb.x, na.y) - ro.y) * inv_dir.y;
+        d.z0 = (sel_mask(m_negz, na.z, nb.y) - ro.z) * inv_dir.z;
+        d.z1 = (sel_mask(m_negz, nb.y, na.z) - ro.z) * inv_dir.z;
+        return d;
+    };
+    // Every ray of the wave is regular: no slab distance is a NaN (the node bounds are finite: shm_bvh_build refuses others), and then the reference's chain —
+    // !(tx0 > ty1 || ty0 > tx1), t0 = max, t1 = min, !(t0 > tz1 || tz0 > t1), ..., t0 < t_max, t1 > 0 — is max3(near) <= min3(far * g) && min3 > 0 (&& max3 < t_max):
+    // the chain tests every near_i against every far_j of ANOTHER axis; the same-axis pairs hold by construction (near_i <= far_i before the * g; a far_i that * g
+    // pushed below near_i is negative, and then t1 > 0 fails on both sides). Two instructions and three compares instead of ten compares and four selects.
+    // One product instead of three: g > 1 and rounding is monotonic, so min3(a g, b g, c g) = min3(a, b, c) g bit for bit
+    // (the far distances are not NaNs here), and its sign is the sign of min3(a, b, c).
+    auto slab_regular = [](const SlabDist& d, Float& t0_out) -> bool {
         const Float g = 1.0f + 2.0f * gamma(3);
-        const Float tx0 = (sel_mask(m_negx, na.x, na.w) - ro.x) * inv_dir.x;
-        Float tx1 = (sel_mask(m_negx, na.w, na.x) - ro.x) * inv_dir.x;
-        const Float ty0 = (sel_mask(m_negy, na.y, nb.x) - ro.y) * inv_dir.y;
-        Float ty1 = (sel_mask(m_negy, nb.x, na.y) - ro.y) * inv_dir.y;
-        const Float tz0 = (sel_mask(m_negz, na.z, nb.y) - ro.z) * inv_dir.z;
-        Float tz1 = (sel_mask(m_negz, nb.y, na.z) - ro.z) * inv_dir.z;
-        if (m_irregular == 0ull) {
-            // Every ray of the wave is regular: no slab distance is a NaN (the node bounds are finite: shm_bvh_build refuses others), and then the reference's chain —
-            // !(tx0 > ty1 || ty0 > tx1), t0 = max, t1 = min, !(t0 > tz1 || tz0 > t1), ..., t0 < t_max, t1 > 0 — is max3(near) <= min3(far * g) && min3 > 0 (&& max3 < t_max):
-            // the chain tests every near_i against every far_j of ANOTHER axis; the same-axis pairs hold by construction (near_i <= far_i before the * g; a far_i that * g
-            // pushed below near_i is negative, and then t1 > 0 fails on both sides). Two instructions and three compares instead of ten compares and four selects.
-            // One product instead of three: g > 1 and rounding is monotonic, so min3(a g, b g, c g) = min3(a, b, c) g bit for bit
-            // (the far distances are not NaNs here), and its sign is the sign of min3(a, b, c).
-            const Float t0 = vmax3(tx0, ty0, tz0), t1 = vmin3(tx1, ty1, tz1);
-            t0_out = t0;
-            return (t0 <= t1 * g) && (t1 > 0.0f);
-        }
-        // bounding_box.rs:520-563 statement for statement (a lane may hold NaNs: comparisons with them are false, the selects keep them)
-        tx1 *= g;
-        ty1 *= g;
-        tz1 *= g;
-        Float t0 = tx0, t1 = tx1;
-        bool ok = !(t0 > ty1 || ty0 > t1);
-        if (ty0 > t0) t0 = ty0;
+        const Float t0 = vmax3(d.x0, d.y0, d.z0), t1 = vmin3(d.x1, d.y1, d.z1);
+        t0_out = t0;
+        return (t0 <= t1 * g) && (t1 > 0.0f);
+    };
+    // bounding_box.rs:520-563 statement for statement (a lane may hold NaNs: comparisons with them are false, the selects keep them)
+    auto slab_chain = [](const SlabDist& d, Float& t0_out) -> bool {
+        const Float g = 1.0f + 2.0f * gamma(3);
+        const Float tx1 = d.x1 * g, ty1 = d.y1 * g, tz1 = d.z1 * g;
+        Float t0 = d.x0, t1 = tx1;
+        bool ok = !(t0 > ty1 || d.y0 > t1);
+        if (d.y0 > t0) t0 = d.y0;
         if (ty1 < t1) t1 = ty1;
-        ok = ok && !(t0 > tz1 || tz0 > t1);
-        if (tz0 > t0) t0 = tz0;
+        ok = ok && !(t0 > tz1 || d.z0 > t1);
+        if (d.z0 > t0) t0 = d.z0;
         if (tz1 < t1) t1 = tz1;
         t0_out = t0;
         return ok && (t1 > 0.0f);
     };
     // the link word a lane stays pending with on a leaf of several primitives: `left` more of them, from the next slot on
     auto next_in_leaf = [](uint32_t left, uint32_t slot) -> uint32_t { return LINK_LEAF | ((left < LINK_COUNT_MAX ? left : LINK_COUNT_MAX) << LINK_COUNT_SHIFT) | (slot + 1u); };
+    // The LDS store is the straight path: the HBM spill (under 1 % of the pushes) lies behind ONE wave-level test, "a pushing lane beyond the window", expected false — as
+    // a per-lane diamond the store sat behind s_and_saveexec / s_xor / a taken s_cbranch_execz / s_andn2_saveexec / s_or (profiles/trace_straight.md)
     auto push = [&](uint32_t link, uint32_t word1) {
-        // two different store flavours, so that the compiler cannot merge them into one flat_store of a selected pointer
-        if (top < st_base + LDS_N * WAVE) *top = u32x2{link, word1};
-        else st_spill_wave[(size_t)(top - (st_base + LDS_N * WAVE)) + lane] = u32x2{link, word1};
+        lds_u2* const lds_end = st_base + LDS_N * WAVE;
+        if (__builtin_expect(__ballot(top >= lds_end) != 0ull, 0)) {
+            // two different store flavours, so that the compiler cannot merge them into one flat_store of a selected pointer
+            if (top < lds_end) *top = u32x2{link, word1};
+            else st_spill_wave[(size_t)(top - lds_end) + lane] = u32x2{link, word1};
+        } else {
+            *top = u32x2{link, word1};
+        }
         top += WAVE;
     };
 
@@ -299,72 +315,87 @@ __device__ __forceinline__ void trace5_body(K5_PARAMS) {
     for (;;) {
         // ---- refill idle lanes from the wave-private chunk [w_next, w_end); one atomic per `chunk` rays ----
         const unsigned long long idle = __ballot(cur == CUR_IDLE);
-        if (GEN) since_other += 1u;
-        if (idle != 0ull) {
-            const int n_idle = __popcll(idle);
-            // GEN: a lane parked on a non-triangle test takes no node step either — the refill threshold counts the lanes that cannot, not only the idle ones (with one
-            // sphere in 4.3 M triangles a parked lane waits ~190 iterations for company: 4 parked + 17 idle lanes left 32 of 64 at a node, against 37 in the triangle scene)
-            // (... once they have waited: where parked work is frequent — every ray of an instanced object parks twice — a round comes every ~16 iterations and
-            //  early refills only break its batches: S3 instanced 171 -> 182 ms when every parked lane counted)
-            const int n_unavailable = (GEN && since_other > 24u) ? n_idle + __popcll(__ballot(cur >= (LINK_LEAF | LINK_OTHER))) : n_idle;
-            if (!exhausted && (n_unavailable >= refill_min || idle == ~0ull)) {
-                while (w_next >= w_end && !exhausted) {
-                    const uint32_t p_begin = part * part_size;
-                    const uint32_t p_end = (p_begin < n) ? ((n - p_begin < part_size) ? n : p_begin + part_size) : p_begin;
-                    uint32_t base = 0;
-                    if (lane == 0) base = atomicAdd(head + part * TRACE_HEAD_STRIDE, chunk);
-                    base = __builtin_amdgcn_readfirstlane(base);
-                    if (base < p_end - p_begin) {
-                        w_next = p_begin + base;
-                        w_end = (p_end - w_next < chunk) ? p_end : w_next + chunk;
-                    } else {
-                        part = (part + 1u == n_parts) ? 0u : part + 1u;
-                        if (--parts_left == 0u) exhausted = true;
-                    }
+        const int n_idle = __popcll(idle);
+        // the refill itself: the next chunk if the wave's own is used up (the queue is exhausted when parts_left is 0), then a ray for each idle lane while they last
+        auto refill = [&]() {
+            while (w_next >= w_end && parts_left != 0u) {
+                const uint32_t p_begin = part * part_size;
+                const uint32_t p_end = (p_begin < n) ? ((n - p_begin < part_size) ? n : p_begin + part_size) : p_begin;
+                uint32_t base = 0;
+                if (lane == 0) base = atomicAdd(head + part * TRACE_HEAD_STRIDE, chunk);
+                base = __builtin_amdgcn_readfirstlane(base);
+                if (base < p_end - p_begin) {
+                    w_next = p_begin + base;
+                    w_end = (p_end - w_next < chunk) ? p_end : w_next + chunk;
+                } else {
+                    part = (part + 1u == n_parts) ? 0u : part + 1u;
+                    parts_left -= 1u;
                 }
-                if (!exhausted) {
+            }
+            if (parts_left != 0u) {
 #ifdef K5_CENSUS
-                    const unsigned long long t_refill0 = __builtin_readcyclecounter();
+                const unsigned long long t_refill0 = __builtin_readcyclecounter();
 #endif
-                    const uint32_t take = min((uint32_t)n_idle, w_end - w_next);
-                    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
-                    if (cur == CUR_IDLE) {
-                        if (rank < take) {
-                            const uint32_t qi = w_next + rank;
-                            path = queue ? queue[qi] : qi;
-                            const float4* rp = reinterpret_cast<const float4*>(rays + path);
-                            const float4 r0 = rp[0], r1 = rp[1];
-                            if (ANY && L) {
-                                const float4 l = L[path], c = contrib[path];
-                                l_new = make_float4(l.x + c.x, l.y + c.y, l.z + c.z, l.w + c.w);
-                            }
-                            sgn = 0u;
-                            set_ray(v3(r0.x, r0.y, r0.z), v3(r0.w, r1.x, r1.y));
-                            t_max = r1.z;
-                            top = st_base;
-                            if (ANY) ph_top = 0u;
-                            // the root: tested where the ray is taken from the queue
-                            cur = root_test(root_a, root_b) ? __float_as_uint(root_b.z) : (uint32_t)CUR_POP;  // (a miss pops the empty stack: done, retired below)
-                            if (ANY) c_nodes += 1u;
+                const uint32_t take = min((uint32_t)n_idle, w_end - w_next);
+                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+                if (cur == CUR_IDLE) {
+                    if (rank < take) {
+                        const uint32_t qi = w_next + rank;
+                        path = queue ? queue[qi] : qi;
+                        const float4* rp = reinterpret_cast<const float4*>(rays + path);
+                        const float4 r0 = rp[0], r1 = rp[1];
+                        if (ANY && L) {
+                            const float4 l = L[path], c = contrib[path];
+                            l_new = make_float4(l.x + c.x, l.y + c.y, l.z + c.z, l.w + c.w);
                         }
+                        sgn = 0u;
+                        set_ray(v3(r0.x, r0.y, r0.z), v3(r0.w, r1.x, r1.y));
+                        t_max = r1.z;
+                        top = st_base;
+                        if (ANY) ph_top = 0u;
+                        // the root: tested where the ray is taken from the queue
+                        cur = root_test(root_a, root_b) ? __float_as_uint(root_b.z) : (uint32_t)CUR_POP;  // (a miss pops the empty stack: done, retired below)
+                        if (ANY) c_nodes += 1u;
                     }
-                    w_next += take;
-                    w_rays += take;
-                    if (!ANY) w_nodes += take;
-                    CENSUS(11, 1); CENSUS(12, take);
-                    m_negx = __ballot((sgn & 1u) != 0u);
-                    m_negy = __ballot((sgn & 2u) != 0u);
-                    m_negz = __ballot((sgn & 4u) != 0u);
-                    m_irregular = __ballot((sgn & 8u) != 0u);
+                }
+                w_next += take;
+                w_rays += take;
+                if (!ANY) w_nodes += take;
+                CENSUS(11, 1); CENSUS(12, take);
+                m_negx = __ballot((sgn & 1u) != 0u);
+                m_negy = __ballot((sgn & 2u) != 0u);
+                m_negz = __ballot((sgn & 4u) != 0u);
+                m_irregular = __ballot((sgn & 8u) != 0u);
 #ifdef K5_CENSUS
-                    CENSUS(13, __builtin_readcyclecounter() - t_refill0);  // (the ballots above consume the loaded rays: the refill's memory wait is inside)
+                CENSUS(13, __builtin_readcyclecounter() - t_refill0);  // (the ballots above consume the loaded rays: the refill's memory wait is inside)
 #endif
+            }
+        };
+        if (GEN) {
+            // The general kernels' gate (their register allocation sits at its limit: the triangle kernels' gate below makes them spill — profiles/trace_straight.md)
+            since_other += 1u;
+            if (idle != 0ull) {
+                // a lane parked on a non-triangle test takes no node step either — the refill threshold counts the lanes that cannot, not only the idle ones (with one
+                // sphere in 4.3 M triangles a parked lane waits ~190 iterations for company: 4 parked + 17 idle lanes left 32 of 64 at a node, against 37 in the triangle scene)
+                // (... once they have waited: where parked work is frequent — every ray of an instanced object parks twice — a round comes every ~16 iterations and
+                //  early refills only break its batches: S3 instanced 171 -> 182 ms when every parked lane counted)
+                const int n_unavailable = since_other > 24u ? n_idle + __popcll(__ballot(cur >= (LINK_LEAF | LINK_OTHER))) : n_idle;
+                const bool wanted = parts_left != 0u && (n_unavailable >= refill_min || idle == ~0ull);
+                // (unlikely, in the seven-wave closest-hit kernel: block frequencies are what the register allocator places its spill code by — 22 spilled VGPRs and
+                //  48 B of scratch with the hint, 60 B without; the other general kernels spill more with it)
+                if ((ANY || SAVE_LDS) ? wanted : __builtin_expect(wanted, 0)) refill();
+                if (__ballot(cur != CUR_IDLE) == 0ull) {
+                    if (parts_left == 0u) break;
+                    continue;  // private chunk was empty: fetch the next one
                 }
             }
-            if (__ballot(cur != CUR_IDLE) == 0ull) {
-                if (exhausted) break;
-                continue;  // private chunk was empty: fetch the next one
-            }
+        } else if (__builtin_expect(n_idle >= refill_at, 0)) {
+            // The triangle kernels: an iteration without a refill pays one popcount and one compare for it (refill_at, above: a wave of 64 idle lanes always comes here,
+            // one without an idle lane never). Behind the end of the queue only "every lane idle" leads here, and that wave is through (a refill takes at least one
+            // ray: it leaves w_next < w_end, and there is an idle lane). The path has ONE way out: it only says so, in refill_at — a scalar select —, and the wave goes
+            // through the rest of the iteration with no lane in any phase, to the test at the back edge (why not a `break`: profiles/trace_straight.md).
+            refill();
+            refill_at = parts_left != 0u ? refill_at : (n_idle == (int)WAVE ? (int)WAVE + 1 : (int)WAVE);
         }
         // ---- one uniform step: every lane that stands on an interior node fetches the block of its two children and tests both (aggregate.rs:92-135) ----
         const bool at_node = cur < (uint32_t)CUR_FIRST_SPECIAL;
@@ -379,8 +410,17 @@ __device__ __forceinline__ void trace5_body(K5_PARAMS) {
             const float4* pn = reinterpret_cast<const float4*>(node_base + off_near);
             const float4* pf = reinterpret_cast<const float4*>(node_base + (off_near ^ 32u));
             const float4 na = pn[0], nb = pn[1], fa = pf[0], fb = pf[1];
+            // The wave's regularity is asked ONCE per step, and the regular wave's path is the straight one: both children by max3 / min3, then one scalar branch, not
+            // taken. A wave that holds an irregular ray goes through the same instructions (on NaNs they compute something nobody reads) and then through the
+            // reference's chain for both children, which replaces the two verdicts and the two t0: the regular wave pays no merge of verdicts and no register copy
+            // (profiles/trace_straight.md).
+            const SlabDist dn = slab_dist(na, nb), df = slab_dist(fa, fb);
             Float t0n, t0f;
-            const bool pre_n = slab(na, nb, t0n), pre_f = slab(fa, fb, t0f);
+            bool pre_n = slab_regular(dn, t0n), pre_f = slab_regular(df, t0f);
+            if (__builtin_expect(m_irregular != 0ull, 0)) {
+                pre_n = slab_chain(dn, t0n);
+                pre_f = slab_chain(df, t0f);
+            }
             const bool hit_n = pre_n && (t0n < t_max), hit_f = pre_f && (t0f < t_max);
             const uint32_t link_n = __float_as_uint(nb.z), link_f = __float_as_uint(fb.z);
             if (ANY) {
@@ -573,9 +613,15 @@ __device__ __forceinline__ void trace5_body(K5_PARAMS) {
                 else {
                     top -= WAVE;
                     u32x2 e;
-                    // two different load flavours, so that the compiler cannot merge them into one flat_load of a selected pointer
-                    if (top < st_base + LDS_N * WAVE) e = *top;
-                    else e = __builtin_nontemporal_load(st_spill_wave + (size_t)(top - (st_base + LDS_N * WAVE)) + lane);
+                    // the LDS load on one side of a wave-level test, as the store is in push()
+                    lds_u2* const lds_end = st_base + LDS_N * WAVE;
+                    if (__builtin_expect(__ballot(top >= lds_end) != 0ull, 0)) {
+                        // two different load flavours, so that the compiler cannot merge them into one flat_load of a selected pointer
+                        if (top < lds_end) e = *top;
+                        else e = __builtin_nontemporal_load(st_spill_wave + (size_t)(top - lds_end) + lane);
+                    } else {
+                        e = *top;
+                    }
                     if (GEN && (e.x & ~LINK_INDEX_MASK) == (uint32_t)CUR_MARKER) {
                         // the instanced aggregate is exhausted: back to the ray of the enclosing tree (primitive.rs:158-171 returns); t_max is the hit found inside (in
                         // the instance's parameterisation, as the reference keeps it) — its record now names the instance — or what it was. The lane pops again in the
@@ -621,6 +667,7 @@ __device__ __forceinline__ void trace5_body(K5_PARAMS) {
             }
             cur = CUR_IDLE;
         }
+        if (!GEN && refill_at > (int)WAVE) break;  // (the triangle kernels' one way out, at the back edge)
     }
 #ifdef K5_CENSUS
     CENSUS(14, __builtin_readcyclecounter() - t_loop0);
