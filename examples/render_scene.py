@@ -9,6 +9,7 @@
     python examples/render_scene.py disk_and_cylinder | quadrics     (PBRT-v4's disk and cylinder: examples/scenes/disk_and_cylinder.pbrt / the builder)
     python examples/render_scene.py cornell_probe                    (examples/scenes/cornell_probe.pbrt: an equal-area probe in the middle of the Cornell box)
     python examples/render_scene.py cornell --spp 256 --adaptive 0.05 [--min-spp 16] [--batch-spp 4]   (adaptive sampling: --spp is the cap)
+    python examples/render_scene.py cornell --spp 4 --frames 16 --orbit 1 --temporal [--denoise]        (a turntable accumulated over time: <name>.fNNN.pfm / .png per frame)
 
 Everything goes through the C ABI of include/shimmer_hip.h (shimmer_amd/abi.py is the ctypes binding): scene description ->
 shm_scene_create -> shm_render_device -> shm_film_read -> shm_film_get_image -> shm_write_pfm. Needs an MI355X: there is no CPU path.
@@ -71,6 +72,19 @@ def make_scene(lib, name, w, h, film=None, camera=None):
     raise SystemExit(f"unknown scene {name}")
 
 
+# where the builders' cameras stand (shimmer_amd/scenes.py): position, what they look at, fov — what --orbit turns
+VIEWS = {name: ((0.0, 1.0, 3.4), (0.0, 1.0, 0.0), 39.0) for name in ("cornell", "spotlit", "textured", "coated", "translucent", "patches")}
+VIEWS.update(instanced=((0.0, 2.2, 7.0), (0.0, 0.8, 0.0), 40.0), ganesha=((0.0, 0.6, 4.2), (0.0, 0.0, 0.0), 38.0), crown=((0.0, 2.2, 7.5), (0.0, 1.2, 0.0), 32.0))
+
+
+def orbit_camera(lib, sc, name, degrees):
+    """The scene's camera turned by `degrees` about the vertical through what it looks at, in the scene's render space (render.camera_in_scene)."""
+    pos, look, fov = (np.array(v, np.float64) for v in VIEWS[name])
+    a = np.radians(degrees)
+    rot = np.array([[np.cos(a), 0.0, np.sin(a)], [0.0, 1.0, 0.0], [-np.sin(a), 0.0, np.cos(a)]])
+    return render.camera_in_scene(lib, sc.builder, look + rot @ (pos - look), look, (0.0, 1.0, 0.0), fov=float(fov))
+
+
 def write_png(path, rgb8):
     h, w, _ = rgb8.shape
     raw = b"".join(b"\x00" + rgb8[y].tobytes() for y in range(h))
@@ -81,6 +95,56 @@ def write_png(path, rgb8):
 
     with open(path, "wb") as f:
         f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)) + chunk(b"IDAT", zlib.compress(raw)) + chunk(b"IEND", b""))
+
+
+def write_ldr_png(path, image, exposure):
+    ldr = np.clip(image * exposure, 0.0, 1.0)
+    ldr = np.where(ldr <= 0.0031308, 12.92 * ldr, 1.055 * np.power(ldr, 1 / 2.4) - 0.055)
+    write_png(path, (ldr * 255 + 0.5).astype(np.uint8))
+
+
+def render_sequence(lib, args, sc, r, w, h):
+    """--frames: one scene, one camera per frame, --spp new samples per frame; with --temporal the frames are accumulated (and, with --denoise, filtered)."""
+    if args.adaptive is not None or args.aovs:
+        raise SystemExit("--frames renders plain frames: no --adaptive, no --aovs")
+    if args.orbit != 0.0 and (args.scene not in VIEWS or args.camera != "scene"):
+        raise SystemExit(f"--orbit knows the cameras of {', '.join(VIEWS)} (and not --camera spherical)")
+    if args.denoise and not args.temporal:
+        raise SystemExit("--frames with --denoise filters the accumulated frame: add --temporal")
+    p = render.make_params(seed=args.seed, spp=args.frames * args.spp, max_depth=args.max_depth, integrator=args.integrator, reference_quirks=not args.quirks_off,
+                           sampler=args.sampler)
+    stem = os.path.splitext(args.output or f"{args.scene.replace(':', '_')}.pfm")[0]
+
+    def write(path_stem, film):
+        img = np.ascontiguousarray(render.film_get_image(lib, film, render.SRGB_FROM_XYZ), np.float32)
+        abi.check(lib, lib.shm_write_pfm(f"{path_stem}.pfm".encode(), img.ctypes.data_as(abi.c_float_p), w, h), "shm_write_pfm")
+        write_ldr_png(f"{path_stem}.png", img, args.exposure)
+
+    if args.temporal:
+        r.temporal_clear()
+    for f in range(args.frames):
+        if args.orbit != 0.0 and f > 0:
+            r.set_camera(orbit_camera(lib, sc, args.scene, args.orbit * f))
+        r.clear()
+        t0 = time.perf_counter()
+        r.render_waves(p, waves=[(f * args.spp, (f + 1) * args.spp)])
+        dt = time.perf_counter() - t0
+        text = f"frame {f}: {args.spp} spp in {dt * 1e3:.1f} ms"
+        if args.temporal:
+            r.gbuffer_clear()
+            r.gbuffer_wave(p, f * args.spp, (f + 1) * args.spp)
+            ms = r.temporal_accumulate(return_ms=True)
+            write(f"{stem}.f{f:03d}", r.read_temporal())
+            text += f", accumulated in {ms:.3f} ms"
+            if args.denoise:
+                den, dms = r.denoise_temporal(return_ms=True)
+                write(f"{stem}.f{f:03d}.denoised", den)
+                text += f", filtered in {dms:.3f} ms"
+        else:
+            write(f"{stem}.f{f:03d}", r.read_film())
+        print(text)
+    print(f"wrote {stem}.f000 .. f{args.frames - 1:03d} (.pfm, .png" + (", .denoised.pfm, .denoised.png)" if args.denoise else ")"))
+    r.close()
 
 
 def main():
@@ -110,6 +174,11 @@ def main():
                          "writes <name>.spp.pfm (the per-pixel sample count) and <name>.variance.pfm (the variance of the pixel's mean, sensor RGB) beside the beauty")
     ap.add_argument("--min-spp", type=int, default=None, help="with --adaptive: samples every tile receives (a multiple of --batch-spp, at least twice it; default 16)")
     ap.add_argument("--batch-spp", type=int, default=None, help="with --adaptive: samples per batch (default 4)")
+    ap.add_argument("--frames", type=int, default=0, metavar="N", help="a sequence of N frames of --spp samples each — frame f draws samples [f spp, (f + 1) spp) — written as "
+                                                                       "<name>.fNNN.pfm and .png")
+    ap.add_argument("--orbit", type=float, default=0.0, metavar="DEG", help="with --frames: the camera turns DEG degrees a frame about what it looks at (shm_scene_set_camera)")
+    ap.add_argument("--temporal", action="store_true", help="with --frames: each frame is accumulated into a history reprojected through the G-buffer (DESIGN.md section 4l); "
+                                                            "with --denoise the accumulated frame is filtered as well (<name>.fNNN.denoised.pfm and .png)")
     ap.add_argument("-o", "--output", default="")
     args = ap.parse_args()
     lib = abi.load_library()
@@ -121,6 +190,8 @@ def main():
     r = render.Renderer(lib, sc.desc, 0)
     p = render.make_params(seed=args.seed, spp=args.spp, max_depth=args.max_depth, integrator=args.integrator, reference_quirks=not args.quirks_off,
                            sampler=args.sampler)
+    if args.frames > 0:
+        return render_sequence(lib, args, sc, r, w, h)
     tile_spp = None
     r.clear()
     t0 = time.perf_counter()
@@ -139,11 +210,7 @@ def main():
     out = args.output or f"{args.scene.replace(':', '_')}.pfm"
     img = np.ascontiguousarray(img, np.float32)
     abi.check(lib, lib.shm_write_pfm(out.encode(), img.ctypes.data_as(abi.c_float_p), w, h), "shm_write_pfm")
-    def write_ldr(path, image):
-        ldr = np.clip(image * args.exposure, 0.0, 1.0)
-        ldr = np.where(ldr <= 0.0031308, 12.92 * ldr, 1.055 * np.power(ldr, 1 / 2.4) - 0.055)
-        write_png(path, (ldr * 255 + 0.5).astype(np.uint8))
-
+    write_ldr = lambda path, image: write_ldr_png(path, image, args.exposure)
     write_ldr(os.path.splitext(out)[0] + ".png", img)
     print("wrote", out, "and", os.path.splitext(out)[0] + ".png")
     if tile_spp is not None:  # what the adaptive render measured and where it spent its samples

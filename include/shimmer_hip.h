@@ -551,6 +551,12 @@ typedef struct ShmScene ShmScene;
 /* Scene lifetime.  `device` is the HIP device ordinal (one process per GPU: pass LOCAL_RANK). */
 SHM_API int shm_scene_create(const ShmSceneDesc* desc, int device, ShmScene** out);
 SHM_API void shm_scene_destroy(ShmScene* scene);
+/* Replace the scene's camera: the next wave renders from `camera`. The scene view is a by-value kernel argument, so nothing is uploaded again; the geometry stays
+ * in the render space it was baked in, which is the space `camera` must be expressed in (shm_camera_create_in, below, builds such a camera). The film, the
+ * G-buffer, the moments and the temporal history are left as they are: the caller clears what it wants cleared. SHM_ERR_INVALID_ARGUMENT, with the cause in
+ * shm_last_error(): a camera whose `kind` is not the scene's (the scene's plan chose its generate kernel by kind) or whose spherical mapping is unknown.
+ * SHM_ERR_UNSUPPORTED on a scene that holds multi-GPU state (from shm_dist_init, or shm_render_sharded, until shm_dist_finalize). */
+SHM_API int shm_scene_set_camera(ShmScene* scene, const ShmCamera* camera);
 
 /* How many primitives got a per-primitive shading record at scene creation (flat triangles of the scene classes whose kernels read one; 0 under SHM_TRI_SHADE=0 and
  * in every other class), and, where build_ms_out is not NULL, the wall-clock milliseconds scene creation spent building them. */
@@ -737,6 +743,67 @@ SHM_API int shm_render_adaptive(ShmScene* scene, const ShmRenderParams* params, 
 SHM_API int shm_denoise_host_moments(const ShmFilmPixel* film, const ShmGBufferPixel* gbuffer, const ShmMomentsPixel* moments, int32_t width, int32_t height,
                                      const double white[3], const ShmDenoiseParams* params, ShmFilmPixel* out);
 
+/* ---- temporal accumulation: the frame blended into a history reprojected through the G-buffer -----------
+ * A pass over the frame just rendered, for a static scene under a moving camera (shm_scene_set_camera). Per pixel it takes c, the guide's validity, a_eff, the
+ * render-space position P and the unit shading normal N exactly as the denoiser does; finds where P lay on the PREVIOUS frame's film — the motion vector
+ * m = raster_prev(P) - raster_cur(P), so that a still camera gives m = 0 exactly and a history that is not blurred —; takes the four bilinear taps of the previous
+ * frame's records around (x + 0.5 + m.x, y + 0.5 + m.y), of which one counts iff it is inside the film, its bilinear weight is above 0, its record has a history, dot(N, N_tap) >= normal_cos_min and
+ * |dot(N, P_tap - P)| <= plane_tolerance * scale (scale: P's depth along the previous camera's axis for a perspective camera, 1 for an orthographic one); and blends:
+ *   no tap counts   length = 1, rgb = c' (c, or c / a_eff when demodulating), m1 = l, m2 = l l with l the mean of c''s three channels
+ *   otherwise       h = the taps' weighted mean; length = min(h.length + 1, max_history); a = max(1 / length, alpha_min); rgb = h.rgb + a (c' - h.rgb); m1 and m2 alike
+ *                   with alpha_min_moments
+ * The result is rgb a_eff. A pixel without a usable guide passes through (its result is c, bit for bit) and gets a record of length 0, which no later frame reads; a P
+ * at or behind a perspective previous camera, or one whose motion is not finite, has no history. Gather only: no pixel writes another's record.
+ * Device and CPU twin run the same header (shm/temporal.h) and give the same bits. */
+typedef struct ShmTemporalParams {
+    float alpha_min;          /* in [0, 1]: least weight of the new frame in the colour; 0 = a plain running mean up to max_history */
+    float alpha_min_moments;  /* the same for the two luminance moments */
+    float max_history;        /* >= 1: cap of the history length */
+    float normal_cos_min;     /* in [-1, 1]: a tap is rejected when dot(N, N_tap) is below it */
+    float plane_tolerance;    /* > 0, +inf allowed: a tap is rejected when |dot(N, P_tap - P)| > plane_tolerance * scale */
+    float albedo_floor;       /* as ShmDenoiseParams::albedo_floor */
+    uint32_t demodulate;      /* as ShmDenoiseParams::demodulate: accumulate c / a_eff and multiply the current a_eff back */
+    uint32_t reserved[1];
+} ShmTemporalParams;
+typedef struct ShmTemporalPixel {   /* 64 bytes; one per pixel, twice per scene (ping-pong) */
+    float rgb[3];     /* accumulated (demodulated) colour */
+    float m1, m2;     /* accumulated luminance and luminance squared of the per-frame colour */
+    float length;     /* history length; 0 = no history here (no guide this frame) */
+    float p[3];       /* this frame's P, render space */
+    float ns[3];      /* this frame's N, unit */
+    uint32_t pad[4];
+} ShmTemporalPixel;
+/* alpha_min 0.2, alpha_min_moments 0.2, max_history 32, normal_cos_min 0.9, plane_tolerance 0.02, albedo_floor 0.01, demodulate 0 (at a few samples per pixel a pixel's a_eff
+ * moves from frame to frame — most of all on an emitter's edge — and a history divided by one frame's a_eff and multiplied by another's is worse than the frame:
+ * profiles/temporal.md) */
+SHM_API int shm_temporal_default_params(ShmTemporalParams* out);
+/* Forget the history: every record's length becomes 0 and the stored camera is dropped, so the next accumulate starts a history at every pixel. The first call
+ * allocates the two record arrays and the result (160 bytes per pixel), which shm_scene_destroy frees. Blocking. */
+SHM_API int shm_temporal_clear(ShmScene* scene);
+/* One frame: the device film and the device G-buffer of the frame just rendered, and the records of the previous call, into the other record array and a device result;
+ * then the scene's current camera is stored as the next call's previous camera. Neither the film nor the G-buffer is written. The first call on a scene, and the first
+ * after shm_temporal_clear, has no previous camera and starts every history. Blocking; ms_out (may be NULL) receives the HIP-event time of the kernel.
+ * SHM_ERR_INVALID_ARGUMENT, with the cause in shm_last_error(): no G-buffer wave since the scene's creation or the last shm_gbuffer_clear; the last G-buffer wave was
+ * not SHM_GBUFFER_SPACE_RENDER; a parameter outside its range. SHM_ERR_UNSUPPORTED: a SHM_CAMERA_SPHERICAL scene. */
+SHM_API int shm_temporal_accumulate_device(ShmScene* scene, const ShmTemporalParams* params, double* ms_out);
+/* Copy the last result — rgb_sum the accumulated sensor RGB, weight_sum 1 (0 where the film's was 0) — or the records just written to a caller-allocated
+ * pixel_bounds-sized row-major array (SHM_ERR_INVALID_ARGUMENT before the first shm_temporal_accumulate_device). */
+SHM_API int shm_temporal_read(ShmScene* scene, ShmFilmPixel* out);
+SHM_API int shm_temporal_read_history(ShmScene* scene, ShmTemporalPixel* out);
+/* The CPU twin (no GPU needed): one frame from read-back buffers. history_in: the previous frame's records, or NULL for none (previous_camera is then not read and may
+ * be NULL). Film coordinates are pixel_bounds' own: (0, 0, width, height). The outputs must not overlap the inputs. */
+SHM_API int shm_temporal_accumulate_host(const ShmFilmPixel* film, const ShmGBufferPixel* gbuffer, const ShmTemporalPixel* history_in,
+                                         const ShmCamera* camera, const ShmCamera* previous_camera, int32_t width, int32_t height, const double white[3],
+                                         const ShmTemporalParams* params, ShmTemporalPixel* history_out, ShmFilmPixel* out);
+/* The a-trous filter of shm_denoise_device over the temporal result in place of the film (it is a ShmFilmPixel array of weight 1, so the kernels take it as they take a
+ * film); the result is read with shm_denoise_read. params->variance_source must be SHM_DENOISE_VARIANCE_SPATIAL. temporal_variance = 1 replaces the filter's initial
+ * variance by max(0, m2 - m1^2) / length at every valid pixel whose record has length >= 4 (SVGF's rule) and keeps the 7x7 spatial estimate elsewhere; 0 is the plain
+ * spatial filter of the accumulated image. SHM_ERR_INVALID_ARGUMENT before the first shm_temporal_accumulate_device, and as shm_denoise_device. */
+SHM_API int shm_denoise_temporal_device(ShmScene* scene, const ShmDenoiseParams* params, uint32_t temporal_variance, double* ms_out);
+/* Its CPU twin: `temporal` as shm_temporal_read gives it, `history` as shm_temporal_read_history does. */
+SHM_API int shm_denoise_temporal_host(const ShmFilmPixel* temporal, const ShmGBufferPixel* gbuffer, const ShmTemporalPixel* history, int32_t width, int32_t height,
+                                      const double white[3], const ShmDenoiseParams* params, uint32_t temporal_variance, ShmFilmPixel* out);
+
 /* ---- multi-GPU (ABI v7) -------------------------------------------------------------------------------------------
  * Pixels are independent and tile ownership is exclusive (the reference's one parallel region, integrator.rs:242-304, relies on that
  * for its unsynchronised film writes), so the frame shards by tiles with the scene replicated per GPU and NO collective while
@@ -844,6 +911,12 @@ typedef struct ShmCameraParams {
     float screen_window[4];       /* "screenwindow" as the file gives it: x0 x1 y0 y1 */
 } ShmCameraParams;
 SHM_API int shm_camera_create(const ShmCameraParams* params, ShmCamera* out, float render_from_world_out[16]);
+/* shm_camera_create with the render space GIVEN instead of chosen by params->render_space (which is not read): render_from_camera = render_from_world *
+ * world_from_camera, in double; camera_from_render and the four minimum differentials are filled as above. For a second camera in the render space an existing
+ * scene's geometry was baked in (shm_scene_set_camera). With the render_from_world a shm_camera_create call returned for the same parameters it gives that call's
+ * ShmCamera bit for bit under SHM_RENDER_SPACE_CAMERA_WORLD and SHM_RENDER_SPACE_WORLD, whose matrix (a translation, the identity) is exact in float; under
+ * SHM_RENDER_SPACE_CAMERA the returned matrix is a rounded inverse and the two agree to that rounding. SHM_ERR_INVALID_ARGUMENT for a singular matrix. */
+SHM_API int shm_camera_create_in(const ShmCameraParams* params, const float render_from_world[16], ShmCamera* out);
 /* PBRT-v4's SphericalCamera for a world_from_camera matrix: `mapping` is SHM_SPHERICAL_*, `render_space` SHM_RENDER_SPACE_* (the same CameraTransform as above). Fills
  * camera_from_raster as described at ShmCamera, camera_from_render and the four minimum differentials (the same 512-sample loop, over this camera's rays).
  * SHM_ERR_INVALID_ARGUMENT for a mapping above 1, a resolution below 1 or a render space above 2. */

@@ -231,6 +231,20 @@ SHM_DENOISE_VARIANCE_SPATIAL, SHM_DENOISE_VARIANCE_MEASURED = 0, 1
 assert C.sizeof(ShmDenoiseParams) == 32
 
 
+class ShmTemporalParams(C.Structure):
+    """The temporal pass's parameters (include/shimmer_hip.h); shm_temporal_default_params fills one."""
+    _fields_ = [("alpha_min", C.c_float), ("alpha_min_moments", C.c_float), ("max_history", C.c_float), ("normal_cos_min", C.c_float), ("plane_tolerance", C.c_float),
+                ("albedo_floor", C.c_float), ("demodulate", C.c_uint32), ("reserved", C.c_uint32 * 1)]
+
+
+class ShmTemporalPixel(C.Structure):
+    """A record of the temporal pass: the accumulated (demodulated) colour, the two luminance moments, the history length, and the frame's P and N."""
+    _fields_ = [("rgb", C.c_float * 3), ("m1", C.c_float), ("m2", C.c_float), ("length", C.c_float), ("p", C.c_float * 3), ("ns", C.c_float * 3), ("pad", C.c_uint32 * 4)]
+
+
+assert C.sizeof(ShmTemporalParams) == 32 and C.sizeof(ShmTemporalPixel) == 64
+
+
 class ShmMomentsPixel(C.Structure):
     """A record of the moments pass (include/shimmer_hip.h): the film pixel as last seen, West's running mean and m2 per channel, W and B."""
     _fields_ = [("prev", C.c_double * 4), ("mean", C.c_double * 3), ("m2", C.c_double * 3), ("weight", C.c_double), ("batches", C.c_double)]
@@ -317,6 +331,18 @@ EXPORTS = {
     "shm_render_adaptive": (C.c_int, [C.c_void_p, C.POINTER(ShmRenderParams), C.POINTER(ShmTile), C.c_uint32, C.POINTER(ShmAdaptiveParams), C.POINTER(C.c_uint32),
                                       C.POINTER(ShmStats)]),
     "shm_denoise_host_moments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(ShmDenoiseParams), C.c_void_p]),
+    "shm_scene_set_camera": (C.c_int, [C.c_void_p, C.POINTER(ShmCamera)]),
+    "shm_camera_create_in": (C.c_int, [C.POINTER(ShmCameraParams), c_float_p, C.POINTER(ShmCamera)]),
+    "shm_temporal_default_params": (C.c_int, [C.POINTER(ShmTemporalParams)]),
+    "shm_temporal_clear": (C.c_int, [C.c_void_p]),
+    "shm_temporal_accumulate_device": (C.c_int, [C.c_void_p, C.POINTER(ShmTemporalParams), C.POINTER(C.c_double)]),
+    "shm_temporal_read": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "shm_temporal_read_history": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "shm_temporal_accumulate_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ShmCamera), C.POINTER(ShmCamera), C.c_int32, C.c_int32, C.POINTER(C.c_double),
+                                               C.POINTER(ShmTemporalParams), C.c_void_p, C.c_void_p]),
+    "shm_denoise_temporal_device": (C.c_int, [C.c_void_p, C.POINTER(ShmDenoiseParams), C.c_uint32, C.POINTER(C.c_double)]),
+    "shm_denoise_temporal_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(ShmDenoiseParams), C.c_uint32,
+                                            C.c_void_p]),
     "shm_last_error": (C.c_char_p, []),
     "shm_device_count": (C.c_int, []),
     "shm_bvh_build": (C.c_int, [c_float_p, C.c_uint32, C.c_int, C.POINTER(ShmBvhNode), c_u32_p, c_u32_p]),

@@ -31,7 +31,8 @@
 #include "../shm/path.h"  // camera_generate_ray_differential for CameraBase::find_minimum_differentials (host use only)
 #include "../shm/gbuffer.h"  // the G-buffer pass's CPU twin, at the end of this file
 #include "../shm/denoise.h"  // the denoiser's, behind it
-#include "../shm/moments.h"  // the moments pass's, last
+#include "../shm/moments.h"  // the moments pass's
+#include "../shm/temporal.h"  // the temporal pass's, last
 #include "flatten.h"
 
 extern "C" __attribute__((visibility("hidden"))) void shm_set_last_error(const char* msg);  // shimmer_hip.hip
@@ -473,11 +474,16 @@ static bool camera_transform(const float world_from_camera[16], uint32_t render_
 // ProjectiveCameraBase::new for either projection (camera.rs:594-642); fov_deg < 0 selects Transform::orthographic(0, 1)
 static int projective_camera(const float world_from_camera[16], float fov_deg, const int32_t full_resolution[2],
                              float lens_radius, float focal_distance, ShmCamera* out, float render_from_world_out[16],
-                             uint32_t render_space = SHM_RENDER_SPACE_CAMERA_WORLD, float frame_aspect_ratio = 0.0f, const float* screen_window = nullptr) {
-    if (!world_from_camera || !full_resolution || !out || full_resolution[0] <= 0 || full_resolution[1] <= 0 || render_space > SHM_RENDER_SPACE_WORLD)
+                             uint32_t render_space = SHM_RENDER_SPACE_CAMERA_WORLD, float frame_aspect_ratio = 0.0f, const float* screen_window = nullptr,
+                             const float* render_from_world_in = nullptr /* shm_camera_create_in: the render space given; render_space is not read */) {
+    if (!world_from_camera || !full_resolution || !out || full_resolution[0] <= 0 || full_resolution[1] <= 0 || (!render_from_world_in && render_space > SHM_RENDER_SPACE_WORLD))
         return SHM_ERR_INVALID_ARGUMENT;
     M4 render_from_camera, render_from_world;
-    if (!camera_transform(world_from_camera, render_space, render_from_camera, render_from_world)) return SHM_ERR_INVALID_ARGUMENT;
+    if (render_from_world_in) {
+        M4 wfc;
+        for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) { wfc.m[i][j] = world_from_camera[i * 4 + j]; render_from_world.m[i][j] = render_from_world_in[i * 4 + j]; }
+        render_from_camera = m4_mul(render_from_world, wfc);
+    } else if (!camera_transform(world_from_camera, render_space, render_from_camera, render_from_world)) return SHM_ERR_INVALID_ARGUMENT;
     // Transform::perspective(fov, 1e-2, 1000) (transform.rs:305-316)
     double n = 1e-2, f = 1000.0;
     M4 persp = m4_identity();
@@ -574,6 +580,13 @@ int shm_camera_create(const ShmCameraParams* p, ShmCamera* out, float render_fro
     if (p->kind == SHM_CAMERA_PERSPECTIVE && !(p->fov_deg > 0.0f)) return SHM_ERR_INVALID_ARGUMENT;
     return projective_camera(p->world_from_camera, p->kind == SHM_CAMERA_PERSPECTIVE ? p->fov_deg : -1.0f, p->full_resolution, p->lens_radius, p->focal_distance, out,
                              render_from_world_out, p->render_space, p->frame_aspect_ratio, p->has_screen_window ? p->screen_window : nullptr);
+}
+
+int shm_camera_create_in(const ShmCameraParams* p, const float render_from_world[16], ShmCamera* out) {
+    if (!p || !render_from_world || (p->kind != SHM_CAMERA_PERSPECTIVE && p->kind != SHM_CAMERA_ORTHOGRAPHIC)) return SHM_ERR_INVALID_ARGUMENT;
+    if (p->kind == SHM_CAMERA_PERSPECTIVE && !(p->fov_deg > 0.0f)) return SHM_ERR_INVALID_ARGUMENT;
+    return projective_camera(p->world_from_camera, p->kind == SHM_CAMERA_PERSPECTIVE ? p->fov_deg : -1.0f, p->full_resolution, p->lens_radius, p->focal_distance, out,
+                             nullptr, 0u, p->frame_aspect_ratio, p->has_screen_window ? p->screen_window : nullptr, render_from_world);
 }
 
 int shm_film_get_image(const ShmFilmPixel* film, uint64_t n_pixels, const float m[9], int write_fp16, float* rgb_out) {
@@ -944,8 +957,9 @@ int shm_gbuffer_resolve(const ShmGBufferPixel* pixels, uint64_t n, const double 
 // shm/denoise.h's pixel functions over the whole film, pass by pass as k_denoise.hip launches them: prepare, variance (where sigma_luminance is finite), one a-trous pass per
 // iteration from one copy of plane A into the other, finish.
 // (`moments`: the records for variance_source = measured — shm_denoise_host_moments — or null: k_denoise_variance_measured's step behind the variance pass)
+// (`temporal`: the temporal pass's records for shm_denoise_temporal_host with temporal_variance = 1, or null: k_temporal_variance's step at the same place)
 static int denoise_host_impl(const ShmFilmPixel* film, const ShmGBufferPixel* gbuffer, const ShmMomentsPixel* moments, int32_t width, int32_t height, const double white[3],
-                             const ShmDenoiseParams* params, ShmFilmPixel* out) {
+                             const ShmDenoiseParams* params, ShmFilmPixel* out, const shm::TemporalRecord* temporal = nullptr) {
     if (!film || !gbuffer || !white || !params || !out || width < 1 || height < 1) { shm_set_last_error("denoise: a null argument or an empty film"); return SHM_ERR_INVALID_ARGUMENT; }
     if (params->variance_source > SHM_DENOISE_VARIANCE_MEASURED) { shm_set_last_error("denoise: unknown variance_source"); return SHM_ERR_INVALID_ARGUMENT; }
     const bool measured = params->variance_source == SHM_DENOISE_VARIANCE_MEASURED;
@@ -973,6 +987,9 @@ static int denoise_host_impl(const ShmFilmPixel* film, const ShmGBufferPixel* gb
                     const double* m = reinterpret_cast<const double*>(moments + q);
                     if (C[q].w != 0.0f && m[11] >= 2.0) A[0][q].w = shm::denoise_measured_variance(m, D[q]);
                 }
+            if (temporal)
+                for (size_t q = 0; q < n; ++q)
+                    if (C[q].w != 0.0f && temporal[q].b.y >= shm::TEMPORAL_VARIANCE_MIN_LENGTH) A[0][q].w = shm::temporal_variance(temporal[q]);
         }
         for (uint32_t i = 0; i < k.iterations; ++i, cur ^= 1)
             for (int y = 0; y < height; ++y)
@@ -996,6 +1013,43 @@ extern "C" int shm_denoise_host_moments(const ShmFilmPixel* film, const ShmGBuff
                                         const double white[3], const ShmDenoiseParams* params, ShmFilmPixel* out) {
     if (!moments) { shm_set_last_error("denoise: no moments"); return SHM_ERR_INVALID_ARGUMENT; }
     return denoise_host_impl(film, gbuffer, moments, width, height, white, params, out);
+}
+
+// ---- the temporal pass's CPU twin (include/shimmer_hip.h, shm_temporal_accumulate_host) ----
+// shm/temporal.h's pixel function over the whole film, as k_temporal_accumulate's lanes take it: every pixel reads the previous records and writes its own.
+static_assert(sizeof(ShmTemporalPixel) == sizeof(shm::TemporalRecord), "a record is a ShmTemporalPixel");
+extern "C" int shm_temporal_accumulate_host(const ShmFilmPixel* film, const ShmGBufferPixel* gbuffer, const ShmTemporalPixel* history_in, const ShmCamera* camera,
+                                            const ShmCamera* previous_camera, int32_t width, int32_t height, const double white[3], const ShmTemporalParams* params,
+                                            ShmTemporalPixel* history_out, ShmFilmPixel* out) {
+    if (!film || !gbuffer || !camera || !white || !params || !history_out || !out || width < 1 || height < 1) { shm_set_last_error("temporal: a null argument or an empty film"); return SHM_ERR_INVALID_ARGUMENT; }
+    if (history_in && !previous_camera) { shm_set_last_error("temporal: a history without the camera it was seen through"); return SHM_ERR_INVALID_ARGUMENT; }
+    const shm::TemporalConfig k{params->alpha_min, params->alpha_min_moments, params->max_history, params->normal_cos_min, params->plane_tolerance, params->albedo_floor, params->demodulate};
+    if (const char* why = shm::temporal_params_error(k)) { shm_set_last_error(why); return SHM_ERR_INVALID_ARGUMENT; }
+    const ShmCamera* cams[2] = {camera, history_in ? previous_camera : camera};
+    shm::TemporalCamera tc[2];
+    for (int i = 0; i < 2; ++i) {
+        if (cams[i]->kind == SHM_CAMERA_SPHERICAL) { shm_set_last_error("temporal: the spherical camera is not reprojected"); return SHM_ERR_UNSUPPORTED; }
+        if (cams[i]->kind > SHM_CAMERA_SPHERICAL) { shm_set_last_error("temporal: unknown camera kind"); return SHM_ERR_INVALID_ARGUMENT; }
+        if (!shm::temporal_camera(cams[i]->camera_from_raster, cams[i]->camera_from_render, cams[i]->kind == SHM_CAMERA_PERSPECTIVE, tc[i])) { shm_set_last_error("temporal: camera_from_raster is singular"); return SHM_ERR_INVALID_ARGUMENT; }
+    }
+    const shm::Float wf[3] = {(shm::Float)white[0], (shm::Float)white[1], (shm::Float)white[2]};
+    const shm::TemporalRecord* history = reinterpret_cast<const shm::TemporalRecord*>(history_in);
+    for (int y = 0; y < height; ++y)
+        for (int x = 0; x < width; ++x) {
+            const size_t q = (size_t)y * (size_t)width + (size_t)x;
+            shm::TemporalRecord rec;
+            shm::temporal_pixel(reinterpret_cast<const double*>(film + q), reinterpret_cast<const double*>(gbuffer + q), wf, history, tc[0], tc[1], x, y, width, height, k, rec,
+                                reinterpret_cast<double*>(out + q));
+            memcpy(history_out + q, &rec, sizeof(rec));
+        }
+    return SHM_OK;
+}
+extern "C" int shm_denoise_temporal_host(const ShmFilmPixel* temporal, const ShmGBufferPixel* gbuffer, const ShmTemporalPixel* history, int32_t width, int32_t height,
+                                         const double white[3], const ShmDenoiseParams* params, uint32_t temporal_variance, ShmFilmPixel* out) {
+    if (!history || !params) { shm_set_last_error("denoise: no temporal records or no parameters"); return SHM_ERR_INVALID_ARGUMENT; }
+    if (params->variance_source != SHM_DENOISE_VARIANCE_SPATIAL) { shm_set_last_error("denoise: the temporal result is filtered with variance_source spatial only"); return SHM_ERR_INVALID_ARGUMENT; }
+    if (temporal_variance > 1u) { shm_set_last_error("denoise: temporal_variance is 0 or 1"); return SHM_ERR_INVALID_ARGUMENT; }
+    return denoise_host_impl(temporal, gbuffer, nullptr, width, height, white, params, out, temporal_variance ? reinterpret_cast<const shm::TemporalRecord*>(history) : nullptr);
 }
 
 // ---- the moments pass's CPU twin and its resolve (include/shimmer_hip.h, shm_moments_update_host / shm_moments_resolve) ----

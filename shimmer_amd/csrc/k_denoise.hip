@@ -9,6 +9,8 @@
 //                        same body at every step. (The plain gather — adjacent pixels per block, every tap from global memory — was built and measured against it and
 //                        lost at every step: profiles/denoise.md.)
 //   k_denoise_finish     one pixel per lane: e a_eff, or c for a pass-through pixel, as a ShmFilmPixel
+// The launches are wf_denoise_run's: shm_denoise_device runs it over the scene's film, shm_denoise_temporal_device (k_temporal.hip) over the temporal pass's result, with
+// that unit's k_temporal_variance behind the variance pass. The kernels do not know which.
 // A workgroup is 32 lanes wide so that each of ds_read_b128's 16-lane groups (lanes {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} of a half wave) lies in ONE tile row and
 // reads 16 different 16-byte slots modulo 16: conflict-free whatever the tile's pitch. (A 16-wide block puts a group on two rows, and the pitch of 20 a 16x16 block's halo
 // tile has then lands lanes 12-15 of one row on the slots of lanes 20-23 of the next.)
@@ -106,22 +108,8 @@ __global__ void __launch_bounds__(DN_BLOCK) k_denoise_finish(const ShmFilmPixel*
 
 }  // namespace
 
-extern "C" {
-
-int shm_denoise_default_params(ShmDenoiseParams* out) {
-    if (!out) return SHM_ERR_INVALID_ARGUMENT;
-    memset(out, 0, sizeof(*out));
-    out->iterations = 5;
-    out->demodulate = 1;
-    out->sigma_luminance = 1.5f;
-    out->sigma_normal = 128.0f;
-    out->sigma_plane = 0.1f;
-    out->albedo_floor = 0.01f;
-    return SHM_OK;
-}
-
-int shm_denoise_device(ShmScene* s, const ShmDenoiseParams* params, double* ms_out) {
-    if (!s || !params) { shm_err() = "denoise: no scene or no parameters"; return SHM_ERR_INVALID_ARGUMENT; }
+// shm_denoise_device's body (wavefront.h): `film` is the scene's film or a ShmFilmPixel array that stands in for it
+int wf_denoise_run(ShmScene* s, const ShmDenoiseParams* params, const ShmFilmPixel* film, const float4* temporal_records, double* ms_out) {
     const DenoiseConfig k{params->iterations, params->demodulate, params->sigma_luminance, params->sigma_normal, params->sigma_plane, params->albedo_floor};
     if (const char* why = denoise_params_error(k)) { shm_err() = why; return SHM_ERR_INVALID_ARGUMENT; }
     if (params->variance_source > SHM_DENOISE_VARIANCE_MEASURED) { shm_err() = "denoise: unknown variance_source"; return SHM_ERR_INVALID_ARGUMENT; }
@@ -154,7 +142,7 @@ int shm_denoise_device(ShmScene* s, const ShmDenoiseParams* params, double* ms_o
     HIP_TRY(hipEventRecord(e_begin, s->stream));
     int cur = 0;
     if (k.iterations > 0) {
-        hipLaunchKernelGGL(k_denoise_prepare, linear, block, 0, s->stream, s->d_film, s->d_gbuffer, (uint32_t)n, (float)white[0], (float)white[1], (float)white[2], k, A[0], B, C, D);
+        hipLaunchKernelGGL(k_denoise_prepare, linear, block, 0, s->stream, film, s->d_gbuffer, (uint32_t)n, (float)white[0], (float)white[1], (float)white[2], k, A[0], B, C, D);
         LAUNCH_TRY("k_denoise_prepare");
         if (!is_inf(k.sigma_luminance)) {  // (nothing reads the variance otherwise but the next iteration's own)
             hipLaunchKernelGGL(k_denoise_variance, tiles, block, 0, s->stream, A[0], B, C, width, height, k);
@@ -162,6 +150,10 @@ int shm_denoise_device(ShmScene* s, const ShmDenoiseParams* params, double* ms_o
             if (measured) {
                 hipLaunchKernelGGL(k_denoise_variance_measured, linear, block, 0, s->stream, A[0], C, D, s->d_moments, (uint32_t)n);
                 LAUNCH_TRY("k_denoise_variance_measured");
+            }
+            if (temporal_records) {
+                int rc;
+                if ((rc = wf_launch_temporal_variance(s->stream, reinterpret_cast<float4*>(A[0]), reinterpret_cast<const float4*>(C), temporal_records, (uint32_t)n)) != SHM_OK) return rc;
             }
         }
         for (uint32_t i = 0; i < k.iterations; ++i, cur ^= 1) {
@@ -173,7 +165,7 @@ int shm_denoise_device(ShmScene* s, const ShmDenoiseParams* params, double* ms_o
             LAUNCH_TRY("k_denoise_atrous");
         }
     }
-    hipLaunchKernelGGL(k_denoise_finish, linear, block, 0, s->stream, s->d_film, (uint32_t)n, A[cur], C, D, k.iterations > 0 ? 1 : 0, s->d_denoised);
+    hipLaunchKernelGGL(k_denoise_finish, linear, block, 0, s->stream, film, (uint32_t)n, A[cur], C, D, k.iterations > 0 ? 1 : 0, s->d_denoised);
     LAUNCH_TRY("k_denoise_finish");
     HIP_TRY(hipEventRecord(e_end, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
@@ -185,6 +177,25 @@ int shm_denoise_device(ShmScene* s, const ShmDenoiseParams* params, double* ms_o
         *ms_out = (double)ms;
     }
     return SHM_OK;
+}
+
+extern "C" {
+
+int shm_denoise_default_params(ShmDenoiseParams* out) {
+    if (!out) return SHM_ERR_INVALID_ARGUMENT;
+    memset(out, 0, sizeof(*out));
+    out->iterations = 5;
+    out->demodulate = 1;
+    out->sigma_luminance = 1.5f;
+    out->sigma_normal = 128.0f;
+    out->sigma_plane = 0.1f;
+    out->albedo_floor = 0.01f;
+    return SHM_OK;
+}
+
+int shm_denoise_device(ShmScene* s, const ShmDenoiseParams* params, double* ms_out) {
+    if (!s || !params) { shm_err() = "denoise: no scene or no parameters"; return SHM_ERR_INVALID_ARGUMENT; }
+    return wf_denoise_run(s, params, s->d_film, nullptr, ms_out);
 }
 
 int shm_denoise_read(ShmScene* s, ShmFilmPixel* out) {

@@ -505,6 +505,22 @@ int shm_scene_shading_records(ShmScene* s, uint64_t* n_records_out, double* buil
     return SHM_OK;
 }
 
+// The camera lives in the scene's two views (the host's flat scene, the by-value kernel argument): both are set, nothing is uploaded. The plan is kept, so the kind stays.
+int shm_scene_set_camera(ShmScene* s, const ShmCamera* camera) {
+    if (!s || !camera) { g_err = "set_camera: no scene or no camera"; return SHM_ERR_INVALID_ARGUMENT; }
+    if (s->dist) { g_err = "set_camera: the scene holds multi-GPU state (shm_dist_init / shm_render_sharded); shm_dist_finalize first"; return SHM_ERR_UNSUPPORTED; }
+    if (camera->kind != s->flat.camera.kind) {
+        g_err = "set_camera: the camera's kind (" + std::to_string(camera->kind) + ") is not the scene's (" + std::to_string(s->flat.camera.kind) + "): the scene's plan chose its generate kernel by kind";
+        return SHM_ERR_INVALID_ARGUMENT;
+    }
+    if (camera->kind == SHM_CAMERA_SPHERICAL && camera->mapping > SHM_SPHERICAL_EQUIRECTANGULAR) { g_err = "spherical camera: unknown mapping (equal-area, equirectangular)"; return SHM_ERR_INVALID_ARGUMENT; }
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(s->stream));  // (every entry point blocks; this only says so)
+    s->flat.camera = *camera;
+    s->dsv.camera = *camera;
+    return SHM_OK;
+}
+
 int shm_film_clear(ShmScene* s) {
     if (!s) return SHM_ERR_INVALID_ARGUMENT;
     HIP_TRY(hipSetDevice(s->device));
@@ -963,6 +979,7 @@ int shm_gbuffer_render_wave(ShmScene* s, const ShmRenderParams* params, uint32_t
     });
     if (rc != SHM_OK) return rc;
     s->gbuffer_filled = true;
+    s->gbuffer_space = space;
     return stats ? add_wave_stats(r, false, stats) : SHM_OK;
 }
 

@@ -424,6 +424,13 @@ struct ShmScene {
     ShmTile* d_moments_tiles = nullptr;    // that pass's own tile list and its per-tile result, one allocation in `allocs`, regrown on demand
     ShmTileError* d_tile_error = nullptr;
     uint32_t moments_tiles_capacity = 0;
+    uint32_t gbuffer_space = 0;            // SHM_GBUFFER_SPACE_* of the last G-buffer wave: the temporal pass reprojects render-space positions only
+    float4* d_temporal[2] = {nullptr, nullptr};  // the temporal pass's two record arrays (k_temporal.hip: four float4 per pixel) and, behind them, its result: one allocation, made by the first shm_temporal_clear / _accumulate_device
+    ShmFilmPixel* d_temporal_out = nullptr;
+    int temporal_cur = 0;                  // which array holds the records just written
+    bool temporal_has_camera = false;      // an accumulate has run since the last clear: temporal_camera is the camera it saw, d_temporal[temporal_cur] its records
+    bool temporal_filled = false;          // d_temporal_out holds a result
+    ShmCamera temporal_camera = {};
 };
 // dist.hip: releases s->dist (RCCL communicator included); called by shm_scene_destroy
 __attribute__((visibility("hidden"))) void wf_dist_release(ShmScene* s);
@@ -540,6 +547,11 @@ struct GBufferArgs {
     int film_weight;
 };
 WF_INTERNAL int wf_launch_gbuffer(ShmScene* s, const GBufferArgs& a);
+// k_denoise.hip: shm_denoise_device's body over `film` — the scene's, or the temporal pass's result (shm_denoise_temporal_device, k_temporal.hip) — into ShmScene::d_denoised;
+// `temporal_records` not null: behind the variance pass, k_temporal.hip's kernel puts the records' temporal variance over plane A's at the pixels whose history is long enough
+WF_INTERNAL int wf_denoise_run(ShmScene* s, const ShmDenoiseParams* params, const ShmFilmPixel* film, const float4* temporal_records, double* ms_out);
+// k_temporal.hip: that kernel, on `stream`; A, C: the denoiser's planes (e.rgb | var, p.xyz | valid)
+WF_INTERNAL int wf_launch_temporal_variance(hipStream_t stream, float4* A, const float4* C, const float4* temporal_records, uint32_t n);
 // The shading launchers of one scene class: a cell of render.hip's table by geometry x image class x sampler x extended build (nullptr: no such
 // build, shm_plan::serving_build), of which select_kernels makes a render's set by the RenderPlan's coordinates. The plan says which of them run; the bounce loop calls them.
 struct ShadeKernels {

@@ -217,6 +217,46 @@ class Renderer:
         abi.check(self.lib, self.lib.shm_denoise(self.handle, C.byref(d), out.ctypes.data_as(C.c_void_p), C.byref(ms)), "shm_denoise")
         return (out, float(ms.value)) if return_ms else out
 
+    # ---- a moving camera and temporal accumulation (include/shimmer_hip.h "temporal accumulation") ----
+    def set_camera(self, camera):
+        """shm_scene_set_camera: the next wave renders from `camera` (an abi.ShmCamera of the scene's kind, in the scene's render space: camera_in_scene builds one).
+        Film, G-buffer, moments and history stay as they are."""
+        abi.check(self.lib, self.lib.shm_scene_set_camera(self.handle, C.byref(camera)), "shm_scene_set_camera")
+
+    def temporal_clear(self):
+        """shm_temporal_clear: forget the history and the camera it was seen through."""
+        abi.check(self.lib, self.lib.shm_temporal_clear(self.handle), "shm_temporal_clear")
+
+    def temporal_accumulate(self, tparams=None, return_ms=False):
+        """shm_temporal_accumulate_device: the device film and G-buffer of the frame just rendered into the history (a render-space G-buffer wave must have run).
+        tparams: an abi.ShmTemporalParams (None: the defaults). Returns the kernel's HIP-event milliseconds when asked; read_temporal gives the result."""
+        t = tparams if tparams is not None else make_temporal_params(self.lib)
+        ms = C.c_double(0.0)
+        abi.check(self.lib, self.lib.shm_temporal_accumulate_device(self.handle, C.byref(t), C.byref(ms)), "shm_temporal_accumulate_device")
+        return float(ms.value) if return_ms else None
+
+    def read_temporal(self):
+        """The accumulated frame as a FILM_DTYPE array: rgb_sum the sensor RGB, weight_sum 1 — what film_get_image takes."""
+        out = np.zeros((self.height, self.width), dtype=FILM_DTYPE)
+        abi.check(self.lib, self.lib.shm_temporal_read(self.handle, out.ctypes.data_as(C.c_void_p)), "shm_temporal_read")
+        return out
+
+    def read_temporal_history(self):
+        """The records the last accumulate wrote, as a TEMPORAL_DTYPE array."""
+        out = np.zeros((self.height, self.width), dtype=TEMPORAL_DTYPE)
+        abi.check(self.lib, self.lib.shm_temporal_read_history(self.handle, out.ctypes.data_as(C.c_void_p)), "shm_temporal_read_history")
+        return out
+
+    def denoise_temporal(self, dparams=None, temporal_variance=1, return_ms=False):
+        """shm_denoise_temporal_device + shm_denoise_read: the a-trous filter over the accumulated frame; temporal_variance 1 takes the filter's initial variance
+        from the history's luminance moments where the history holds four frames or more."""
+        d = dparams if dparams is not None else make_denoise_params(self.lib)
+        out = np.zeros((self.height, self.width), dtype=FILM_DTYPE)
+        ms = C.c_double(0.0)
+        abi.check(self.lib, self.lib.shm_denoise_temporal_device(self.handle, C.byref(d), int(temporal_variance), C.byref(ms)), "shm_denoise_temporal_device")
+        abi.check(self.lib, self.lib.shm_denoise_read(self.handle, out.ctypes.data_as(C.c_void_p)), "shm_denoise_read")
+        return (out, float(ms.value)) if return_ms else out
+
     # ---- adaptive sampling (include/shimmer_hip.h "adaptive sampling"; DESIGN.md section 4k) ----
     def moments_clear(self):
         """shm_moments_clear: zero records that count from the device film as it stands."""
@@ -352,6 +392,119 @@ def render_denoised(lib, desc, params, dparams=None, device=0, matrix=None, rend
         den, ms = r.denoise(dparams, return_ms=True)
     return {"film": film, "denoised": den, "noisy": film_get_image(lib, film, matrix), "image": film_get_image(lib, den, matrix), "gbuffer": g, "stats": stats,
             "denoise_ms": ms}
+
+
+TEMPORAL_DTYPE = np.dtype([("rgb", "<f4", (3,)), ("m1", "<f4"), ("m2", "<f4"), ("length", "<f4"), ("p", "<f4", (3,)), ("ns", "<f4", (3,)), ("pad", "<u4", (4,))])
+assert TEMPORAL_DTYPE.itemsize == C.sizeof(abi.ShmTemporalPixel)
+
+
+def make_temporal_params(lib, **overrides):
+    """shm_temporal_default_params, with any of alpha_min, alpha_min_moments, max_history, normal_cos_min, plane_tolerance, albedo_floor, demodulate set by keyword."""
+    t = abi.ShmTemporalParams()
+    abi.check(lib, lib.shm_temporal_default_params(C.byref(t)), "shm_temporal_default_params")
+    names = ("alpha_min", "alpha_min_moments", "max_history", "normal_cos_min", "plane_tolerance", "albedo_floor", "demodulate")
+    return _with_overrides("make_temporal_params", t, names, overrides)
+
+
+def temporal_accumulate_host(lib, film, gbuffer, white, camera, history=None, previous_camera=None, tparams=None):
+    """shm_temporal_accumulate_host, the temporal pass's CPU twin: one frame from (H, W) FILM_DTYPE and GBUFFER_DTYPE arrays, gbuffer_white's W, the frame's
+    abi.ShmCamera and — where there is a previous frame — its TEMPORAL_DTYPE records and camera. Returns (the new records, the FILM_DTYPE result): what
+    Renderer.read_temporal_history / read_temporal give for the same inputs, bit for bit. No GPU needed."""
+    f = np.ascontiguousarray(film, dtype=FILM_DTYPE)
+    g = np.ascontiguousarray(gbuffer, dtype=GBUFFER_DTYPE)
+    if f.ndim != 2 or g.shape != f.shape:
+        raise ValueError("temporal_accumulate_host: film and gbuffer must be (height, width) arrays of one shape")
+    h = None
+    if history is not None:
+        h = np.ascontiguousarray(history, dtype=TEMPORAL_DTYPE)
+        if h.shape != f.shape:
+            raise ValueError("temporal_accumulate_host: history must have the film's shape")
+    t = tparams if tparams is not None else make_temporal_params(lib)
+    w = (C.c_double * 3)(*[float(x) for x in white])
+    records = np.zeros(f.shape, dtype=TEMPORAL_DTYPE)
+    out = np.zeros(f.shape, dtype=FILM_DTYPE)
+    abi.check(lib, lib.shm_temporal_accumulate_host(f.ctypes.data_as(C.c_void_p), g.ctypes.data_as(C.c_void_p), None if h is None else h.ctypes.data_as(C.c_void_p),
+                                                    C.byref(camera), None if previous_camera is None else C.byref(previous_camera), f.shape[1], f.shape[0], w,
+                                                    C.byref(t), records.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)), "shm_temporal_accumulate_host")
+    return records, out
+
+
+def denoise_temporal_host(lib, temporal, gbuffer, history, white, dparams=None, temporal_variance=1):
+    """shm_denoise_temporal_host: Renderer.denoise_temporal's CPU twin, from read_temporal's, read_gbuffer's and read_temporal_history's arrays."""
+    f = np.ascontiguousarray(temporal, dtype=FILM_DTYPE)
+    g = np.ascontiguousarray(gbuffer, dtype=GBUFFER_DTYPE)
+    h = np.ascontiguousarray(history, dtype=TEMPORAL_DTYPE)
+    if f.ndim != 2 or g.shape != f.shape or h.shape != f.shape:
+        raise ValueError("denoise_temporal_host: temporal, gbuffer and history must be (height, width) arrays of one shape")
+    d = dparams if dparams is not None else make_denoise_params(lib)
+    w = (C.c_double * 3)(*[float(x) for x in white])
+    out = np.zeros(f.shape, dtype=FILM_DTYPE)
+    abi.check(lib, lib.shm_denoise_temporal_host(f.ctypes.data_as(C.c_void_p), g.ctypes.data_as(C.c_void_p), h.ctypes.data_as(C.c_void_p), f.shape[1], f.shape[0], w,
+                                                 C.byref(d), int(temporal_variance), out.ctypes.data_as(C.c_void_p)), "shm_denoise_temporal_host")
+    return out
+
+
+def camera_in_scene(lib, builder_or_rfw, pos, look_at, up, fov=90.0, full_resolution=None, lens_radius=0.0, focal_distance=1e6, orthographic=False,
+                    frame_aspect_ratio=0.0, screen_window=None):
+    """A second camera for a scene that exists: shm_look_at + shm_camera_create_in, in the render space the scene's geometry was baked in. builder_or_rfw: the
+    SceneBuilder the scene was made from (its render_from_world and film resolution are taken) or a (4, 4) render_from_world with `full_resolution` given.
+    Returns the abi.ShmCamera Renderer.set_camera takes."""
+    rfw = getattr(builder_or_rfw, "render_from_world", builder_or_rfw)
+    if rfw is None:
+        raise ValueError("camera_in_scene: the builder has no camera yet (set_camera_look_at returns and keeps render_from_world)")
+    if full_resolution is None:
+        film = getattr(builder_or_rfw, "film", None)
+        if film is None:
+            raise ValueError("camera_in_scene: full_resolution is needed with a bare render_from_world")
+        full_resolution = tuple(film.full_resolution)
+    rfw32 = np.ascontiguousarray(rfw, dtype=np.float32).reshape(16)
+    wfc32 = np.zeros(16, np.float32)
+    f32 = lambda v: np.ascontiguousarray(v, dtype=np.float32)
+    pos32, look32, up32 = f32(pos), f32(look_at), f32(up)
+    abi.check(lib, lib.shm_look_at(pos32.ctypes.data_as(abi.c_float_p), look32.ctypes.data_as(abi.c_float_p), up32.ctypes.data_as(abi.c_float_p),
+                                   wfc32.ctypes.data_as(abi.c_float_p)), "shm_look_at")
+    p = abi.ShmCameraParams()
+    p.kind = abi.SHM_CAMERA_ORTHOGRAPHIC if orthographic else abi.SHM_CAMERA_PERSPECTIVE
+    p.world_from_camera[:] = [float(x) for x in wfc32]
+    p.fov_deg = float(fov)
+    p.full_resolution[:] = [int(full_resolution[0]), int(full_resolution[1])]
+    p.lens_radius, p.focal_distance, p.frame_aspect_ratio = float(lens_radius), float(focal_distance), float(frame_aspect_ratio)
+    if screen_window is not None:
+        p.has_screen_window = 1
+        p.screen_window[:] = [float(x) for x in screen_window]
+    cam = abi.ShmCamera()
+    abi.check(lib, lib.shm_camera_create_in(C.byref(p), rfw32.ctypes.data_as(abi.c_float_p), C.byref(cam)), "shm_camera_create_in")
+    return cam
+
+
+def render_frames(lib, desc, cameras, params, tparams=None, dparams=None, temporal_variance=1, device=0, matrix=None, renderer=None):
+    """A sequence of frames of one static scene under a moving camera, accumulated over time. cameras: one abi.ShmCamera per frame (camera_in_scene; None keeps the
+    camera as it is). params.samples_per_pixel is the TOTAL over the sequence and a multiple of the frame count: frame f renders samples [f spp, (f + 1) spp) of it,
+    so that no two frames share a sample. Per frame: set_camera, clear film and G-buffer, one render wave and one G-buffer wave over those samples,
+    temporal_accumulate, and — with dparams — denoise_temporal. Returns a list of dicts: "film", "temporal" and, where filtered, "denoised" (FILM_DTYPE), "image"
+    (film_get_image of the last of them under `matrix`) and "temporal_ms"."""
+    n = len(cameras)
+    if n < 1 or params.samples_per_pixel % n:
+        raise ValueError("render_frames: params.samples_per_pixel is the total over the frames and must be a multiple of their count")
+    spp = params.samples_per_pixel // n
+    frames = []
+    with _renderer_for(lib, desc, device, renderer) as r:
+        r.temporal_clear()
+        for f, cam in enumerate(cameras):
+            if cam is not None:
+                r.set_camera(cam)
+            r.clear()
+            r.gbuffer_clear()
+            r.render_waves(params, waves=[(f * spp, (f + 1) * spp)])
+            r.gbuffer_wave(params, f * spp, (f + 1) * spp)
+            ms = r.temporal_accumulate(tparams, return_ms=True)
+            out = {"film": r.read_film(), "temporal": r.read_temporal(), "temporal_ms": ms}
+            last = out["temporal"]
+            if dparams is not None:
+                last = out["denoised"] = r.denoise_temporal(dparams, temporal_variance)
+            out["image"] = film_get_image(lib, last, matrix)
+            frames.append(out)
+    return frames
 
 
 MOMENTS_DTYPE = np.dtype([("prev", "<f8", (4,)), ("mean", "<f8", (3,)), ("m2", "<f8", (3,)), ("weight", "<f8"), ("batches", "<f8")])

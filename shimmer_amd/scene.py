@@ -157,6 +157,7 @@ class SceneBuilder:
         self.spec = []         # list of float32 arrays (spectrum pool)
         self.spec_len = 0
         self.camera = None
+        self.render_from_world = None  # (4, 4) f32: what the camera call returned, for a later camera in the same render space (render.camera_in_scene)
         self.film = None
         self._keep = []
         self._tri_count = 0
@@ -800,6 +801,7 @@ class SceneBuilder:
             abi.check(lib, lib.shm_camera_perspective(_fptr(wfc32), float(fov), res, float(lens_radius), float(focal_distance),
                                                       C.byref(cam), _fptr(rfw)), "shm_camera_perspective")
         self.camera = cam
+        self.render_from_world = rfw.reshape(4, 4).copy()
         return rfw.reshape(4, 4)
 
     SPHERICAL_MAPPINGS = {"equalarea": abi.SHM_SPHERICAL_EQUAL_AREA, "equirectangular": abi.SHM_SPHERICAL_EQUIRECTANGULAR}
@@ -817,6 +819,7 @@ class SceneBuilder:
         abi.check(lib, lib.shm_camera_spherical(_fptr(wfc32), self.SPHERICAL_MAPPINGS[mapping], res, abi.SHM_RENDER_SPACE_CAMERA_WORLD, C.byref(cam), _fptr(rfw)),
                   "shm_camera_spherical")
         self.camera = cam
+        self.render_from_world = rfw.reshape(4, 4).copy()
         return rfw.reshape(4, 4)
 
     # ---- finalize ----
