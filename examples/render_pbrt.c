@@ -3,7 +3,9 @@
  * through the C ABI of include/shimmer_hip.h, with no Python and no torch in the process.
  *
  *   gcc -O2 -I include examples/render_pbrt.c -L shimmer_amd/csrc -lshimmer_hip -Wl,-rpath,$PWD/shimmer_amd/csrc -o render_pbrt
- *   ./render_pbrt scene.pbrt [out.pfm] [--spp N] [--devices K]
+ *   ./render_pbrt scene.pbrt [out.pfm] [--spp N] [--devices K] [--png out.png]
+ * --png: the picture as well — the display pass (shm_display with its defaults: ACES, sRGB, exposure 1, under the film's output matrix) on the film where it was
+ * rendered, written by shm_write_png. The render then runs on one scene on the first device, whose film the pass reads; the PFM is that film's.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -18,14 +20,16 @@ static int die(const char* what) {
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        fprintf(stderr, "usage: %s scene.pbrt [out.pfm] [--spp N] [--devices K]\n", argv[0]);
+        fprintf(stderr, "usage: %s scene.pbrt [out.pfm] [--spp N] [--devices K] [--png out.png]\n", argv[0]);
         return 2;
     }
     const char* out_path = NULL;
+    const char* png_path = NULL;
     int spp = 0, n_devices = 0;
     for (int i = 2; i < argc; ++i) {
         if (!strcmp(argv[i], "--spp") && i + 1 < argc) spp = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--devices") && i + 1 < argc) n_devices = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--png") && i + 1 < argc) png_path = argv[++i];
         else out_path = argv[i];
     }
     ShmPbrtScene* s = NULL;
@@ -44,8 +48,28 @@ int main(int argc, char** argv) {
     ShmStats* stats = (ShmStats*)calloc((size_t)n_devices, sizeof(ShmStats));
     float* rgb = (float*)malloc(sizeof(float) * 3 * (size_t)w * (size_t)h);
     if (!film || !stats || !rgb) { fprintf(stderr, "out of memory\n"); return 1; }
-    /* ImageTileIntegrator::render on every device: tiles sharded inside the library, film rows gathered over xGMI */
-    if (shm_render_multi(&s->desc, devices, n_devices, &s->params, film, stats) != SHM_OK) return die("shm_render_multi");
+    if (png_path) {
+        /* one scene on the first device: ImageTileIntegrator::render into its film, which the display pass then reads in HBM (4 bytes per pixel come back) */
+        ShmScene* scene = NULL;
+        uint32_t n_tiles = 0;
+        ShmTile* tiles = (ShmTile*)malloc(sizeof(ShmTile) * (size_t)((w + 7) / 8) * (size_t)((h + 7) / 8));
+        uint32_t* rgba8 = (uint32_t*)malloc(sizeof(uint32_t) * (size_t)w * (size_t)h);
+        ShmDisplayParams dp;
+        if (!tiles || !rgba8) { fprintf(stderr, "out of memory\n"); return 1; }
+        n_devices = 1;
+        if (shm_scene_create(&s->desc, devices[0], &scene) != SHM_OK) return die("shm_scene_create");
+        if (shm_tile_bounds(pb, 8, 8, tiles, &n_tiles) != SHM_OK) return die("shm_tile_bounds");
+        if (shm_render(scene, &s->params, tiles, n_tiles, film, stats) != SHM_OK) return die("shm_render");
+        if (shm_display_default_params(&dp) != SHM_OK) return die("shm_display_default_params");
+        memcpy(dp.output_rgb_from_sensor_rgb, s->output_rgb_from_sensor_rgb, sizeof(dp.output_rgb_from_sensor_rgb));
+        if (shm_display(scene, &dp, rgba8, NULL, NULL) != SHM_OK) return die("shm_display");
+        if (shm_write_png(png_path, rgba8, w, h) != SHM_OK) return die("shm_write_png");
+        shm_scene_destroy(scene);
+        free(rgba8); free(tiles);
+    } else if (shm_render_multi(&s->desc, devices, n_devices, &s->params, film, stats) != SHM_OK) {
+        /* (ImageTileIntegrator::render on every device: tiles sharded inside the library, film rows gathered over xGMI) */
+        return die("shm_render_multi");
+    }
     unsigned long long rays = 0;
     double ms = 0.0;
     for (int i = 0; i < n_devices; ++i) {

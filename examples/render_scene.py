@@ -10,11 +10,13 @@
     python examples/render_scene.py cornell_probe                    (examples/scenes/cornell_probe.pbrt: an equal-area probe in the middle of the Cornell box)
     python examples/render_scene.py cornell --spp 256 --adaptive 0.05 [--min-spp 16] [--batch-spp 4]   (adaptive sampling: --spp is the cap)
     python examples/render_scene.py cornell --spp 4 --frames 16 --orbit 1 --temporal [--denoise]        (a turntable accumulated over time: <name>.fNNN.pfm / .png per frame)
+    python examples/render_scene.py cornell --tonemap aces --auto-exposure [--dither] [--frames 16 --orbit 1 --frame-time 0.033]   (the .png from the display pass on the device: DESIGN.md section 4m)
 
 Everything goes through the C ABI of include/shimmer_hip.h (shimmer_amd/abi.py is the ctypes binding): scene description ->
 shm_scene_create -> shm_render_device -> shm_film_read -> shm_film_get_image -> shm_write_pfm. Needs an MI355X: there is no CPU path.
 """
 import argparse
+import ctypes as C
 import os
 import struct
 import sys
@@ -103,6 +105,39 @@ def write_ldr_png(path, image, exposure):
     write_png(path, (ldr * 255 + 0.5).astype(np.uint8))
 
 
+TONEMAPS = {"none": abi.SHM_TONEMAP_NONE, "reinhard": abi.SHM_TONEMAP_REINHARD, "aces": abi.SHM_TONEMAP_ACES}
+
+
+class Pictures:
+    """The script's .png files. Without a display option: the host arithmetic above on the float image. With one (--tonemap, --auto-exposure, --dither,
+    --frame-time): the display pass on the stage's buffer where it lies on the device — 4 bytes per pixel come back — written by
+    shm_write_png; --exposure is then the manual exposure or, with --auto-exposure, the compensation."""
+
+    def __init__(self, lib, r, args):
+        self.lib, self.r, self.args = lib, r, args
+        self.on = args.tonemap is not None or args.auto_exposure or args.dither or args.frame_time is not None
+        self.frame_scale = None  # the scale the frame's first picture was given: its other pictures take the same (one adaptation step per frame)
+        if self.on and args.auto_exposure:
+            r.display_clear()
+
+    def next_frame(self):
+        self.frame_scale = None
+
+    def write(self, path, source, image=None):
+        """source: abi.SHM_DISPLAY_SOURCE_*, the stage that produced the picture; image: its float image, for the host arithmetic."""
+        a = self.args
+        if not self.on:
+            return write_ldr_png(path, image, a.exposure)
+        metered = a.auto_exposure and self.frame_scale is None
+        d = render.make_display_params(self.lib, source=source, tonemap=TONEMAPS[a.tonemap or "none"], dither=int(a.dither), auto_exposure=int(metered),
+                                       exposure=a.exposure if metered or not a.auto_exposure else self.frame_scale, dt=a.frame_time or 0.0,
+                                       output_rgb_from_sensor_rgb=render.SRGB_FROM_XYZ)
+        rgba8, state = self.r.display(d, return_state=True)
+        if metered:
+            self.frame_scale = state["scale"]
+        render.write_png(self.lib, path, rgba8)
+
+
 def render_sequence(lib, args, sc, r, w, h):
     """--frames: one scene, one camera per frame, --spp new samples per frame; with --temporal the frames are accumulated (and, with --denoise, filtered)."""
     if args.adaptive is not None or args.aovs:
@@ -113,16 +148,34 @@ def render_sequence(lib, args, sc, r, w, h):
         raise SystemExit("--frames with --denoise filters the accumulated frame: add --temporal")
     p = render.make_params(seed=args.seed, spp=args.frames * args.spp, max_depth=args.max_depth, integrator=args.integrator, reference_quirks=not args.quirks_off,
                            sampler=args.sampler)
-    stem = os.path.splitext(args.output or f"{args.scene.replace(':', '_')}.pfm")[0]
+    out = args.output or f"{args.scene.replace(':', '_')}.pfm"
+    stem = os.path.splitext(out)[0]
+    pictures = Pictures(lib, r, args)
+    pfm = not (pictures.on and out.endswith(".png"))  # -o <name>.png with a display option: pictures only, and no float image is read back
 
-    def write(path_stem, film):
-        img = np.ascontiguousarray(render.film_get_image(lib, film, render.SRGB_FROM_XYZ), np.float32)
-        abi.check(lib, lib.shm_write_pfm(f"{path_stem}.pfm".encode(), img.ctypes.data_as(abi.c_float_p), w, h), "shm_write_pfm")
-        write_ldr_png(f"{path_stem}.png", img, args.exposure)
+    def write(path_stem, source, read):
+        img = None
+        if pfm:
+            img = np.ascontiguousarray(render.film_get_image(lib, read(), render.SRGB_FROM_XYZ), np.float32)
+            abi.check(lib, lib.shm_write_pfm(f"{path_stem}.pfm".encode(), img.ctypes.data_as(abi.c_float_p), w, h), "shm_write_pfm")
+        pictures.write(f"{path_stem}.png", source, img)
+
+    def denoise_temporal():
+        """The filter over the accumulated frame, left on the device: (read, its milliseconds)."""
+        ms = C.c_double(0.0)
+        d = render.make_denoise_params(lib)
+        abi.check(lib, lib.shm_denoise_temporal_device(r.handle, C.byref(d), 1, C.byref(ms)), "shm_denoise_temporal_device")
+
+        def read():
+            den = np.zeros((h, w), dtype=render.FILM_DTYPE)
+            abi.check(lib, lib.shm_denoise_read(r.handle, den.ctypes.data_as(C.c_void_p)), "shm_denoise_read")
+            return den
+        return read, float(ms.value)
 
     if args.temporal:
         r.temporal_clear()
     for f in range(args.frames):
+        pictures.next_frame()
         if args.orbit != 0.0 and f > 0:
             r.set_camera(orbit_camera(lib, sc, args.scene, args.orbit * f))
         r.clear()
@@ -134,16 +187,17 @@ def render_sequence(lib, args, sc, r, w, h):
             r.gbuffer_clear()
             r.gbuffer_wave(p, f * args.spp, (f + 1) * args.spp)
             ms = r.temporal_accumulate(return_ms=True)
-            write(f"{stem}.f{f:03d}", r.read_temporal())
+            write(f"{stem}.f{f:03d}", abi.SHM_DISPLAY_SOURCE_TEMPORAL, r.read_temporal)
             text += f", accumulated in {ms:.3f} ms"
             if args.denoise:
-                den, dms = r.denoise_temporal(return_ms=True)
-                write(f"{stem}.f{f:03d}.denoised", den)
+                read, dms = denoise_temporal()
+                write(f"{stem}.f{f:03d}.denoised", abi.SHM_DISPLAY_SOURCE_DENOISED, read)
                 text += f", filtered in {dms:.3f} ms"
         else:
-            write(f"{stem}.f{f:03d}", r.read_film())
+            write(f"{stem}.f{f:03d}", abi.SHM_DISPLAY_SOURCE_FILM, r.read_film)
         print(text)
-    print(f"wrote {stem}.f000 .. f{args.frames - 1:03d} (.pfm, .png" + (", .denoised.pfm, .denoised.png)" if args.denoise else ")"))
+    kinds = (".pfm, .png" if pfm else ".png") + ((", .denoised.pfm, .denoised.png" if pfm else ", .denoised.png") if args.denoise else "")
+    print(f"wrote {stem}.f000 .. f{args.frames - 1:03d} ({kinds})")
     r.close()
 
 
@@ -179,6 +233,15 @@ def main():
     ap.add_argument("--orbit", type=float, default=0.0, metavar="DEG", help="with --frames: the camera turns DEG degrees a frame about what it looks at (shm_scene_set_camera)")
     ap.add_argument("--temporal", action="store_true", help="with --frames: each frame is accumulated into a history reprojected through the G-buffer (DESIGN.md section 4l); "
                                                             "with --denoise the accumulated frame is filtered as well (<name>.fNNN.denoised.pfm and .png)")
+    ap.add_argument("--tonemap", default=None, choices=sorted(TONEMAPS), help="the display pass's tone curve (DESIGN.md section 4m). This and the next three options make "
+                                                                              "every .png the script writes come from the display pass on the device (the stage that "
+                                                                              "produced the image is its source), written by shm_write_png; with them -o <name>.png "
+                                                                              "writes pictures only and reads no float image back")
+    ap.add_argument("--auto-exposure", action="store_true", help="meter the exposure from the frame's log-luminance histogram; --exposure is then a compensation, and over "
+                                                                 "--frames the exposure adapts by --frame-time a frame")
+    ap.add_argument("--dither", action="store_true", help="8x8 ordered dither before the 8-bit quantisation")
+    ap.add_argument("--frame-time", type=float, default=None, metavar="SECONDS", help="with --frames and --auto-exposure: the time between two frames (the adaptation's dt; "
+                                                                                      "0 or absent: every frame jumps to its own exposure)")
     ap.add_argument("-o", "--output", default="")
     args = ap.parse_args()
     lib = abi.load_library()
@@ -202,17 +265,19 @@ def main():
         aparams = render.make_adaptive_params(lib, threshold=args.adaptive, **over)
         tile_spp, st = r.render_adaptive(p, aparams)
     dt = time.perf_counter() - t0
-    film = r.read_film()
     rays = st["rays_closest"] + st["rays_any"]
     spp_text = f"{args.spp} spp" if tile_spp is None else f"{st['paths'] / (w * h):.1f} spp on average (tiles from {tile_spp.min()} to {tile_spp.max()}, cap {args.spp})"
     print(f"{sc.name}: {w}x{h} x {spp_text}, {rays / 1e6:.1f} Mrays in {dt * 1e3:.1f} ms = {rays / dt / 1e6:.0f} Mray/s")
-    img = render.film_get_image(lib, film, render.SRGB_FROM_XYZ)  # RgbFilm::get_image with an sRGB output matrix
     out = args.output or f"{args.scene.replace(':', '_')}.pfm"
-    img = np.ascontiguousarray(img, np.float32)
-    abi.check(lib, lib.shm_write_pfm(out.encode(), img.ctypes.data_as(abi.c_float_p), w, h), "shm_write_pfm")
-    write_ldr = lambda path, image: write_ldr_png(path, image, args.exposure)
-    write_ldr(os.path.splitext(out)[0] + ".png", img)
-    print("wrote", out, "and", os.path.splitext(out)[0] + ".png")
+    pictures = Pictures(lib, r, args)
+    pfm = not (pictures.on and out.endswith(".png"))  # -o <name>.png with a display option: the picture only, and no float image is read back
+    img = None
+    if pfm:
+        img = render.film_get_image(lib, r.read_film(), render.SRGB_FROM_XYZ)  # RgbFilm::get_image with an sRGB output matrix
+        img = np.ascontiguousarray(img, np.float32)
+        abi.check(lib, lib.shm_write_pfm(out.encode(), img.ctypes.data_as(abi.c_float_p), w, h), "shm_write_pfm")
+    pictures.write(os.path.splitext(out)[0] + ".png", abi.SHM_DISPLAY_SOURCE_FILM, img)
+    print(*(("wrote", out, "and", os.path.splitext(out)[0] + ".png") if pfm else ("wrote", out)))
     if tile_spp is not None:  # what the adaptive render measured and where it spent its samples
         stem = os.path.splitext(out)[0]
         count = np.ascontiguousarray(np.repeat(render.tile_spp_image(tile_spp, w, h)[..., None], 3, axis=2), np.float32)
@@ -229,12 +294,18 @@ def main():
         print("wrote", ", ".join(f"{stem}.{n}.pfm" for n in ("albedo", "normal", "position")), f"(coverage {float(aov['coverage'].mean()):.3f})")
     if args.denoise:  # the film is still on the device; the pass fills the G-buffer the filter is guided by (a second pass after --aovs's gives the same sums)
         r.gbuffer(p)
-        den, ms = r.denoise(return_ms=True)
-        dimg = np.ascontiguousarray(render.film_get_image(lib, den, render.SRGB_FROM_XYZ), np.float32)
         stem = os.path.splitext(out)[0]
-        abi.check(lib, lib.shm_write_pfm(f"{stem}.denoised.pfm".encode(), dimg.ctypes.data_as(abi.c_float_p), w, h), "shm_write_pfm")
-        write_ldr(f"{stem}.denoised.png", dimg)
-        print(f"wrote {stem}.denoised.pfm and {stem}.denoised.png (denoiser: {ms:.3f} ms)")
+        dimg = None
+        if pfm:
+            den, ms = r.denoise(return_ms=True)
+            dimg = np.ascontiguousarray(render.film_get_image(lib, den, render.SRGB_FROM_XYZ), np.float32)
+            abi.check(lib, lib.shm_write_pfm(f"{stem}.denoised.pfm".encode(), dimg.ctypes.data_as(abi.c_float_p), w, h), "shm_write_pfm")
+        else:  # the result stays on the device: the display pass reads it there
+            ms_c, dparams = C.c_double(0.0), render.make_denoise_params(lib)
+            abi.check(lib, lib.shm_denoise_device(r.handle, C.byref(dparams), C.byref(ms_c)), "shm_denoise_device")
+            ms = float(ms_c.value)
+        pictures.write(f"{stem}.denoised.png", abi.SHM_DISPLAY_SOURCE_DENOISED, dimg)
+        print((f"wrote {stem}.denoised.pfm and {stem}.denoised.png" if pfm else f"wrote {stem}.denoised.png") + f" (denoiser: {ms:.3f} ms)")
     r.close()
 
 

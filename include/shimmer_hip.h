@@ -804,6 +804,80 @@ SHM_API int shm_denoise_temporal_device(ShmScene* scene, const ShmDenoiseParams*
 SHM_API int shm_denoise_temporal_host(const ShmFilmPixel* temporal, const ShmGBufferPixel* gbuffer, const ShmTemporalPixel* history, int32_t width, int32_t height,
                                       const double white[3], const ShmDenoiseParams* params, uint32_t temporal_variance, ShmFilmPixel* out);
 
+/* ---- the display pass: auto-exposure, tone mapping and 8-bit output on the device ------------------------
+ * From a float film to a picture, while the film is still in HBM: 32 bytes per pixel in, 4 out. Per pixel, in this order:
+ *   linear     rgb = rgb_sum / weight_sum (where the weight is not 0) times output_rgb_from_sensor_rgb: shm_film_get_image's arithmetic with write_fp16 = 0
+ *   luminance  Y = 0.2126 R + 0.7152 G + 0.0722 B
+ *   histogram  256 bins of log2(Y): bin 0 below log2_min, bin 255 at and above log2_max, bins 1 .. 254 of equal width between. A pixel counts iff its weight_sum is
+ *              not 0 and Y is finite and above 0.
+ *   exposure   the mean of the bins' centres (bins 0 and 255: log2_min and log2_max) over the counted mass between percentile_low N and percentile_high N, a bin that
+ *              straddles an end counted in part; log2_target = log2(key) - mean, 0 where nothing counts
+ *   adapt      log2_exposure = previous + (log2_target - previous) (1 - exp(-adaptation_rate dt)); log2_target itself when the scene has no valid state yet, dt <= 0 or
+ *              adaptation_rate <= 0. scale = exposure 2^log2_exposure
+ *   sanitise   c = c scale > 0 ? min(c scale, 65504) : 0 per channel: NaN and negative values become 0, +inf the reference's f16 cap
+ *   tone       SHM_TONEMAP_NONE; SHM_TONEMAP_REINHARD: Yd = Y (1 + Y / white^2) / (1 + Y) on the luminance, every channel times Yd / Y; SHM_TONEMAP_ACES: Narkowicz's
+ *              fit x (2.51 x + 0.03) / (x (2.43 x + 0.59) + 0.14) per channel. Then a clamp to [0, 1].
+ *   transfer   SHM_TRANSFER_LINEAR, or SHM_TRANSFER_SRGB: v <= 0.0031308 ? 12.92 v : 1.055 v^(1 / 2.4) - 0.055
+ *   quantise   floor(255 v + 0.5); with dither, floor(255 v + (b + 0.5) / 64), b the 8x8 recursive Bayer matrix at (x & 7, y & 7) of the pixel's film coordinates.
+ *              The pixel is the four bytes R, G, B, 255 in memory order.
+ * With auto_exposure = 0 the histogram, the exposure and the adaptation are skipped: scale = exposure, and neither the counts nor the state change.
+ * Device and CPU twin run the same header (shm/display.h), with its own log2, log and exp, and give the same bits. */
+#define SHM_DISPLAY_SOURCE_FILM 0u      /* the scene's film */
+#define SHM_DISPLAY_SOURCE_DENOISED 1u  /* the denoiser's last result (shm_denoise_device / shm_denoise_temporal_device) */
+#define SHM_DISPLAY_SOURCE_TEMPORAL 2u  /* the temporal pass's last result (shm_temporal_accumulate_device) */
+#define SHM_TONEMAP_NONE 0u
+#define SHM_TONEMAP_REINHARD 1u
+#define SHM_TONEMAP_ACES 2u
+#define SHM_TRANSFER_LINEAR 0u
+#define SHM_TRANSFER_SRGB 1u
+typedef struct ShmDisplayParams {   /* 96 bytes; offsets in the comments */
+    uint32_t source;            /*  0: SHM_DISPLAY_SOURCE_* (the CPU twin takes its film as an argument and only checks the value) */
+    uint32_t tonemap;           /*  4: SHM_TONEMAP_* */
+    uint32_t transfer;          /*  8: SHM_TRANSFER_* */
+    uint32_t auto_exposure;     /* 12: 0: scale = exposure; otherwise the histogram's exposure, adapted, times `exposure` as a compensation */
+    uint32_t dither;            /* 16: 0 or not 0 */
+    float exposure;             /* 20: > 0 */
+    float key;                  /* 24: > 0: the luminance the metered mean is brought to */
+    float white;                /* 28: > 0: SHM_TONEMAP_REINHARD's white point */
+    float log2_min, log2_max;   /* 32, 36: the histogram's range, log2_min < log2_max */
+    float percentile_low, percentile_high;   /* 40, 44: 0 <= low < high <= 1 */
+    float adaptation_rate;      /* 48: per second; <= 0: no adaptation */
+    float dt;                   /* 52: seconds since the previous frame; <= 0: no adaptation */
+    float output_rgb_from_sensor_rgb[9];   /* 56: row-major 3x3, as shm_film_get_image takes it */
+    uint32_t reserved[1];       /* 92 */
+} ShmDisplayParams;
+typedef struct ShmDisplayState {   /* 32 bytes */
+    float log2_target;     /*  0: what the last auto-exposed frame metered */
+    float log2_exposure;   /*  4: the adapted exposure: what the next frame adapts from */
+    float scale;           /*  8: what that frame's colours were multiplied by */
+    uint32_t counted;      /* 12: the pixels its histogram counted */
+    uint32_t valid;        /* 16: 0: no auto-exposed frame yet (the next one jumps to its target) */
+    uint32_t reserved[3];  /* 20 */
+} ShmDisplayState;
+/* source FILM, tonemap ACES, transfer SRGB, auto_exposure 0, dither 0, exposure 1, key 0.18, white 4, log2_min -16, log2_max 16 (about eight bins per stop),
+ * percentiles 0.10 and 0.95, adaptation_rate 3, dt 0, the identity matrix */
+SHM_API int shm_display_default_params(ShmDisplayParams* out);
+/* Forget the adaptation state (and zero the counts): the next auto-exposed frame jumps to its target. The first call allocates the pass's buffers — the RGBA8 image,
+ * the histogram's per-workgroup slabs, the 256 counts and the state — which shm_scene_destroy frees. Blocking. */
+SHM_API int shm_display_clear(ShmScene* scene);
+/* One frame: params->source into the scene's RGBA8 image, three launches with no host round trip between them (one with auto_exposure = 0). None of the three sources is
+ * written. Blocking; state_out (may be NULL) receives the state as the call leaves it, ms_out (may be NULL) the HIP-event time of the launches.
+ * SHM_ERR_INVALID_ARGUMENT, with the cause in shm_last_error(): a source that holds no result; a parameter outside its range. */
+SHM_API int shm_display_device(ShmScene* scene, const ShmDisplayParams* params, ShmDisplayState* state_out, double* ms_out);
+/* Copy the last image (one uint32_t per pixel: R | G << 8 | B << 16 | 255 << 24, pixel_bounds-sized, row-major) or the counts of the last auto-exposed frame to the host
+ * (SHM_ERR_INVALID_ARGUMENT before the first shm_display_device). */
+SHM_API int shm_display_read(ShmScene* scene, uint32_t* rgba8_out);
+SHM_API int shm_display_read_histogram(ShmScene* scene, uint32_t counts_out[256]);
+/* The RGBA8 image's device pointer and size in bytes, as shm_film_device_ptr gives the film's: for interop (SHM_ERR_INVALID_ARGUMENT before the first
+ * shm_display_device or shm_display_clear: there is no buffer yet). */
+SHM_API int shm_display_device_ptr(ShmScene* scene, void** ptr_out, uint64_t* bytes_out);
+/* shm_display_device and shm_display_read in one call */
+SHM_API int shm_display(ShmScene* scene, const ShmDisplayParams* params, uint32_t* rgba8_out, ShmDisplayState* state_out, double* ms_out);
+/* The CPU twin (no GPU needed): one frame from a read-back film. state_in_out: the state before the frame and after it (NULL: no state, and none kept); counts_out
+ * (may be NULL): the frame's 256 counts. With auto_exposure = 0 neither is read or written. */
+SHM_API int shm_display_host(const ShmFilmPixel* film, int32_t width, int32_t height, const ShmDisplayParams* params, ShmDisplayState* state_in_out,
+                             uint32_t* counts_out, uint32_t* rgba8_out);
+
 /* ---- multi-GPU (ABI v7) -------------------------------------------------------------------------------------------
  * Pixels are independent and tile ownership is exclusive (the reference's one parallel region, integrator.rs:242-304, relies on that
  * for its unsynchronised film writes), so the frame shards by tiles with the scene replicated per GPU and NO collective while
@@ -939,6 +1013,9 @@ SHM_API int shm_film_get_image(const ShmFilmPixel* film, uint64_t n_pixels, cons
                        float* rgb_out);
 /* Image::write_pfm (image.rs:1333-1377): RGB float, bottom-up rows, little-endian (scale -1). */
 SHM_API int shm_write_pfm(const char* path, const float* rgb, int32_t width, int32_t height);
+/* An 8-bit RGB PNG (colour type 2, rows top-down) of an RGBA8 image as shm_display_read gives it; the alpha byte is dropped. Stored deflate blocks: no compression and
+ * no dependency. SHM_ERR_INVALID_ARGUMENT: a null argument, an empty image, a path that cannot be opened. */
+SHM_API int shm_write_png(const char* path, const uint32_t* rgba8, int32_t width, int32_t height);
 /* TriQuadMesh::read_ply (shape/mesh.rs:179-358; the "plymesh" shape, shape/shape.rs:97-135): vertex element with float x y z
  * [nx ny nz] [u v | s t | texture_u texture_v | texture_s texture_t], face element with an int list vertex_indices /
  * vertex_index (triangles and quads; a quad v0 v1 v2 v3 is stored in bilinear-patch order v0 v1 v3 v2) and optionally

@@ -245,6 +245,27 @@ class ShmTemporalPixel(C.Structure):
 assert C.sizeof(ShmTemporalParams) == 32 and C.sizeof(ShmTemporalPixel) == 64
 
 
+class ShmDisplayParams(C.Structure):
+    """The display pass's parameters (include/shimmer_hip.h); shm_display_default_params fills one."""
+    _fields_ = [("source", C.c_uint32), ("tonemap", C.c_uint32), ("transfer", C.c_uint32), ("auto_exposure", C.c_uint32), ("dither", C.c_uint32), ("exposure", C.c_float),
+                ("key", C.c_float), ("white", C.c_float), ("log2_min", C.c_float), ("log2_max", C.c_float), ("percentile_low", C.c_float), ("percentile_high", C.c_float),
+                ("adaptation_rate", C.c_float), ("dt", C.c_float), ("output_rgb_from_sensor_rgb", C.c_float * 9), ("reserved", C.c_uint32 * 1)]
+
+
+class ShmDisplayState(C.Structure):
+    """What an auto-exposed frame leaves for the next: the metered target, the adapted exposure, the scale it gave, the pixels counted."""
+    _fields_ = [("log2_target", C.c_float), ("log2_exposure", C.c_float), ("scale", C.c_float), ("counted", C.c_uint32), ("valid", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n in ("log2_target", "log2_exposure", "scale", "counted", "valid")}
+
+
+SHM_DISPLAY_SOURCE_FILM, SHM_DISPLAY_SOURCE_DENOISED, SHM_DISPLAY_SOURCE_TEMPORAL = 0, 1, 2
+SHM_TONEMAP_NONE, SHM_TONEMAP_REINHARD, SHM_TONEMAP_ACES = 0, 1, 2
+SHM_TRANSFER_LINEAR, SHM_TRANSFER_SRGB = 0, 1
+assert C.sizeof(ShmDisplayParams) == 96 and C.sizeof(ShmDisplayState) == 32
+
+
 class ShmMomentsPixel(C.Structure):
     """A record of the moments pass (include/shimmer_hip.h): the film pixel as last seen, West's running mean and m2 per channel, W and B."""
     _fields_ = [("prev", C.c_double * 4), ("mean", C.c_double * 3), ("m2", C.c_double * 3), ("weight", C.c_double), ("batches", C.c_double)]
@@ -343,6 +364,15 @@ EXPORTS = {
     "shm_denoise_temporal_device": (C.c_int, [C.c_void_p, C.POINTER(ShmDenoiseParams), C.c_uint32, C.POINTER(C.c_double)]),
     "shm_denoise_temporal_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(ShmDenoiseParams), C.c_uint32,
                                             C.c_void_p]),
+    "shm_display_default_params": (C.c_int, [C.POINTER(ShmDisplayParams)]),
+    "shm_display_clear": (C.c_int, [C.c_void_p]),
+    "shm_display_device": (C.c_int, [C.c_void_p, C.POINTER(ShmDisplayParams), C.POINTER(ShmDisplayState), C.POINTER(C.c_double)]),
+    "shm_display_read": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "shm_display_read_histogram": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "shm_display_device_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
+    "shm_display": (C.c_int, [C.c_void_p, C.POINTER(ShmDisplayParams), C.c_void_p, C.POINTER(ShmDisplayState), C.POINTER(C.c_double)]),
+    "shm_display_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(ShmDisplayParams), C.POINTER(ShmDisplayState), C.c_void_p, C.c_void_p]),
+    "shm_write_png": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32]),
     "shm_last_error": (C.c_char_p, []),
     "shm_device_count": (C.c_int, []),
     "shm_bvh_build": (C.c_int, [c_float_p, C.c_uint32, C.c_int, C.POINTER(ShmBvhNode), c_u32_p, c_u32_p]),

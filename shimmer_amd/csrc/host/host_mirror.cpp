@@ -32,7 +32,8 @@
 #include "../shm/gbuffer.h"  // the G-buffer pass's CPU twin, at the end of this file
 #include "../shm/denoise.h"  // the denoiser's, behind it
 #include "../shm/moments.h"  // the moments pass's
-#include "../shm/temporal.h"  // the temporal pass's, last
+#include "../shm/temporal.h"  // the temporal pass's
+#include "../shm/display.h"  // the display pass's, last
 #include "flatten.h"
 
 extern "C" __attribute__((visibility("hidden"))) void shm_set_last_error(const char* msg);  // shimmer_hip.hip
@@ -637,6 +638,84 @@ int shm_write_pfm(const char* path, const float* rgb, int32_t width, int32_t hei
     return SHM_OK;
 }
 
+// An 8-bit RGB PNG without a compressor: the scanlines (filter 0) in stored deflate blocks of at most 65535 bytes inside one zlib stream, one IDAT chunk.
+namespace {
+uint32_t png_crc(uint32_t crc, const uint8_t* p, size_t n) {  // CRC-32 (reflected 0xedb88320), a byte at a time through the usual 256-entry table
+    static const std::vector<uint32_t> table = [] {
+        std::vector<uint32_t> t(256);
+        for (uint32_t i = 0; i < 256; ++i) {
+            uint32_t c = i;
+            for (int b = 0; b < 8; ++b) c = (c >> 1) ^ (0xedb88320u & (0u - (c & 1u)));
+            t[i] = c;
+        }
+        return t;
+    }();
+    for (size_t i = 0; i < n; ++i) crc = table[(crc ^ p[i]) & 0xffu] ^ (crc >> 8);
+    return crc;
+}
+void png_be32(std::vector<uint8_t>& v, uint32_t x) {
+    for (int s = 24; s >= 0; s -= 8) v.push_back((uint8_t)(x >> s));
+}
+bool png_chunk(FILE* fp, const char tag[4], const std::vector<uint8_t>& data) {
+    std::vector<uint8_t> head;
+    png_be32(head, (uint32_t)data.size());
+    head.insert(head.end(), tag, tag + 4);
+    uint32_t crc = png_crc(0xffffffffu, head.data() + 4, 4);
+    crc = png_crc(crc, data.data(), data.size()) ^ 0xffffffffu;
+    std::vector<uint8_t> tail;
+    png_be32(tail, crc);
+    return fwrite(head.data(), 1, 8, fp) == 8 && (data.empty() || fwrite(data.data(), 1, data.size(), fp) == data.size()) && fwrite(tail.data(), 1, 4, fp) == 4;
+}
+}  // namespace
+
+int shm_write_png(const char* path, const uint32_t* rgba8, int32_t width, int32_t height) {
+    if (!path || !rgba8 || width <= 0 || height <= 0) { shm_set_last_error("PNG: a null argument or an empty image"); return SHM_ERR_INVALID_ARGUMENT; }
+    const size_t row = 1 + 3 * (size_t)width, raw = row * (size_t)height;
+    const size_t n_blocks = (raw + 65534) / 65535;
+    if (2 + raw + 5 * n_blocks + 4 > 0x7fffffffull) { shm_set_last_error("PNG: the image does not fit one IDAT chunk"); return SHM_ERR_INVALID_ARGUMENT; }
+    FILE* fp = fopen(path, "wb");
+    if (!fp) { shm_set_last_error((std::string("PNG: cannot open ") + path).c_str()); return SHM_ERR_INVALID_ARGUMENT; }
+    std::vector<uint8_t> lines(raw);
+    for (int32_t y = 0; y < height; ++y) {
+        uint8_t* l = lines.data() + (size_t)y * row;
+        *l++ = 0;  // filter: none
+        for (int32_t x = 0; x < width; ++x) {
+            const uint32_t p = rgba8[(size_t)y * (size_t)width + (size_t)x];
+            *l++ = (uint8_t)p; *l++ = (uint8_t)(p >> 8); *l++ = (uint8_t)(p >> 16);
+        }
+    }
+    std::vector<uint8_t> z;
+    z.reserve(2 + raw + 5 * n_blocks + 4);
+    z.push_back(0x78); z.push_back(0x01);
+    uint32_t a = 1, b = 0;  // Adler-32
+    for (size_t at = 0; at < raw; at += 65535) {
+        const size_t len = std::min<size_t>(65535, raw - at);
+        z.push_back(at + len == raw ? 1 : 0);
+        z.push_back((uint8_t)len); z.push_back((uint8_t)(len >> 8));
+        z.push_back((uint8_t)~len); z.push_back((uint8_t)(~len >> 8));
+        z.insert(z.end(), lines.begin() + (ptrdiff_t)at, lines.begin() + (ptrdiff_t)(at + len));
+        for (size_t i = at; i < at + len;) {  // (5552: the most bytes the two 32-bit sums take before they must be reduced)
+            const size_t stop = std::min(at + len, i + 5552);
+            for (; i < stop; ++i) {
+                a += lines[i];
+                b += a;
+            }
+            a %= 65521u;
+            b %= 65521u;
+        }
+    }
+    png_be32(z, (b << 16) | a);
+    std::vector<uint8_t> ihdr;
+    png_be32(ihdr, (uint32_t)width);
+    png_be32(ihdr, (uint32_t)height);
+    const uint8_t rest[5] = {8, 2, 0, 0, 0};  // bit depth, colour type RGB, deflate, adaptive filtering, no interlace
+    ihdr.insert(ihdr.end(), rest, rest + 5);
+    static const uint8_t signature[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
+    const bool ok = fwrite(signature, 1, 8, fp) == 8 && png_chunk(fp, "IHDR", ihdr) && png_chunk(fp, "IDAT", z) && png_chunk(fp, "IEND", {});
+    if (fclose(fp) != 0 || !ok) { shm_set_last_error("PNG: a write failed"); return SHM_ERR_INTERNAL; }
+    return SHM_OK;
+}
+
 
 // ---- TriQuadMesh::read_ply, shape/mesh.rs:194-287 ---------------------------------------------------------------
 namespace {
@@ -1087,5 +1166,68 @@ extern "C" int shm_moments_resolve(const ShmMomentsPixel* moments, uint64_t n, f
     if (!moments || !out8) { shm_set_last_error("moments: a null argument"); return SHM_ERR_INVALID_ARGUMENT; }
     if (!(floor > 0.0f) || shm::is_inf(floor)) { shm_set_last_error("adaptive: floor is NaN, infinite or not above 0"); return SHM_ERR_INVALID_ARGUMENT; }
     for (uint64_t q = 0; q < n; ++q) shm::moments_resolve_pixel(reinterpret_cast<const double*>(moments + q), floor, out8 + 8 * q);
+    return SHM_OK;
+}
+
+// ---- the display pass's defaults and its CPU twin (include/shimmer_hip.h, shm_display_default_params / shm_display_host) ----
+static_assert(sizeof(ShmDisplayParams) == 96 && sizeof(ShmDisplayState) == 32, "include/shimmer_hip.h: the display structs' layout");
+
+extern "C" int shm_display_default_params(ShmDisplayParams* out) {
+    if (!out) return SHM_ERR_INVALID_ARGUMENT;
+    memset(out, 0, sizeof(*out));
+    out->source = SHM_DISPLAY_SOURCE_FILM;
+    out->tonemap = SHM_TONEMAP_ACES;
+    out->transfer = SHM_TRANSFER_SRGB;
+    out->exposure = 1.0f;
+    out->key = 0.18f;
+    out->white = 4.0f;
+    out->log2_min = -16.0f;
+    out->log2_max = 16.0f;
+    out->percentile_low = 0.10f;
+    out->percentile_high = 0.95f;
+    out->adaptation_rate = 3.0f;
+    out->dt = 0.0f;
+    out->output_rgb_from_sensor_rgb[0] = out->output_rgb_from_sensor_rgb[4] = out->output_rgb_from_sensor_rgb[8] = 1.0f;
+    return SHM_OK;
+}
+
+// shm/display.h's functions over the whole film, in k_display.hip's three steps: every pixel into the counts (integers: the order is free), the exposure and the
+// adaptation once over the 256 counts, every pixel through the map.
+extern "C" int shm_display_host(const ShmFilmPixel* film, int32_t width, int32_t height, const ShmDisplayParams* params, ShmDisplayState* state_in_out, uint32_t* counts_out,
+                                uint32_t* rgba8_out) {
+    if (!film || !params || !rgba8_out || width < 1 || height < 1) { shm_set_last_error("display: a null argument or an empty film"); return SHM_ERR_INVALID_ARGUMENT; }
+    shm::DisplayConfig k{params->tonemap, params->transfer, params->dither ? 1u : 0u, params->exposure, params->key, params->white, params->log2_min, params->log2_max,
+                         params->percentile_low, params->percentile_high, params->adaptation_rate, params->dt, {}};
+    for (int i = 0; i < 9; ++i) k.m[i] = params->output_rgb_from_sensor_rgb[i];
+    if (const char* why = shm::display_params_error(params->source, k)) { shm_set_last_error(why); return SHM_ERR_INVALID_ARGUMENT; }
+    const size_t n = (size_t)width * (size_t)height;
+    float scale = params->exposure;
+    if (params->auto_exposure) {
+        uint32_t counts[shm::DISPLAY_BINS] = {};
+        for (size_t q = 0; q < n; ++q) {
+            const double* f = reinterpret_cast<const double*>(film + q);
+            float c[3];
+            shm::display_linear_rgb(f, k.m, c);
+            const int b = shm::display_bin(f[3], shm::display_luminance(c), k.log2_min, k.log2_max);
+            if (b >= 0) ++counts[b];
+        }
+        shm::DisplayAdaptation a{state_in_out ? state_in_out->log2_exposure : 0.0f, state_in_out ? state_in_out->valid : 0u};
+        uint32_t counted = 0;
+        const float target = shm::display_exposure_target(counts, k, counted);
+        scale = shm::display_adapt(target, k, a);
+        if (counts_out) memcpy(counts_out, counts, sizeof(counts));
+        if (state_in_out) {
+            state_in_out->log2_target = target;
+            state_in_out->log2_exposure = a.log2_exposure;
+            state_in_out->scale = scale;
+            state_in_out->counted = counted;
+            state_in_out->valid = a.valid;
+        }
+    }
+    for (size_t q = 0; q < n; ++q) {
+        float c[3];
+        shm::display_linear_rgb(reinterpret_cast<const double*>(film + q), k.m, c);
+        rgba8_out[q] = shm::display_map_pixel(c, scale, (uint32_t)(q % (size_t)width), (uint32_t)(q / (size_t)width), k);
+    }
     return SHM_OK;
 }

@@ -431,6 +431,10 @@ struct ShmScene {
     bool temporal_has_camera = false;      // an accumulate has run since the last clear: temporal_camera is the camera it saw, d_temporal[temporal_cur] its records
     bool temporal_filled = false;          // d_temporal_out holds a result
     ShmCamera temporal_camera = {};
+    uint32_t* d_display = nullptr;         // the display pass's RGBA8 image (k_display.hip), pixel_bounds-sized, and, behind it, the histogram's per-workgroup slabs and the 256 counts + state: one allocation, made by the first shm_display_clear / _device
+    uint32_t* d_display_slabs = nullptr;
+    uint32_t* d_display_state = nullptr;   // 256 counts, then a ShmDisplayState
+    bool display_filled = false;           // d_display holds an image
 };
 // dist.hip: releases s->dist (RCCL communicator included); called by shm_scene_destroy
 __attribute__((visibility("hidden"))) void wf_dist_release(ShmScene* s);

@@ -257,6 +257,36 @@ class Renderer:
         abi.check(self.lib, self.lib.shm_denoise_read(self.handle, out.ctypes.data_as(C.c_void_p)), "shm_denoise_read")
         return (out, float(ms.value)) if return_ms else out
 
+    # ---- the display pass (include/shimmer_hip.h "the display pass") ----
+    def display_clear(self):
+        """shm_display_clear: forget the auto-exposure's adaptation state; the next auto-exposed frame jumps to its target."""
+        abi.check(self.lib, self.lib.shm_display_clear(self.handle), "shm_display_clear")
+
+    def display(self, dparams=None, return_state=False, return_ms=False):
+        """shm_display: dparams.source (the film, the denoiser's result or the temporal pass's) exposed, tone-mapped, encoded and quantised on the device, read back as an
+        (H, W, 4) uint8 array R, G, B, 255. dparams: an abi.ShmDisplayParams (None: the defaults). With return_state / return_ms the result is a tuple that also holds the
+        abi.ShmDisplayState as a dict / the launches' HIP-event milliseconds, in that order."""
+        d = dparams if dparams is not None else make_display_params(self.lib)
+        out = np.zeros((self.height, self.width), dtype=np.uint32)
+        state, ms = abi.ShmDisplayState(), C.c_double(0.0)
+        abi.check(self.lib, self.lib.shm_display(self.handle, C.byref(d), out.ctypes.data_as(C.c_void_p), C.byref(state), C.byref(ms)), "shm_display")
+        image = out.view(np.uint8).reshape(self.height, self.width, 4)
+        if not (return_state or return_ms):
+            return image
+        return (image,) + ((state.as_dict(),) if return_state else ()) + ((float(ms.value),) if return_ms else ())
+
+    def read_display_histogram(self):
+        """The 256 counts of the last auto-exposed frame (uint32)."""
+        out = np.zeros(256, np.uint32)
+        abi.check(self.lib, self.lib.shm_display_read_histogram(self.handle, out.ctypes.data_as(C.c_void_p)), "shm_display_read_histogram")
+        return out
+
+    def display_device_ptr(self):
+        """(device pointer, bytes) of the RGBA8 image: for interop, as film_device_ptr."""
+        p, n = C.c_void_p(), C.c_uint64()
+        abi.check(self.lib, self.lib.shm_display_device_ptr(self.handle, C.byref(p), C.byref(n)), "shm_display_device_ptr")
+        return p.value, n.value
+
     # ---- adaptive sampling (include/shimmer_hip.h "adaptive sampling"; DESIGN.md section 4k) ----
     def moments_clear(self):
         """shm_moments_clear: zero records that count from the device film as it stands."""
@@ -477,12 +507,56 @@ def camera_in_scene(lib, builder_or_rfw, pos, look_at, up, fov=90.0, full_resolu
     return cam
 
 
-def render_frames(lib, desc, cameras, params, tparams=None, dparams=None, temporal_variance=1, device=0, matrix=None, renderer=None):
+DISPLAY_PARAM_NAMES = ("source", "tonemap", "transfer", "auto_exposure", "dither", "exposure", "key", "white", "log2_min", "log2_max", "percentile_low", "percentile_high",
+                       "adaptation_rate", "dt", "output_rgb_from_sensor_rgb")
+
+
+def make_display_params(lib, **overrides):
+    """shm_display_default_params (the film through ACES and sRGB at exposure 1, no auto-exposure, no dither), with any of DISPLAY_PARAM_NAMES set by keyword.
+    output_rgb_from_sensor_rgb: anything numpy turns into nine floats, row-major (SRGB_FROM_XYZ)."""
+    d = abi.ShmDisplayParams()
+    abi.check(lib, lib.shm_display_default_params(C.byref(d)), "shm_display_default_params")
+    if overrides.get("output_rgb_from_sensor_rgb") is not None:
+        m = np.asarray(overrides["output_rgb_from_sensor_rgb"], np.float32).reshape(9)
+        overrides = dict(overrides, output_rgb_from_sensor_rgb=(C.c_float * 9)(*[float(x) for x in m]))
+    return _with_overrides("make_display_params", d, DISPLAY_PARAM_NAMES, overrides)
+
+
+def display_host(lib, film, width, height, dparams=None, state=None):
+    """shm_display_host, the display pass's CPU twin: a FILM_DTYPE array of width * height pixels into (rgba8 as (height, width, 4) uint8, the 256 counts as uint32, the
+    abi.ShmDisplayState after the frame) — what Renderer.display and read_display_histogram give for the same film and state, bit for bit. state: the
+    abi.ShmDisplayState before the frame (None: a fresh one); it is not modified. Without auto_exposure the counts are zeros and the state comes back as it went in.
+    No GPU needed."""
+    f = np.ascontiguousarray(film, dtype=FILM_DTYPE)
+    if f.size != int(width) * int(height):
+        raise ValueError("display_host: the film does not hold width * height pixels")
+    d = dparams if dparams is not None else make_display_params(lib)
+    st = abi.ShmDisplayState.from_buffer_copy(state) if state is not None else abi.ShmDisplayState()
+    counts = np.zeros(256, np.uint32)
+    out = np.zeros((int(height), int(width)), np.uint32)
+    abi.check(lib, lib.shm_display_host(f.ctypes.data_as(C.c_void_p), int(width), int(height), C.byref(d), C.byref(st), counts.ctypes.data_as(C.c_void_p),
+                                        out.ctypes.data_as(C.c_void_p)), "shm_display_host")
+    return out.view(np.uint8).reshape(int(height), int(width), 4), counts, st
+
+
+def write_png(lib, path, rgba8):
+    """shm_write_png: an (H, W, 4) uint8 (or (H, W) uint32) image as Renderer.display gives it into an 8-bit RGB PNG; the alpha byte is dropped."""
+    a = np.ascontiguousarray(rgba8)
+    if a.dtype == np.uint8 and a.ndim == 3 and a.shape[2] == 4:
+        a = a.view(np.uint32).reshape(a.shape[0], a.shape[1])
+    if a.dtype != np.uint32 or a.ndim != 2:
+        raise ValueError("write_png: an (H, W, 4) uint8 or (H, W) uint32 image")
+    abi.check(lib, lib.shm_write_png(os.fsencode(path), a.ctypes.data_as(C.c_void_p), a.shape[1], a.shape[0]), "shm_write_png")
+
+
+def render_frames(lib, desc, cameras, params, tparams=None, dparams=None, temporal_variance=1, device=0, matrix=None, renderer=None, display=None):
     """A sequence of frames of one static scene under a moving camera, accumulated over time. cameras: one abi.ShmCamera per frame (camera_in_scene; None keeps the
     camera as it is). params.samples_per_pixel is the TOTAL over the sequence and a multiple of the frame count: frame f renders samples [f spp, (f + 1) spp) of it,
     so that no two frames share a sample. Per frame: set_camera, clear film and G-buffer, one render wave and one G-buffer wave over those samples,
     temporal_accumulate, and — with dparams — denoise_temporal. Returns a list of dicts: "film", "temporal" and, where filtered, "denoised" (FILM_DTYPE), "image"
-    (film_get_image of the last of them under `matrix`) and "temporal_ms"."""
+    (film_get_image of the last of them under `matrix`) and "temporal_ms". display: an abi.ShmDisplayParams (make_display_params) — every frame's dict then also
+    holds "display", the (H, W, 4) uint8 picture the display pass makes of the last of those stages on the device (display.source is not read: the stage decides),
+    and "display_state"; the auto-exposure's state is cleared before the first frame and adapts from frame to frame by display.dt."""
     n = len(cameras)
     if n < 1 or params.samples_per_pixel % n:
         raise ValueError("render_frames: params.samples_per_pixel is the total over the frames and must be a multiple of their count")
@@ -490,6 +564,10 @@ def render_frames(lib, desc, cameras, params, tparams=None, dparams=None, tempor
     frames = []
     with _renderer_for(lib, desc, device, renderer) as r:
         r.temporal_clear()
+        if display is not None:
+            r.display_clear()
+            shown = abi.ShmDisplayParams.from_buffer_copy(display)
+            shown.source = abi.SHM_DISPLAY_SOURCE_TEMPORAL if dparams is None else abi.SHM_DISPLAY_SOURCE_DENOISED
         for f, cam in enumerate(cameras):
             if cam is not None:
                 r.set_camera(cam)
@@ -503,6 +581,8 @@ def render_frames(lib, desc, cameras, params, tparams=None, dparams=None, tempor
             if dparams is not None:
                 last = out["denoised"] = r.denoise_temporal(dparams, temporal_variance)
             out["image"] = film_get_image(lib, last, matrix)
+            if display is not None:
+                out["display"], out["display_state"] = r.display(shown, return_state=True)
             frames.append(out)
     return frames
 
