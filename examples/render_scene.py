@@ -7,6 +7,7 @@
     python examples/render_scene.py diffuse_transmission | translucent   (PBRT-v4's diffuse transmission material: the scene file / the builder)
     python examples/render_scene.py cornell --camera spherical [--mapping equirectangular]   (PBRT-v4's spherical camera in place of the scene's own)
     python examples/render_scene.py disk_and_cylinder | quadrics     (PBRT-v4's disk and cylinder: examples/scenes/disk_and_cylinder.pbrt / the builder)
+    python examples/render_scene.py cutout | cutouts                 (PBRT-v4's shape alpha: examples/scenes/cutout.pbrt / the builder, scenes.cutout_scene)
     python examples/render_scene.py cornell_probe                    (examples/scenes/cornell_probe.pbrt: an equal-area probe in the middle of the Cornell box)
     python examples/render_scene.py cornell --spp 256 --adaptive 0.05 [--min-spp 16] [--batch-spp 4]   (adaptive sampling: --spp is the cap)
     python examples/render_scene.py cornell --spp 4 --frames 16 --orbit 1 --temporal [--denoise]        (a turntable accumulated over time: <name>.fNNN.pfm / .png per frame)
@@ -30,7 +31,7 @@ from shimmer_amd import abi, render, scenes  # noqa: E402
 
 
 def make_scene(lib, name, w, h, film=None, camera=None):
-    if camera is not None and (name in ("checkerboard", "diffuse_transmission", "cornell_probe", "disk_and_cylinder") or name.startswith(("procedural", "fuzz:"))):
+    if camera is not None and (name in ("checkerboard", "diffuse_transmission", "cornell_probe", "disk_and_cylinder", "cutout") or name.startswith(("procedural", "fuzz:"))):
         raise SystemExit(f"--camera does not apply to {name}: a scene file has its own camera, and the procedural and fuzz generators take none")
     if name == "cornell":
         return scenes.cornell_box(lib, w, h, camera=camera, film=film)
@@ -41,11 +42,12 @@ def make_scene(lib, name, w, h, film=None, camera=None):
         return scenes.cornell_box(lib, w, h, camera=camera, textured=True, film=film)
     if name == "coated":
         return scenes.cornell_box(lib, w, h, camera=camera, coated=True, film=film)
-    if name in ("checkerboard", "diffuse_transmission", "cornell_probe", "disk_and_cylinder"):
+    if name in ("checkerboard", "diffuse_transmission", "cornell_probe", "disk_and_cylinder", "cutout"):
         # scene FILES through the C++ front end (their own film size; --filter is the file's): PBRT-v4's procedural textures (examples/scenes/checkerboard.pbrt); a back-lit
         # sheet of PBRT-v4's diffuse transmission material in the Cornell box (examples/scenes/diffuse_transmission.pbrt: the extended *_dl kernels); PBRT-v4's
         # spherical camera as an equal-area probe in the middle of the box (examples/scenes/cornell_probe.pbrt; the file's camera: --camera does not apply)
         # ; PBRT-v4's disk and cylinder as a lamp post whose emitter is a disk (examples/scenes/disk_and_cylinder.pbrt: the extended kernels and k_trace_quadrics.hip's)
+        # ; PBRT-v4's shape alpha as a fence, a caged ball and a half-transparent veil in front of a wall (examples/scenes/cutout.pbrt: k_trace_alpha.hip's kernels)
         import ctypes as C
         from types import SimpleNamespace
         out = C.POINTER(abi.ShmPbrtScene)()
@@ -59,6 +61,8 @@ def make_scene(lib, name, w, h, film=None, camera=None):
         return scenes.procedural_cornell(lib, w, h, which={"procedural": "checker", "procedural-general": "general", "procedural-coated": "coated"}[name], film=film)
     if name == "quadrics":  # the same shapes through the Python builder (scenes.quadric_scene)
         return scenes.quadric_scene(lib, "glass", w, h, film=film)
+    if name == "cutouts":  # the same feature through the Python builder (scenes.cutout_scene)
+        return scenes.cutout_scene(lib, "glass", w, h, film=film, disk=True, n_leaves=24)
     if name == "patches":
         return scenes.cornell_box(lib, w, h, camera=camera, patches=True, film=film)
     if name == "instanced":

@@ -72,7 +72,8 @@ typedef struct ShmTriangleMesh {
     const float* uv;                /* 2*n_vertices or NULL */
     uint8_t reverse_orientation;
     uint8_t transform_swaps_handedness;
-    uint8_t pad[6];
+    uint8_t pad[2];
+    uint32_t alpha;                 /* PBRT-v4's shape alpha (see below ShmSphere): 0 = none, else 1 + index into ShmSceneDesc::float_textures */
 } ShmTriangleMesh;
 
 /* BilinearPatchMesh (src/shape/mesh.rs:289-376) for BilinearPatch (src/shape/bilinear_patch.rs), vertices in render space.
@@ -86,7 +87,8 @@ typedef struct ShmBilinearPatchMesh {
     const float* uv;                /* 2*n_vertices or NULL */
     uint8_t reverse_orientation;
     uint8_t transform_swaps_handedness;
-    uint8_t pad[6];
+    uint8_t pad[2];
+    uint32_t alpha;                 /* shape alpha: 0 = none, else 1 + index into ShmSceneDesc::float_textures */
 } ShmBilinearPatchMesh;
 
 /* Sphere (src/shape/sphere.rs:27-38); matrices row-major m[r][c] as SquareMatrix<4>.
@@ -103,8 +105,16 @@ typedef struct ShmSphere {
     uint8_t reverse_orientation;
     uint8_t transform_swaps_handedness;
     uint8_t quadric;   /* SHM_QUADRIC_* */
-    uint8_t pad[5];
+    uint8_t pad[1];
+    uint32_t alpha;    /* shape alpha: 0 = none, else 1 + index into ShmSceneDesc::float_textures */
 } ShmSphere;
+/* Shape alpha (PBRT-v4's "float alpha" / "texture alpha" shape parameter; the reference has none): ShmTriangleMesh::alpha, ShmBilinearPatchMesh::alpha and
+ * ShmSphere::alpha name a float texture that cuts holes in every primitive of the shape. Where the shape's own test has accepted a candidate hit, the texture is
+ * evaluated at the candidate's p, uv and geometric normal (all differentials zero): a >= 1 accepts, a <= 0 rejects, anything between rejects where
+ * HashFloat(ray.o, ray.d) > a — a stochastic cutout that is the same for the same ray —; a rejected candidate is a miss. Closest-hit and any-hit (shadow) rays
+ * run the same test. The fields are carved out of the structs' former padding: a zeroed one is "no alpha", and no size or offset changed.
+ * shm_scene_create answers an index beyond the table with SHM_ERR_INVALID_ARGUMENT and alpha on a primitive that is also an area light with SHM_ERR_UNSUPPORTED
+ * (PBRT-v4 masks the emitted radiance and the light's sampling by the alpha as well: not carried). */
 
 enum { SHM_SHAPE_TRIANGLE = 0, SHM_SHAPE_SPHERE = 1, SHM_SHAPE_BILINEAR_PATCH = 2,
        SHM_SHAPE_INSTANCE = 3 /* ABI v6: a TransformedPrimitive (primitive.rs:136-176): shape_index = index into ShmSceneDesc::instances;

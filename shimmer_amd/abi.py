@@ -55,20 +55,31 @@ class ShmBvhNode(C.Structure):
 class ShmTriangleMesh(C.Structure):
     _fields_ = [("n_triangles", C.c_uint32), ("n_vertices", C.c_uint32), ("vertex_indices", c_u32_p), ("p", c_float_p),
                 ("n", c_float_p), ("s", c_float_p), ("uv", c_float_p), ("reverse_orientation", C.c_uint8),
-                ("transform_swaps_handedness", C.c_uint8), ("pad", C.c_uint8 * 6)]
+                ("transform_swaps_handedness", C.c_uint8), ("pad", C.c_uint8 * 2), ("alpha", C.c_uint32)]  # alpha: 0 = none, else 1 + float texture index
 
 
 class ShmBilinearPatchMesh(C.Structure):
     _fields_ = [("n_patches", C.c_uint32), ("n_vertices", C.c_uint32), ("vertex_indices", c_u32_p), ("p", c_float_p),
                 ("n", c_float_p), ("uv", c_float_p), ("reverse_orientation", C.c_uint8),
-                ("transform_swaps_handedness", C.c_uint8), ("pad", C.c_uint8 * 6)]
+                ("transform_swaps_handedness", C.c_uint8), ("pad", C.c_uint8 * 2), ("alpha", C.c_uint32)]
+
+
+class _FormerPad:
+    """ShmSphere.pad as it was before PBRT-v4's shape alpha had a name: the five bytes behind `quadric` (the header's pad[1] + alpha), at the class `.offset` / `.size`,
+    of an instance a live ctypes view of them. (A plain field cannot overlap `alpha`, and a union would put an unnamed member at the end of _fields_.)"""
+    offset, size = 155, 5
+
+    def __get__(self, obj, cls):
+        return self if obj is None else (C.c_uint8 * self.size).from_buffer(obj, self.offset)
 
 
 class ShmSphere(C.Structure):
     _fields_ = [("radius", C.c_float), ("z_min", C.c_float), ("z_max", C.c_float), ("theta_z_min", C.c_float),
                 ("theta_z_max", C.c_float), ("phi_max", C.c_float), ("render_from_object", C.c_float * 16),
                 ("object_from_render", C.c_float * 16), ("reverse_orientation", C.c_uint8),
-                ("transform_swaps_handedness", C.c_uint8), ("quadric", C.c_uint8), ("pad", C.c_uint8 * 5)]
+                ("transform_swaps_handedness", C.c_uint8), ("quadric", C.c_uint8), ("_pad0", C.c_uint8),
+                ("alpha", C.c_uint32)]  # alpha: 0 = none, else 1 + float texture index
+    pad = _FormerPad()
 
 
 class ShmPrimitive(C.Structure):

@@ -35,6 +35,8 @@ struct FlatScene {
                                                 // spot_cos_theta), zeros otherwise: SceneView::light_prim_recs
     bool has_diffuse_transmission = false;  // a SHM_MATERIAL_DIFFUSE_TRANSMISSION: selects the same kernels (shm/bxdf.h, SHM_DIFFUSE_TRANSMISSION)
     bool has_directed_lights = false;  // a SHM_LIGHT_DISTANT or SHM_LIGHT_SPOT: selects the *_dl shading kernels (wavefront.h, K_DELTA_LIGHTS)
+    bool has_alpha = false;            // a shape with an alpha texture (PBRT-v4's cutouts, shm/alpha.h): selects k_trace_alpha.hip's traversal kernels; an alpha-tested TRIANGLE
+                                       // is a non-triangle record to the traversal's plan (has_spheres, n_quadric_patch_prims): it parks for the alpha test
     bool has_quadric_kinds = false;    // a sphere record that is a disk or a cylinder (ShmSphere::quadric): selects the same shading kernels and k_trace_quadrics.hip's traversal kernels (shm/shapes.h, SHM_QUADRICS)
     std::vector<uint32_t> infinite_lights;
     std::vector<float> spectrum_data;
@@ -43,7 +45,7 @@ struct FlatScene {
     ShmFilm film;
     uint32_t max_leaf_depth = 0;  // deepest leaf (root = 0); bounds the traversal stack
     float scene_radius = 0.0f;
-    uint64_t n_quadric_patch_prims = 0;  // primitive records that are spheres or bilinear patches (instances not counted): a scene where they are MANY runs the traversal
+    uint64_t n_quadric_patch_prims = 0;  // primitive records that are spheres, bilinear patches or alpha-tested triangles (instances not counted): a scene where they are MANY runs the traversal
                                          // kernels' five-wave instantiations (k_trace.hip, TRACE_GEN_HEAVY: the parked round's registers instead of its spill code)
     bool has_spheres = false;  // any non-triangle shape (sphere or bilinear patch): selects k_trace5<.., GEN = true> and the general-geometry shading instantiations
     bool has_layered = false;  // any Coated* material: selects the k_shade instantiation that carries LayeredBxDF
@@ -397,8 +399,11 @@ inline int flatten_scene(const ShmSceneDesc* d, FlatScene& out, std::string& err
         if (pr.area_light >= (int32_t)d->n_lights) { err = "primitive area light out of range"; return SHM_ERR_INVALID_ARGUMENT; }
         rec.material = pr.material;
         rec.area_light = pr.area_light;
+        // PBRT-v4's shape alpha (shm/alpha.h): the shape's float texture, 0 = none, else 1 + index
+        uint32_t alpha = 0u;
         if (pr.shape_kind == SHM_SHAPE_SPHERE) {
             if (pr.shape_index >= d->n_spheres) { err = "sphere index out of range"; return SHM_ERR_INVALID_ARGUMENT; }
+            alpha = d->spheres[pr.shape_index].alpha;
             out.n_quadric_patch_prims += 1u;
             rec.kind_index = shm::PRIM_SPHERE_BIT | pr.shape_index;
             out.has_spheres = true;
@@ -418,6 +423,14 @@ inline int flatten_scene(const ShmSceneDesc* d, FlatScene& out, std::string& err
             rec.kind_index = shm::triangle_is_degenerate(shm::ld3(rec.p0), shm::ld3(rec.p1), shm::ld3(rec.p2)) ? shm::PRIM_DEGENERATE_BIT : 0u;
             rec.mesh = m;
             rec.tri = pr.shape_index;
+            alpha = mesh.alpha;
+            if (alpha != 0u && alpha <= shm::PRIM_INDEX_MASK) {
+                // in the low bits of the word the traversal's leaf phase reads anyway ("0 for a triangle" without alpha; nothing reads them of a triangle but shm/alpha.h):
+                // to the traversal such a triangle is a non-triangle record — it parks, and the wave's next round of other tests runs the triangle and the alpha test
+                rec.kind_index |= alpha;
+                out.n_quadric_patch_prims += 1u;
+                out.has_spheres = true;
+            }
         } else if (pr.shape_kind == SHM_SHAPE_BILINEAR_PATCH) {
             if (pr.shape_index >= n_patches) { err = "bilinear patch index out of range"; return SHM_ERR_INVALID_ARGUMENT; }
             uint32_t m = (uint32_t)(std::upper_bound(patch_base.begin(), patch_base.end(), pr.shape_index) - patch_base.begin()) - 1;
@@ -442,6 +455,7 @@ inline int flatten_scene(const ShmSceneDesc* d, FlatScene& out, std::string& err
             px.area = shm::blp_area(c[0], c[1], c[2], c[3], is_rect);
             px.flags = (is_rect ? 1u : 0u) | ((((mesh.reverse_orientation != 0) ^ (mesh.transform_swaps_handedness != 0)) ? 2u : 0u)) |
                        (mesh.n ? 4u : 0u) | (mesh.uv ? 8u : 0u);
+            px.alpha = alpha = mesh.alpha;
             rec.kind_index = shm::PRIM_PATCH_BIT | pr.shape_index;
             out.n_quadric_patch_prims += 1u;
             out.has_spheres = true;
@@ -453,6 +467,12 @@ inline int flatten_scene(const ShmSceneDesc* d, FlatScene& out, std::string& err
         } else {
             err = "unsupported shape kind";
             return SHM_ERR_UNSUPPORTED;
+        }
+        if (alpha != 0u) {
+            if (alpha > d->n_float_textures || alpha > shm::PRIM_INDEX_MASK) { err = "shape alpha: float texture index out of range"; return SHM_ERR_INVALID_ARGUMENT; }
+            // (PBRT-v4 masks an emitter's radiance and its sampling by the alpha as well: a second feature)
+            if (pr.area_light >= 0) { err = "shape alpha on a primitive that is also an area light is not supported"; return SHM_ERR_UNSUPPORTED; }
+            out.has_alpha = true;
         }
         out.prim_recs[s] = rec;
     }

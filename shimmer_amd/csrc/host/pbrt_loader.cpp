@@ -11,7 +11,7 @@
 // CoordSysTransform ReverseOrientation Camera (perspective / orthographic / spherical) Film (rgb) Sampler PixelFilter (box gaussian mitchell sinc triangle) Integrator Option
 // WorldBegin AttributeBegin/End Attribute (per-target default parameters) Material MakeNamedMaterial NamedMaterial Texture (float / spectrum: constant scale mix
 // directionmix imagemap) AreaLightSource (diffuse) LightSource (point, infinite: uniform or an environment image) Shape (trianglemesh
-// bilinearmesh sphere disk cylinder plymesh) ObjectBegin/End ObjectInstance Include; spectra as "spectrum" samples / named tables / files, "blackbody",
+// bilinearmesh sphere disk cylinder plymesh, each with PBRT-v4's "float alpha" / "texture alpha") ObjectBegin/End ObjectInstance Include; spectra as "spectrum" samples / named tables / files, "blackbody",
 // and "rgb" through the sRGB rgb2spec table (the `.spec` file the reference loads); PNG images (the only format the reference reads,
 // host/image_io.hpp) for textures, normal maps and environment lights. What the reference itself leaves todo!() or this backend does not
 // take (media, Import, portals, animated transforms, other colour spaces) is reported as SHM_ERR_UNSUPPORTED with the line number, never
@@ -838,6 +838,29 @@ private:
             m.swaps = swaps_handedness(rfo.m);
             return m;
         };
+        // PBRT-v4's shape alpha, "float alpha" [v] or "texture alpha" "name", on every shape: 0 = none, else 1 + the float texture's index. A constant 1 (or more) cuts
+        // nothing and stores nothing, as PBRT-v4 drops it; a constant 0 keeps its texture — the shape exists and is invisible (PBRT-v4 drops the shape instead: the same image)
+        uint32_t alpha = 0u;
+        if (const Param* p = ps.find("alpha")) {
+            if (p->type == "texture") {
+                auto it = float_texture_names_.find(p->s.empty() ? "" : p->s[0]);
+                if (it == float_texture_names_.end()) fail(tk.where(p->line) + ": Couldn't find float texture named \"" + (p->s.empty() ? "" : p->s[0]) + "\"");
+                alpha = it->second + 1u;
+            } else {
+                if (p->f.empty()) fail(tk.where(p->line) + ": parameter \"alpha\" needs a value");
+                if (p->f[0] < 1.0f) {
+                    ShmFloatTexture t;
+                    memset(&t, 0, sizeof(t));
+                    t.kind = SHM_FLOATTEX_CONSTANT;
+                    t.value = p->f[0];
+                    a_->float_textures.push_back(t);
+                    alpha = (uint32_t)a_->float_textures.size();
+                }
+            }
+            if (alpha != 0u && gs_.area_light.on)
+                fail(tk.where(line) + ": \"alpha\" on an emissive shape is not supported (PBRT-v4 masks the emitted radiance and the light's sampling by it as well)", SHM_ERR_UNSUPPORTED);
+        }
+        const size_t n_spheres_before = a_->spheres.size();
         if (type == "sphere") {
             const float radius = ps.one_float("radius", 1.0f);
             a_->add_sphere(radius, ps.one_float("zmin", -radius), ps.one_float("zmax", radius), ps.one_float("phimax", 360.0f), rfo, reverse, (uint32_t)gs_.material,
@@ -863,6 +886,7 @@ private:
             if (!S.empty() && S.size() != 3 * nv) fail(tk.where(line) + ": Number of \"S\"s for triangle mesh must match \"P\"s.");
             if (!N.empty() && N.size() != 3 * nv) fail(tk.where(line) + ": Number of \"N\"s for triangle mesh must match \"P\"s.");
             Assembly::Mesh m = transformed_mesh(P, N, S, UV);
+            m.alpha = alpha;
             for (int v : vi) { if (v < 0 || (size_t)v >= nv) fail(tk.where(line) + ": trianglemesh has out-of-bounds vertex index"); m.vi.push_back((uint32_t)v); }
             a_->add_mesh(std::move(m), (uint32_t)gs_.material, gs_.area_light, object_);
         } else if (type == "bilinearmesh") {  // bilinear_patch.rs create
@@ -876,6 +900,7 @@ private:
             if (!UV.empty() && UV.size() != 2 * nv) fail(tk.where(line) + ": Number of \"uv\"s must match \"P\"s.");
             if (!N.empty() && N.size() != 3 * nv) fail(tk.where(line) + ": Number of \"N\"s must match \"P\"s.");
             Assembly::Mesh m = transformed_mesh(P, N, std::vector<float>(), UV);
+            m.alpha = alpha;
             for (int v : vi) { if (v < 0 || (size_t)v >= nv) fail(tk.where(line) + ": bilinearmesh has out-of-bounds vertex index"); m.vi.push_back((uint32_t)v); }
             a_->add_patch_mesh(std::move(m), (uint32_t)gs_.material, gs_.area_light, object_);
         } else if (type == "plymesh") {  // shape/shape.rs:97-135
@@ -887,17 +912,20 @@ private:
             shm_ply_free(&pm);
             if (!tri.empty()) {
                 Assembly::Mesh m = transformed_mesh(P, N, std::vector<float>(), UV);
+                m.alpha = alpha;
                 for (int32_t v : tri) m.vi.push_back((uint32_t)v);
                 a_->add_mesh(std::move(m), (uint32_t)gs_.material, gs_.area_light, object_);
             }
             if (!quad.empty()) {
                 Assembly::Mesh m = transformed_mesh(P, N, std::vector<float>(), UV);
+                m.alpha = alpha;
                 for (int32_t v : quad) m.vi.push_back((uint32_t)v);
                 a_->add_patch_mesh(std::move(m), (uint32_t)gs_.material, gs_.area_light, object_);
             }
         } else {
             fail(tk.where(line) + ": shape \"" + type + "\" is not supported by this backend (sphere, disk, cylinder, trianglemesh, bilinearmesh, plymesh)", SHM_ERR_UNSUPPORTED);
         }
+        for (size_t i = n_spheres_before; i < a_->spheres.size(); ++i) a_->spheres[i].alpha = alpha;  // (sphere, disk, cylinder: the record this call appended)
     }
     std::string resolve(const std::string& f) const { return (f.empty() || f[0] == '/' || base_dir_.empty()) ? f : base_dir_ + "/" + f; }
 

@@ -64,6 +64,8 @@ struct SceneFacts {
     bool diffuse_only = true, has_material_textures = false, has_image_light = false, has_spheres = false, has_instances = false;
     bool extended = false;         // a distant or spot light, a diffuse transmission material or a disk / cylinder: the *_dl builds (wavefront.h, K_DELTA_LIGHTS) and no others
     bool has_quadric_kinds = false;  // a disk or a cylinder (ShmSphere::quadric): the traversal kernels of k_trace_quadrics.hip (and `extended`: the shading kernels that know the shapes)
+    bool has_alpha = false;          // a shape with an alpha texture (shm/alpha.h): the traversal kernels of k_trace_alpha.hip (its alpha-tested triangles count as non-triangle records
+                                     // in has_spheres and patch_heavy: flatten.h)
     bool has_plain_diffuse = false, plain_quarter = false;  // primitives on a plain DiffuseMaterial: any / a quarter or more by count or by surface area
     bool patch_heavy = false, has_quadric_patch = false;    // spheres / bilinear patches: a twelfth of the primitive records or more / any
     bool small_tree = false, has_prims = false;             // fewer than 4096 BVH nodes / any primitive record
@@ -77,6 +79,7 @@ inline SceneFacts scene_facts(const shm_host::FlatScene& f) {
     s.diffuse_only = f.diffuse_only; s.has_material_textures = f.has_material_textures; s.has_image_light = f.has_image_light;
     s.has_spheres = f.has_spheres; s.has_instances = f.has_instances;
     s.has_quadric_kinds = f.has_quadric_kinds;
+    s.has_alpha = f.has_alpha;
     s.extended = f.has_directed_lights || f.has_diffuse_transmission || f.has_quadric_kinds;
     s.has_plain_diffuse = f.n_plain_diffuse_prims > 0;
     // (round 6: ... or a quarter of the SURFACE AREA — hits fall by area, not by count: a textured 4.3 M-triangle object in a plain room of 14 triangles sent every wall and

@@ -179,6 +179,7 @@ public:
         std::vector<float> p, n, s, uv;
         std::vector<uint32_t> vi;
         bool reverse = false, swaps = false;
+        uint32_t alpha = 0;  // PBRT-v4's shape alpha: 0 = none, else 1 + index into float_textures (ShmTriangleMesh / ShmBilinearPatchMesh::alpha; a sphere's: ShmSphere::alpha)
     };
     struct Prim {
         uint32_t kind, index, material;
@@ -698,6 +699,7 @@ public:
             mm.uv = m.uv.empty() ? nullptr : m.uv.data();
             mm.reverse_orientation = m.reverse;
             mm.transform_swaps_handedness = m.swaps;
+            mm.alpha = m.alpha;
             out->meshes.push_back(mm);
         }
         for (const Mesh& m : a.patch_meshes) {
@@ -711,6 +713,7 @@ public:
             pm.uv = m.uv.empty() ? nullptr : m.uv.data();
             pm.reverse_orientation = m.reverse;
             pm.transform_swaps_handedness = m.swaps;
+            pm.alpha = m.alpha;
             out->patch_meshes.push_back(pm);
         }
         if (a.spec.empty()) a.spec.push_back(0.0f);

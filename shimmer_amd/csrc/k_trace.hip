@@ -46,6 +46,9 @@ constexpr TraceKernel TRACE_KERNELS_ANY_STRICT[2] = {k_trace5_any_strict<false>,
 __global__ void k_reset_trace_heads(uint32_t* heads) { for (uint32_t i = threadIdx.x; i < TRACE_QUEUE_PARTS * TRACE_HEAD_STRIDE; i += blockDim.x) heads[i] = 0; }
 }  // namespace
 
+// k_trace_alpha.hip (scenes with shape alpha): the launch's SceneView to HBM (TraceSide::d_view), in stream order in front of the traversal kernel that reads the scene through it
+WF_INTERNAL void wf_trace_alpha_store_view(hipStream_t stream, const SceneView& view, SceneView* dst);
+
 void wf_trace_census() {
 #ifdef K5_CENSUS
     unsigned long long c[32];
@@ -84,21 +87,35 @@ int wf_trace_prepare(ShmScene* s) {
             s->allocs.push_back(g);
             side.d_gen_save = static_cast<float4*>(g);
         }
+        if (s->plan.f.has_alpha) {  // k_trace_alpha.hip: the alpha texture's evaluators read the scene through a SceneView in memory
+            void* v = nullptr;
+            if (hipMalloc(&v, sizeof(SceneView)) != hipSuccess) { shm_err() = "hipMalloc of the traversal kernels' scene view failed"; return SHM_ERR_OUT_OF_MEMORY; }
+            s->allocs.push_back(v);
+            side.d_view = static_cast<SceneView*>(v);
+        }
     }
     return SHM_OK;
 }
 
 // One launch through the kernel table, by the plan's coordinates: the scene's variant, the ray kind and — any hit only — the render's strictness; a scene with a disk or a
-// cylinder takes k_trace_quadrics.hip's kernel of the same row (same grid, same spill, same save areas: wf_trace_prepare sized them by the row)
+// cylinder takes k_trace_quadrics.hip's kernel of the same row (same grid, same spill, same save areas: wf_trace_prepare sized them by the row), a scene with a cutout
+// (shape alpha) k_trace_alpha.hip's, which knows both
 int wf_launch_trace(ShmScene* s, int ray, bool any_strict, const TraceArgs& t) {
     const TraceSide& side = s->trace[ray];
     const ScenePlan& p = s->plan;
     const bool any = ray == RAY_ANY;
-    const TraceKernel kernel = p.f.has_quadric_kinds ? wf_trace_quadrics_kernel(p.trace_variant, ray, any && any_strict)
+    const TraceKernel kernel = p.f.has_alpha ? wf_trace_alpha_kernel(p.trace_variant, ray, any && any_strict)
+                               : p.f.has_quadric_kinds ? wf_trace_quadrics_kernel(p.trace_variant, ray, any && any_strict)
                                : ((any && any_strict) ? TRACE_KERNELS_ANY_STRICT[trace_strict_variant(p.trace_variant) - TRACE_GEN] : TRACE_KERNELS[p.trace_variant][ray]);
-    if (!kernel) { shm_err() = "internal: no traversal kernel with the disk and the cylinder for this scene's row"; return SHM_ERR_INTERNAL; }
+    if (!kernel) { shm_err() = "internal: no traversal kernel with shape alpha or the disk and the cylinder for this scene's row"; return SHM_ERR_INTERNAL; }
+    SceneView view = s->dsv;
+    if (p.f.has_alpha) {
+        if (!side.d_view) { shm_err() = "internal: a scene with shape alpha without its traversal scene view"; return SHM_ERR_INTERNAL; }
+        view.call_copy = side.d_view;  // (the copy names itself: the evaluators hand it on to each other)
+        wf_trace_alpha_store_view(t.stream, view, side.d_view);
+    }
     hipLaunchKernelGGL(k_reset_trace_heads, dim3(1), dim3(64), 0, t.stream, side.d_heads);
-    hipLaunchKernelGGL(kernel, dim3(side.blocks), dim3(TRACE_BLOCK), 0, t.stream, s->dsv, t.queue, t.n_ptr, t.n_direct, side.d_heads, t.rays, t.hits, t.occluded, t.L, t.contrib,
+    hipLaunchKernelGGL(kernel, dim3(side.blocks), dim3(TRACE_BLOCK), 0, t.stream, view, t.queue, t.n_ptr, t.n_direct, side.d_heads, t.rays, t.hits, t.occluded, t.L, t.contrib,
                        s->d_counters, side.d_spill, side.spill_levels, any ? p.refill_min_any : p.refill_min, any ? p.leaf_min_any : p.leaf_min, (int)TRACE_QUEUE_PARTS,
                        p.trace_rays_per_lane, t.hit16, s->d_big_leaf_n, side.d_gen_save, any ? p.other_min_any : p.other_min, t.hit2);
     LAUNCH_TRY(any ? "k_trace<any>" : "k_trace<closest>");

@@ -1,6 +1,7 @@
-// k_trace.inl — the traversal body (trace5_body) and what makes an entry point of it (TRACE_KERNEL): the text k_trace.hip and k_trace_quadrics.hip share, the way
-// k_generate_spherical.hip shares k_generate.inl. k_trace.hip holds the kernels of every scene; k_trace_quadrics.hip sets K_QUADRICS (wavefront.h) and holds the general
-// rows a second time, with PBRT-v4's disk and cylinder compiled into the sphere test (shm/shapes.h), for the scenes that hold one. The algorithm's description: k_trace.hip.
+// k_trace.inl — the traversal body (trace5_body) and what makes an entry point of it (TRACE_KERNEL): the text k_trace.hip, k_trace_quadrics.hip and k_trace_alpha.hip share,
+// the way k_generate_spherical.hip shares k_generate.inl. k_trace.hip holds the kernels of every scene; k_trace_quadrics.hip sets K_QUADRICS (wavefront.h) and holds the general
+// rows a second time, with PBRT-v4's disk and cylinder compiled into the sphere test (shm/shapes.h), for the scenes that hold one; k_trace_alpha.hip sets K_ALPHA as well and
+// holds them a third time, with PBRT-v4's shape alpha (shm/alpha.h) in the parked round, for the scenes with a cutout. The algorithm's description: k_trace.hip.
 #pragma once
 #include "wavefront.h"
 
@@ -457,7 +458,8 @@ __device__ __forceinline__ void trace5_body(K5_PARAMS) {
                     const float4* pr = reinterpret_cast<const float4*>(prim_base + (size_t)slot * sizeof(PrimRec));
                     const float4 q0 = pr[0], q1 = pr[1], q2 = pr[2];
                     const uint32_t kind = __float_as_uint(q2.y);
-                    tested = !GEN || (kind & NOT_A_TRIANGLE) == 0u;
+                    // (K_ALPHA: a triangle whose mesh has an alpha texture — the low bits of the same word, shm/alpha.h — parks like a sphere: the parked round tests it)
+                    tested = !GEN || ((kind & NOT_A_TRIANGLE) == 0u && (!K_ALPHA || (kind & PRIM_INDEX_MASK) == 0u));
                     // (the precomputed degeneracy flag is applied to the RESULT: tested first, the compiler fetched the flag word, waited, and only then fetched the vertices — two dependent
                     //  round trips per leaf; degenerate triangles are rare and the test itself has no side effect; GEN: so is "this record is no triangle at all" — the test has no side effect)
                     TriangleIntersection ti;
@@ -551,7 +553,15 @@ __device__ __forceinline__ void trace5_body(K5_PARAMS) {
                             save_ray_state(1);  // (... and nothing of it is live across the test; the five-wave build WITHOUT this save / restore: 40 / 14 spilled VGPRs instead of 10 / 0, S3 as patches 3 736 -> 3 572 Mray/s)
                             bool got;
                             Float t_hit, h0, h1, h2, h_phi;
-                            if (kind & PRIM_SPHERE_BIT) {
+                            const bool alpha_tri = K_ALPHA && (kind & NOT_A_TRIANGLE) == 0u;  // (K_ALPHA: the third kind of parked test, an alpha-tested triangle)
+                            if (alpha_tri) {
+                                // the leaf phase's test, with its PRIM_DEGENERATE_BIT rule: the ray constants are the loop's own
+                                TriangleIntersection ti;
+                                ti.t = 0.0f; ti.b0 = 0.0f; ti.b1 = 0.0f; ti.b2 = 0.0f;
+                                got = intersect_triangle_nondegenerate(ro, rs, t_max, v3(q0.x, q0.y, q0.z), v3(q0.w, q1.x, q1.y), v3(q1.z, q1.w, q2.x), ti);
+                                got = got && !(kind & PRIM_DEGENERATE_BIT);
+                                t_hit = ti.t; h0 = ti.b0; h1 = ti.b1; h2 = ti.b2; h_phi = 0.0f;
+                            } else if (kind & PRIM_SPHERE_BIT) {
                                 // Sphere::intersect (sphere.rs:95-196); the hit record carries p_obj and phi
                                 QuadricIntersection qi;
                                 qi.t_hit = 0.0f; qi.p_obj = v3s(0.0f); qi.phi = 0.0f;
@@ -564,12 +574,26 @@ __device__ __forceinline__ void trace5_body(K5_PARAMS) {
                                 got = blp_intersect(ro, rd, t_max, v3(q0.x, q0.y, q0.z), v3(q0.w, q1.x, q1.y), v3(q1.z, q1.w, q2.x), v3(q2.z, q2.w, q3.z), bi);  // (p11: in the record's spare words, flatten.h)
                                 t_hit = bi.t; h0 = bi.u; h1 = bi.v; h2 = 0.0f; h_phi = 0.0f;
                             }
+                            if (K_ALPHA && got) {
+                                // PBRT-v4's shape alpha (shm/alpha.h, the text the oracle's prim_intersect runs): the candidate stands or is a miss. Inside the save / restore
+                                // bracket — the texture evaluation is a real call, and nothing of the loop is live across it; (ro, rd) is the ray the shape test ran with,
+                                // inside an instance the instance-space one. The scene is read through SceneView::call_copy, which wf_launch_trace points at a copy in HBM.
+                                const PrimRec& rec = *reinterpret_cast<const PrimRec*>(prim_base + (size_t)slot * sizeof(PrimRec));
+                                const uint32_t alpha = prim_alpha(sv, rec);
+                                if (alpha != 0u) {
+                                    Hit cand;
+                                    cand.prim = (int32_t)slot; cand.t = t_hit; cand.b0 = h0; cand.b1 = h1; cand.b2 = h2; cand.phi = h_phi;
+                                    got = alpha_accept(sv, rec, alpha, cand, ro, rd);
+                                }
+                            }
                             restore_ray_state(1);
                             if (got) {
                                 sgn |= SGN_HIT | SGN_HIT_INSIDE;
                                 if (!ANY) {
                                     t_max = t_hit;
-                                    if (hit16) {  // the split form (scenes without instances): bit 30 of the primitive word says "read the second record" (t, phi)
+                                    if (hit16 && alpha_tri) {  // (a triangle's hit is its 16-byte record, as the leaf phase writes it)
+                                        reinterpret_cast<float4*>(hits)[path] = make_float4(__int_as_float((int32_t)slot), h0, h1, h2);
+                                    } else if (hit16) {  // the split form (scenes without instances): bit 30 of the primitive word says "read the second record" (t, phi)
                                         reinterpret_cast<float4*>(hits)[path] = make_float4(__int_as_float((int32_t)(slot | HIT_HAS_SECOND)), h0, h1, h2);
                                         hit2[path] = make_float4(t_hit, h_phi, 0.0f, 0.0f);
                                     } else {
@@ -704,3 +728,5 @@ __device__ __forceinline__ void trace5_body(K5_PARAMS) {
 using TraceKernel = void (*)(K5_PARAMS);
 // k_trace_quadrics.hip: the kernel of a general row (TRACE_GEN, TRACE_GEN_HEAVY) with the disk and the cylinder; any hit: the STRICT pair's where `any_strict`
 WF_INTERNAL TraceKernel wf_trace_quadrics_kernel(int variant, int ray, bool any_strict);
+// k_trace_alpha.hip: the same six with PBRT-v4's shape alpha (K_ALPHA) and the disk and the cylinder
+WF_INTERNAL TraceKernel wf_trace_alpha_kernel(int variant, int ray, bool any_strict);

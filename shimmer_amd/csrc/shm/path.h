@@ -22,6 +22,7 @@
 #include "filter.h"
 #include "scene.h"
 #include "texture.h"
+#include "alpha.h"
 
 namespace shm {
 

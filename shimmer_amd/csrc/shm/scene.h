@@ -22,7 +22,7 @@ namespace shm {
 
 struct PrimRec {
     Float p0[3], p1[3], p2[3];
-    uint32_t kind_index;  // bit 31: sphere, bit 30: bilinear patch; low bits: sphere / patch index (0 for a triangle)
+    uint32_t kind_index;  // bit 31: sphere, bit 30: bilinear patch; low bits: sphere / patch index (a triangle: its mesh's alpha texture, 0 = none, else 1 + index: shm/alpha.h)
     uint32_t mesh;        // triangle: mesh id                 | bilinear patch: p11.x (bits)
     uint32_t tri;         // triangle: global triangle index   | bilinear patch: p11.y
     // ... and, filling the record to 64 bytes, the ShmPrimitive fields the shading kernels read of a hit: one aligned 64-byte fetch gives a triangle test its three vertices
@@ -39,7 +39,8 @@ struct PatchExtra {
     Float area;      // BilinearPatch::new (bilinear_patch.rs:40-69)
     uint32_t flags;  // bit 0: is_rectangle (:108-142), bit 1: reverse_orientation ^ transform_swaps_handedness,
                      // bit 2: the mesh has per-vertex normals, bit 3: per-vertex uv (attributes through SceneView::patch_vi)
-    uint32_t pad[3];
+    uint32_t alpha;  // the patch mesh's alpha texture: 0 = none, else 1 + index into SceneView::float_textures (shm/alpha.h)
+    uint32_t pad[2];
 };
 static_assert(sizeof(PatchExtra) == 32, "PatchExtra must be 32 bytes");
 constexpr uint32_t PRIM_PATCH_BIT = 0x40000000u;
@@ -284,26 +285,8 @@ SHM_HD SurfaceInteraction hit_interaction_local(const SceneView& sv, const Hit& 
     return triangle_interaction(tr, ti, wo);
 }
 
-// Primitive::intersect for one leaf-order slot (primitive.rs:95-103 -> shape/shape.rs:164-170).
-// Updates hit/t_max on acceptance exactly as aggregate.rs:101-110 does.
-SHM_HD bool prim_intersect(const SceneView& sv, uint32_t slot, V3 ro, V3 rd, Float t_max, Hit& h) {
-    const PrimRec& pr = sv.prim_recs[slot];
-    if (pr.kind_index & PRIM_SPHERE_BIT) {
-        QuadricIntersection qi;
-        if (!sphere_basic_intersect(sv.spheres[pr.kind_index & PRIM_INDEX_MASK], ro, rd, t_max, qi)) return false;
-        h.prim = (int32_t)slot; h.t = qi.t_hit; h.b0 = qi.p_obj.x; h.b1 = qi.p_obj.y; h.b2 = qi.p_obj.z; h.phi = qi.phi;
-        return true;
-    }
-    if (pr.kind_index & PRIM_PATCH_BIT) {
-        BilinearIntersection bi;
-        if (!blp_intersect(ro, rd, t_max, ld3(pr.p0), ld3(pr.p1), ld3(pr.p2), ld3(sv.patches[pr.kind_index & PRIM_INDEX_MASK].p11), bi)) return false;
-        h.prim = (int32_t)slot; h.t = bi.t; h.b0 = bi.u; h.b1 = bi.v; h.b2 = 0.0f; h.phi = 0.0f;
-        return true;
-    }
-    TriangleIntersection ti;
-    if (!intersect_triangle(ro, rd, t_max, ld3(pr.p0), ld3(pr.p1), ld3(pr.p2), ti)) return false;
-    h.prim = (int32_t)slot; h.t = ti.t; h.b0 = ti.b0; h.b1 = ti.b1; h.b2 = ti.b2; h.phi = 0.0f;
-    return true;
-}
+// Primitive::intersect for one leaf-order slot (primitive.rs:95-103 -> shape/shape.rs:164-170): the shape's test and, behind it, PBRT-v4's alpha test, which evaluates a
+// float texture — shm/alpha.h (included by shm/path.h) holds the body.
+SHM_HD bool prim_intersect(const SceneView& sv, uint32_t slot, V3 ro, V3 rd, Float t_max, Hit& h);
 
 }  // namespace shm

@@ -23,6 +23,12 @@
 #define K_QUADRICS K_DELTA_LIGHTS
 #endif
 #define SHM_QUADRICS K_QUADRICS
+// K_ALPHA (a translation unit's switch; only k_trace_alpha.hip sets it): PBRT-v4's shape alpha (shm/alpha.h) in the traversal body (k_trace.inl) — an alpha-tested triangle
+// parks, and the parked round runs the alpha test behind its three shape tests. Without it both fold away: the traversal kernels of every scene without a cutout
+// (FlatScene::has_alpha) are those of a build without the feature.
+#ifndef K_ALPHA
+#define K_ALPHA false
+#endif
 #include "host/flatten.h"
 #include "shm/bvh_link.h"
 #include "host/bvh_pairs.hpp"
@@ -371,6 +377,8 @@ struct TraceSide {
     uint32_t* d_spill = nullptr;   // ... per resident lane, in HBM
     float4* d_gen_save = nullptr;  // trace5_body<., GEN> (scenes with spheres / patches / instances): per resident lane two 48-byte areas for the ray state
     uint32_t* d_heads = nullptr;   // the queue's head words: [TRACE_QUEUE_PARTS][TRACE_HEAD_STRIDE]
+    SceneView* d_view = nullptr;   // scenes with shape alpha (k_trace_alpha.hip): the SceneView of the launch in HBM, which the texture evaluators that are real calls read the
+                                   // scene through (SceneView::call_copy; the shading kernels keep theirs in LDS, which these kernels' rows have none to spare of)
 };
 struct ShmScene {
     int device = 0;

@@ -609,13 +609,22 @@ class SceneBuilder:
         return len(self.lights) - 1
 
     # ---- shapes ----
+    def _alpha_of(self, alpha):
+        """A shape's `alpha=` (PBRT-v4's "float alpha" / "texture alpha"): None = no cutout; a number = a constant (1 or more cuts nothing and stores nothing, as
+        PBRT-v4 drops it; 0 keeps the shape, invisible); an ftex_* handle (an int) = that float texture. Returns the ABI field: 0, or 1 + the texture's index."""
+        if alpha is None:
+            return 0
+        if isinstance(alpha, (int, np.integer)) and not isinstance(alpha, bool):
+            return int(alpha) + 1
+        return 0 if float(alpha) >= 1.0 else self.ftex_constant(float(alpha)) + 1
+
     def add_mesh(self, p, vi, material, n=None, s=None, uv=None, reverse_orientation=False, swaps_handedness=False,
-                 emission=None, emission_scale=1.0, two_sided=False):
-        """trianglemesh: vertices already in render space. emission = dense 471 table -> one area light per triangle."""
+                 emission=None, emission_scale=1.0, two_sided=False, alpha=None):
+        """trianglemesh: vertices already in render space. emission = dense 471 table -> one area light per triangle. alpha: see _alpha_of."""
         p = _as_f32(p, (-1, 3))
         vi = np.ascontiguousarray(vi, dtype=np.uint32).reshape(-1, 3)
         mesh = dict(p=p, vi=vi, n=None if n is None else _as_f32(n, (-1, 3)), s=None if s is None else _as_f32(s, (-1, 3)),
-                    uv=None if uv is None else _as_f32(uv, (-1, 2)), reverse=bool(reverse_orientation), swaps=bool(swaps_handedness))
+                    uv=None if uv is None else _as_f32(uv, (-1, 2)), reverse=bool(reverse_orientation), swaps=bool(swaps_handedness), alpha=self._alpha_of(alpha))
         self.meshes.append(mesh)
         base = self._tri_count
         ntri = vi.shape[0]
@@ -634,7 +643,7 @@ class SceneBuilder:
         self._n_prims += ntri
         return first_prim
 
-    def add_ply(self, lib, filename, material, render_from_object=None, reverse_orientation=False, **light):
+    def add_ply(self, lib, filename, material, render_from_object=None, reverse_orientation=False, alpha=None, **light):
         """The "plymesh" shape (shape/shape.rs:97-135): TriQuadMesh::read_ply through the host mirror, then a TriangleMesh of its
         triangles and a BilinearPatchMesh of its quads, both with the file's n and uv (zeros where the file has none: the reference
         hands those over too). Positions go to render space as TriangleMesh::new does (mesh.rs:42-64): points through the matrix,
@@ -659,6 +668,9 @@ class SceneBuilder:
             nr = -nr
         swaps = bool(np.linalg.det(rfo[:3, :3].astype(np.float64)) < 0)
         first_tri = first_patch = None
+        field = self._alpha_of(alpha)
+        if field:
+            light = dict(light, alpha=field - 1)  # (as a handle: one texture for both meshes of the file)
         if tri is not None:
             first_tri = self.add_mesh(pr.astype(np.float32), tri.astype(np.uint32), material, n=nr, uv=uv, reverse_orientation=reverse_orientation,
                                       swaps_handedness=swaps, **light)
@@ -668,13 +680,13 @@ class SceneBuilder:
         return first_tri, first_patch
 
     def add_patch_mesh(self, p, vi, material, n=None, uv=None, reverse_orientation=False, swaps_handedness=False, emission=None,
-                       emission_scale=1.0, two_sided=False):
+                       emission_scale=1.0, two_sided=False, alpha=None):
         """bilinearmesh (shape/mesh.rs:289-376): vertices in render space, 4 indices per patch in the order p00, p10, p01, p11
         (bilinear_patch.rs:87-98). emission -> one DiffuseAreaLight per patch."""
         p = _as_f32(p, (-1, 3))
         vi = np.ascontiguousarray(vi, dtype=np.uint32).reshape(-1, 4)
         self.patch_meshes.append(dict(p=p, vi=vi, n=None if n is None else _as_f32(n, (-1, 3)), uv=None if uv is None else _as_f32(uv, (-1, 2)),
-                                      reverse=bool(reverse_orientation), swaps=bool(swaps_handedness)))
+                                      reverse=bool(reverse_orientation), swaps=bool(swaps_handedness), alpha=self._alpha_of(alpha)))
         base, n = self._patch_count, vi.shape[0]
         self._patch_count += n
         first_prim = self._n_prims
@@ -691,7 +703,7 @@ class SceneBuilder:
         return first_prim
 
     def add_sphere(self, radius, material, render_from_object=None, reverse_orientation=False, z_min=None, z_max=None,
-                   phi_max=360.0, emission=None, emission_scale=1.0, two_sided=False):
+                   phi_max=360.0, emission=None, emission_scale=1.0, two_sided=False, alpha=None):
         rfo = IDENTITY if render_from_object is None else _as_f32(render_from_object, (4, 4))
         ofr = np.linalg.inv(rfo.astype(np.float64)).astype(np.float32)
         s = abi.ShmSphere()
@@ -708,6 +720,7 @@ class SceneBuilder:
         s.object_from_render[:] = [float(x) for x in ofr.ravel()]
         s.reverse_orientation = int(reverse_orientation)
         s.transform_swaps_handedness = int(np.linalg.det(rfo[:3, :3].astype(np.float64)) < 0)
+        s.alpha = self._alpha_of(alpha)
         self.spheres.append(s)
         prim_index = self._n_prims
         li = -1
@@ -721,7 +734,7 @@ class SceneBuilder:
 
     # PBRT-v4's disk and cylinder (the reference has neither): quadrics in the sphere's record, told apart by ShmSphere.quadric; still SHM_SHAPE_SPHERE primitives, and
     # prim_bounds' sphere box — (-r, -r, z_min) .. (r, r, z_max) through render_from_object — is theirs too (a disk's z_min == z_max is its height)
-    def _add_quadric(self, kind, radius, z_min, z_max, inner, phi_max, area, material, render_from_object, reverse_orientation, emission, emission_scale, two_sided):
+    def _add_quadric(self, kind, radius, z_min, z_max, inner, phi_max, area, material, render_from_object, reverse_orientation, emission, emission_scale, two_sided, alpha=None):
         rfo = IDENTITY if render_from_object is None else _as_f32(render_from_object, (4, 4))
         ofr = np.linalg.inv(rfo.astype(np.float64)).astype(np.float32)
         s = abi.ShmSphere()
@@ -733,6 +746,7 @@ class SceneBuilder:
         s.object_from_render[:] = [float(x) for x in ofr.ravel()]
         s.reverse_orientation = int(reverse_orientation)
         s.transform_swaps_handedness = int(np.linalg.det(rfo[:3, :3].astype(np.float64)) < 0)
+        s.alpha = self._alpha_of(alpha)
         self.spheres.append(s)
         prim_index = self._n_prims
         li = -1
@@ -744,19 +758,19 @@ class SceneBuilder:
         return prim_index
 
     def add_disk(self, radius, material, height=0.0, inner_radius=0.0, phi_max=360.0, render_from_object=None, reverse_orientation=False,
-                 emission=None, emission_scale=1.0, two_sided=False):
+                 emission=None, emission_scale=1.0, two_sided=False, alpha=None):
         """PBRT-v4's Shape "disk": the annulus inner_radius <= rho <= radius of the plane z = height, its normal +z in object space. Area phi_max (r^2 - inner^2) / 2."""
         return self._add_quadric(abi.SHM_QUADRIC_DISK, radius, height, height, inner_radius, phi_max,
                                  lambda s: f32(f32(s.phi_max) * f32(f32(f32(s.radius) * f32(s.radius)) - f32(f32(s.theta_z_min) * f32(s.theta_z_min)))) * f32(0.5),
-                                 material, render_from_object, reverse_orientation, emission, emission_scale, two_sided)
+                                 material, render_from_object, reverse_orientation, emission, emission_scale, two_sided, alpha)
 
     def add_cylinder(self, radius, material, z_min=-1.0, z_max=1.0, phi_max=360.0, render_from_object=None, reverse_orientation=False,
-                     emission=None, emission_scale=1.0, two_sided=False):
+                     emission=None, emission_scale=1.0, two_sided=False, alpha=None):
         """PBRT-v4's Shape "cylinder": radius around the object's z axis between z_min and z_max (ordered here), its normal pointing outwards. Area (z_max - z_min) r phi_max."""
         lo, hi = min(z_min, z_max), max(z_min, z_max)
         return self._add_quadric(abi.SHM_QUADRIC_CYLINDER, radius, lo, hi, 0.0, phi_max,
                                  lambda s: f32(f32(f32(s.z_max) - f32(s.z_min)) * f32(s.radius)) * f32(s.phi_max),
-                                 material, render_from_object, reverse_orientation, emission, emission_scale, two_sided)
+                                 material, render_from_object, reverse_orientation, emission, emission_scale, two_sided, alpha)
 
     # ---- camera / film ----
     # PixelFilter: name -> (SHM_FILTER_*, PBRT-v4's default radius, its default parameters: sigma | B, C | tau)
@@ -952,6 +966,7 @@ class SceneBuilder:
             mm.s = _fptr(m["s"]) if m["s"] is not None else None
             mm.uv = _fptr(m["uv"]) if m["uv"] is not None else None
             mm.reverse_orientation, mm.transform_swaps_handedness = int(m["reverse"]), int(m["swaps"])
+            mm.alpha = int(m["alpha"])
         spheres = (abi.ShmSphere * max(1, len(self.spheres)))(*self.spheres)
         patch_meshes = (abi.ShmBilinearPatchMesh * max(1, len(self.patch_meshes)))()
         for i, m in enumerate(self.patch_meshes):
@@ -962,6 +977,7 @@ class SceneBuilder:
             pm.n = _fptr(m["n"]) if m["n"] is not None else None
             pm.uv = _fptr(m["uv"]) if m["uv"] is not None else None
             pm.reverse_orientation, pm.transform_swaps_handedness = int(m["reverse"]), int(m["swaps"])
+            pm.alpha = int(m["alpha"])
         materials = (abi.ShmMaterial * len(self.materials))(*self.materials)
         spec = np.concatenate(self.spec).astype(np.float32) if self.spec else np.zeros(1, np.float32)
         d = abi.ShmSceneDesc()

@@ -436,7 +436,8 @@ def cube_sphere(n, seed=1234, amplitude=0.15, shuffle_seed=99, as_quads=False, q
     return verts, tris
 
 
-def ganesha_proxy(lib, width=1024, height=1024, n=599, with_room=True, coated=False, variant=None, floor_filter="ewa", quad_fraction=None, object_material=None, film=None, extra_lights=None, camera=None):
+def ganesha_proxy(lib, width=1024, height=1024, n=599, with_room=True, coated=False, variant=None, floor_filter="ewa", quad_fraction=None, object_material=None, film=None, extra_lights=None, camera=None,
+                  cutout_fraction=None, cutout_alpha=True):
     """S3 (configs C3/C5): n=599 gives 6*599^2*2 = 4 305 612 triangles and 2 152 808 vertices.
     coated=True: the object is CoatedDiffuse (the material of the reference's Ganesha render, images/shimmer-ganesha-1.png).
     variant (round 5: the shapes a real PBRT-v4 scene mixes into its triangles; same camera, room and object):
@@ -453,7 +454,9 @@ def ganesha_proxy(lib, width=1024, height=1024, n=599, with_room=True, coated=Fa
                        TransformedPrimitives in the object's place — the class instancing exists for: most rays cross several instance boxes, each a transformed sub-traversal
       "quads"          (round 6) the object's 6 n^2 cells as bilinear patches instead of 12 n^2 triangles: what a quad PLY file becomes in the reference
       "environment"    no room and no window: the object on its ground plane under an ImageInfinitelight (light.rs:805-981) — escaped rays look the map up, next-event
-                       estimation samples its (compensated) piecewise-constant distribution"""
+                       estimation samples its (compensated) piecewise-constant distribution
+    cutout_fraction (no variant): that share of the object's triangles — every k-th one — as a second mesh with uv coordinates and, with `cutout_alpha`, PBRT-v4's shape
+    alpha: a 64 x 32 checkerboard over the sphere's (longitude, latitude). `cutout_alpha=False`: the same two meshes uncut (the workload's partner in a measurement)."""
     assert variant in (None, "patch_emitter", "one_sphere", "instanced", "environment", "textured_floor", "textured_hidden", "quads", "smooth", "mesh_emitter", "textured_object", "instance_grid", "one_disk", "one_cylinder")
     b = SceneBuilder()
     b.set_film(width, height, **(film or {}))
@@ -478,6 +481,17 @@ def ganesha_proxy(lib, width=1024, height=1024, n=599, with_room=True, coated=Fa
         verts, tris = cube_sphere(n, as_quads=variant == "quads")
     if quad_fraction is not None:
         pass
+    elif cutout_fraction is not None:
+        assert variant is None and 0.0 < cutout_fraction <= 1.0
+        cut = (np.arange(tris.shape[0]) * float(cutout_fraction)).astype(np.int64)
+        cut = np.concatenate([[True], cut[1:] != cut[:-1]])  # every k-th triangle, spread over the whole object
+        vr = _to_render(verts, rfw)
+        d = verts / np.linalg.norm(verts, axis=1, keepdims=True)
+        uv = np.stack([0.5 + np.arctan2(d[:, 2], d[:, 0]) / (2 * np.pi), 0.5 - np.arcsin(np.clip(d[:, 1], -1, 1)) / np.pi], 1).astype(np.float32)
+        if (~cut).any():
+            b.add_mesh(vr, tris[~cut], obj)
+        holes = b.ftex_checkerboard(None, None, mapping=b.add_texture_mapping("uv", su=64.0, sv=32.0)) if cutout_alpha else None
+        b.add_mesh(vr, tris[cut], obj, uv=uv, alpha=holes)
     elif variant == "quads":
         # (round 6) the object as 6 n^2 BILINEAR PATCHES — the reference turns every quad face of a PLY file into one (shape/shape.rs:97-137), and the showcase Ganesha is
         # a quad PLY: the class a real scene's traversal runs in, every leaf a parked non-triangle test
@@ -997,3 +1011,82 @@ def quadric_scene(lib, variant="lean", width=40, height=32, film=None, n_disks=9
         for s in b.spheres:
             s.quadric = abi.SHM_QUADRIC_SPHERE
     return _finish(b, lib, rfw=rfw, name=f"disks and cylinders ({variant})" + (" as spheres" if as_spheres else ""))
+
+
+def cutout_scene(lib, variant="lean", width=32, height=32, film=None, alpha="checker", disk=False, n_leaves=0, cut=True):
+    """PBRT-v4's shape alpha (`alpha=` of the SceneBuilder's shapes) in one small scene per scene class: an open box lit by a quad emitter overhead and in front, and in
+    front of its back wall a quad of two triangles cut by a 4 x 4 checkerboard over its (u, v) — seen directly, and as the shadow it casts on the wall —, a bilinear patch
+    cut by dots, and a sphere cut by a checkerboard over its (phi, theta). `variant`:
+      "lean"         every material a DiffuseMaterial
+      "glass"        the cut sphere is smooth glass: the material-sorted fused kernel
+      "coated"       the floor a coated diffuse material: the staged LayeredBxDF kernels
+      "textured"     the cut quad's reflectance is an image texture over the same (u, v)
+      "environment"  an environment map beside the emitter
+      "instances"    a cut quad and a cut sphere inside an object that is instanced twice
+    `alpha`: the quad's texture — "checker", a number (a constant) or None; `disk`: a cut annulus as well (PBRT-v4's disk: the extended kernels); `n_leaves`: that many
+    small cut triangles scattered in front of the wall; `cut=False`: the same shapes without any alpha (what a build that ignores the field would render)."""
+    assert variant in ("lean", "glass", "coated", "textured", "environment", "instances")
+    b = SceneBuilder()
+    b.set_film(width, height, **(film or {}))
+    rfw = np.asarray(b.set_camera_look_at(lib, (0.0, 1.0, 3.6), (0.0, 0.9, 0.0), (0, 1, 0), 40.0), np.float32).reshape(4, 4)
+
+    def place(m, at):
+        m = np.array(m, np.float64)
+        m[:3, 3] = at
+        return (rfw.astype(np.float64) @ m).astype(np.float32)
+
+    def a(tex):
+        return tex if cut else None
+
+    grey = b.material_diffuse(0.55)
+    floor_m = b.material_coated_diffuse(reflectance=0.5, roughness=0.1) if variant == "coated" else b.material_diffuse(_two_point_spectrum(b, 0.3, 0.6))
+    p, vi = _box((-1.6, 0.0, -1.5), (1.6, 2.4, 1.5), faces="xXz")
+    b.add_mesh(_to_render(p, rfw), vi, b.material_diffuse(_two_point_spectrum(b, 0.6, 0.4)))
+    p, vi = _quad((-1.6, 0.0, -1.5), (-1.6, 0.0, 1.5), (1.6, 0.0, 1.5), (1.6, 0.0, -1.5))
+    b.add_mesh(_to_render(p, rfw), vi, floor_m)
+    p, vi = _quad((-0.4, 2.3, 0.6), (0.4, 2.3, 0.6), (0.4, 2.3, 1.2), (-0.4, 2.3, 1.2))
+    b.add_mesh(_to_render(p, rfw), vi, b.material_diffuse(0.0), emission=blackbody_dense(5500.0), emission_scale=14.0)
+    # the cut quad: (u, v) = (0, 0) .. (1, 1) over it, four cells each way
+    uv = np.array([[0, 0], [1, 0], [1, 1], [0, 1]], np.float32)
+    checker4 = b.ftex_checkerboard(None, None, mapping=b.add_texture_mapping("uv", su=4.0, sv=4.0))
+    quad_alpha = checker4 if alpha == "checker" else alpha
+    quad_m = b.material_diffuse(b.add_image_texture(test_image(16, 3), filter="bilinear")) if variant == "textured" else b.material_diffuse(_two_point_spectrum(b, 0.7, 0.2))
+    p, vi = _quad((-0.9, 0.3, -0.6), (0.3, 0.3, -0.6), (0.3, 1.7, -0.6), (-0.9, 1.7, -0.6))
+    b.add_mesh(_to_render(p, rfw), vi, quad_m, uv=uv, alpha=a(quad_alpha))
+    # a skewed bilinear patch cut by dots, eight cells each way
+    dots = b.ftex_dots(0.0, 1.0, mapping=b.add_texture_mapping("uv", su=6.0, sv=6.0))
+    pp = np.array([(0.5, 0.2, 0.2), (1.3, 0.2, -0.1), (0.5, 1.1, 0.0), (1.3, 1.3, -0.4)], np.float32)
+    b.add_patch_mesh(_to_render(pp, rfw), np.array([[0, 1, 2, 3]], np.uint32), grey, uv=np.array([[0, 0], [1, 0], [0, 1], [1, 1]], np.float32), alpha=a(dots))
+    # a sphere cut by a checkerboard over (phi / phi_max, theta): a cage
+    cage = b.ftex_checkerboard(None, None, mapping=b.add_texture_mapping("uv", su=8.0, sv=4.0))
+    up = np.array([[1, 0, 0, 0], [0, 0, 1, 0], [0, -1, 0, 0], [0, 0, 0, 1]], np.float64)  # object +z -> world +y
+    b.add_sphere(0.4, b.material_dielectric(1.5) if variant == "glass" else grey, render_from_object=place(up, (-0.2, 0.45, 0.5)), alpha=a(cage))
+    if disk:
+        b.add_disk(0.45, grey, inner_radius=0.1, phi_max=300.0, render_from_object=place(np.eye(4), (0.9, 1.8, -0.9)), alpha=a(0.5))
+    if n_leaves:
+        rng = np.random.Generator(np.random.PCG64(17))
+        leaf = b.ftex_checkerboard(None, None, mapping=b.add_texture_mapping("uv", su=2.0, sv=2.0))
+        ps, vis = [], []
+        for k in range(n_leaves):
+            c = np.array([rng.uniform(-1.4, 1.4), rng.uniform(0.2, 2.1), rng.uniform(-1.3, -0.8)])
+            e0, e1 = rng.uniform(-0.15, 0.15, 3), rng.uniform(-0.15, 0.15, 3)
+            ps += [c, c + e0, c + e1]
+            vis.append([3 * k, 3 * k + 1, 3 * k + 2])
+        b.add_mesh(_to_render(np.array(ps, np.float32), rfw), np.array(vis, np.uint32), grey, uv=np.tile(np.array([[0, 0], [1, 0], [0, 1]], np.float32), (n_leaves, 1)), alpha=a(leaf))
+    if variant == "environment":
+        rot = np.array([[1, 0, 0, 0], [0, 0, 1, 0], [0, -1, 0, 0], [0, 0, 0, 1]], np.float32)
+        b.light_image_infinite(environment_image(16), scale=0.3, render_from_light=rot)
+    if variant == "instances":
+        b.begin_object("fence")
+        p, vi = _quad((-0.3, 0.0, 0.0), (0.3, 0.0, 0.0), (0.3, 0.8, 0.0), (-0.3, 0.8, 0.0))
+        b.add_mesh(p, vi, quad_m, uv=uv, alpha=a(quad_alpha))
+        ball = up.copy()
+        ball[:3, 3] = (0.0, 1.0, 0.0)
+        b.add_sphere(0.2, grey, render_from_object=ball.astype(np.float32), alpha=a(cage))
+        b.end_object()
+        for k, (x, z, sy) in enumerate(((-1.1, 0.7, 1.0), (1.0, 0.9, 1.3))):
+            m = np.diag([1.0, sy, 1.0, 1.0])
+            ang = 0.4 + 0.7 * k
+            m[:3, :3] = np.array([[np.cos(ang), 0, np.sin(ang)], [0, 1, 0], [-np.sin(ang), 0, np.cos(ang)]]) @ m[:3, :3]
+            b.add_instance("fence", place(m, (x, 0.0, z)))
+    return _finish(b, lib, rfw=rfw, name=f"cutouts ({variant})" + ("" if cut else " uncut"))
