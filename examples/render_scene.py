@@ -11,6 +11,8 @@
     python examples/render_scene.py cornell_probe                    (examples/scenes/cornell_probe.pbrt: an equal-area probe in the middle of the Cornell box)
     python examples/render_scene.py cornell --spp 256 --adaptive 0.05 [--min-spp 16] [--batch-spp 4]   (adaptive sampling: --spp is the cap)
     python examples/render_scene.py cornell --spp 4 --frames 16 --orbit 1 --temporal [--denoise]        (a turntable accumulated over time: <name>.fNNN.pfm / .png per frame)
+    python examples/render_scene.py cornell --integrator ambientocclusion [--ao-distance 0.5] [--spp 4 --frames 16 --orbit 1 --temporal --denoise --tonemap aces]   (PBRT-v4's ambient occlusion: the cheap frame)
+    python examples/render_scene.py ambient_occlusion                (examples/scenes/integrators/ambient_occlusion.pbrt: the integrator named by the scene file)
     python examples/render_scene.py cornell --tonemap aces --auto-exposure [--dither] [--frames 16 --orbit 1 --frame-time 0.033]   (the .png from the display pass on the device: DESIGN.md section 4m)
 
 Everything goes through the C ABI of include/shimmer_hip.h (shimmer_amd/abi.py is the ctypes binding): scene description ->
@@ -30,8 +32,21 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from shimmer_amd import abi, render, scenes  # noqa: E402
 
 
+def file_integrator(p, sc, args):
+    """The integrator of a render: what the command line names; where it names none, what the scene file names (the ambient occlusion integrator with its two
+    parameters: examples/scenes/integrators/ambient_occlusion.pbrt); "path" otherwise. --ao-distance and --ao-sampling, where given, override the file's values."""
+    fp = getattr(sc, "file_params", None)
+    if args.integrator is None and fp is not None and fp.integrator == abi.SHM_INTEGRATOR_AMBIENT_OCCLUSION:
+        p.integrator = fp.integrator
+        if args.ao_sampling is None:
+            p.ao_uniform_sample = fp.ao_uniform_sample
+        if args.ao_distance is None:
+            p.ao_max_distance = fp.ao_max_distance
+    return p
+
+
 def make_scene(lib, name, w, h, film=None, camera=None):
-    if camera is not None and (name in ("checkerboard", "diffuse_transmission", "cornell_probe", "disk_and_cylinder", "cutout") or name.startswith(("procedural", "fuzz:"))):
+    if camera is not None and (name in ("checkerboard", "diffuse_transmission", "cornell_probe", "disk_and_cylinder", "cutout", "ambient_occlusion") or name.startswith(("procedural", "fuzz:"))):
         raise SystemExit(f"--camera does not apply to {name}: a scene file has its own camera, and the procedural and fuzz generators take none")
     if name == "cornell":
         return scenes.cornell_box(lib, w, h, camera=camera, film=film)
@@ -42,19 +57,21 @@ def make_scene(lib, name, w, h, film=None, camera=None):
         return scenes.cornell_box(lib, w, h, camera=camera, textured=True, film=film)
     if name == "coated":
         return scenes.cornell_box(lib, w, h, camera=camera, coated=True, film=film)
-    if name in ("checkerboard", "diffuse_transmission", "cornell_probe", "disk_and_cylinder", "cutout"):
+    if name in ("checkerboard", "diffuse_transmission", "cornell_probe", "disk_and_cylinder", "cutout", "ambient_occlusion"):
         # scene FILES through the C++ front end (their own film size; --filter is the file's): PBRT-v4's procedural textures (examples/scenes/checkerboard.pbrt); a back-lit
         # sheet of PBRT-v4's diffuse transmission material in the Cornell box (examples/scenes/diffuse_transmission.pbrt: the extended *_dl kernels); PBRT-v4's
         # spherical camera as an equal-area probe in the middle of the box (examples/scenes/cornell_probe.pbrt; the file's camera: --camera does not apply)
         # ; PBRT-v4's disk and cylinder as a lamp post whose emitter is a disk (examples/scenes/disk_and_cylinder.pbrt: the extended kernels and k_trace_quadrics.hip's)
         # ; PBRT-v4's shape alpha as a fence, a caged ball and a half-transparent veil in front of a wall (examples/scenes/cutout.pbrt: k_trace_alpha.hip's kernels)
+        # ; PBRT-v4's ambient occlusion integrator, named by the file (examples/scenes/integrators/ambient_occlusion.pbrt: file_integrator below takes it over unless --integrator is given)
         import ctypes as C
         from types import SimpleNamespace
         out = C.POINTER(abi.ShmPbrtScene)()
-        path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "scenes", name + ".pbrt")
+        # (the scene that names another integrator than the oracle has lives one folder down: examples/scenes/*.pbrt are the files every integrator of the oracle renders)
+        path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "scenes", *((["integrators"] if name == "ambient_occlusion" else []) + [name + ".pbrt"]))
         abi.check(lib, lib.shm_scene_load_pbrt(path.encode(), C.byref(out)), "shm_scene_load_pbrt")
         res = out.contents.desc.film.full_resolution
-        return SimpleNamespace(desc=out.contents.desc, name=name + ".pbrt", res=(res[0], res[1]), keep=out)
+        return SimpleNamespace(desc=out.contents.desc, name=name + ".pbrt", res=(res[0], res[1]), keep=out, file_params=out.contents.params)
     if name == "translucent":  # the same material through the Python builder: the sheet and the tall box of scenes.cornell_box
         return scenes.cornell_box(lib, w, h, camera=camera, film=film, diffuse_transmission="sheet tall")
     if name in ("procedural", "procedural-general", "procedural-coated"):  # the same textures through the Python builder (scenes.procedural_cornell)
@@ -150,8 +167,9 @@ def render_sequence(lib, args, sc, r, w, h):
         raise SystemExit(f"--orbit knows the cameras of {', '.join(VIEWS)} (and not --camera spherical)")
     if args.denoise and not args.temporal:
         raise SystemExit("--frames with --denoise filters the accumulated frame: add --temporal")
-    p = render.make_params(seed=args.seed, spp=args.frames * args.spp, max_depth=args.max_depth, integrator=args.integrator, reference_quirks=not args.quirks_off,
-                           sampler=args.sampler)
+    p = render.make_params(seed=args.seed, spp=args.frames * args.spp, max_depth=args.max_depth, integrator=args.integrator or "path", reference_quirks=not args.quirks_off,
+                           sampler=args.sampler, ao_max_distance=args.ao_distance or 0.0, ao_uniform_sample=args.ao_sampling == "uniform")
+    p = file_integrator(p, sc, args)
     out = args.output or f"{args.scene.replace(':', '_')}.pfm"
     stem = os.path.splitext(out)[0]
     pictures = Pictures(lib, r, args)
@@ -212,7 +230,10 @@ def main():
     ap.add_argument("--res", type=int, default=512)
     ap.add_argument("--height", type=int, default=0)
     ap.add_argument("--max-depth", type=int, default=5)
-    ap.add_argument("--integrator", default="path", choices=["path", "simplepath", "randomwalk"])
+    ap.add_argument("--integrator", default=None, choices=["path", "simplepath", "randomwalk", "ambientocclusion"],
+                    help="ambientocclusion: PBRT-v4's AO integrator — a clay render, one short occlusion ray per sample (DESIGN.md section 4o); every other option composes with it. Default: the scene file's integrator where it names this one, else path")
+    ap.add_argument("--ao-distance", type=float, default=None, metavar="D", help="with the ambient occlusion integrator: the occlusion rays' length (0: unbounded; default: the scene file's, else 0)")
+    ap.add_argument("--ao-sampling", default=None, choices=["cosine", "uniform"], help="with the ambient occlusion integrator: the hemisphere sampling (default: the scene file's, else cosine)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--exposure", type=float, default=1.0)
     ap.add_argument("--sampler", default="independent", choices=["independent", "zsobol"], help="ShmRenderParams::sampler (DESIGN.md \"Sampler\")")
@@ -255,8 +276,9 @@ def main():
     sc = make_scene(lib, args.scene, w, h, film=dict(filter=args.filter), camera=dict(type="spherical", mapping=args.mapping) if args.camera == "spherical" else None)
     w, h = getattr(sc, "res", (w, h))
     r = render.Renderer(lib, sc.desc, 0)
-    p = render.make_params(seed=args.seed, spp=args.spp, max_depth=args.max_depth, integrator=args.integrator, reference_quirks=not args.quirks_off,
-                           sampler=args.sampler)
+    p = render.make_params(seed=args.seed, spp=args.spp, max_depth=args.max_depth, integrator=args.integrator or "path", reference_quirks=not args.quirks_off,
+                           sampler=args.sampler, ao_max_distance=args.ao_distance or 0.0, ao_uniform_sample=args.ao_sampling == "uniform")
+    p = file_integrator(p, sc, args)
     if args.frames > 0:
         return render_sequence(lib, args, sc, r, w, h)
     tile_spp = None

@@ -491,7 +491,18 @@ typedef struct ShmRenderParams {
      * the default) or SHM_SAMPLER_RANDOMIZE_NONE (1, the bare sequence). Callers that zero `pad` keep the independent sampler. */
     uint8_t sampler;
     uint8_t sampler_randomization;
-    uint8_t pad[5];
+    /* The ambient occlusion integrator's two parameters (SHM_INTEGRATOR_AMBIENT_OCCLUSION), carved out of the five bytes that were `pad`: no size
+     * or offset changed, `pad` still names the five bytes, and a caller that zeroes them gets PBRT-v4's defaults. Every other integrator ignores them.
+     *   ao_uniform_sample  0 (the default, PBRT-v4's "cossample" true): cosine-weighted hemisphere sampling; anything else: uniform hemisphere sampling, pdf 1 / (2 pi)
+     *   ao_max_distance    0 (the default, PBRT-v4's "maxdistance" infinity): the occlusion ray is unbounded; a finite positive value is its t_max. Negative or NaN:
+     *                      SHM_ERR_INVALID_ARGUMENT */
+    union {
+        uint8_t pad[5];
+        struct __attribute__((packed)) {
+            uint8_t ao_uniform_sample;
+            float ao_max_distance;   /* at offset 28 of the struct: aligned */
+        };
+    };
 } ShmRenderParams;
 enum {
     SHM_SAMPLER_INDEPENDENT = 0,
@@ -504,7 +515,14 @@ enum {
 enum {
     SHM_INTEGRATOR_PATH = 0,        /* PathIntegrator,       integrator.rs:748-963 */
     SHM_INTEGRATOR_SIMPLE_PATH = 1, /* SimplePathIntegrator, integrator.rs:573-733 */
-    SHM_INTEGRATOR_RANDOM_WALK = 2  /* RandomWalkIntegrator, integrator.rs:445-563: le + f cos Li / (1/4pi), folded innermost-first */
+    SHM_INTEGRATOR_RANDOM_WALK = 2, /* RandomWalkIntegrator, integrator.rs:445-563: le + f cos Li / (1/4pi), folded innermost-first */
+    /* PBRT-v4's AOIntegrator (`Integrator "ambientocclusion"`; the reference has none): one camera ray and one occlusion ray per sample, no material, texture or light.
+     * At a hit, with n the geometric normal facing the camera ray and u the 2-D draw behind the camera sample: wi = Frame::from_z(n).from_local(w(u)), w cosine- or
+     * uniform-hemisphere distributed (ShmRenderParams::ao_uniform_sample), and if the interaction's spawn_ray(wi) is unoccluded within ao_max_distance
+     * L = illum_scale * illuminant(lambda) * dot(wi, n) / (pi * pdf), else 0. An escaped camera ray is black. illuminant: ShmSceneDesc::color_space.illuminant, which
+     * must be there (SHM_ERR_INVALID_ARGUMENT otherwise); illum_scale = 1 / its CIE Y, computed in double at scene creation and rounded to float once. max_depth is not
+     * looked at. The film is the ordinary film: every pass behind it takes it unchanged. */
+    SHM_INTEGRATOR_AMBIENT_OCCLUSION = 3
 };
 
 /* Tile (tile.rs:5-7): Bounds2i, max exclusive. */
@@ -649,6 +667,17 @@ SHM_API int shm_gbuffer_samples_host(const ShmSceneDesc* desc, const ShmRenderPa
                                      const int32_t* sample_index, const ShmHit* hits, uint32_t n, double* out);
 SHM_API int shm_gbuffer_rho_host(const ShmSceneDesc* desc, const ShmRenderParams* params, const int32_t* pixels_xy, const int32_t* sample_index,
                                  const ShmHit* hits, uint32_t n, float* out);
+/* The ambient occlusion integrator's CPU twin (SHM_INTEGRATOR_AMBIENT_OCCLUSION; no GPU needed): the same shared arithmetic (shm/ao.h) on the host, one sample at a time.
+ * Given the closest hits of the samples' camera rays (shm_gbuffer_camera_rays gives the rays: they are the path integrator's), per sample i:
+ *   rays_out[i]          the occlusion ray with its t_max (zeros where none is queued)
+ *   queued_out[i]        1: the ray is queued; 0: none — the camera ray escaped, or the direction's density is 0 — and the sample is black
+ *   sample_out[5 i ..]   r, g, b: what film_sample_rgb makes of the sample's radiance IF the occlusion ray is unoccluded (zeros where none is queued); the filter weight w;
+ *                        the density the direction was drawn with (0 where none is queued)
+ * A film pixel from these, as the film kernel makes it: over the pixel's samples in increasing sample index, in double, rgb_sum[c] += (double)(w * (unoccluded ? rgb[c] : 0.0f))
+ * and weight_sum += (double)w, where `unoccluded` is: queued, and an any-hit traversal of rays_out[i] finds nothing. Parameters and scene are checked as shm_render_wave
+ * checks them (a negative or NaN ao_max_distance, a scene without an illuminant: SHM_ERR_INVALID_ARGUMENT). */
+SHM_API int shm_ao_samples_host(const ShmSceneDesc* desc, const ShmRenderParams* params, const int32_t* pixels_xy, const int32_t* sample_index, const ShmHit* hits,
+                                uint32_t n, ShmRay* rays_out, uint8_t* queued_out, float* sample_out);
 /* W_c: the sum of the 471-entry table of sensor channel c (1 nm steps), in double — a surface of rho = 1 has an expected albedo sum / W_c of 1. */
 SHM_API int shm_gbuffer_white(const ShmSceneDesc* desc, double white[3]);
 /* The sums as images, 15 floats per pixel: p[3], n[3], ns[3], uv[2] — each sum / weight_hit —, albedo[3] = (M a) / (M W) per channel with a the albedo sums

@@ -66,8 +66,12 @@ class ShmBilinearPatchMesh(C.Structure):
 
 class _FormerPad:
     """ShmSphere.pad as it was before PBRT-v4's shape alpha had a name: the five bytes behind `quadric` (the header's pad[1] + alpha), at the class `.offset` / `.size`,
-    of an instance a live ctypes view of them. (A plain field cannot overlap `alpha`, and a union would put an unnamed member at the end of _fields_.)"""
+    of an instance a live ctypes view of them. (A plain field cannot overlap `alpha`, and a union would put an unnamed member at the end of _fields_.)
+    ShmRenderParams.pad likewise: the five bytes behind `sampler_randomization`, which the ambient occlusion integrator's two parameters now name."""
     offset, size = 155, 5
+
+    def __init__(self, offset=155, size=5):
+        self.offset, self.size = offset, size
 
     def __get__(self, obj, cls):
         return self if obj is None else (C.c_uint8 * self.size).from_buffer(obj, self.offset)
@@ -190,7 +194,14 @@ class ShmRenderParams(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("samples_per_pixel", C.c_int32), ("max_depth", C.c_int32), ("regularize", C.c_uint8),
                 ("disable_pixel_jitter", C.c_uint8), ("disable_wavelength_jitter", C.c_uint8), ("force_diffuse", C.c_uint8),
                 ("integrator", C.c_uint8), ("sample_lights", C.c_uint8), ("sample_bsdf", C.c_uint8), ("disable_texture_filtering", C.c_uint8),
-                ("disable_reference_quirks", C.c_uint8), ("sampler", C.c_uint8), ("sampler_randomization", C.c_uint8), ("pad", C.c_uint8 * 5)]
+                ("disable_reference_quirks", C.c_uint8), ("sampler", C.c_uint8), ("sampler_randomization", C.c_uint8),
+                # the ambient occlusion integrator's parameters, in the header's union with pad[5]: 0 = cosine sampling / 0 = an infinite distance
+                ("ao_uniform_sample", C.c_uint8), ("ao_max_distance", C.c_float)]
+    pad = _FormerPad(27, 5)
+
+
+assert C.sizeof(ShmRenderParams) == 32 and ShmRenderParams.ao_uniform_sample.offset == 27 and ShmRenderParams.ao_max_distance.offset == 28
+SHM_INTEGRATOR_AMBIENT_OCCLUSION = 3
 
 
 class ShmTile(C.Structure):
@@ -347,6 +358,8 @@ EXPORTS = {
                                            C.c_uint32, C.POINTER(C.c_double)]),
     "shm_gbuffer_rho_host": (C.c_int, [C.POINTER(ShmSceneDesc), C.POINTER(ShmRenderParams), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_uint32,
                                        c_float_p]),
+    "shm_ao_samples_host": (C.c_int, [C.POINTER(ShmSceneDesc), C.POINTER(ShmRenderParams), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_uint32, C.c_void_p,
+                                      C.c_void_p, c_float_p]),
     "shm_gbuffer_white": (C.c_int, [C.POINTER(ShmSceneDesc), C.POINTER(C.c_double)]),
     "shm_gbuffer_resolve": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_double), c_float_p, c_float_p]),
     "shm_denoise_default_params": (C.c_int, [C.POINTER(ShmDenoiseParams)]),

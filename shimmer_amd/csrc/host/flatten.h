@@ -137,6 +137,14 @@ struct FlatScene {
     }
 };
 
+// What a render under the ambient occlusion integrator (SHM_INTEGRATOR_AMBIENT_OCCLUSION, shm/ao.h) refuses — shm_render_wave and the CPU twin say the same words —:
+// null if the parameters and the scene can render
+inline const char* ao_params_error(const ShmRenderParams& params, const FlatScene& flat) {
+    if (!(params.ao_max_distance >= 0.0f)) return "ambient occlusion: ao_max_distance is negative or NaN (0 = infinite, or a positive distance)";
+    if (flat.cs_illuminant.empty()) return "ambient occlusion: the scene has no illuminant (ShmSceneDesc::color_space.illuminant is NULL)";
+    return nullptr;
+}
+
 // n_textures > 0 only for the SpectrumTexture slots of a material (a, b, c): eta and light spectra are plain Spectrum values
 inline bool check_spectrum(const ShmSpectrum& s, uint32_t n_floats, std::string& err, uint32_t n_textures = 0, bool* is_texture = nullptr) {
     if (s.kind == SHM_SPECTRUM_TEXTURE_NODE) {
@@ -586,6 +594,8 @@ inline int flatten_scene(const ShmSceneDesc* d, FlatScene& out, std::string& err
         }
         out.has_image_light = true;  // (has_textures: set where flatten_scene returns)
     }
+    // the colour space's illuminant, kept wherever the description carries one: the ambient occlusion integrator's light (shm/ao.h). No class fact reads it.
+    if (out.cs_illuminant.empty() && d->color_space.illuminant) out.cs_illuminant.assign(d->color_space.illuminant, d->color_space.illuminant + 471);
 
     // FloatTexture node table (texture.rs:88-305): children precede parents, nesting <= 4 (float_texture_evaluate's bound)
     if (d->n_float_textures) {

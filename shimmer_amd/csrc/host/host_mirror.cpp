@@ -33,8 +33,10 @@
 #include "../shm/denoise.h"  // the denoiser's, behind it
 #include "../shm/moments.h"  // the moments pass's
 #include "../shm/temporal.h"  // the temporal pass's
-#include "../shm/display.h"  // the display pass's, last
+#include "../shm/display.h"  // the display pass's
+#include "../shm/ao.h"  // the ambient occlusion integrator's, last
 #include "flatten.h"
+#include "illuminant_scale.hpp"
 
 extern "C" __attribute__((visibility("hidden"))) void shm_set_last_error(const char* msg);  // shimmer_hip.hip
 
@@ -991,6 +993,44 @@ int shm_gbuffer_rho_host(const ShmSceneDesc* desc, const ShmRenderParams* params
         const shm::Hit hit = gbuffer_host_hit(hits[i]);
         const shm::GBufferSurface s = g.tex ? shm::gbuffer_surface<true>(g.sv, r.d, aux, hit, lambda, *params) : shm::gbuffer_surface<false>(g.sv, r.d, aux, hit, lambda, *params);
         for (int k = 0; k < 4; ++k) { o[k] = s.rho.v[k]; o[4 + k] = s.lambda.lambda[k]; o[8 + k] = s.lambda.pdf[k]; }
+    }
+    return SHM_OK;
+}
+
+// ---- the ambient occlusion integrator's CPU twin (include/shimmer_hip.h, shm_ao_samples_host): the scene flattened as above, the camera ray K1's, and
+//      shm::ao_sample — the function k_shade_ao runs on the device — with the float illum_scale shm_scene_create computes ----
+int shm_ao_samples_host(const ShmSceneDesc* desc, const ShmRenderParams* params, const int32_t* pixels_xy, const int32_t* sample_index, const ShmHit* hits, uint32_t n,
+                        ShmRay* rays_out, uint8_t* queued_out, float* sample_out) {
+    if (!pixels_xy || !sample_index || !hits || !rays_out || !queued_out || !sample_out) return SHM_ERR_INVALID_ARGUMENT;
+    GBufferHost g;
+    const int rc = gbuffer_host_open(desc, params, g);
+    if (rc != SHM_OK) return rc;
+    if (const char* e = shm_host::ao_params_error(*params, g.flat)) { shm_set_last_error(e); return SHM_ERR_INVALID_ARGUMENT; }
+    const float illum_scale = host_illuminant_scale(g.flat.cs_illuminant.data());
+    for (uint32_t i = 0; i < n; ++i) {
+        if (!gbuffer_host_hit_ok(g, hits[i])) { shm_set_last_error("a hit names a primitive the scene does not hold"); return SHM_ERR_INVALID_ARGUMENT; }
+        const int px = pixels_xy[2 * i], py = pixels_xy[2 * i + 1];
+        shm::Rng rng = shm::sampler_start_pixel_sample(px, py, sample_index[i], params->seed, g.zs);
+        shm::Wavelengths lambda;
+        shm::Float w;
+        shm::AuxRays aux = shm::aux_none();
+        const shm::Ray r = shm::generate_camera_ray(g.sv, px, py, rng, params->disable_wavelength_jitter != 0, params->disable_pixel_jitter != 0, lambda, w,
+                                                    g.tex ? &aux : nullptr, params->samples_per_pixel);  // (rng: now directly behind the camera sample)
+        memset(&rays_out[i], 0, sizeof(ShmRay));
+        queued_out[i] = 0;
+        float* o = sample_out + 5ull * i;
+        o[0] = o[1] = o[2] = o[4] = 0.0f;
+        o[3] = w;
+        if (hits[i].prim < 0) continue;
+        shm::Spec contrib;
+        shm::Float pdf = 0.0f;
+        if (!shm::ao_sample(g.sv, gbuffer_host_hit(hits[i]), r.d, rng, lambda, params->ao_uniform_sample != 0, params->ao_max_distance, illum_scale, rays_out[i], contrib, &pdf)) continue;
+        queued_out[i] = 1;
+        o[4] = pdf;
+        // K3 adds the contribution to L = 0 (0 + c == c), and K6 takes L as film_add_samples does (render.hip)
+        if (g.sv.quirks_off && !shm::spec_is_finite(contrib)) contrib = shm::spec_const(0.0f);
+        const shm::V3 rgb = shm::film_sample_rgb(g.sv, contrib, lambda);
+        o[0] = rgb.x; o[1] = rgb.y; o[2] = rgb.z;
     }
     return SHM_OK;
 }

@@ -141,7 +141,7 @@ private:
     int32_t width_ = 0, height_ = 0, waves_ = 0;
 };
 
-// integrator.rs:16-42: all three names of the reference; anything else is its "Unknown integrator" panic.
+// integrator.rs:16-42: all three names of the reference, and PBRT-v4's "ambientocclusion"; anything else is the reference's "Unknown integrator" panic.
 inline std::unique_ptr<Integrator> create_integrator(const std::string& name, const PathIntegratorParameters& parameters,
                                                      const ShmSceneDesc& scene, int device = 0) {
     if (name == "path") return std::make_unique<WavefrontPathIntegrator>(scene, parameters, device);
@@ -149,6 +149,9 @@ inline std::unique_ptr<Integrator> create_integrator(const std::string& name, co
     if (name == "simplepath") return std::make_unique<WavefrontPathIntegrator>(scene, parameters, device, (uint8_t)SHM_INTEGRATOR_SIMPLE_PATH);
     // ImageTileIntegrator::create_random_walk_integrator (integrator.rs:149-175)
     if (name == "randomwalk") return std::make_unique<WavefrontPathIntegrator>(scene, parameters, device, (uint8_t)SHM_INTEGRATOR_RANDOM_WALK);
+    // PBRT-v4's AOIntegrator, which the reference does not have: the same driver again, with the defaults of its two parameters ("cossample" true, "maxdistance" infinity:
+    // the zeroed ShmRenderParams::ao_* fields)
+    if (name == "ambientocclusion") return std::make_unique<WavefrontPathIntegrator>(scene, parameters, device, (uint8_t)SHM_INTEGRATOR_AMBIENT_OCCLUSION);
     throw IntegratorError("Unknown integrator " + name);
 }
 

@@ -23,9 +23,11 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <limits>
 #include <set>
 #include <sstream>
 
+#include "illuminant_scale.hpp"
 #include "image_io.hpp"
 #include "scene_assembly.hpp"
 
@@ -222,6 +224,8 @@ public:
         float white_balance = 0.0f;
         uint32_t render_space = SHM_RENDER_SPACE_CAMERA_WORLD;
         bool disable_pixel_jitter = false, disable_wavelength_jitter = false, force_diffuse = false, disable_texture_filtering = false;
+        bool ao_cos_sample = true;      // Integrator "ambientocclusion": "bool cossample" (PBRT-v4's default) ...
+        float ao_max_distance = 0.0f;   // ... and "float maxdistance" as ShmRenderParams::ao_max_distance takes it: 0 = infinite, PBRT-v4's default
     } settings_;
 
     // a directive's parameter list, each parameter stamped with the colour space in effect (ParameterDictionary::new(params,
@@ -1240,7 +1244,15 @@ private:
             need_world(t, tk, false);
             settings_.integrator = read_string(tk, t);
             const Params ps = read_params(tk);
-            if (settings_.integrator != "path" && settings_.integrator != "simplepath" && settings_.integrator != "randomwalk") fail(tk.where(t.line) + ": Unknown integrator " + settings_.integrator);
+            // (the reference's three names, integrator.rs:16-42, and PBRT-v4's "ambientocclusion", which the reference does not have)
+            if (settings_.integrator != "path" && settings_.integrator != "simplepath" && settings_.integrator != "randomwalk" && settings_.integrator != "ambientocclusion")
+                fail(tk.where(t.line) + ": Unknown integrator " + settings_.integrator);
+            if (settings_.integrator == "ambientocclusion") {  // AOIntegrator::Create: "cossample" true, "maxdistance" infinity
+                settings_.ao_cos_sample = ps.one_bool("cossample", true);
+                const float md = ps.one_float("maxdistance", std::numeric_limits<float>::infinity());
+                if (!(md > 0.0f)) fail(tk.where(t.line) + ": ambientocclusion: \"maxdistance\" must be positive");
+                settings_.ao_max_distance = std::isinf(md) ? 0.0f : md;
+            }
             settings_.max_depth = ps.one_int("maxdepth", 5);
             settings_.regularize = ps.one_bool("regularize", false);
             settings_.sample_lights = ps.one_bool("samplelights", true);
@@ -1376,7 +1388,10 @@ static int load_text(const std::string& text, const std::string& name, const std
         p.sampler_randomization = st.randomization == "none" ? SHM_SAMPLER_RANDOMIZE_NONE : SHM_SAMPLER_FASTOWEN;
         // SHM_REFERENCE_QUIRKS (include/shimmer_hip.h ShmRenderParams::disable_reference_quirks): ON unless the host's environment says 0 / off
         if (const char* q = getenv("SHM_REFERENCE_QUIRKS")) p.disable_reference_quirks = (!strcmp(q, "0") || !strcmp(q, "off") || !strcmp(q, "OFF")) ? 1 : 0;
-        p.integrator = st.integrator == "path" ? SHM_INTEGRATOR_PATH : (st.integrator == "simplepath" ? SHM_INTEGRATOR_SIMPLE_PATH : SHM_INTEGRATOR_RANDOM_WALK);
+        p.integrator = st.integrator == "path" ? SHM_INTEGRATOR_PATH : (st.integrator == "simplepath" ? SHM_INTEGRATOR_SIMPLE_PATH
+                       : (st.integrator == "ambientocclusion" ? SHM_INTEGRATOR_AMBIENT_OCCLUSION : SHM_INTEGRATOR_RANDOM_WALK));
+        p.ao_uniform_sample = st.ao_cos_sample ? 0 : 1;
+        p.ao_max_distance = st.ao_max_distance;
         snprintf(scene->integrator, sizeof(scene->integrator), "%s", st.integrator.c_str());
         snprintf(scene->output_filename, sizeof(scene->output_filename), "%s", st.filename.c_str());
         Assembly::film_output_matrix(st.white_balance, scene->output_rgb_from_sensor_rgb, loader.film_color_space());
@@ -1398,6 +1413,14 @@ static int load_text(const std::string& text, const std::string& name, const std
 }
 
 }  // namespace pbrt
+
+// host/illuminant_scale.hpp: SpectrumToY = <Y, s> / CIE_Y_integral. Here because the CIE tables are this unit's (host/spectral_tables.inc).
+float host_illuminant_scale(const float* illuminant) {
+    static const std::vector<float> y = PBRT_TABLE(CIE_Y), yi = PBRT_TABLE(CIE_Y_INTEGRAL);
+    double acc = 0.0;
+    for (int i = 0; i < 471; ++i) acc += (double)y[i] * (double)illuminant[i];
+    return (float)((double)yi[0] / acc);
+}
 
 extern "C" {
 

@@ -21,7 +21,8 @@ enum : int { IMG_NONE, IMG_TEX, IMG_ENV, N_IMG };  // no image / image textures 
 // the pixel filter's class: box (and every filter under options.disable_pixel_jitter: k_generate, k_film) / triangle / tabulated with a constant weight (gaussian) /
 // tabulated with a signed one (Mitchell, sinc)
 enum : int { FLT_BOX, FLT_TRIANGLE, FLT_TABULATED, FLT_TABULATED_SIGNED, N_FLT };
-enum : int { ROUTE_LEAN, ROUTE_STAGED, ROUTE_SIMPLE, ROUTE_RANDOM_WALK };
+enum : int { ROUTE_LEAN, ROUTE_STAGED, ROUTE_SIMPLE, ROUTE_RANDOM_WALK,
+              ROUTE_AO };  // PBRT-v4's ambient occlusion integrator: k_shade_ao (k_ao.hip) in a vertex's place, and the bounce loop runs once whatever max_depth says
 constexpr int NEVER = 1 << 30;  // a bounce no render reaches (max_depth <= 254)
 // The table's null cells, by image class: the textured classes have no lean kernel (direct or diverted) and no k_generate<., LEAN>. serving_build and has_generate_build
 // (below) go by it.
@@ -229,6 +230,7 @@ inline ScenePlan scene_plan(const SceneFacts& f, const Knobs& k) {
 
 struct RenderPlan {
     int route = ROUTE_LEAN;  // what shades a vertex: k_shade<lean> alone / the staged pipeline (k_vertex -> k_scatter<class>, or the fused all-materials kernel) / the other integrators
+                             // (ROUTE_AO, like them: 32-byte hit records, K1's full record, no known-constants bounce 0; of the coordinates below it reads zs, flt and spherical)
     bool lean_first = false; // bounce 0 on known constants: k_generate<., LEAN> wrote no record and no identity queue
     // the render's hit records: 16 bytes {primitive, b0, b1, b2} where every kernel that reads them takes that form (triangle and textured scenes; with spheres / patches the
     // split form, a second record with t and phi — not with instances: a hit inside one names it in the 32-byte record); kept: double-buffered by bounce parity
@@ -258,7 +260,8 @@ inline RenderPlan render_plan(const ScenePlan& s, const ShmRenderParams& o) {
     const bool path = o.integrator == SHM_INTEGRATOR_PATH, fd = o.force_diffuse != 0, layered = f.has_class[CLS_LAYERED];
     // staged shading: everything but the lean class, which keeps the fused kernel (one BxDF class: nothing to sort, and the parameter block would be pure traffic);
     // options.force_diffuse always takes the staged path
-    p.route = !path ? (o.integrator == SHM_INTEGRATOR_RANDOM_WALK ? ROUTE_RANDOM_WALK : ROUTE_SIMPLE) : ((!s.lean || fd) ? ROUTE_STAGED : ROUTE_LEAN);
+    p.route = !path ? (o.integrator == SHM_INTEGRATOR_RANDOM_WALK ? ROUTE_RANDOM_WALK : (o.integrator == SHM_INTEGRATOR_AMBIENT_OCCLUSION ? ROUTE_AO : ROUTE_SIMPLE))
+                    : ((!s.lean || fd) ? ROUTE_STAGED : ROUTE_LEAN);
     const bool staged = p.route == ROUTE_STAGED;
     p.lean_first = path && !fd && s.first_bounce;
     p.hit16 = path && (!f.has_spheres || !f.has_instances);

@@ -745,6 +745,9 @@ public:
             d.color_space.rgb2spec_scale = a.rgb2spec().scale.data();
             d.color_space.rgb2spec_data = a.rgb2spec().data.data();
             d.color_space.illuminant = a.cs_illuminant().data();
+        } else {  // ... and the illuminant alone in every other scene: the ambient occlusion integrator's light (shm/ao.h) — nothing else of such a scene reads it
+            if (a.cs_illuminants[CS_SRGB].empty()) a.cs_illuminants[CS_SRGB] = illuminant_dense(CS_SRGB);
+            d.color_space.illuminant = a.cs_illuminant().data();
         }
         out->owner = std::move(self_owned);
         return out;

@@ -488,6 +488,7 @@ int shm_scene_create(const ShmSceneDesc* desc, int device, ShmScene** out) {
     for (hipStream_t& st : s->stream_cls) if (hipStreamCreate(&st) != hipSuccess) { g_err = "hipStreamCreate failed"; return fail(SHM_ERR_DEVICE); }
     if ((rc = upload_scene(s)) != SHM_OK) return fail(rc);
     s->plan = scene_plan(scene_facts(s->flat), read_knobs());
+    if (!s->flat.cs_illuminant.empty()) s->ao_illum_scale = host_illuminant_scale(s->flat.cs_illuminant.data());
     s->lds_tables = wf_lds_tables(s, LDS_TABLE_BUDGET);
     s->lds_tables_small = wf_lds_tables(s, LDS_TABLE_BUDGET_SMALL);
     if (s->plan.tri_shade && (rc = build_tri_shade(s)) != SHM_OK) return fail(rc);
@@ -689,6 +690,7 @@ static int shade_vertex(Render& r, const ShadeArgs& sa, int bounce, bool overlap
     const RenderPlan& p = r.plan;
     const ShadeKernels& k = r.k;
     if (p.route == ROUTE_RANDOM_WALK) return k.randomwalk(s, sa);
+    if (p.route == ROUTE_AO) return wf_launch_shade_ao(s, sa, p.zs);  // (outside the table: one build for every scene class, k_ao.hip)
     if (p.route == ROUTE_SIMPLE) return k.simple(s, sa);
     if (p.route == ROUTE_LEAN) return k.lean(s, sa);
     if (!p.staged_bounce(bounce)) return k.fused_all(s, sa);
@@ -754,7 +756,11 @@ static int render_batch(Render& r, const uint32_t* pixels, uint32_t n_pix) {
     r.used_overlap = r.used_overlap || overlap;
     hipEvent_t k3_done = nullptr;
     const int shade_blocks = s->n_cu * 4;  // (the fused / vertex / scatter launchers scale this by their own waves per SIMD)
-    for (int bounce = 0; bounce <= params->max_depth; ++bounce) {
+    // The ambient occlusion integrator is this loop run once, whatever max_depth says: its shade kernel queues the occlusion rays and the any-hit launch behind it adds
+    // the unoccluded contributions into L — at bounce 0, where a path render of max_depth 0 traces no shadow ray
+    const bool ao = p.route == ROUTE_AO;
+    const int last_bounce = ao ? 0 : params->max_depth;
+    for (int bounce = 0; bounce <= last_bounce; ++bounce) {
         if (p.hit_kept) hits.keep_previous(bounce);
         const int sh = bounce & 1;
         if (!overlap && bounce >= p.late_overlap_bounce) {
@@ -781,7 +787,7 @@ static int render_batch(Render& r, const uint32_t* pixels, uint32_t n_pix) {
             hipEventRecord(s1, s->stream);
             r.ev_shade.push_back({s0, s1});
         }
-        if (bounce < params->max_depth && p.route != ROUTE_RANDOM_WALK) {
+        if ((bounce < params->max_depth || ao) && p.route != ROUTE_RANDOM_WALK) {
             hipEvent_t c = ev.get(), d = ev.get();
             if (overlap) {
                 hipEvent_t shaded = ev.get();
@@ -862,7 +868,10 @@ int shm_render_wave(ShmScene* s, const ShmRenderParams* params, const ShmTile* t
                     int32_t sample_end, ShmStats* stats) {
     if (!wave_args_ok(s, params, tiles, n_tiles, sample_begin, sample_end)) return SHM_ERR_INVALID_ARGUMENT;
     if (params->max_depth < 0 || params->max_depth > 254) { g_err = "max_depth out of range"; return SHM_ERR_INVALID_ARGUMENT; }
-    if (params->integrator > SHM_INTEGRATOR_RANDOM_WALK) { g_err = "unknown integrator"; return SHM_ERR_UNSUPPORTED; }
+    if (params->integrator > SHM_INTEGRATOR_AMBIENT_OCCLUSION) { g_err = "unknown integrator"; return SHM_ERR_UNSUPPORTED; }
+    if (params->integrator == SHM_INTEGRATOR_AMBIENT_OCCLUSION) {  // (its two parameters are read by no other integrator, and checked for no other)
+        if (const char* e = shm_host::ao_params_error(*params, s->flat)) { g_err = e; return SHM_ERR_INVALID_ARGUMENT; }
+    }
     // (the random walk's batches are capped at 16 Mi paths: 32 B per depth per path beside the path state)
     const bool random_walk = params->integrator == SHM_INTEGRATOR_RANDOM_WALK;
     Render r(s, params);

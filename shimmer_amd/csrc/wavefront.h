@@ -33,6 +33,7 @@
 #include "shm/bvh_link.h"
 #include "host/bvh_pairs.hpp"
 #include "host/render_plan.hpp"
+#include "host/illuminant_scale.hpp"
 // K_DELTA_LIGHTS (a translation unit's switch, like K_ZSOBOL below): PBRT-v4's distant and spot lights are compiled into a unit's light sampling only where it is true
 // (shm/path.h, SHM_DELTA_LIGHTS). The Makefile compiles every unit that samples lights once more with it into *_dl (and *_zs_dl) objects, whose kernels carry a _dl
 // suffix and whose launchers are the <., DL = true> specializations of wf_shade (below); the render's plan (host/render_plan.hpp, RenderPlan::dl) names that set for a scene that holds such a light
@@ -443,6 +444,8 @@ struct ShmScene {
     uint32_t* d_display_slabs = nullptr;
     uint32_t* d_display_state = nullptr;   // 256 counts, then a ShmDisplayState
     bool display_filled = false;           // d_display holds an image
+    float ao_illum_scale = 0.0f;           // the ambient occlusion integrator's illum_scale: 1 / CIE Y of the colour space's illuminant, in double at scene creation, rounded once
+                                           // (0: the scene came without an illuminant, and a render under that integrator is refused)
 };
 // dist.hip: releases s->dist (RCCL communicator included); called by shm_scene_destroy
 __attribute__((visibility("hidden"))) void wf_dist_release(ShmScene* s);
@@ -559,6 +562,9 @@ struct GBufferArgs {
     int film_weight;
 };
 WF_INTERNAL int wf_launch_gbuffer(ShmScene* s, const GBufferArgs& a);
+// k_ao.hip: the ambient occlusion integrator's shade kernel, k_shade_ao (shm/ao.h), over q_active[cur] — one build for every scene class, one instantiation per sampler;
+// it fills the shadow buffers and the shadow queue as a path vertex's light sample does (ShmScene::ao_illum_scale rides along as an argument)
+WF_INTERNAL int wf_launch_shade_ao(ShmScene* s, const ShadeArgs& a, bool zs);
 // k_denoise.hip: shm_denoise_device's body over `film` — the scene's, or the temporal pass's result (shm_denoise_temporal_device, k_temporal.hip) — into ShmScene::d_denoised;
 // `temporal_records` not null: behind the variance pass, k_temporal.hip's kernel puts the records' temporal variance over plane A's at the pixels whose history is long enough
 WF_INTERNAL int wf_denoise_run(ShmScene* s, const ShmDenoiseParams* params, const ShmFilmPixel* film, const float4* temporal_records, double* ms_out);

@@ -18,13 +18,17 @@ FILM_DTYPE = np.dtype([("rgb_sum", "<f8", (3,)), ("weight_sum", "<f8")])
 
 def make_params(seed=0, spp=4, max_depth=5, regularize=False, disable_pixel_jitter=False, disable_wavelength_jitter=False,
                 integrator="path", sample_lights=True, sample_bsdf=True, force_diffuse=False, disable_texture_filtering=False, reference_quirks=True,
-                sampler="independent", randomization="fastowen"):
-    """sampler: "independent" (the default) or "zsobol"; randomization ("fastowen" or "none") applies to "zsobol" only."""
+                sampler="independent", randomization="fastowen", ao_max_distance=0.0, ao_uniform_sample=False):
+    """sampler: "independent" (the default) or "zsobol"; randomization ("fastowen" or "none") applies to "zsobol" only.
+    integrator "ambientocclusion" (PBRT-v4's): ao_max_distance 0 (or inf) is an unbounded occlusion ray, ao_uniform_sample picks uniform over cosine hemisphere sampling;
+    the other integrators ignore both."""
     p = abi.ShmRenderParams()
     p.sampler = {"independent": abi.SHM_SAMPLER_INDEPENDENT, "zsobol": abi.SHM_SAMPLER_ZSOBOL}[sampler]
     p.sampler_randomization = {"fastowen": abi.SHM_SAMPLER_FASTOWEN, "none": abi.SHM_SAMPLER_RANDOMIZE_NONE}[randomization]
     p.integrator = {"path": abi.SHM_INTEGRATOR_PATH, "simplepath": abi.SHM_INTEGRATOR_SIMPLE_PATH,
-                    "randomwalk": abi.SHM_INTEGRATOR_RANDOM_WALK}[integrator]
+                    "randomwalk": abi.SHM_INTEGRATOR_RANDOM_WALK, "ambientocclusion": abi.SHM_INTEGRATOR_AMBIENT_OCCLUSION}[integrator]
+    p.ao_uniform_sample = int(bool(ao_uniform_sample))
+    p.ao_max_distance = 0.0 if ao_max_distance == float("inf") else float(ao_max_distance)
     p.sample_lights, p.sample_bsdf = int(sample_lights), int(sample_bsdf)
     p.force_diffuse, p.disable_texture_filtering = int(force_diffuse), int(disable_texture_filtering)
     p.disable_reference_quirks = 0 if reference_quirks else 1  # SHM_REFERENCE_QUIRKS (SURVEY 7): ON = reference-exact (the default)

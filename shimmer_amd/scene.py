@@ -1014,6 +1014,13 @@ class SceneBuilder:
                 ils = (abi.ShmImageInfiniteLight * len(self.image_lights))(*self.image_lights)
                 d.n_image_lights, d.image_lights = len(self.image_lights), ils
                 self._keep.append(ils)
+        if not d.color_space.illuminant:
+            # every scene carries its colour space's illuminant (sRGB: D65, as in use_srgb_color_space) — the ambient occlusion integrator's light; the rgb2spec table
+            # stays with the scenes that need it, and nothing else of a scene reads the illuminant
+            illum = self.color_space["illuminant"] if self.color_space is not None else piecewise_to_dense(*piecewise_from_interleaved(tables()["CIE_ILLUM_D6500"], True))
+            illum = _as_f32(illum)
+            d.color_space.illuminant = _fptr(illum)
+            self._keep.append(illum)
         if self.spot_lights:
             sps = (abi.ShmSpotLight * len(self.spot_lights))(*self.spot_lights)
             d.n_spot_lights, d.spot_lights = len(self.spot_lights), sps
